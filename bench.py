@@ -17,6 +17,11 @@ the ranks, the reduced camera system all-reduced by RCCL on the solver's stream 
 
 Sub-records in the same JSON line (rank 0, measured after the headline region): `config3` (sonar + depth + per-frame
 extrinsics), `config4_single_gpu`, `config5` (pose graph), `cpu_baseline` at 1 / 2 / all host threads.
+
+`--dump-outputs DIR`: after the timed steps, rank 0 writes what the last timed step handed its caller as DIR/<name>.npy
+(float64): the window's poses, speed / bias states, landmarks and summary -- or, with `--workload posegraph`, the optimised
+keyframe poses and summary; summary.npy = initial cost, final cost, iterations, successful steps, termination code.  The
+inputs are seeded, so two builds run with the same arguments can be compared array by array.
 """
 import argparse
 import json
@@ -24,6 +29,7 @@ import os
 import socket
 import subprocess
 import sys
+import tempfile
 import threading
 import time
 
@@ -77,15 +83,42 @@ def timed_solves(est, fids, lids, snap, steps, warmup, iters, sync):
     return times, its, last
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def write_outputs(out_dir, **arrays):
+    """--dump-outputs: each array as out_dir/<name>.npy in float64"""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def dump_window_outputs(out_dir, est, fids, lids):
+    """what the caller of the timed path (prepare + solve_prepared + finish) receives after the last timed step"""
+    s = est.summary()
+    lms = [est.get_landmark(l) for l in lids]
+    write_outputs(out_dir,
+                  T_WS=np.stack([est.get_T_WS(f) for f in fids]),
+                  speed_and_bias=np.stack([est.get_speed_and_bias(f) for f in fids]),
+                  landmarks=np.stack([m["point"] for m in lms]),
+                  landmark_quality=np.array([m["quality"] for m in lms]),
+                  summary=np.array([s["initial_cost"], s["final_cost"], s["iterations"], s["successful"], s["termination"]]))
+
+
 def cpu_baseline(spec, budget_s=6.0):
     """Oracle (CPU restatement of the reference's Ceres path) on the same window: optimize(10) from the same start, at
     1 thread, 2 threads (what the pipeline uses, ThreadedKFVio.cpp:1086) and all host cores."""
     from oracle import orc
     from svin_amd import synthetic as syn
-    try:
-        lib = orc.lib(orc.build(native=True, out="/tmp/liborc_native.so"))
-    except Exception:
-        lib = orc.lib()
+    with tempfile.TemporaryDirectory() as tmp:   # private: a fixed /tmp name fails once another user owns it
+        try:
+            lib = orc.lib(orc.build(native=True, out=os.path.join(tmp, "liborc_native.so")))
+        except Exception:
+            lib = orc.lib()
     nproc = os.cpu_count() or 1
     rows = {}
     for nt in sorted({1, 2, nproc}):
@@ -200,7 +233,8 @@ def main_posegraph(args):
     path does not shard: N > 1 runs replicas."""
     import torch
     rank, world, local_rank, dist = init_distributed(args)
-    out = posegraph_record(args, rank, world, local_rank, dist, args.steps, args.warmup, cpu=not args.no_cpu_baseline and world == 1)
+    out = posegraph_record(args, rank, world, local_rank, dist, args.steps, args.warmup, cpu=not args.no_cpu_baseline and world == 1,
+                           dump_dir=args.dump_outputs)
     if rank == 0:
         emit(out)
     if dist is not None:
@@ -208,19 +242,20 @@ def main_posegraph(args):
     return out
 
 
-def posegraph_record(args, rank, world, local_rank, dist, steps, warmup, cpu):
+def posegraph_record(args, rank, world, local_rank, dist, steps, warmup, cpu, dump_dir=None):
     import torch
     from svin_amd import synthetic_pg as spg
     from svin_amd.posegraph import PoseGraph
     spec = spg.make_pose_graph(n=5000, laps=20, loop_every=25, seed=7 + rank)
 
-    def one_step():
+    def one_step(keep_poses=False):
         g = PoseGraph(local_rank, six_dof=args.six_dof)
         earliest, cur = spg.feed(g, spec)
         s = g.optimize(earliest, cur)
         part = g.partition()
+        poses = g.poses() if keep_poses else None
         g.close()
-        return s, part
+        return s, part, poses
 
     for _ in range(warmup):
         one_step()
@@ -228,8 +263,8 @@ def posegraph_record(args, rank, world, local_rank, dist, steps, warmup, cpu):
         dist.barrier()
     torch.cuda.synchronize()
     total_t, total_it, dense_t, dense_n, last, part = 0.0, 0, 0.0, 0, None, None
-    for _ in range(steps):
-        last, part = one_step()
+    for k in range(steps):
+        last, part, poses = one_step(keep_poses=dump_dir is not None and k == steps - 1)
         total_t += last["solve_seconds"]
         total_it += last["iterations"]
         dense_t += part["dense_solve_seconds"]
@@ -240,6 +275,9 @@ def posegraph_record(args, rank, world, local_rank, dist, steps, warmup, cpu):
     total_t, total_it = reduce_time_and_count(dist, total_t, total_it)
     if rank != 0:
         return None
+    if dump_dir is not None:
+        write_outputs(dump_dir, positions=poses[0], quaternions=poses[1],
+                      summary=np.array([last["initial_cost"], last["final_cost"], last["iterations"], last["successful"], last["termination"]]))
     value = total_it / total_t
     d = part["separator_unknowns"]
     flops = d ** 3 / 3.0 + 2.0 * d * d     # Cholesky + the two triangular solves of the separator system
@@ -769,8 +807,12 @@ def main():
     ap.add_argument("--sharded-transport", default="rccl", choices=["rccl", "stage"],
                     help="collectives of the sharded config-#4 sub-record: rccl (native, on the solver's stream) or stage (gloo over "
                          "host-staged buffers: the ranks may then share one GPU -- how a 1-GPU box runs the N > 1 record's code)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float64)")
     ap.add_argument("--sharded-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.sharded_child:
         protect_stdout()
         if args.gpus == 1:
@@ -804,6 +846,8 @@ def main():
         dist.barrier()
     t_region = time.perf_counter() - t_region
     total_t, total_it = reduce_time_and_count(dist, sum(times), sum(its))
+    if rank == 0 and args.dump_outputs:
+        dump_window_outputs(args.dump_outputs, est, fids, lids)
 
     out = None
     if rank == 0:

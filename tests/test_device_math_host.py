@@ -8,7 +8,6 @@ distortion models.  (The GPU parity tests proper live in test_gpu_parity.py and 
 import ctypes as C
 import os
 import subprocess
-import tempfile
 
 import numpy as np
 import pytest
@@ -20,8 +19,8 @@ pd = C.POINTER(C.c_double)
 
 
 @pytest.fixture(scope="module")
-def shim():
-    out = os.path.join(tempfile.gettempdir(), "svin_dmath_host_shim.so")
+def shim(tmp_path_factory):
+    out = str(tmp_path_factory.mktemp("dmath") / "svin_dmath_host_shim.so")
     subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", out,
                            os.path.join(HERE, "csrc", "dmath_host_shim.cpp")])
     return C.CDLL(out)
