@@ -254,6 +254,22 @@ int svin_ba_is_parameter_block_constant(svin_ba* h, uint64_t block_id);         
  * block's type cannot take.  svin_ba_linearize reports the 6-DoF system; a window holding such a block cannot marginalise. */
 int svin_ba_reset_parameterization(svin_ba* h, uint64_t block_id, int parameterization);
 int svin_ba_get_parameterization(svin_ba* h, uint64_t block_id);   /* the value above, SVIN_ERR_NOT_FOUND for an unknown block */
+/* Map::getLhs (src/Map.cpp:105-150): H = sum of J^T J over every residual touching the block, J the minimal Jacobian
+ * (EvaluateWithMinimalJacobians) at the current values -- square-root information included, loss function excluded; constant
+ * blocks alike.  6 x 6 for pose and extrinsics blocks (a reduced pose manifold keeps six columns), 9 x 9 speed / bias, 3 x 3
+ * landmarks; a block no residual touches gets H = 0.  Sources: reprojection residuals, HomogeneousPointErrors, every small factor
+ * (host residuals through their callbacks; an IMU factor may re-integrate, as the reference's ImuError does) and the diagonal block
+ * of the marginalisation prior's J^T J.  The first call computes every block of the window in one device pass and keeps the result;
+ * later calls are look-ups until an entry point that can change a value, the graph, a parameterisation or the prior is called
+ * (read-only queries such as get_parameter_block, get_T_WS or get_landmark keep the result).  Both wait for a running marginalisation job.
+ * get_lhs: returns mdim and writes H row-major; -mdim if cap < mdim * mdim; SVIN_ERR_NOT_FOUND for an unknown id.
+ * get_lhs_blocks: writes the n blocks back to back (dims[i] x dims[i] each, dims may be NULL) and returns the total number of
+ * doubles; H = NULL only sizes (dims are filled), a cap_doubles below the total is SVIN_ERR_INVALID_ARG, any unknown id
+ * SVIN_ERR_NOT_FOUND.  Not available in landmark-sharded mode (world > 1): SVIN_ERR_UNSUPPORTED. */
+int svin_ba_get_lhs(svin_ba* h, uint64_t block_id, double* H, int cap);
+int64_t svin_ba_get_lhs_blocks(svin_ba* h, int n, const uint64_t* block_ids, int32_t* dims, double* H, int64_t cap_doubles);
+/* inspection: the number of all-blocks getLhs passes the handle has run (a look-up does not count) */
+int64_t svin_ba_get_lhs_pass_count(svin_ba* h);
 /* Map::residuals(id) (src/Map.cpp:576-587): ids of every residual touching the block, in insertion order; returns the
  * count (may exceed cap), SVIN_ERR_NOT_FOUND for an unknown block */
 int svin_ba_residuals_of(svin_ba* h, uint64_t block_id, uint64_t* residual_ids, int cap);

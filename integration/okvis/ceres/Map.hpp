@@ -350,6 +350,21 @@ class Map {
     need();
     return svin_ba_reset_parameterization(h_, id, parameterization) == 1;
   }
+  /// Map::getLhs (Map.hpp:132, Map.cpp:105-150): sum of J^T J over the block's residuals, minimal Jacobians at the backend's
+  /// current values (those of the last solve or setter), no loss function.  A template because this header includes no Eigen:
+  /// MatrixT needs resize(rows, cols) and operator()(row, col), which Eigen::MatrixXd has.  The first call computes every block of
+  /// the window in one device pass; later calls are look-ups (svin_ba_get_lhs) until a call that changes a value, the graph, a
+  /// parameterisation or the prior.  Read-only calls (parameterBlockPtr right after getLhs, as Estimator.cpp:902-923) keep it.
+  template <class MatrixT>
+  void getLhs(uint64_t parameterBlockId, MatrixT& H) const {
+    need();
+    double buf[81];
+    const int md = svin_ba_get_lhs(h_, parameterBlockId, buf, 81);
+    if (md <= 0) throw std::runtime_error(std::string("svin_ba_get_lhs: ") + svin_ba_last_error());
+    H.resize(md, md);
+    for (int i = 0; i < md; ++i)
+      for (int j = 0; j < md; ++j) H(i, j) = buf[i * md + j];
+  }
   /// Map::parameterBlockPtr (Map.hpp:166-170): a snapshot of the block (values, id, fixed, time stamp / initialised flag)
   std::shared_ptr<okvis::ceres::ParameterBlock> parameterBlockPtr(uint64_t id) const {
     need();

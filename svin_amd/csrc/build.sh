@@ -12,11 +12,11 @@ stale() {  # stale <object> <source>
   for h in $HEADERS; do [ "$h" -nt "$1" ] && return 0; done
   return 1
 }
-for f in kernels.hip marg.hip posegraph.hip resident.hip; do
+for f in kernels.hip marg.hip posegraph.hip resident.hip lhs.hip; do
   if stale obj/$f.o $f; then hipcc $FLAGS -c $f -o obj/$f.o; fi
 done
 for f in window.cpp capi.cpp host_eval.cpp; do
   if stale obj/$f.o $f; then hipcc $FLAGS -x hip -c $f -o obj/$f.o; fi
 done
-hipcc --offload-arch=gfx950 -shared -fPIC -o ../libsvin_ba.so obj/kernels.hip.o obj/marg.hip.o obj/posegraph.hip.o obj/resident.hip.o obj/window.cpp.o obj/capi.cpp.o obj/host_eval.cpp.o
+hipcc --offload-arch=gfx950 -shared -fPIC -o ../libsvin_ba.so obj/kernels.hip.o obj/marg.hip.o obj/posegraph.hip.o obj/resident.hip.o obj/lhs.hip.o obj/window.cpp.o obj/capi.cpp.o obj/host_eval.cpp.o
 echo "built $(cd .. && pwd)/libsvin_ba.so"

@@ -293,6 +293,19 @@ void launchCost(const DeviceProblem& p, hipStream_t s);                  // sums
 void launchImuPropagation(const DevImu* im /*device*/, const uint32_t* T, const double* M, double* io, double* jac, double* cov,
                           int* used, hipStream_t s);
 void launchLandmarkQuality(const DeviceProblem& p, double* quality, hipStream_t s);
+// ---- Map::getLhs of every parameter block in one pass (lhs.hip).  Items: (camera-side block, observation range) -- key < nPose a
+// pose slot, else extrinsics slot key - nPose; partial[item] gets its 21 upper-triangle sums.  Blocks: one per pose / extrinsics /
+// speed-bias block, result at out[out .. out + md * md) (row-major, full); facs: (factor index, first column of the block in the
+// factor's FactorLin::J) per small factor touching it.  The landmark blocks go to out[lmOut + 9 l] in CSR order.
+struct LhsItem { int key, begin, end, pad; };
+struct LhsBlock {
+  int out, md;
+  int item0, item1;      // its work items [item0, item1) (pose / extrinsics blocks)
+  int fac0, fac1;        // its entries of facs
+  int priorOrd, priorMd; // its rows of the prior (priorMd 0: not in the prior, or fixed when it was marginalised)
+};
+void launchLhsAll(const DeviceProblem& p, const LhsItem* items, int nItems, const LhsBlock* blocks, int nBlocks, const int2* facs,
+                  double* partial, double* out, size_t lmOut, hipStream_t s);
 // Jacobian-evaluation micro-benchmark entry: B independent copies of the observation set
 void launchEvalReprojBatched(const DeviceProblem& p, int copies, double* rOut, double* JpOut, double* JlOut,
                              double* JeOut, hipStream_t s);

@@ -3052,6 +3052,140 @@ int Window::getPrior(double* H, double* b0, double* J, double* e0, uint64_t* ids
   return m;
 }
 
+// ------------------------------------------------------------------------------------------ Map::getLhs (Map.cpp:105-150)
+int Window::lhsDim(uint64_t id) const {
+  if (const Block* b = findBlock(id)) return b->kind == B_SB ? 9 : 6;   // a pose on a reduced manifold keeps its six columns
+  return lmIndex_.count(id) ? 3 : 0;
+}
+// One pass over the whole window (lhs.hip): the small factors' records at the current point (host residuals through their
+// callbacks, IMU factors re-integrating where the reference's ImuError would), then the three getLhs kernels.  Work items of the
+// camera-side sums: block k's share of the observation table is cut into max(obs_k / 256, N / 16384) ranges, so that every item
+// evaluates about 256 observations or scans at most ~16 K table entries.
+void Window::computeLhs() {
+  pack();
+  const DeviceProblem& p = prob_;
+  hipStream_t s = stream_;
+  const size_t nP = poseIds_.size(), nE = extIds_.size(), nS = sbIds_.size();
+  const size_t offExt = 36 * (size_t)p.nPose, offSb = offExt + 36 * (size_t)p.nExt, offLm = offSb + 81 * (size_t)p.nSb;
+  const size_t total = offLm + 9 * (size_t)p.L;
+  // work items of the camera-side blocks
+  std::vector<LhsItem> items;
+  std::vector<int> itemPtr(nP + nE + 1, 0);
+  const int minSplit = std::max(1, (p.N + 16383) / 16384);
+  for (size_t k = 0; k < nP + nE; ++k) {
+    itemPtr[k] = (int)items.size();
+    const Block& b = blocks_.at(k < nP ? poseIds_[k] : extIds_[k - nP]);
+    if (b.nObs == 0) continue;
+    const int split = std::min(std::max(minSplit, (b.nObs + 255) / 256), std::max(1, p.N / 64));
+    const int key = k < nP ? (int)k : p.nPose + (int)(k - nP);
+    for (int i = 0; i < split; ++i)
+      items.push_back(LhsItem{key, (int)((long long)p.N * i / split), (int)((long long)p.N * (i + 1) / split), 0});
+  }
+  itemPtr[nP + nE] = (int)items.size();
+  // small factors per block (factor table order), prior rows per block
+  std::unordered_map<uint64_t, std::vector<int2>> facOf;
+  for (size_t f = 0; f < factorIds_.size(); ++f) {
+    const Factor& fac = factors_.at(factorIds_[f]);
+    int col = 0;
+    for (int b = 0; b < fac.nblk; ++b) {
+      facOf[fac.blocks[b]].push_back(make_int2((int)f, col));
+      col += blocks_.at(fac.blocks[b]).kind == B_SB ? 9 : 6;
+    }
+  }
+  std::unordered_map<uint64_t, std::pair<int, int>> priorOf;
+  if (hasPrior_ && p.priorM > 0)
+    for (const PriorBlockHost& pb : priorBlocks_)
+      if (pb.mdim > 0) priorOf[pb.id] = std::make_pair(pb.ord, pb.mdim);
+  std::vector<LhsBlock> blk;
+  std::vector<int2> facs;
+  lhsOff_.clear();
+  auto addBlock = [&](uint64_t id, size_t out, int md, int item0, int item1) {
+    LhsBlock q{(int)out, md, item0, item1, (int)facs.size(), (int)facs.size(), 0, 0};
+    auto f = facOf.find(id);
+    if (f != facOf.end()) { facs.insert(facs.end(), f->second.begin(), f->second.end()); q.fac1 = (int)facs.size(); }
+    auto pr = priorOf.find(id);
+    if (pr != priorOf.end()) { q.priorOrd = pr->second.first; q.priorMd = pr->second.second; }
+    blk.push_back(q);
+    lhsOff_[id] = out;
+  };
+  for (size_t i = 0; i < nP; ++i) addBlock(poseIds_[i], 36 * i, 6, itemPtr[i], itemPtr[i + 1]);
+  for (size_t i = 0; i < nE; ++i) addBlock(extIds_[i], offExt + 36 * i, 6, itemPtr[nP + i], itemPtr[nP + i + 1]);
+  for (size_t i = 0; i < nS; ++i) addBlock(sbIds_[i], offSb + 81 * i, 9, 0, 0);
+  // landmarks in CSR order (as observationIds lists them)
+  if (residentUsed_) {
+    size_t l = 0;
+    for (const Landmark* lp : lmByHandle_)
+      if (lp && !lp->obs.empty()) lhsOff_[lp->id] = offLm + 9 * l++;
+  } else {
+    for (size_t l = 0; l < lmIds_.size(); ++l) lhsOff_[lmIds_[l]] = offLm + 9 * l;
+  }
+  // device pass
+  dLhs_.reserve(std::max<size_t>(total, 1));
+  dLhsPartial_.reserve(std::max<size_t>(21 * items.size(), 1));
+  dLhsItems_.reserve(std::max<size_t>(items.size(), 1));
+  dLhsBlocks_.reserve(std::max<size_t>(blk.size(), 1));
+  dLhsFacs_.reserve(std::max<size_t>(facs.size(), 1));
+  if (!items.empty()) HIP_OK(hipMemcpyAsync(dLhsItems_.p, items.data(), sizeof(LhsItem) * items.size(), hipMemcpyHostToDevice, s));
+  if (!blk.empty()) HIP_OK(hipMemcpyAsync(dLhsBlocks_.p, blk.data(), sizeof(LhsBlock) * blk.size(), hipMemcpyHostToDevice, s));
+  if (!facs.empty()) HIP_OK(hipMemcpyAsync(dLhsFacs_.p, facs.data(), sizeof(int2) * facs.size(), hipMemcpyHostToDevice, s));
+  if (p.F > 0) {
+    evaluateHostFactors(false, s);
+    launchEvalFactors(p, false, s);
+  }
+  launchLhsAll(p, dLhsItems_.p, (int)items.size(), dLhsBlocks_.p, (int)blk.size(), dLhsFacs_.p, dLhsPartial_.p, dLhs_.p, offLm, s);
+  lhsHost_.assign(total, 0.0);
+  std::vector<DevImu> hImu(p.nImu);
+  if (total > 0) HIP_OK(hipMemcpyAsync(lhsHost_.data(), dLhs_.p, sizeof(double) * total, hipMemcpyDeviceToHost, s));
+  if (p.F > 0 && p.nImu > 0) HIP_OK(hipMemcpyAsync(hImu.data(), p.imus, sizeof(DevImu) * p.nImu, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipStreamSynchronize(s));
+  // the evaluation may have re-preintegrated: keep the state, as the reference's ImuError keeps its mutable members
+  if (p.F > 0 && p.nImu > 0) {
+    int k = 0;
+    for (uint64_t fid : factorIds_) {
+      Factor& f = factors_.at(fid);
+      if (f.kind == F_IMU) f.imu = hImu[k++];
+    }
+  }
+  lhsValid_ = true;
+  ++lhsPasses_;
+}
+int Window::getLhs(uint64_t id, double* H, int cap) {
+  if (world_ > 1 || rcclComm_) return -4 /* SVIN_ERR_UNSUPPORTED */;
+  quiesce();
+  const int md = lhsDim(id);
+  if (md == 0) return -2 /* SVIN_ERR_NOT_FOUND */;
+  if (cap < md * md) return -md;
+  if (!lhsValid_) computeLhs();
+  auto it = lhsOff_.find(id);
+  if (it == lhsOff_.end()) std::fill(H, H + md * md, 0.0);
+  else std::memcpy(H, lhsHost_.data() + it->second, sizeof(double) * md * md);
+  return md;
+}
+long long Window::getLhsBlocks(int n, const uint64_t* ids, int32_t* dims, double* H, long long capDoubles) {
+  if (world_ > 1 || rcclComm_) return -4 /* SVIN_ERR_UNSUPPORTED */;
+  if (n < 0 || (n > 0 && !ids)) return -1 /* SVIN_ERR_INVALID_ARG */;
+  quiesce();
+  long long total = 0;
+  for (int i = 0; i < n; ++i) {
+    const int md = lhsDim(ids[i]);
+    if (md == 0) return -2 /* SVIN_ERR_NOT_FOUND */;
+    if (dims) dims[i] = md;
+    total += (long long)md * md;
+  }
+  if (!H) return total;
+  if (capDoubles < total) return -1 /* SVIN_ERR_INVALID_ARG */;
+  if (!lhsValid_) computeLhs();
+  double* q = H;
+  for (int i = 0; i < n; ++i) {
+    const int md = lhsDim(ids[i]);
+    auto it = lhsOff_.find(ids[i]);
+    if (it == lhsOff_.end()) std::fill(q, q + md * md, 0.0);
+    else std::memcpy(q, lhsHost_.data() + it->second, sizeof(double) * md * md);
+    q += md * md;
+  }
+  return total;
+}
+
 // ------------------------------------------------------------------------------------------ measurement hooks
 int Window::benchJacobianEval(int copies, int iters, double* meanMs, double* bytes, double* backToBackMs) {
   pack();

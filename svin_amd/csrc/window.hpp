@@ -330,6 +330,15 @@ class Window {
   int getPrior(double* H, double* b0, double* J, double* e0, uint64_t* ids, int32_t* ord, int32_t* mdim,
                int32_t* nBlocks, int capM);
   int describeBlock(uint64_t id, uint64_t* frame, int32_t* kind, int32_t* index) const;
+  // Map::getLhs (Map.cpp:105-150): sum of J^T J over the residuals of a block, minimal Jacobians at the current values, no loss.
+  // Answered from the window's last all-blocks pass (lhs.hip), which is kept until invalidateLhs() -- called by every entry point of
+  // the C ABI but the two below, so that a change of a value, the graph, a parameterisation or the prior can never be missed.
+  // getLhs: the block's minimal dimension (H row-major), -mdim when cap < mdim^2, SVIN_ERR_NOT_FOUND, SVIN_ERR_UNSUPPORTED (sharded).
+  // getLhsBlocks: the blocks back to back, dims[i]^2 doubles each; returns the total (H == nullptr: sizes only).
+  int getLhs(uint64_t id, double* H, int cap);
+  long long getLhsBlocks(int n, const uint64_t* ids, int32_t* dims, double* H, long long capDoubles);
+  void invalidateLhs() { lhsValid_ = false; }
+  long long lhsPassCount() const { return lhsPasses_; }   // all-blocks passes run so far (inspection: one per change)
   const MargPre& margPre() const { return margPre_; }
   // Map::parameterBlockPtr / id2parameterBlockMap as values (Map.hpp:166-170, :188): type 0 pose, 1 extrinsics, 2 speed/bias,
   // 3 landmark; returns the ambient dimension (7 / 9 / 4) or SVIN_ERR_NOT_FOUND
@@ -537,6 +546,16 @@ class Window {
   DevBuf<BatchSlot> batchSlotsDev_;
   BatchSlot* batchSlotsHost_ = nullptr;
   size_t batchSlotsHostCap_ = 0;
+  int lhsDim(uint64_t id) const;   // minimal dimension of a block for getLhs (6 / 6 / 9 / 3), 0 = unknown
+  void computeLhs();               // the all-blocks pass: lhsHost_ / lhsOff_
+  bool lhsValid_ = false;
+  long long lhsPasses_ = 0;
+  std::vector<double> lhsHost_;
+  std::unordered_map<uint64_t, size_t> lhsOff_;   // block id -> its matrix in lhsHost_ (blocks no residual touches are absent: H = 0)
+  DevBuf<double> dLhs_, dLhsPartial_;
+  DevBuf<LhsItem> dLhsItems_;
+  DevBuf<LhsBlock> dLhsBlocks_;
+  DevBuf<int2> dLhsFacs_;
 };
 
 std::string& lastError();

@@ -76,6 +76,7 @@ EXPORTS = [
     "svin_host_manifold_minus", "svin_host_manifold_plus_jacobian", "svin_host_manifold_lift_jacobian",
     "svin_host_manifold_minus_jacobian", "svin_ba_get_parameter_block", "svin_ba_parameter_block_ids",
     "svin_ba_get_all_landmark_observations", "svin_ba_bench_allreduce", "svin_ba_get_marg_pre", "svin_ba_get_marg_pre_blocks",
+    "svin_ba_get_lhs", "svin_ba_get_lhs_blocks", "svin_ba_get_lhs_pass_count",
 ]
 
 ID_PROVIDER_FN = C.CFUNCTYPE(C.c_uint64, C.c_void_p)
@@ -169,6 +170,9 @@ def load_library():
     sig("svin_ba_debug_peek_solver_scratch", i32, vp, u64, u64, pd)
     sig("svin_ba_get_prior", i32, vp, pd, pd, pd, pd, pu64, pi32, pi32, pi32, i32)
     sig("svin_ba_describe_block", i32, vp, u64, pu64, pi32, pi32)
+    sig("svin_ba_get_lhs", i32, vp, u64, pd, i32)
+    sig("svin_ba_get_lhs_blocks", C.c_int64, vp, i32, pu64, pi32, pd, C.c_int64)
+    sig("svin_ba_get_lhs_pass_count", C.c_int64, vp)
     sig("svin_ba_bench_jacobian_eval", i32, vp, i32, i32, pd, pd)
     sig("svin_ba_bench_jacobian_eval_b2b", i32, vp, i32, i32, pd, pd, pd)
     sig("svin_ba_set_pack_mode", i32, vp, i32)
@@ -833,6 +837,33 @@ class Estimator:
         if self.L.svin_ba_describe_block(self.h, int(bid), C.byref(f), C.byref(k), C.byref(ix)) != 1:
             return None
         return int(f.value), int(k.value), int(ix.value)
+
+    def get_lhs(self, block_id):
+        """Map::getLhs (Map.cpp:105-150): sum of J^T J over the block's residuals, minimal Jacobians at the current values, no loss;
+        (6, 6) pose / extrinsics, (9, 9) speed / bias, (3, 3) landmark.  Repeated calls with nothing changed in between are look-ups."""
+        H = np.zeros(81)
+        md = self._check(self.L.svin_ba_get_lhs(self.h, int(block_id), _d(H), 81), "get_lhs")
+        return H[:md * md].reshape(md, md).copy()
+
+    def lhs_pass_count(self):
+        """all-blocks getLhs passes run so far (a cached look-up does not count)"""
+        return int(self._check(self.L.svin_ba_get_lhs_pass_count(self.h), "lhs_pass_count"))
+
+    def get_lhs_blocks(self, ids):
+        """get_lhs of every id of the list from one call: a list of square matrices"""
+        ids = np.ascontiguousarray(np.asarray(list(ids), dtype=np.uint64))
+        n = len(ids)
+        dims = np.zeros(max(n, 1), np.int32)
+        total = self._check(self.L.svin_ba_get_lhs_blocks(self.h, n, ids.ctypes.data_as(pu64), dims.ctypes.data_as(pi32), None, 0),
+                            "get_lhs_blocks")
+        H = np.zeros(max(total, 1))
+        self._check(self.L.svin_ba_get_lhs_blocks(self.h, n, ids.ctypes.data_as(pu64), dims.ctypes.data_as(pi32), _d(H), total),
+                    "get_lhs_blocks")
+        out, o = [], 0
+        for d in dims[:n]:
+            out.append(H[o:o + d * d].reshape(d, d).copy())
+            o += d * d
+        return out
 
     def marg(self, cap=2048):
         ids, ordr, md, nb = np.zeros(512, np.uint64), np.zeros(512, np.int32), np.zeros(512, np.int32), C.c_int32()
