@@ -328,8 +328,8 @@ uint64_t svin_ba_map_add_depth_error(svin_ba* h, uint64_t pose_block, double dep
  * residual_dim residuals and, per block, the residual_dim x (6 | 9) row-major Jacobian in MINIMAL coordinates (what
  * ErrorInterface::EvaluateWithMinimalJacobians delivers: pose delta = (dr, dalpha), q <- exp(dalpha) * q); it returns non-zero on
  * success (::ceres::CostFunction::Evaluate's bool).  Called from the thread that optimises, before every evaluation launch, with one
- * stream synchronisation each time: a slow path for graphs third parties build through okvis::ceres::Map.  No loss function; no
- * landmark blocks; residual_dim <= 15; at most 4 blocks and 30 minimal columns.  Such a window is neither batched nor
+ * stream synchronisation each time: a slow path for graphs third parties build through okvis::ceres::Map.  A loss function:
+ * svin_ba_map_set_residual_loss.  No landmark blocks; residual_dim <= 15; at most 4 blocks and 30 minimal columns.  Such a window is neither batched nor
  * marginalised nor sharded.  Returns the residual id, 0 if refused. */
 typedef int (*svin_cost_function)(void* user, const double* const* parameters, double* residuals, double** jacobians_minimal);
 uint64_t svin_ba_map_add_host_residual(svin_ba* h, const uint64_t* block_ids, int n_blocks, int residual_dim, svin_cost_function fn, void* user);
@@ -340,6 +340,20 @@ uint64_t svin_ba_map_add_reprojection_error(svin_ba* h, uint64_t pose_block, uin
                                             uint64_t cam_idx, const double uv[2], const double information[4]);
 /* Map::removeResidualBlock for any residual of the graph (Map.cpp:467-492) */
 int svin_ba_map_remove_residual_block(svin_ba* h, uint64_t residual_id);
+/* The loss function of a residual (Map::addResidualBlock's loss_function): SVIN_LOSS_NONE (ceres::TrivialLoss, or NULL),
+ * SVIN_LOSS_CAUCHY (ceres::CauchyLoss(scale)), SVIN_LOSS_HUBER (ceres::HuberLoss(scale)); scale finite and > 0 (ignored by NONE, which
+ * reports 1).  Works on reprojection residuals (add_observation, map_add_reprojection_error; they start at CauchyLoss(1)) and on
+ * every small factor, host residuals included (they start at NONE).  Applied on the device as Ceres' corrector does (both losses
+ * have rho'' <= 0: residual and Jacobian scale by sqrt(rho')), in the solve and in the marginalisation; get_lhs stays loss-free.
+ * Returns 1; SVIN_ERR_NOT_FOUND for an unknown residual; SVIN_ERR_INVALID_ARG for an unknown kind or a bad scale;
+ * SVIN_ERR_UNSUPPORTED for the marginalisation prior, a HomogeneousPointError, a window whose 15 distinct reprojection losses are
+ * all taken, and anything but the default in landmark-sharded mode (world > 1).  svin_ba_set_distributed(_rccl) with world > 1
+ * returns SVIN_ERR_UNSUPPORTED for a window that already has a non-default loss. */
+#define SVIN_LOSS_NONE 0
+#define SVIN_LOSS_CAUCHY 1
+#define SVIN_LOSS_HUBER 2
+int svin_ba_map_set_residual_loss(svin_ba* h, uint64_t residual_id, int kind, double scale);
+int svin_ba_map_get_residual_loss(svin_ba* h, uint64_t residual_id, int* kind, double* scale);
 
 /* ---- keyframe hand-off to pose_graph: the estimator-side content of the keyframe message that
  * ThreadedKFVio::optimizationLoop assembles (okvis_multisensor_processing/src/ThreadedKFVio.cpp:1147-1240).  For every

@@ -10,16 +10,24 @@
 namespace ceres {
 struct ResidualBlock;
 typedef ResidualBlock* ResidualBlockId;   // opaque handle carrying the core's residual id
-/// The loss objects a caller hands to Map::addResidualBlock.  They carry no arithmetic: the device solver applies
-/// CauchyLoss(1) to reprojection residuals (Estimator.cpp:69) and no loss to everything else; Map checks that the object it is
-/// given names exactly that.
+/// The loss objects a caller hands to Map::addResidualBlock.  They carry no arithmetic: Map reads the kind and the scale and the
+/// device solver applies the loss (svin_ba_map_set_residual_loss).  TrivialLoss, CauchyLoss(a) and HuberLoss(a) are the ones it
+/// takes; Map throws for any other LossFunction.
 class LossFunction {
  public:
   virtual ~LossFunction() {}
 };
+class TrivialLoss : public LossFunction {};
 class CauchyLoss : public LossFunction {
  public:
   explicit CauchyLoss(double a) : a_(a) {}
+  double a() const { return a_; }
+ private:
+  double a_;
+};
+class HuberLoss : public LossFunction {
+ public:
+  explicit HuberLoss(double a) : a_(a) {}
   double a() const { return a_; }
  private:
   double a_;

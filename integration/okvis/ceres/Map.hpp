@@ -6,9 +6,10 @@
 // okvis::Estimator created); this class is a view onto it.  What does NOT survive, and why:
 //   * addResidualBlock with an ARBITRARY caller-supplied ::ceres::CostFunction (Map.cpp:341-376): a device solver cannot
 //     call virtual CPU cost functions.  Since round 6 any error term that implements ErrorInterface is accepted and evaluated by
-//     the host between the launches (a slow path, pose / speed-bias blocks, no loss); a bare ::ceres::CostFunction is not (there
+//     the host between the launches (a slow path, pose / speed-bias blocks); a bare ::ceres::CostFunction is not (there
 //     is no Ceres).  The fast path: addParameterBlock, and addResidualBlock for the error-term
-//     classes of this directory (PoseError, HomogeneousPointError, ReprojectionError<GEOMETRY> under CauchyLoss(1)) -- each
+//     classes of this directory (PoseError, HomogeneousPointError, ReprojectionError<GEOMETRY>; losses: TrivialLoss, CauchyLoss(a),
+//     HuberLoss(a), none on a HomogeneousPointError) -- each
 //     maps onto a factor kind of the device solver (svin_ba_map_*), so that a program shaped like the reference's own tests
 //     (okvis_ceres/test/TestHomogeneousPointError.cpp:57-99, TestMap.cpp:60-150) builds its graph block by block, checks
 //     Jacobians with isJacobianCorrect, solves and reads the estimates back from its parameter-block objects.
@@ -78,8 +79,8 @@ class Map {
 
   enum Parameterization { HomogeneousPoint, Pose6d, Pose3d, Pose4d, Pose2d, Trivial };   // Map.hpp:97-105
 
-  /// Map.hpp:71-86.  lossFunctionPtr is always NULL here: the Cauchy loss of the reprojection residuals
-  /// (Estimator.cpp:69) is applied inside the device solver, there is no ::ceres::LossFunction object to point to.
+  /// Map.hpp:71-86.  lossFunctionPtr is the object the caller passed to addResidualBlock (NULL for residuals added otherwise, e.g.
+  /// by the estimator: their loss lives in the device solver, svin_ba_map_get_residual_loss reports it).
   struct ResidualBlockSpec {
     ResidualBlockSpec() : residualBlockId(0), lossFunctionPtr(0) {}
     ResidualBlockSpec(::ceres::ResidualBlockId id, ::ceres::LossFunction* loss, std::shared_ptr<ErrorInterface> e)
@@ -169,15 +170,18 @@ class Map {
   bool setParameterBlockConstant(std::shared_ptr<okvis::ceres::ParameterBlock> b) { b->setFixed(true); return setParameterBlockConstant(b->id()); }
   bool setParameterBlockVariable(std::shared_ptr<okvis::ceres::ParameterBlock> b) { b->setFixed(false); return setParameterBlockVariable(b->id()); }
 
-  /// Map::addResidualBlock (Map.cpp:341-376) for the error terms of this directory.  PoseError: no loss.
+  /// Map::addResidualBlock (Map.cpp:341-376) for the error terms of this directory.  PoseError: NULL, TrivialLoss, CauchyLoss(a)
+  /// or HuberLoss(a).
   ::ceres::ResidualBlockId addResidualBlock(std::shared_ptr<PoseError> e, ::ceres::LossFunction* loss, std::shared_ptr<okvis::ceres::ParameterBlock> x0) {
-    need(); noLoss(loss);
+    need();
+    double la = 1.0;
+    const int lk = lossKindOf(loss, &la);
     double meas[7], info[36];
     const okvis::kinematics::Transformation& T = e->measurement();
     for (int k = 0; k < 3; ++k) meas[k] = T.r()[k];
     meas[3] = T.q().x(); meas[4] = T.q().y(); meas[5] = T.q().z(); meas[6] = T.q().w();
     for (int a = 0; a < 6; ++a) for (int b = 0; b < 6; ++b) info[a * 6 + b] = e->information()(a, b);
-    return record(svin_ba_map_add_pose_error(h_, x0->id(), meas, info), e, {x0});
+    return withLoss(record(svin_ba_map_add_pose_error(h_, x0->id(), meas, info), e, {x0}, loss), lk, la);
   }
   /// HomogeneousPointError(measurement, information) on a landmark block: no loss (TestHomogeneousPointError.cpp:74-78)
   ::ceres::ResidualBlockId addResidualBlock(std::shared_ptr<HomogeneousPointError> e, ::ceres::LossFunction* loss,
@@ -186,16 +190,15 @@ class Map {
     const double meas[4] = {e->measurement()[0], e->measurement()[1], e->measurement()[2], e->measurement()[3]};
     return record(svin_ba_add_homogeneous_point_error(h_, x0->id(), meas, e->informationRowMajor()), e, {x0});
   }
-  /// ReprojectionError<GEOMETRY>(geometry, cameraId, measurement, information) under CauchyLoss(1) on (T_WS, hp_W, T_SC)
-  /// (TestMap.cpp:104-108, Estimator::addObservation).  information: a multiple of the identity.
+  /// ReprojectionError<GEOMETRY>(geometry, cameraId, measurement, information) on (T_WS, hp_W, T_SC) (TestMap.cpp:104-108,
+  /// Estimator::addObservation) under NULL / TrivialLoss (none), CauchyLoss(a) or HuberLoss(a).  information: a multiple of the identity.
   template <class GEOMETRY_T>
   ::ceres::ResidualBlockId addResidualBlock(std::shared_ptr<ReprojectionError<GEOMETRY_T> > e, ::ceres::LossFunction* loss,
                                             std::shared_ptr<okvis::ceres::ParameterBlock> pose, std::shared_ptr<okvis::ceres::ParameterBlock> point,
                                             std::shared_ptr<okvis::ceres::ParameterBlock> extrinsics) {
     need();
-    const ::ceres::CauchyLoss* cauchy = dynamic_cast<const ::ceres::CauchyLoss*>(loss);
-    if (!cauchy || cauchy->a() != 1.0)
-      throw std::runtime_error("okvis::ceres::Map (svin_ba shim): reprojection residuals are solved under CauchyLoss(1) (Estimator.cpp:69)");
+    double la = 1.0;
+    const int lk = lossKindOf(loss, &la);
     const void* key = e->cameraGeometry().get();
     auto it = cams_.find(key);
     if (it == cams_.end()) {
@@ -206,18 +209,23 @@ class Map {
       it = cams_.emplace(key, cam).first;
     }
     const double uv[2] = {e->measurement()[0], e->measurement()[1]};
-    return record(svin_ba_map_add_reprojection_error(h_, pose->id(), point->id(), extrinsics->id(), (uint64_t)it->second, uv, e->informationRowMajor()),
-                  e, {pose, point, extrinsics});
+    return withLoss(record(svin_ba_map_add_reprojection_error(h_, pose->id(), point->id(), extrinsics->id(), (uint64_t)it->second, uv,
+                                                          e->informationRowMajor()),
+                           e, {pose, point, extrinsics}, loss),
+                    lk, la);
   }
   /// Map::addResidualBlock (Map.cpp:341-376) for ANY OTHER error term that implements ErrorInterface (the reference hands any
   /// ::ceres::CostFunction to Ceres): the object is evaluated by the HOST before every evaluation launch of the solve
   /// (svin_ba_map_add_host_residual: EvaluateWithMinimalJacobians at the current / candidate blocks, residual and minimal Jacobians to
-  /// the device).  Pose / extrinsics and speed / bias blocks only, no loss, residual dimension <= 15, at most four blocks; a slow
-  /// path by construction.  Returns NULL when the backend refuses the residual (Map.cpp:349-351).
+  /// the device).  Pose / extrinsics and speed / bias blocks only, residual dimension <= 15, at most four blocks; a slow path by
+  /// construction; the loss (NULL, TrivialLoss, CauchyLoss(a), HuberLoss(a)) is applied on the device.  Returns NULL when the
+  /// backend refuses the residual (Map.cpp:349-351).
   template <class ERROR_T>
   ::ceres::ResidualBlockId addResidualBlock(std::shared_ptr<ERROR_T> e, ::ceres::LossFunction* loss,
                                             std::vector<std::shared_ptr<okvis::ceres::ParameterBlock> > blocks) {
-    need(); noLoss(loss);
+    need();
+    double la = 1.0;
+    const int lk = lossKindOf(loss, &la);
     if (blocks.empty() || blocks.size() > 4 || blocks.size() != e->parameterBlocks()) return nullptr;
     std::unique_ptr<HostTerm> term(new HostTerm);
     uint64_t ids[4] = {0, 0, 0, 0};
@@ -230,7 +238,7 @@ class Map {
     const uint64_t rid = svin_ba_map_add_host_residual(h_, ids, (int)blocks.size(), (int)term->m, &Map::hostTrampoline, term.get());
     if (rid == 0) return nullptr;
     hostTerms_[rid] = std::move(term);
-    return record(rid, e, std::move(blocks));
+    return withLoss(record(rid, e, std::move(blocks), loss), lk, la);
   }
   template <class ERROR_T>
   ::ceres::ResidualBlockId addResidualBlock(std::shared_ptr<ERROR_T> e, ::ceres::LossFunction* loss, std::shared_ptr<okvis::ceres::ParameterBlock> x0) {
@@ -451,7 +459,8 @@ class Map {
         for (int b = 0; b < nb[i] && b < 4; ++b) d.push_back((size_t)dims[4 * i + b]);
         e = std::make_shared<ResidualView>(kind[i], (size_t)m[i], d);
       }
-      out.push_back(ResidualBlockSpec(reinterpret_cast< ::ceres::ResidualBlockId>(rids[i]), nullptr, e));
+      auto bt = built_.find(rids[i]);
+      out.push_back(ResidualBlockSpec(reinterpret_cast< ::ceres::ResidualBlockId>(rids[i]), bt == built_.end() ? nullptr : bt->second.loss, e));
     }
     return out;
   }
@@ -487,21 +496,44 @@ class Map {
     owned_ = true;
   }
   static void noLoss(const ::ceres::LossFunction* loss) {
-    if (loss) throw std::runtime_error("okvis::ceres::Map (svin_ba shim): only reprojection residuals take a loss function (CauchyLoss(1))");
+    if (loss) throw std::runtime_error("okvis::ceres::Map (svin_ba shim): a HomogeneousPointError takes no loss function");
+  }
+  /// the SVIN_LOSS_* kind and scale of a loss object: NULL / TrivialLoss, CauchyLoss(a), HuberLoss(a); throws for any other
+  static int lossKindOf(const ::ceres::LossFunction* loss, double* a) {
+    *a = 1.0;
+    if (!loss || dynamic_cast<const ::ceres::TrivialLoss*>(loss)) return SVIN_LOSS_NONE;
+    if (const ::ceres::CauchyLoss* c = dynamic_cast<const ::ceres::CauchyLoss*>(loss)) { *a = c->a(); return SVIN_LOSS_CAUCHY; }
+    if (const ::ceres::HuberLoss* hb = dynamic_cast<const ::ceres::HuberLoss*>(loss)) { *a = hb->a(); return SVIN_LOSS_HUBER; }
+    throw std::runtime_error("okvis::ceres::Map (svin_ba shim): only TrivialLoss, CauchyLoss(a) and HuberLoss(a) are supported");
+  }
+  /// a residual just added: give it its loss on the device (it is removed again if the backend refuses the loss)
+  ::ceres::ResidualBlockId withLoss(::ceres::ResidualBlockId res, int kind, double a) {
+    if (!res) return res;
+    const uint64_t rid = reinterpret_cast<uint64_t>(res);
+    const int rc = svin_ba_map_set_residual_loss(h_, rid, kind, a);
+    if (rc != 1) {
+      const std::string why = svin_ba_last_error();
+      removeResidualBlock(res);
+      throw std::runtime_error("okvis::ceres::Map (svin_ba shim): svin_ba_map_set_residual_loss failed (" + std::to_string(rc) + ") " + why);
+    }
+    return res;
   }
   /// a residual added through addResidualBlock: the error-term object (kept alive, evaluated by isJacobianCorrect) and its blocks
   struct Built {
     std::function<bool(double const* const*, double*, double**, double**)> eval;
     size_t m;
     std::vector<std::shared_ptr<okvis::ceres::ParameterBlock> > blocks;
+    ::ceres::LossFunction* loss = nullptr;   // the object the caller passed (ResidualBlockSpec::lossFunctionPtr)
   };
   template <class ERROR_T>
-  ::ceres::ResidualBlockId record(uint64_t rid, std::shared_ptr<ERROR_T> e, std::vector<std::shared_ptr<okvis::ceres::ParameterBlock> > blocks) {
+  ::ceres::ResidualBlockId record(uint64_t rid, std::shared_ptr<ERROR_T> e, std::vector<std::shared_ptr<okvis::ceres::ParameterBlock> > blocks,
+                                  ::ceres::LossFunction* loss = nullptr) {
     if (rid == 0) return nullptr;   // refused: unknown block, wrong block type (Map.cpp:349-351 returns NULL too)
     Built b;
     b.eval = [e](double const* const* p, double* r, double** J, double** Jm) { return e->EvaluateWithMinimalJacobians(p, r, J, Jm); };
     b.m = e->residualDim();
     b.blocks = std::move(blocks);
+    b.loss = loss;
     built_[rid] = std::move(b);
     return reinterpret_cast< ::ceres::ResidualBlockId>(rid);
   }

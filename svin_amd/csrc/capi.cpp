@@ -247,6 +247,10 @@ int svin_ba_set_distributed(svin_ba* h, int rank, int world, svin_allreduce_fn f
     svin::lastError() = "set_distributed: at most " + std::to_string(svin::kScalGatherSlots / 2) + " ranks (one node of MI355X)";
     return SVIN_ERR_INVALID_ARG;
   }
+  if (world > 1 && ro(h).hasNonDefaultLoss()) {   // (svin_ba_map_set_residual_loss refuses them in sharded mode, too)
+    svin::lastError() = "set_distributed: the window has residuals with a non-default loss function (not available in sharded mode)";
+    return SVIN_ERR_UNSUPPORTED;
+  }
   win(h).setDistributed(rank, world, fn, user);
   return 1;
 } CATCH_ALL(SVIN_ERR_DEVICE)
@@ -261,7 +265,12 @@ int svin_ba_set_distributed_rccl(svin_ba* h, int rank, int world, const unsigned
     svin::lastError() = "set_distributed_rccl: at most " + std::to_string(svin::kScalGatherSlots / 2) + " ranks (one node of MI355X)";
     return SVIN_ERR_INVALID_ARG;
   }
-  GUARD_BEGIN return win(h).setDistributedRccl(rank, world, id);
+  GUARD_BEGIN
+  if (world > 1 && ro(h).hasNonDefaultLoss()) {
+    svin::lastError() = "set_distributed_rccl: the window has residuals with a non-default loss function (not available in sharded mode)";
+    return SVIN_ERR_UNSUPPORTED;
+  }
+  return win(h).setDistributedRccl(rank, world, id);
   GUARD_END(SVIN_ERR_DEVICE)
 }
 int svin_ba_set_solver_tolerances(svin_ba* h, double f, double g, double p) try {
@@ -709,6 +718,19 @@ uint64_t svin_ba_map_add_reprojection_error(svin_ba* h, uint64_t pose_block, uin
 int svin_ba_map_remove_residual_block(svin_ba* h, uint64_t rid) {
   if (!h) return SVIN_ERR_INVALID_ARG;
   GUARD_BEGIN return win(h).mapRemoveResidualBlock(rid);
+  GUARD_END(SVIN_ERR_DEVICE)
+}
+static int lossCode(int r) {
+  return r == 1 ? 1 : (r == -2 ? SVIN_ERR_NOT_FOUND : (r == -3 ? SVIN_ERR_UNSUPPORTED : SVIN_ERR_INVALID_ARG));
+}
+int svin_ba_map_set_residual_loss(svin_ba* h, uint64_t rid, int kind, double scale) {
+  if (!h) return SVIN_ERR_INVALID_ARG;
+  GUARD_BEGIN return lossCode(win(h).setResidualLoss(rid, kind, scale));
+  GUARD_END(SVIN_ERR_DEVICE)
+}
+int svin_ba_map_get_residual_loss(svin_ba* h, uint64_t rid, int* kind, double* scale) {
+  if (!h) return SVIN_ERR_INVALID_ARG;
+  GUARD_BEGIN return lossCode(ro(h).getResidualLoss(rid, kind, scale));
   GUARD_END(SVIN_ERR_DEVICE)
 }
 int svin_ba_get_lhs(svin_ba* h, uint64_t block_id, double* H, int cap) {

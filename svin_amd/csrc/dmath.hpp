@@ -304,5 +304,23 @@ SVIN_HD void cauchyLoss(double s, double& rho0, double& rho1, double& rho2) {
   rho1 = inv > 2.2250738585072014e-308 ? inv : 2.2250738585072014e-308;
   rho2 = -(inv * inv);
 }
+// a residual's loss (Ceres loss_function.cc: TrivialLoss, CauchyLoss(a), HuberLoss(a); kind 0 / 1 / 2) on s = |r|^2: rho and rho'.
+// Both have rho'' <= 0, so Ceres' Corrector scales the residual and the Jacobian by sqrt(rho') and rho'' is never needed.  With
+// a = 1 the Cauchy branch is cauchyLoss bit for bit (b = c = 1).
+SVIN_HD void residualLoss(int kind, double a, double s, double& rho0, double& rho1) {
+  if (kind == 1) {
+    const double b = a * a, c = 1.0 / b;
+    const double sum = 1.0 + s * c, inv = 1.0 / sum;
+    rho0 = b * log(sum);
+    rho1 = inv > 2.2250738585072014e-308 ? inv : 2.2250738585072014e-308;
+  } else if (kind == 2 && s > a * a) {
+    const double r = sqrt(s), q = a / r;
+    rho0 = 2.0 * a * r - a * a;
+    rho1 = q > 2.2250738585072014e-308 ? q : 2.2250738585072014e-308;
+  } else {
+    rho0 = s;
+    rho1 = 1.0;
+  }
+}
 
 }  // namespace svin

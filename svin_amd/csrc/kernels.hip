@@ -435,10 +435,12 @@ __device__ __forceinline__ void evalReprojBlock(int block, double* smem, double*
                                                 const uint32_t* __restrict__ obsIdx, const int* __restrict__ obsLm,
                                                 double* __restrict__ r, double* __restrict__ Jp, double* __restrict__ Jl,
                                                 double* __restrict__ Je, double* __restrict__ costPartial, size_t stride,
-                                                const LmDefer df = LmDefer(), const double* __restrict__ lmPrior = nullptr) {
+                                                const LmDefer df = LmDefer(), const double* __restrict__ lmPrior = nullptr,
+                                                const double* __restrict__ lossTab = nullptr) {
   double* sPose = smem;                      // nPose*7
   double* sExt = sPose + nPose * 7;          // nExt*7
   CameraModel* sCam = reinterpret_cast<CameraModel*>(sExt + nExt * 7);  // nCam
+  double* sLoss = reinterpret_cast<double*>(sCam + nCam);               // 2 kMaxLosses (lossTab only: kLossTabBytes)
   for (int i = threadIdx.x; i < nPose * 7; i += blockDim.x) sPose[i] = pose[i];
   for (int i = threadIdx.x; i < nExt * 7; i += blockDim.x) sExt[i] = ext[i];
   {
@@ -446,6 +448,8 @@ __device__ __forceinline__ void evalReprojBlock(int block, double* smem, double*
     double* dst = reinterpret_cast<double*>(sCam);
     for (int i = threadIdx.x; i < nCam * (int)(sizeof(CameraModel) / 8); i += blockDim.x) dst[i] = src[i];
   }
+  if (ROBUST && lossTab)
+    for (int i = threadIdx.x; i < 2 * kMaxLosses; i += blockDim.x) sLoss[i] = lossTab[i];
   __syncthreads();
   const int i = block * blockDim.x + threadIdx.x;
   double cost = 0, stepSq = 0, xSq = 0;
@@ -500,9 +504,15 @@ __device__ __forceinline__ void evalReprojBlock(int block, double* smem, double*
     }
     const double s = rr[0] * rr[0] + rr[1] * rr[1];
     if (ROBUST && !isPrior) {
-      // Ceres Corrector for CauchyLoss(1): rho'' < 0 always -> residual and Jacobian scale by sqrt(rho')
+      // Ceres Corrector: rho'' <= 0 for every loss the window takes -> residual and Jacobian scale by sqrt(rho').  Without a loss
+      // table every observation has CauchyLoss(1); with one, the selector in bits 28-31 of the packed index picks its entry
       double rho0, rho1, rho2;
-      cauchyLoss(s, rho0, rho1, rho2);
+      if (lossTab) {
+        const int sel = (int)(idx >> 28);
+        residualLoss((int)sLoss[2 * sel], sLoss[2 * sel + 1], s, rho0, rho1);
+      } else {
+        cauchyLoss(s, rho0, rho1, rho2);
+      }
       cost = 0.5 * rho0;
       const double sc = sqrt(rho1);
       rr[0] *= sc; rr[1] *= sc;
@@ -555,18 +565,18 @@ __global__ __launch_bounds__(128) void k_eval_reproj(int N, int nPose, int nExt,
                                                      double* __restrict__ r, double* __restrict__ Jp,
                                                      double* __restrict__ Jl, double* __restrict__ Je,
                                                      double* __restrict__ costPartial, size_t stride,
-                                                     const double* __restrict__ lmPrior) {
+                                                     const double* __restrict__ lmPrior, const double* __restrict__ lossTab) {
   extern __shared__ double smem[];
   __shared__ double red[4];
   evalReprojBlock<ROBUST, WITH_EXT>(blockIdx.x, smem, red, N, nPose, nExt, nCam, pose, ext, lm, cams, obsUv, obsW, obsIdx,
-                                    obsLm, r, Jp, Jl, Je, costPartial, stride, LmDefer(), lmPrior);
+                                    obsLm, r, Jp, Jl, Je, costPartial, stride, LmDefer(), lmPrior, lossTab);
 }
 
 static int evalGrid(int N) { return (N + 127) / 128; }
 
 void launchEvalReproj(const DeviceProblem& p, bool cand, bool robust, hipStream_t s) {
   if (p.N == 0) return;
-  const size_t smem = (size_t)(p.nPose * 7 + p.nExt * 7) * 8 + (size_t)p.nCam * sizeof(CameraModel);
+  const size_t smem = (size_t)(p.nPose * 7 + p.nExt * 7) * 8 + (size_t)p.nCam * sizeof(CameraModel) + kLossTabBytes;
   const int grid = evalGrid(p.N);
   const double* pose = cand ? p.poseC : p.pose;
   const double* ext = cand ? p.extC : p.ext;
@@ -578,7 +588,7 @@ void launchEvalReproj(const DeviceProblem& p, bool cand, bool robust, hipStream_
   double* cp = p.partial + (size_t)PS_COST_REPROJ * kMaxPartials;
 #define LAUNCH(R, E)                                                                                              \
   hipLaunchKernelGGL((k_eval_reproj<R, E>), dim3(grid), dim3(128), smem, s, p.N, p.nPose, p.nExt, p.nCam, pose, ext, \
-                     lm, p.cams, p.obsUv, p.obsW, p.obsIdx, p.obsLm, r, Jp, Jl, Je, cp, (size_t)p.N, p.lmPrior)
+                     lm, p.cams, p.obsUv, p.obsW, p.obsIdx, p.obsLm, r, Jp, Jl, Je, cp, (size_t)p.N, p.lmPrior, p.lossTab)
   if (robust) { if (p.anyExtVariable) LAUNCH(true, true); else LAUNCH(true, false); }
   else { if (p.anyExtVariable) LAUNCH(false, true); else LAUNCH(false, false); }
 #undef LAUNCH
@@ -596,11 +606,11 @@ void launchEvalReprojBatched(const DeviceProblem& p, int copies, double* rOut, d
   if (p.anyExtVariable)
     hipLaunchKernelGGL((k_eval_reproj<true, true>), dim3(grid), dim3(128), smem, s, NB, p.nPose, p.nExt, p.nCam, p.pose,
                        p.ext, p.lm, p.cams, p.obsUv, p.obsW, p.obsIdx, p.obsLm, rOut, JpOut, JlOut, JeOut,
-                       (double*)nullptr, (size_t)NB, p.lmPrior);
+                       (double*)nullptr, (size_t)NB, p.lmPrior, (const double*)nullptr);
   else
     hipLaunchKernelGGL((k_eval_reproj<true, false>), dim3(grid), dim3(128), smem, s, NB, p.nPose, p.nExt, p.nCam,
                        p.pose, p.ext, p.lm, p.cams, p.obsUv, p.obsW, p.obsIdx, p.obsLm, rOut, JpOut, JlOut, JeOut,
-                       (double*)nullptr, (size_t)NB, p.lmPrior);
+                       (double*)nullptr, (size_t)NB, p.lmPrior, (const double*)nullptr);
 }
 
 // ================================================================ K2: small factors (one workgroup each)
@@ -1419,6 +1429,14 @@ __device__ __forceinline__ int blockOff(const DeviceProblem& p, int kind, int sl
   return p.sbOff[slot];
 }
 
+// a factor's share of the cost, 0.5 rho(|r|^2) of its loss (LOSS_NONE: 0.5 |r|^2), and sqrt(rho') beside its record (r and J stay
+// as evaluated: Map::getLhs reads them; the solve's consumers scale by lin.sc)
+__device__ __forceinline__ void factorLossStore(const DeviceProblem& p, const DevFactor& fac, FactorLin& lin, int f, double sq) {
+  double rho0, rho1;
+  residualLoss(fac.lossKind, fac.lossScale, sq, rho0, rho1);
+  lin.sc = sqrt(rho1);
+  cstore(p.partial + (size_t)PS_COST_FACTORS * kMaxPartials + f, 0.5 * rho0);
+}
 __device__ __forceinline__ void evalFactorBlock(const DeviceProblem& p, int cand, int f, FactorShared& sh) {
   const int t = threadIdx.x;
   const DevFactor& fac = p.factors[f];
@@ -1444,7 +1462,7 @@ __device__ __forceinline__ void evalFactorBlock(const DeviceProblem& p, int cand
     if (t < 64) {
       const double rv = (t < m && t < 16) ? lin.r[t] : 0.0;
       const double c = rowSum16(rv * rv);
-      if (t == 0) cstore(p.partial + (size_t)PS_COST_FACTORS * kMaxPartials + f, 0.5 * c);
+      if (t == 0) factorLossStore(p, fac, lin, f, c);
     }
     return;
   }
@@ -1716,7 +1734,7 @@ __device__ __forceinline__ void evalFactorBlock(const DeviceProblem& p, int cand
   if (t < 64) {
     const double rv = ((t & 15) < m && t < 16) ? sh.rw[t & 15] : 0.0;
     const double c = rowSum16(rv * rv);
-    if (t == 0) cstore(p.partial + (size_t)PS_COST_FACTORS * kMaxPartials + f, 0.5 * c);
+    if (t == 0) factorLossStore(p, fac, lin, f, c);
   }
   if (t >= 192 && t < 196) { lin.off[t - 192] = tblOff; lin.dim[t - 192] = tblDim; }
   if (t == 196) { lin.m = m; lin.ncols = ncols; }
@@ -1829,7 +1847,7 @@ __device__ __forceinline__ void k_eval_all_body(const DeviceProblem& p, int cand
   } else {
     SVIN_ARGS(SA(p.poseC), SA(p.pose), SA(p.extC), SA(p.ext), SA(p.lm), SA(p.lmC), SA(p.cams), SA(p.obsUv), SA(p.obsW), SA(p.obsIdx),
               SA(p.obsLm), SA(p.rCand), SA(p.JpCand), SA(p.JlCand), SA(p.partial), SA(p.scal), SA(p.vL), SA(p.yL), SA(p.lmPtr), SA(p.N),
-              SA(p.nPose), SA(p.nExt), SA(p.nCam));
+              SA(p.nPose), SA(p.nExt), SA(p.nCam), SA(p.lossTab));
   }
   TRACE(16);
   if ((int)blockIdx.x < F) {
@@ -1852,7 +1870,7 @@ __device__ __forceinline__ void k_eval_all_body(const DeviceProblem& p, int cand
                                     cand ? p.extC : p.ext, defer ? p.lm : (cand ? p.lmC : p.lm), p.cams, p.obsUv, p.obsW, p.obsIdx, p.obsLm,
                                     cand ? p.rCand : p.rCur, cand ? p.JpCand : p.JpCur, cand ? p.JlCand : p.JlCur,
                                     cand ? p.JeCand : p.JeCur, p.partial + (size_t)PS_COST_REPROJ * kMaxPartials, (size_t)p.N,
-                                    df, p.lmPrior);
+                                    df, p.lmPrior, p.lossTab);
   }
   TRACE(18);
   if (sumCost) {
@@ -1885,7 +1903,7 @@ template <bool WITH_EXT>
 __device__ __forceinline__ void evalReprojSplitBody(const DeviceProblem& p, int cand, double* smem) {
   SVIN_ARGS(SA(p.poseC), SA(p.pose), SA(p.extC), SA(p.ext), SA(p.lm), SA(p.lmC), SA(p.cams), SA(p.obsUv), SA(p.obsW), SA(p.obsIdx),
             SA(p.obsLm), SA(p.rCand), SA(p.JpCand), SA(p.JlCand), SA(p.partial), SA(p.scal), SA(p.vL), SA(p.yL), SA(p.lmPtr), SA(p.N),
-            SA(p.nPose), SA(p.nExt), SA(p.nCam));
+            SA(p.nPose), SA(p.nExt), SA(p.nCam), SA(p.lossTab));
   const bool defer = cand && p.lmDeferred;
   LmDefer df;
   if (defer) {
@@ -1899,7 +1917,7 @@ __device__ __forceinline__ void evalReprojSplitBody(const DeviceProblem& p, int 
                                   cand ? p.extC : p.ext, defer ? p.lm : (cand ? p.lmC : p.lm), p.cams, p.obsUv, p.obsW, p.obsIdx, p.obsLm,
                                   cand ? p.rCand : p.rCur, cand ? p.JpCand : p.JpCur, cand ? p.JlCand : p.JlCur,
                                   cand ? p.JeCand : p.JeCur, p.partial + (size_t)PS_COST_REPROJ * kMaxPartials, (size_t)p.N,
-                                  df, p.lmPrior);
+                                  df, p.lmPrior, p.lossTab);
 }
 // blocks [0, F): the small factors, block F (hasPrior): the marginalisation prior; the block that finishes last sums the cost
 __device__ __forceinline__ void evalRestSplitBody(const DeviceProblem& p, int cand, int nR, int hasPrior, FactorShared& sh) {
@@ -1946,11 +1964,11 @@ __global__ __launch_bounds__(256) void k_eval_rest_split(DeviceProblem p, int ca
 constexpr int kEvalSplitBlocks = 512;   // more evaluation blocks than this: reprojection blocks in a launch of their own (launchEvalAll)
 // fused evaluation possible: factors and observations present, camera-owning rank, staging area fits
 bool canFuseEvaluation(const DeviceProblem& p) {
-  const size_t stage = (size_t)(p.nPose + p.nExt) * 7 * 8 + (size_t)p.nCam * sizeof(CameraModel) + 64;
+  const size_t stage = (size_t)(p.nPose + p.nExt) * 7 * 8 + (size_t)p.nCam * sizeof(CameraModel) + kLossTabBytes + 64;
   return p.F > 0 && p.N > 0 && stage <= sizeof(FactorShared) && (p.N + 255) / 256 + p.F <= kMaxPartials;
 }
 static size_t evalSplitStageBytes(const DeviceProblem& p) {
-  return (size_t)48 * 8 + (size_t)(p.nPose + p.nExt) * 7 * 8 + (size_t)p.nCam * sizeof(CameraModel) + 64;
+  return (size_t)48 * 8 + (size_t)(p.nPose + p.nExt) * 7 * 8 + (size_t)p.nCam * sizeof(CameraModel) + kLossTabBytes + 64;
 }
 void launchEvalAll(const DeviceProblem& p, bool cand, bool sumCost, hipStream_t s) {
   const int nR = (p.N + 255) / 256, pri = p.priorM > 0 ? 1 : 0;
@@ -2038,6 +2056,7 @@ static int priorAccBlocks(const DeviceProblem& p) { return (p.priorM > 0 && p.ow
 __device__ void factorsAccumulate(const DeviceProblem& p, int f, int* colRow) {
   const FactorLin& lin = p.linCur[f];
   const int m = lin.m, nc = lin.ncols;
+  const double sc2 = lin.sc * lin.sc;
   // column -> reduced row map (colRow: 30 ints of LDS)
   if (threadIdx.x < 30) {
     int c = threadIdx.x, row = -1, base = 0;
@@ -2054,11 +2073,13 @@ __device__ void factorsAccumulate(const DeviceProblem& p, int f, int* colRow) {
     if (ra < 0 || rb < 0) continue;
     double s = 0;
     for (int k = 0; k < m; ++k) s += lin.J[k * nc + a] * lin.J[k * nc + b];
+    s *= sc2;   // the loss corrector (1 without a loss)
     atomicAdd(&p.S[(size_t)ra * p.ldS + rb], s);
     if (a == b) {
       atomicAdd(&p.hC[ra], s);
       double g = 0;
       for (int k = 0; k < m; ++k) g += lin.J[k * nc + a] * lin.r[k];
+      g *= sc2;
       atomicAdd(&p.gRed[ra], g);
       atomicAdd(&p.gFull[ra], g);
     }
@@ -7108,9 +7129,11 @@ __device__ __forceinline__ void k_post_solve_body(const DeviceProblem& p, int nL
         }
         // the four column quarters of a row sit in the four 16-lane rows of the wave
         const double uvA = uv + __shfl_xor(uv, 16, 64), uyA = uy + __shfl_xor(uy, 16, 64);
-        const double uvT = uvA + __shfl_xor(uvA, 32, 64), uyT = uyA + __shfl_xor(uyA, 32, 64);
+        double uvT = uvA + __shfl_xor(uvA, 32, 64), uyT = uyA + __shfl_xor(uyA, 32, 64);
         if (cq == 0 && a < m) {
-          const double r = lin.r[a];
+          const double sc = lin.sc;   // the loss corrector: J v, J y and r scale by sqrt(rho')
+          const double r = sc * lin.r[a];
+          uvT *= sc; uyT *= sc;
           acc[0] += uvT * uvT; acc[1] += uyT * uyT; acc[2] += uvT * uyT; acc[3] += uvT * r; acc[4] += uyT * r;
         }
       }

@@ -24,10 +24,16 @@ constexpr int kMaxCams = 8;
 constexpr int kDensePoseCap = 256;   // k_schur_dense stages the pose -> row map of at most this many poses in LDS
 constexpr int kPriorCam = 15;   // camera field of a packed index that marks a landmark-prior pseudo-observation (HomogeneousPointError)
 
-// packed per-observation index: pose slot (12 bit) | ext slot (12 bit) | camera (4 bit)
-inline __host__ __device__ uint32_t packObs(int pose, int ext, int cam) {
-  return (uint32_t)pose | ((uint32_t)ext << 12) | ((uint32_t)cam << 24);
+// packed per-observation index: pose slot (12 bit) | ext slot (12 bit) | camera (4 bit) | loss selector (4 bit, an entry of the
+// window's loss table DeviceProblem::lossTab; 0 = CauchyLoss(1)).  `cam` may carry the selector in its bits 4-7 (a packed index
+// shifted right by 24, as the resident kernels pass it on)
+inline __host__ __device__ uint32_t packObs(int pose, int ext, int cam, int loss = 0) {
+  return (uint32_t)pose | ((uint32_t)ext << 12) | ((uint32_t)cam << 24) | ((uint32_t)loss << 28);
 }
+// residual loss functions (Ceres' TrivialLoss, CauchyLoss(a), HuberLoss(a)): dmath.hpp residualLoss
+enum LossKind : int { LOSS_NONE = 0, LOSS_CAUCHY = 1, LOSS_HUBER = 2 };
+constexpr int kMaxLosses = 15;   // entries of a window's reprojection loss table (entry 0: CauchyLoss(1))
+constexpr size_t kLossTabBytes = (size_t)2 * kMaxLosses * 8;   // (kind, a) per entry, as doubles: the LDS the evaluation stages
 
 struct ImuParams {
   double a_max, g_max, sigma_g_c, sigma_a_c, sigma_bg, sigma_ba, sigma_gw_c, sigma_aw_c, tau, g;
@@ -53,13 +59,16 @@ enum BlockKind : int { B_POSE = 0, B_EXT = 1, B_SB = 2, B_LM = 3 };
 struct DevFactor {
   int kind, nblk, m, imuIndex;
   int blkKind[4], blkSlot[4];
+  int lossKind, lossPad;   // LossKind of the factor (LOSS_NONE by default) and its scale a
+  double lossScale;
   double meas[9];       // pose prior: T(7); sb prior: 9; sonar: range, heading, mean(3); depth: depth, firstDepth
   double aux[8];        // sonar: T_SSo(7)
   double sqrtInfo[81];  // row-major m x m (upper-triangular L^T)
 };
 struct FactorLin {
   double r[15];
-  double J[15 * 30];  // row-major m x ncols, blocks concatenated in order
+  double J[15 * 30];  // row-major m x ncols, blocks concatenated in order (r and J WITHOUT the loss: Map::getLhs reads them)
+  double sc;          // sqrt(rho') of the factor's loss at r (1 without one): every consumer of the solve scales r and J by it
   int off[4], dim[4], m, ncols;
 };
 
@@ -221,6 +230,7 @@ struct DeviceProblem {
   // they do not read, and launchSolveReduced skips them -- build and solve of an iteration must then see the same mu / initScale,
   // which is what the trust-region loop does anyway.
   int sideLane;
+  const double* lossTab;   // reprojection loss table: (kind, a) per selector of the packed index; nullptr = every selector 0 (CauchyLoss(1))
 };
 
 // ---- batched solve (svin_ba_solve_prepared_batch: B independent windows of equal launch geometry through ONE launch sequence per

@@ -148,6 +148,7 @@ __global__ __launch_bounds__(256) void k_marg_accum_factors(DeviceProblem p, Mar
   for (int f = 0; f < md.F; ++f) {
     const FactorLin& lin = p.linCur[f];
     const int mm = lin.m, nc = lin.ncols;
+    const double sc2 = lin.sc * lin.sc;   // the factor's loss corrector (MarginalizationError.cpp:283-330), 1 without a loss
     __syncthreads();
     if (threadIdx.x < 30) {
       int c = threadIdx.x, row = -1, base = 0;
@@ -164,11 +165,11 @@ __global__ __launch_bounds__(256) void k_marg_accum_factors(DeviceProblem p, Mar
       if (ra < 0 || rb < 0) continue;
       double s = 0;
       for (int k = 0; k < mm; ++k) s += lin.J[k * nc + a] * lin.J[k * nc + b];
-      md.U[(size_t)ra * md.m + rb] += s;             // distinct columns of one factor are distinct rows of U
+      md.U[(size_t)ra * md.m + rb] += s * sc2;       // distinct columns of one factor are distinct rows of U
       if (a == b) {
         double g = 0;
         for (int k = 0; k < mm; ++k) g += lin.J[k * nc + a] * lin.r[k];
-        md.ba[ra] -= g;
+        md.ba[ra] -= g * sc2;
       }
     }
   }
@@ -1532,7 +1533,7 @@ int Window::applyMarginalizationStrategy(size_t numKeyframes, size_t numImuFrame
       hUv.push_back(jo.o.uv[0]); hUv.push_back(jo.o.uv[1]);
       hW.push_back(obsWeight(jo.o.size));
       const int es = sExt.count(jo.extId) ? sExt.at(jo.extId) : 0;
-      hIdx.push_back(packObs(sPose.at(jo.o.poseId), es, jo.o.cam));
+      hIdx.push_back(packObs(sPose.at(jo.o.poseId), es, jo.o.cam, jo.o.loss));
       hObsLm.push_back(sLm.at(jo.lmId));
       hLmPtr[sLm.at(jo.lmId) + 1]++;
     }
@@ -1553,6 +1554,7 @@ int Window::applyMarginalizationStrategy(size_t numKeyframes, size_t numImuFrame
         else if (sExt.count(id)) { df.blkKind[b] = B_EXT; df.blkSlot[b] = sExt.at(id); }
         else { df.blkKind[b] = B_SB; df.blkSlot[b] = sSb.at(id); }
       }
+      df.lossKind = f.lossKind; df.lossScale = f.lossScale;
       std::memcpy(df.meas, f.meas, sizeof(df.meas));
       std::memcpy(df.aux, f.aux, sizeof(df.aux));
       std::memcpy(df.sqrtInfo, f.sqrtInfo, sizeof(df.sqrtInfo));
@@ -1567,6 +1569,7 @@ int Window::applyMarginalizationStrategy(size_t numKeyframes, size_t numImuFrame
       hFac.push_back(df);
     }
     const int F = (int)hFac.size();
+    const bool lossOn = nLoss_ > 1;   // observations with a loss other than CauchyLoss(1): the job evaluates them through the loss table
     // The job is asynchronous (nothing below waits for the device): every table travels in the one pinned block of
     // flushStaged, which waits for the previous block's DMA itself.
     tm2 = nowSec();
@@ -1612,6 +1615,7 @@ int Window::applyMarginalizationStrategy(size_t numKeyframes, size_t numImuFrame
       stage(bOP, oPose); stage(bOE, oExt); stage(bOS, oSb); stage(bLmPtr, hLmPtr); stage(bObsLm, hObsLm); stage(bIdx, hIdx);
       stage(bFac, hFac); stage(bImu, hImu); stage(bImuT, hImuT); stage(bImuM, hImuM);
       stage(dCams_, cameras_);
+      if (lossOn) stage(dLossTab_, lossTab_);   // (a fixed-size member: appended to, never reallocated or rewritten)
       stage(bIdxList, idxLists);
       if (deviceJob) {
         stage(res_.poseClass, poseClass); stage(res_.poseSlotOfH, jobPoseSlot); stage(res_.extSlotOfH, jobExtSlot);
@@ -1664,7 +1668,7 @@ int Window::applyMarginalizationStrategy(size_t numKeyframes, size_t numImuFrame
     double** dbgScalPtr = runInline ? &dbgScal : nullptr;
     // (explicit captures: the job buffers are reached through `this` -- a by-value capture of the DevBuf aliases above would copy,
     // and later free, the buffers themselves; lmOrder / dense / toMarginalize are only read by the inline inspection path)
-    auto launchJob = [this, tables, pendingPtr, N, Lm, m, F, nk, nm, mm, L3, n2k, oldPriorM, oldPrior, anyExtVar, deviceJob, nPoseJ, nExtJ,
+    auto launchJob = [this, tables, pendingPtr, lossOn, N, Lm, m, F, nk, nm, mm, L3, n2k, oldPriorM, oldPrior, anyExtVar, deviceJob, nPoseJ, nExtJ,
                       nSbJ, nImuJ, nCamJ, keepPre, margEig, dbgScalPtr, s, &lmOrder, &dense, &toMarginalize]() {
       MargBuffers& mb = margBuf_;
       auto &bPose = mb.bPose, &bExt = mb.bExt, &bSb = mb.bSb, &bLm = mb.bLm, &bUv = mb.bUv, &bW = mb.bW, &bLin = mb.bLin,
@@ -1711,6 +1715,7 @@ int Window::applyMarginalizationStrategy(size_t numKeyframes, size_t numImuFrame
     q.poseC = bPose.p; q.extC = bExt.p; q.sbC = bSb.p; q.lmC = bLm.p;
     q.poseOff = bOP.p; q.extOff = bOE.p; q.sbOff = bOS.p;
     q.cams = dCams_.p;
+    q.lossTab = lossOn ? dLossTab_.p : nullptr;
     q.lmPtr = bLmPtr.p; q.obsUv = bUv.p; q.obsW = bW.p; q.obsIdx = bIdx.p; q.obsLm = bObsLm.p;
     q.rCur = bLin.p; q.JpCur = bLin.p + (size_t)2 * N; q.JlCur = bLin.p + (size_t)14 * N; q.JeCur = bLin.p + (size_t)20 * N;
     q.factors = bFac.p; q.linCur = bFacLin.p; q.linCand = bFacLin.p;
@@ -1720,7 +1725,7 @@ int Window::applyMarginalizationStrategy(size_t numKeyframes, size_t numImuFrame
     md.m = m; md.Lm = Lm; md.N = N; md.F = F;
     md.U = bU.p; md.ba = bVec.p; md.W = bW2.p; md.V = bV.p; md.bb = bVec.p + mm;
     double* vb = bVec.p + mm + L3;
-    // M1: evaluate at the linearisation points (Cauchy corrector as in :283-330) and accumulate
+    // M1: evaluate at the linearisation points (each residual's loss corrector as in :283-330) and accumulate
     if (N > 0) {
       launchEvalReproj(q, false, true, s);
       const dim3 camGrid(q.nPose + q.nExt, anyExtVar ? 1 + q.nCam : 1);

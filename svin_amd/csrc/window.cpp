@@ -181,6 +181,7 @@ void Window::setDistributed(int rank, int world, AllReduceFn fn, void* user) {
 }
 
 Window::Window(int device) : device_(device) {
+  lossTab_[0] = (double)LOSS_CAUCHY; lossTab_[1] = 1.0;   // entry 0: the CauchyLoss(1) every reprojection residual starts with
   int count = 0;
   if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
     throw std::runtime_error("svin_ba: no HIP device available (this backend has no CPU fallback)");
@@ -883,7 +884,7 @@ uint64_t Window::mapAddDepthError(uint64_t poseBlock, double depth, double infor
 // read back, the callback computes the residual and the Jacobians in MINIMAL coordinates (6 columns per pose / extrinsics block,
 // 9 per speed / bias block -- what ErrorInterface::EvaluateWithMinimalJacobians returns), and the record the device kernels
 // consume (FactorLin) is written for it.  A slow path by construction -- one stream synchronisation per evaluation -- for graphs
-// built through okvis::ceres::Map by third parties; no loss function, no landmark blocks (they are eliminated on the device
+// built through okvis::ceres::Map by third parties; its loss function is applied on the device (setResidualLoss), no landmark blocks (they are eliminated on the device
 // from reprojection residuals alone), residual dimension <= 15, at most 4 blocks / 30 minimal columns.
 uint64_t Window::mapAddHostResidual(const uint64_t* blockIds, int nBlocks, int residualDim, int (*fn)(void*, const double* const*, double*, double**),
                                     void* user) {
@@ -920,6 +921,7 @@ void Window::evaluateHostFactors(bool cand, hipStream_t s) {
     FactorLin L;
     std::memset(&L, 0, sizeof(L));
     L.m = f.m;
+    L.sc = 1.0;   // (the evaluation launch applies the factor's loss: factorLossStore)
     for (int b = 0; b < f.nblk; ++b) {
       const Block& blk = blocks_.at(f.blocks[b]);
       if (blk.kind == B_POSE) { const int sl = poseSlot_.at(blk.id); params[b] = &hp[(size_t)7 * sl]; L.off[b] = hPoseOffKeep_[(size_t)sl]; L.dim[b] = 6; }
@@ -1166,6 +1168,76 @@ int Window::residualKind(uint64_t resId) const {
   auto it = factors_.find(resId);
   return it == factors_.end() ? -1 : it->second.kind;
 }
+int Window::setResidualLoss(uint64_t resId, int kind, double scale) {
+  const int rk = residualKind(resId);
+  if (rk < 0) return -2;
+  if ((kind != LOSS_NONE && kind != LOSS_CAUCHY && kind != LOSS_HUBER) || !std::isfinite(scale) || !(scale > 0.0)) return -5;
+  if (rk == 101 || rk == 102) return -3;   // the prior has no loss; a HomogeneousPointError's rows are split over two pseudo-observations
+  if (kind == LOSS_NONE) scale = 1.0;
+  const bool isDefault = rk == 100 ? (kind == LOSS_CAUCHY && scale == 1.0) : kind == LOSS_NONE;
+  if ((world_ > 1 || rcclComm_) && !isDefault) return -3;
+  quiesce();
+  if (rk != 100) {
+    Factor& f = factors_.at(resId);
+    f.lossKind = kind; f.lossScale = scale;
+    return 1;
+  }
+  uint64_t node = 0;
+  obsRes2Lm_.find(resId, &node);
+  Landmark& lm = *reinterpret_cast<Landmark*>((uintptr_t)node);
+  Observation* ob = nullptr;
+  for (Observation& o : lm.obs)
+    if (o.resId == resId) ob = &o;
+  if (!ob) return -2;
+  int sel = -1;
+  for (int e = 0; e < nLoss_ && sel < 0; ++e)
+    if (lossTab_[2 * e] == (double)kind && lossTab_[2 * e + 1] == scale) sel = e;
+  if (sel < 0) {
+    if (nLoss_ == kMaxLosses) return -3;
+    sel = nLoss_++;
+    lossTab_[2 * sel] = (double)kind; lossTab_[2 * sel + 1] = scale;
+  }
+  if (ob->loss == sel) return 1;
+  ob->loss = (uint8_t)sel;
+  // the device-resident observation table carries the selector in its packed handle: patch the record if it has not left the
+  // add log yet, else rebuild the table at the next pack()
+  if (residentValid_) {
+    if (ob->pendEpoch == epoch_ && ob->pendIdx < addLog_.size() && addLog_[ob->pendIdx].seq == (uint32_t)resId)
+      addLog_[ob->pendIdx].hnd = packObs(ob->poseH, ob->extH, ob->cam, ob->loss);
+    else
+      invalidateResident();
+  }
+  return 1;
+}
+bool Window::hasNonDefaultLoss() const {
+  for (const auto& kv : factors_)
+    if (kv.second.lossKind != LOSS_NONE) return true;
+  if (nLoss_ > 1)
+    for (const auto& kv : landmarks_)
+      for (const Observation& o : kv.second.obs)
+        if (o.loss != 0) return true;
+  return false;
+}
+int Window::getResidualLoss(uint64_t resId, int* kind, double* scale) const {
+  const int rk = residualKind(resId);
+  if (rk < 0) return -2;
+  if (rk == 101 || rk == 102) return -3;
+  int k = LOSS_NONE;
+  double a = 1.0;
+  if (rk == 100) {
+    uint64_t node = 0;
+    obsRes2Lm_.find(resId, &node);
+    const Landmark& lm = *reinterpret_cast<const Landmark*>((uintptr_t)node);
+    for (const Observation& o : lm.obs)
+      if (o.resId == resId) { k = (int)lossTab_[2 * o.loss]; a = lossTab_[2 * o.loss + 1]; }
+  } else {
+    const Factor& f = factors_.at(resId);
+    k = f.lossKind; a = f.lossScale;
+  }
+  if (kind) *kind = k;
+  if (scale) *scale = a;
+  return 1;
+}
 int Window::residualInfo(int n, const uint64_t* resIds, int32_t* kind, int32_t* m, int32_t* nBlocks, int32_t* dims4) const {
   int known = 0;
   for (int i = 0; i < n; ++i) {
@@ -1411,7 +1483,7 @@ void Window::flushResident(hipStream_t s, bool wantOrder, std::vector<StagedCopy
       for (Observation& o : lm->obs) {
         o.pendEpoch = 0;
         WinAdd ad;
-        ad.lmH = lm->handle; ad.seq = (uint32_t)o.resId; ad.hnd = packObs(o.poseH, o.extH, o.cam); ad.pad = 0;
+        ad.lmH = lm->handle; ad.seq = (uint32_t)o.resId; ad.hnd = packObs(o.poseH, o.extH, o.cam, o.loss); ad.pad = 0;
         ad.u = o.uv[0]; ad.v = o.uv[1]; ad.w = obsWeight(o.size);
         addLog_.push_back(ad);
       }
@@ -1680,7 +1752,7 @@ void Window::pack(bool solveFollows) {
         hUv[2 * o] = ob.uv[0]; hUv[2 * o + 1] = ob.uv[1];
         // information = I * 64/size^2 ; sqrt information = its (scalar) Cholesky factor
         hW[o] = lm.fixed ? -obsWeight(ob.size) : obsWeight(ob.size);
-        hIdx[o] = packObs(poseCache.at(ob.poseId), extCache.at(extIdOf(ob)), ob.cam);
+        hIdx[o] = packObs(poseCache.at(ob.poseId), extCache.at(extIdOf(ob)), ob.cam, ob.loss);
         hObsLm[o] = (int)slot;
         ++o;
       }
@@ -1721,6 +1793,7 @@ void Window::pack(bool solveFollows) {
     DevFactor df;
     std::memset(&df, 0, sizeof(df));
     df.kind = f.kind; df.nblk = f.nblk; df.m = f.m; df.imuIndex = -1;
+    df.lossKind = f.lossKind; df.lossScale = f.lossScale;
     for (int b = 0; b < f.nblk; ++b) blkKindSlot(f.blocks[b], df.blkKind[b], df.blkSlot[b]);
     std::memcpy(df.meas, f.meas, sizeof(df.meas));
     std::memcpy(df.aux, f.aux, sizeof(df.aux));
@@ -1744,7 +1817,7 @@ void Window::pack(bool solveFollows) {
   if (phantom) {
     DevFactor df;
     std::memset(&df, 0, sizeof(df));
-    df.kind = F_POSE_PRIOR; df.nblk = 1; df.m = 6; df.imuIndex = -1;
+    df.kind = F_POSE_PRIOR; df.nblk = 1; df.m = 6; df.imuIndex = -1; df.lossScale = 1.0;
     df.blkKind[0] = B_POSE; df.blkSlot[0] = phantomSlot;
     df.meas[6] = 1.0;
     for (int k = 0; k < 6; ++k) df.sqrtInfo[k * 6 + k] = 1.0;
@@ -1813,6 +1886,7 @@ void Window::pack(bool solveFollows) {
   upload(dPoseOff_, hPoseOff, s); upload(dExtOff_, hExtOff, s); upload(dSbOff_, hSbOff, s);
   if (!hLocked.empty()) upload(dLockedRows_, hLocked, s);
   upload(dCams_, cameras_, s);
+  if (nLoss_ > 1) upload(dLossTab_, lossTab_, s);
   ResidentArgs ra;
   std::memset(&ra, 0, sizeof(ra));
   // this frame's slot of every pose / extrinsics block handle (the resident observation records name blocks by handle)
@@ -2178,6 +2252,7 @@ void Window::pack(bool solveFollows) {
   p.poseC = dPoseC_.p; p.extC = dExtC_.p; p.sbC = dSbC_.p; p.lmC = dLmC_.p;
   p.poseOff = dPoseOff_.p; p.extOff = dExtOff_.p; p.sbOff = dSbOff_.p;
   p.cams = dCams_.p;
+  p.lossTab = nLoss_ > 1 ? dLossTab_.p : nullptr;
   p.schurDense = schurDense ? 1 : 0;
   p.schurPanels = schurPanels ? 1 : 0; p.nPanelBlocks = nPanelBlocks; p.nPanelPairs = nPanelPairs;
   p.schurBlocks = schurBlocks ? 1 : 0; p.nSlots = (int)hSlotBlk.size();

@@ -65,6 +65,7 @@ struct Observation {
   uint32_t pendIdx = 0, pendEpoch = 0;   // position in the add log while the record has not reached the device (resident.hpp)
   uint16_t poseH = 0, extH = 0;           // Block::handle of the pose and the extrinsics block (the extrinsics id: Window::extIdOf)
   uint8_t cam = 0;
+  uint8_t loss = 0;                       // entry of the window's reprojection loss table (0: CauchyLoss(1)); packObs bits 28-31
 };
 static_assert(sizeof(Observation) == 64, "Observation is meant to fill one cache line");
 // square-root information of a reprojection residual: Estimator::addObservation passes 64 / size^2 * I (implementation/
@@ -107,6 +108,8 @@ struct Factor {
   // F_HOST: the caller's cost function (svin_ba.h svin_cost_function) and its context
   int (*hostFn)(void*, const double* const*, double*, double**) = nullptr;
   void* hostUser = nullptr;
+  int lossKind = LOSS_NONE;     // Map::addResidualBlock's loss function (DevFactor::lossKind / lossScale)
+  double lossScale = 1.0;
 };
 
 struct StateInfo { uint64_t id = 0; bool exists = false; };
@@ -279,6 +282,11 @@ class Window {
   int residualsOf(uint64_t blockId, std::vector<uint64_t>& out) const;    // Map::residuals        Map.cpp:576-587
   int parametersOf(uint64_t resId, std::vector<uint64_t>& out) const;     // Map::parameters       Map.cpp:602-620
   int residualKind(uint64_t resId) const;
+  // the loss function of a residual (LossKind, scale a > 0): reprojection residuals and small factors of every kind (host residuals
+  // included).  1, or -2 unknown residual, -3 unsupported (prior, landmark prior, full loss table, sharded mode), -5 invalid argument
+  int setResidualLoss(uint64_t resId, int kind, double scale);
+  int getResidualLoss(uint64_t resId, int* kind, double* scale) const;
+  bool hasNonDefaultLoss() const;   // a reprojection residual off CauchyLoss(1) or a factor with a loss (sharded mode refuses both)
   // kind, residual dimension and the ambient dimensions of the blocks of a list of residuals in one call (what the shim's
   // Map::residuals / errorInterfacePtr need per residual: sizes and type, ErrorInterface::residualDim / parameterBlockDim)
   int residualInfo(int n, const uint64_t* resIds, int32_t* kind, int32_t* m, int32_t* nBlocks, int32_t* dims4) const;   // -1 unknown, 100 reprojection, 101 marginalisation prior, 102 landmark prior, else FactorKind
@@ -524,6 +532,12 @@ class Window {
   DevBuf<uint32_t> dBlkPairs_;
   DevBuf<double> dSlotRec_, dBlkPartial_;
   DevBuf<CameraModel> dCams_;
+  // reprojection loss table: (kind, a) per entry, nLoss_ entries in use (entry 0: CauchyLoss(1)).  Fixed size and only appended to,
+  // so that an asynchronous job staging it never sees it move or change under an entry it uses.  nLoss_ == 1: DeviceProblem::lossTab
+  // stays null and the evaluation takes its CauchyLoss(1) path
+  std::vector<double> lossTab_ = std::vector<double>(2 * kMaxLosses, 0.0);
+  int nLoss_ = 1;
+  DevBuf<double> dLossTab_;
   DevBuf<double> dObsUv_, dObsW_;
   DevBuf<uint32_t> dObsIdx_;
   DevBuf<double> dLin_[2];  // r(2N) Jp(12N) Jl(6N) Je(12N) each

@@ -77,7 +77,11 @@ EXPORTS = [
     "svin_host_manifold_minus_jacobian", "svin_ba_get_parameter_block", "svin_ba_parameter_block_ids",
     "svin_ba_get_all_landmark_observations", "svin_ba_bench_allreduce", "svin_ba_get_marg_pre", "svin_ba_get_marg_pre_blocks",
     "svin_ba_get_lhs", "svin_ba_get_lhs_blocks", "svin_ba_get_lhs_pass_count",
+    "svin_ba_map_set_residual_loss", "svin_ba_map_get_residual_loss",
 ]
+
+# residual loss functions (svin_ba_map_set_residual_loss): ceres::TrivialLoss, CauchyLoss(a), HuberLoss(a)
+SVIN_LOSS_NONE, SVIN_LOSS_CAUCHY, SVIN_LOSS_HUBER = 0, 1, 2
 
 ID_PROVIDER_FN = C.CFUNCTYPE(C.c_uint64, C.c_void_p)
 
@@ -173,6 +177,8 @@ def load_library():
     sig("svin_ba_get_lhs", i32, vp, u64, pd, i32)
     sig("svin_ba_get_lhs_blocks", C.c_int64, vp, i32, pu64, pi32, pd, C.c_int64)
     sig("svin_ba_get_lhs_pass_count", C.c_int64, vp)
+    sig("svin_ba_map_set_residual_loss", i32, vp, u64, i32, C.c_double)
+    sig("svin_ba_map_get_residual_loss", i32, vp, u64, C.POINTER(C.c_int32), pd)
     sig("svin_ba_bench_jacobian_eval", i32, vp, i32, i32, pd, pd)
     sig("svin_ba_bench_jacobian_eval_b2b", i32, vp, i32, i32, pd, pd, pd)
     sig("svin_ba_set_pack_mode", i32, vp, i32)
@@ -973,6 +979,17 @@ class Estimator:
 
     def map_remove_residual_block(self, rid):
         return self._check(self.L.svin_ba_map_remove_residual_block(self.h, rid), "map_remove_residual_block") == 1
+
+    def map_set_residual_loss(self, rid, kind, scale=1.0):
+        """svin_ba_map_set_residual_loss: SVIN_LOSS_NONE / _CAUCHY / _HUBER with scale a on a reprojection residual or a small
+        factor.  Raises on an error code (unknown residual, bad kind or scale, prior / HomogeneousPointError, full loss table)."""
+        return self._check(self.L.svin_ba_map_set_residual_loss(self.h, rid, int(kind), float(scale)), "map_set_residual_loss") == 1
+
+    def map_get_residual_loss(self, rid):
+        """(kind, scale) of a residual's loss"""
+        k, a = C.c_int32(), np.zeros(1)
+        self._check(self.L.svin_ba_map_get_residual_loss(self.h, rid, C.byref(k), _d(a)), "map_get_residual_loss")
+        return int(k.value), float(a[0])
 
     def residual_info(self, rids):
         """[(kind, residual dimension, [block dimensions])] for a list of residual ids (one call)"""
