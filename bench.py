@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""Headline benchmark: Gauss-Newton iterations/s of the sliding-window BA backend + Jacobian-eval roofline.
+"""Headline benchmark: Gauss-Newton iterations/s of the sliding-window BA backend (+ Jacobian-eval roofline with --full).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
 
 Workload (BASELINE.json configs[1]): synthetic stereo+IMU window, 10 keyframes / 2 000 landmarks /
 20 000 reprojection residuals / 9 IMU factors, seed 20250629, FP64.  One *step* = one
@@ -11,12 +11,16 @@ Gauss-Newton iterations completed / wall time of the K solves (device-synchronis
 
 N > 1: `--gpus N` launches N ranks itself (torch.distributed.run, one process per GPU) unless it already runs under
 such a launcher, in which case WORLD_SIZE must equal N.  The headline stays config #2 with one replica window per rank
-(the window is far below the size where sharding pays, SURVEY.md 8(e): weak scaling, no data-path collective); the
-line additionally carries `sharded_config4`: ONE 64-keyframe / 50 000-landmark window whose landmarks are split over
-the ranks, the reduced camera system all-reduced by RCCL on the solver's stream every iteration.
+(the window is far below the size where sharding pays, SURVEY.md 8(e): weak scaling, no data-path collective); with
+--full the line additionally carries `sharded_config4`: ONE 64-keyframe / 50 000-landmark window whose landmarks are
+split over the ranks, the reduced camera system all-reduced by RCCL on the solver's stream every iteration.
 
-Sub-records in the same JSON line (rank 0, measured after the headline region): `config3` (sonar + depth + per-frame
-extrinsics), `config4_single_gpu`, `config5` (pose graph), `cpu_baseline` at 1 / 2 / all host threads.
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line: the headline and what the
+timed steps themselves tell (`config`).  `--full` adds everything else, measured after the headline region on rank 0:
+the K1 roofline, `kernel_ms` and `solver` of the headline window, the sub-records `config3` (sonar + depth + per-frame
+extrinsics), `config4_single_gpu`, `sliding_window` / `sliding_window_rig_v2`, `concurrent`, `batched`, `config5` /
+`config5_6dof` (pose graph), `cpu_baseline` at 1 / 2 / all host threads, and `summary`; with `--workload posegraph`
+the `cpu_baseline` of the graph.  `--no-extras` and `--no-cpu-baseline` drop parts of that again.
 
 `--dump-outputs DIR`: after the timed steps, rank 0 writes what the last timed step handed its caller as DIR/<name>.npy
 (float64): the window's poses, speed / bias states, landmarks and summary -- or, with `--workload posegraph`, the optimised
@@ -233,7 +237,8 @@ def main_posegraph(args):
     path does not shard: N > 1 runs replicas."""
     import torch
     rank, world, local_rank, dist = init_distributed(args)
-    out = posegraph_record(args, rank, world, local_rank, dist, args.steps, args.warmup, cpu=not args.no_cpu_baseline and world == 1,
+    out = posegraph_record(args, rank, world, local_rank, dist, args.steps, args.warmup,
+                           cpu=args.full and not args.no_cpu_baseline and world == 1,
                            dump_dir=args.dump_outputs)
     if rank == 0:
         emit(out)
@@ -794,16 +799,19 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--copies", type=int, default=256, help="window replicas for the HBM-resident Jacobian-eval roofline")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the config3 / config4 / config5 / sharded sub-records")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the roofline and kernel times, the sub-records (other configurations, "
+                         "sliding windows, concurrent handles, batched solve, pose graph, sharded config #4) and the CPU baseline")
+    ap.add_argument("--copies", type=int, default=256, help="--full: window replicas for the HBM-resident Jacobian-eval roofline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the sub-records (roofline and kernel times stay)")
     ap.add_argument("--workload", default="window", choices=["window", "posegraph"],
                     help="window = BASELINE configs[1] (the north-star metric, default); posegraph = configs[4], the "
                          "global pose-graph optimisation (SURVEY 8(f) N1), reported as its own line")
     ap.add_argument("--six-dof", action="store_true", help="posegraph: optimize6DoFPoseGraph instead of the 4-DoF one")
     ap.add_argument("--force-sharded", action="store_true",
-                    help="run the sharded config-#4 sub-record even with one rank (one-rank RCCL communicator: every collective "
-                         "really runs): the only way to exercise that code path on a 1-GPU box")
+                    help="--full: run the sharded config-#4 sub-record even with one rank (one-rank RCCL communicator: every "
+                         "collective really runs): the only way to exercise that code path on a 1-GPU box")
     ap.add_argument("--sharded-transport", default="rccl", choices=["rccl", "stage"],
                     help="collectives of the sharded config-#4 sub-record: rccl (native, on the solver's stream) or stage (gloo over "
                          "host-staged buffers: the ranks may then share one GPU -- how a 1-GPU box runs the N > 1 record's code)")
@@ -818,6 +826,8 @@ def main():
         if args.gpus == 1:
             args.force_sharded = True
         return main_sharded_child(args)
+    if args.force_sharded and not args.full:
+        ap.error("--force-sharded adds the sharded sub-record, which only --full measures")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args))
     protect_stdout()
@@ -872,6 +882,7 @@ def main():
                        "pcie_inclusive": {"value": its[-1] / (med + last["upload_time"] + last["download_time"]), "unit": "GN iterations/s",
                                           "upload_ms": 1e3 * last["upload_time"], "download_ms": 1e3 * last["download_time"]}},
         }
+    if rank == 0 and args.full:
         # roofline of the dominant streaming kernel (K1 reprojection residual + Jacobian evaluation) on an
         # HBM-resident batch of replicas; HIP events on the kernel's own stream
         # `achieved` is taken from 20 launches enqueued BACK TO BACK between one pair of events (the write-back of launch i
@@ -948,7 +959,7 @@ def main():
                          "achieved_tflops": (d ** 3 / 3.0 + 2.0 * d * d) / (so * 1e-3) / 1e12, "peak_tflops": F64_MFMA_PEAK_TFLOPS,
                          "note": "latency-bound pivot chain at d = 150, see DESIGN.md"}
     del est
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         extras = {}
         if (world > 1 or args.force_sharded) and not os.environ.get("SVIN_BENCH_NO_SHARDED") and rank == 0:
             # The sharded window runs in ranks of its OWN (one fresh process per GPU, started from here): a collective that
@@ -1006,10 +1017,11 @@ def main():
                 extras["config5_6dof"] = {"error": repr(ex)}
             out.update(extras)
     if rank == 0:
-        if not args.no_cpu_baseline and world == 1:
-            out["cpu_baseline"] = cpu_baseline(syn.make_window(seed=20250629))
-            out["config"]["speedup_vs_cpu_baseline"] = out["value"] / out["cpu_baseline"]["value"]
-        out["summary"] = summary_of(out)   # LAST key: the headline of every sub-record survives a truncated tail of this line
+        if args.full:
+            if not args.no_cpu_baseline and world == 1:
+                out["cpu_baseline"] = cpu_baseline(syn.make_window(seed=20250629))
+                out["config"]["speedup_vs_cpu_baseline"] = out["value"] / out["cpu_baseline"]["value"]
+            out["summary"] = summary_of(out)   # LAST key: the headline of every sub-record survives a truncated tail of this line
         emit(out)
     if dist is not None:
         dist.barrier()

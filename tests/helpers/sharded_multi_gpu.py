@@ -1,6 +1,6 @@
 """One rank of the landmark-sharded solve on SEVERAL GPUs (tests/test_gpu_multigpu.py): one process per GPU, started by
-torch.distributed.run, native RCCL on the solver's stream (svin_ba_set_distributed_rccl) -- the transport the driver's
-`bench.py --gpus N` uses.  BASELINE configs[3] at full size unless a size is given.
+torch.distributed.run, native RCCL on the solver's stream (svin_ba_set_distributed_rccl) -- the transport of the
+sharded record of `bench.py --gpus N --full`.  BASELINE configs[3] at full size unless a size is given.
 usage (under torch.distributed.run): sharded_multi_gpu.py <out-prefix> [P L n_obs]
 environment: SVIN_TEST_KILL_RANK=r -- rank r leaves (exit code 17) after the communicator is up and before the first collective
 of the solve: the other ranks block in ncclAllReduce until the launcher takes the group down."""

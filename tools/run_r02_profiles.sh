@@ -4,7 +4,7 @@ OUT=$PWD/gpurun_out/r02prof; mkdir -p $OUT
 REPO=$PWD
 cd /tmp && export TMPDIR=/tmp
 # 1. kernel trace of the headline command (the bench line that goes with it is written next to it)
-rocprofv3 --kernel-trace --stats -d $OUT/trace -o b -- python $REPO/bench.py --no-cpu-baseline --no-extras > $OUT/bench_under_rocprof.json 2> $OUT/trace.log
+rocprofv3 --kernel-trace --stats -d $OUT/trace -o b -- python $REPO/bench.py --full --no-cpu-baseline --no-extras > $OUT/bench_under_rocprof.json 2> $OUT/trace.log
 python $REPO/tools/prof_summary.py $OUT/trace/b_results.db > $OUT/bench_kernel_stats.txt 2>&1
 # 2. counter passes (PMC only with --kernel-trace; each pass within the SQ slot budget)
 rocprofv3 --pmc SQ_INSTS_VALU_MFMA_MOPS_F64 SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES --kernel-trace -d $OUT/pmc1 -o b -- python $REPO/tools/solver_kernels.py > $OUT/pmc1.log 2>&1

@@ -5,7 +5,7 @@ OUT=$PWD/gpurun_out/r04prof; mkdir -p $OUT
 REPO=$PWD
 cd /tmp && export TMPDIR=/tmp
 # 1. kernel trace of the headline command (the bench line that goes with it is written next to it)
-rocprofv3 --kernel-trace --stats -d $OUT/trace -o b -- python $REPO/bench.py --no-cpu-baseline --no-extras > $OUT/bench_under_rocprof.json 2> $OUT/trace.log
+rocprofv3 --kernel-trace --stats -d $OUT/trace -o b -- python $REPO/bench.py --full --no-cpu-baseline --no-extras > $OUT/bench_under_rocprof.json 2> $OUT/trace.log
 python $REPO/tools/prof_summary.py $OUT/trace/b_results.db > $OUT/bench_kernel_stats.txt 2>&1
 # 2. K1 (Jacobian evaluation) on the HBM-resident batch: kernel-trace average, then FETCH_SIZE / WRITE_SIZE in separate passes
 rocprofv3 --kernel-trace --stats -d $OUT/k1t -o b -- python $REPO/tools/k1_bench.py > $OUT/k1_trace.log 2>&1

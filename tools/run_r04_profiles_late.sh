@@ -3,7 +3,7 @@
 set -x
 OUT=$PWD/gpurun_out/r04late; mkdir -p $OUT
 REPO=$PWD
-python bench.py > $OUT/bench_v3.json 2> $OUT/bench_v3.err
+python bench.py --full > $OUT/bench_v3.json 2> $OUT/bench_v3.err
 cd /tmp && export TMPDIR=/tmp
 SVIN_WIDE_BENCH=1 rocprofv3 --kernel-trace --stats -d $OUT/c4t -o b -- python $REPO/tools/widetime.py > $OUT/c4_trace.log 2>&1
 python $REPO/tools/prof_summary.py $OUT/c4t/b_results.db > $OUT/config4_bench_kernel_stats.txt 2>&1

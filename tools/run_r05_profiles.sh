@@ -4,10 +4,10 @@ set -x
 OUT=$PWD/gpurun_out/r05prof; mkdir -p $OUT
 REPO=$PWD
 # 0. the bench line itself (all sub-records)
-python bench.py > $OUT/bench_v1.json 2> $OUT/bench_v1.err
+python bench.py --full > $OUT/bench_v1.json 2> $OUT/bench_v1.err
 cd /tmp && export TMPDIR=/tmp
 # 1. kernel trace of the headline command (the bench line that goes with it is written next to it) + the launch timeline with gaps
-rocprofv3 --kernel-trace --stats -d $OUT/trace -o b -- python $REPO/bench.py --no-cpu-baseline --no-extras > $OUT/bench_under_rocprof.json 2> $OUT/trace.log
+rocprofv3 --kernel-trace --stats -d $OUT/trace -o b -- python $REPO/bench.py --full --no-cpu-baseline --no-extras > $OUT/bench_under_rocprof.json 2> $OUT/trace.log
 python $REPO/tools/prof_summary.py $OUT/trace/b_results.db > $OUT/bench_kernel_stats.txt 2>&1
 python $REPO/tools/iter_gaps.py $OUT/trace/b_results.db > $OUT/bench_iteration_gaps.txt 2>&1
 # 2. K1 (Jacobian evaluation) on the HBM-resident batch: kernel-trace average, then FETCH_SIZE / WRITE_SIZE in separate passes
