@@ -44,11 +44,18 @@ void ensureDynamicLds(const void* fn, size_t bytes) {
   std::lock_guard<std::mutex> lock(mtx);
   auto it = granted.find(key);
   if (it != granted.end() && it->second >= bytes) return;
-  // a refused attribute is not cached: the launch that follows fails, its hipGetLastError() check reports it, and the
-  // next caller tries again instead of trusting a size that was never granted
+  // a refused attribute is not cached: it throws, and the next caller tries again instead of trusting a size that was
+  // never granted
   const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
   if (e != hipSuccess) throw std::runtime_error(std::string("hipFuncSetAttribute(MaxDynamicSharedMemorySize, ") + std::to_string(bytes) + "): " + hipGetErrorString(e));
   granted[key] = bytes;
+}
+void launchFailed(const void* kernel, dim3 grid, dim3 block, size_t ldsBytes, hipError_t e) {
+  const char* name = hipKernelNameRefByPtr(kernel, nullptr);
+  throw std::runtime_error(std::string("launch of ") + (name ? name : "?") + " (grid " + std::to_string(grid.x) + "x" +
+                           std::to_string(grid.y) + "x" + std::to_string(grid.z) + ", block " + std::to_string(block.x) + "x" +
+                           std::to_string(block.y) + "x" + std::to_string(block.z) + ", " + std::to_string(ldsBytes) +
+                           " bytes of LDS): " + hipGetErrorString(e));
 }
 
 // (the A/B switches of the reduced solve -- SVIN_NO_LL, SVIN_NO_SB_ELIM, SVIN_NO_LDS_BORDER -- live in the library's one option
@@ -152,7 +159,6 @@ extern "C" void svin_debug_trace(unsigned long long* out, int reset) {
 // side stream of a solver stream (one per device and stream, created on first use, kept for the life of the process) with the
 // events of the fork / join around what runs on it
 struct SideLane { hipStream_t side = nullptr; hipEvent_t fork = nullptr, mid = nullptr, join = nullptr; };
-#define HIP_LAUNCH_OK(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) throw std::runtime_error(std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
 static std::mutex g_sideLaneMutex;
 static std::map<std::pair<int, hipStream_t>, SideLane> g_sideLanes;
 // (called by the owner of `s` before it destroys the stream: the side stream has nothing in flight that `s` has not waited for)
@@ -170,14 +176,14 @@ void releaseSideLane(hipStream_t s) {
 }
 static SideLane& sideLaneOf(hipStream_t s) {
   int dev = 0;
-  HIP_LAUNCH_OK(hipGetDevice(&dev));
+  HIP_OK(hipGetDevice(&dev));
   std::lock_guard<std::mutex> lock(g_sideLaneMutex);
   SideLane& l = g_sideLanes[std::make_pair(dev, s)];
   if (!l.side) {
-    HIP_LAUNCH_OK(hipStreamCreateWithFlags(&l.side, hipStreamNonBlocking));
-    HIP_LAUNCH_OK(hipEventCreateWithFlags(&l.fork, hipEventDisableTiming));
-    HIP_LAUNCH_OK(hipEventCreateWithFlags(&l.mid, hipEventDisableTiming));
-    HIP_LAUNCH_OK(hipEventCreateWithFlags(&l.join, hipEventDisableTiming));
+    HIP_OK(hipStreamCreateWithFlags(&l.side, hipStreamNonBlocking));
+    HIP_OK(hipEventCreateWithFlags(&l.fork, hipEventDisableTiming));
+    HIP_OK(hipEventCreateWithFlags(&l.mid, hipEventDisableTiming));
+    HIP_OK(hipEventCreateWithFlags(&l.join, hipEventDisableTiming));
   }
   return l;
 }
@@ -255,7 +261,7 @@ __global__ __launch_bounds__(256) void k_pack_lower(DeviceProblem p, int unpack)
 size_t packedSystemDoubles(const DeviceProblem& p) { return (size_t)p.d * (p.d + 1) / 2 + (size_t)3 * p.d; }
 void launchPackSystem(const DeviceProblem& p, bool unpack, hipStream_t s) {
   if (p.d <= 0) return;
-  hipLaunchKernelGGL(k_pack_lower, dim3(p.d + 1), dim3(256), 0, s, p, unpack ? 1 : 0);
+  launch(k_pack_lower, dim3(p.d + 1), dim3(256), 0, s, p, unpack ? 1 : 0);
 }
 // Sharded mode: the wall-clock time limit (Estimator::setOptimizationTimeLimit) is the one host decision that is not a
 // function of all-reduced numbers.  Each rank writes its own vote into the free slots of scalar group A right before that
@@ -264,10 +270,10 @@ __global__ __launch_bounds__(64) void k_set_stop_vote(SolverScalars* scal, doubl
   if (threadIdx.x == 0) { scal->spareA0 = vote; scal->spareA1 = 0.0; }
 }
 void launchSetStopVote(SolverScalars* scal, double vote, hipStream_t s) {
-  hipLaunchKernelGGL(k_set_stop_vote, dim3(1), dim3(64), 0, s, scal, vote);
+  launch(k_set_stop_vote, dim3(1), dim3(64), 0, s, scal, vote);
 }
 void launchPublishScalars(const SolverScalars* scal, ScalarMailbox* mailbox, unsigned long long seq, hipStream_t s) {
-  hipLaunchKernelGGL(k_publish_scalars, dim3(1), dim3(64), 0, s, scal, mailbox, seq);
+  launch(k_publish_scalars, dim3(1), dim3(64), 0, s, scal, mailbox, seq);
 }
 
 // Block-wide reduction of K values at once: out[k] valid in threads 0..K-1 (as `mine`), `red` holds 4*K doubles.
@@ -586,12 +592,10 @@ void launchEvalReproj(const DeviceProblem& p, bool cand, bool robust, hipStream_
   double* Jl = cand ? p.JlCand : p.JlCur;
   double* Je = cand ? p.JeCand : p.JeCur;
   double* cp = p.partial + (size_t)PS_COST_REPROJ * kMaxPartials;
-#define LAUNCH(R, E)                                                                                              \
-  hipLaunchKernelGGL((k_eval_reproj<R, E>), dim3(grid), dim3(128), smem, s, p.N, p.nPose, p.nExt, p.nCam, pose, ext, \
-                     lm, p.cams, p.obsUv, p.obsW, p.obsIdx, p.obsLm, r, Jp, Jl, Je, cp, (size_t)p.N, p.lmPrior, p.lossTab)
-  if (robust) { if (p.anyExtVariable) LAUNCH(true, true); else LAUNCH(true, false); }
-  else { if (p.anyExtVariable) LAUNCH(false, true); else LAUNCH(false, false); }
-#undef LAUNCH
+  const auto kernel = robust ? (p.anyExtVariable ? k_eval_reproj<true, true> : k_eval_reproj<true, false>)
+                              : (p.anyExtVariable ? k_eval_reproj<false, true> : k_eval_reproj<false, false>);
+  launch(kernel, dim3(grid), dim3(128), smem, s, p.N, p.nPose, p.nExt, p.nCam, pose, ext, lm, p.cams, p.obsUv, p.obsW, p.obsIdx,
+         p.obsLm, r, Jp, Jl, Je, cp, (size_t)p.N, p.lmPrior, p.lossTab);
 }
 
 // Jacobian-evaluation roofline kernel on `copies` independent replicas of the window (HBM-resident
@@ -604,13 +608,13 @@ void launchEvalReprojBatched(const DeviceProblem& p, int copies, double* rOut, d
   const int NB = p.N * copies;
   const int grid = evalGrid(NB);
   if (p.anyExtVariable)
-    hipLaunchKernelGGL((k_eval_reproj<true, true>), dim3(grid), dim3(128), smem, s, NB, p.nPose, p.nExt, p.nCam, p.pose,
-                       p.ext, p.lm, p.cams, p.obsUv, p.obsW, p.obsIdx, p.obsLm, rOut, JpOut, JlOut, JeOut,
-                       (double*)nullptr, (size_t)NB, p.lmPrior, (const double*)nullptr);
+    launch(k_eval_reproj<true, true>, dim3(grid), dim3(128), smem, s, NB, p.nPose, p.nExt, p.nCam, p.pose,
+           p.ext, p.lm, p.cams, p.obsUv, p.obsW, p.obsIdx, p.obsLm, rOut, JpOut, JlOut, JeOut,
+           (double*)nullptr, (size_t)NB, p.lmPrior, (const double*)nullptr);
   else
-    hipLaunchKernelGGL((k_eval_reproj<true, false>), dim3(grid), dim3(128), smem, s, NB, p.nPose, p.nExt, p.nCam,
-                       p.pose, p.ext, p.lm, p.cams, p.obsUv, p.obsW, p.obsIdx, p.obsLm, rOut, JpOut, JlOut, JeOut,
-                       (double*)nullptr, (size_t)NB, p.lmPrior, (const double*)nullptr);
+    launch(k_eval_reproj<true, false>, dim3(grid), dim3(128), smem, s, NB, p.nPose, p.nExt, p.nCam,
+           p.pose, p.ext, p.lm, p.cams, p.obsUv, p.obsW, p.obsIdx, p.obsLm, rOut, JpOut, JlOut, JeOut,
+           (double*)nullptr, (size_t)NB, p.lmPrior, (const double*)nullptr);
 }
 
 // ================================================================ K2: small factors (one workgroup each)
@@ -1758,13 +1762,11 @@ __global__ __launch_bounds__(256) void k_eval_factors(DeviceProblem p, int cand,
 
 void launchImuPropagation(const DevImu* im, const uint32_t* T, const double* M, double* io, double* jac, double* cov,
                           int* used, hipStream_t s) {
-  hipLaunchKernelGGL(k_imu_propagation, dim3(1), dim3(256), 0, s, im, T, M, io, jac, cov, used);
+  launch(k_imu_propagation, dim3(1), dim3(256), 0, s, im, T, M, io, jac, cov, used);
 }
 
 void launchEvalFactors(const DeviceProblem& p, bool cand, hipStream_t s, bool sumCost) {
-  if (p.F == 0) return;
-  hipLaunchKernelGGL(k_eval_factors, dim3(p.F), dim3(256), 0, s, p, cand ? 1 : 0,
-                     sumCost ? (p.N > 0 ? evalGrid(p.N) : 0) : -1);
+  launch(k_eval_factors, dim3(p.F), dim3(256), 0, s, p, cand ? 1 : 0, sumCost ? (p.N > 0 ? evalGrid(p.N) : 0) : -1);
 }
 // which kernel of evaluateAll sums the cost: 2 = prior evaluation, 1 = factor evaluation, 0 = separate launch
 int costSummedBy(const DeviceProblem& p) {
@@ -1830,7 +1832,7 @@ __global__ __launch_bounds__(256) void k_prior_eval(DeviceProblem p, int cand, i
 void launchEvalPrior(const DeviceProblem& p, bool cand, hipStream_t s, bool sumCost, int reprojBlocks) {
   if (p.priorM == 0 || !p.ownsCamera) return;
   const int nA = reprojBlocks >= 0 ? reprojBlocks : (p.N > 0 ? evalGrid(p.N) : 0);
-  hipLaunchKernelGGL(k_prior_eval, dim3(1), dim3(256), 0, s, p, cand ? 1 : 0, sumCost ? nA : -1);
+  launch(k_prior_eval, dim3(1), dim3(256), 0, s, p, cand ? 1 : 0, sumCost ? nA : -1);
 }
 
 // Fused evaluation for the trust-region loop: blocks [0, F) evaluate the small factors (IMU re-preintegration can
@@ -1980,15 +1982,15 @@ void launchEvalAll(const DeviceProblem& p, bool cand, bool sumCost, hipStream_t 
     //  reprojection blocks instead of behind them -- the side chain then ends before the main one needs it, but the reprojection
     //  launch takes 41 us instead of 27 next to it: 0.65 again.  A side stream of the highest priority changes nothing either: the
     //  one workgroup of k_sb_factor / the few of k_sb_forward run 4-5 x slower next to k_schur_rows whatever the queue says.)
-    if (p.anyExtVariable) hipLaunchKernelGGL(k_eval_reproj_split<true>, dim3(nR), dim3(256), stage, s, p, cand ? 1 : 0);
-    else hipLaunchKernelGGL(k_eval_reproj_split<false>, dim3(nR), dim3(256), stage, s, p, cand ? 1 : 0);
-    hipLaunchKernelGGL(k_eval_rest_split, dim3(p.F + pri), dim3(256), 0, s, p, cand ? 1 : 0, nR, pri);
+    if (p.anyExtVariable) launch(k_eval_reproj_split<true>, dim3(nR), dim3(256), stage, s, p, cand ? 1 : 0);
+    else launch(k_eval_reproj_split<false>, dim3(nR), dim3(256), stage, s, p, cand ? 1 : 0);
+    launch(k_eval_rest_split, dim3(p.F + pri), dim3(256), 0, s, p, cand ? 1 : 0, nR, pri);
     return;
   }
   if (p.anyExtVariable)
-    hipLaunchKernelGGL(k_eval_all<true>, dim3(p.F + nR + pri), dim3(256), 0, s, p, cand ? 1 : 0, nR, sumCost ? 1 : 0, pri);
+    launch(k_eval_all<true>, dim3(p.F + nR + pri), dim3(256), 0, s, p, cand ? 1 : 0, nR, sumCost ? 1 : 0, pri);
   else
-    hipLaunchKernelGGL(k_eval_all<false>, dim3(p.F + nR + pri), dim3(256), 0, s, p, cand ? 1 : 0, nR, sumCost ? 1 : 0, pri);
+    launch(k_eval_all<false>, dim3(p.F + nR + pri), dim3(256), 0, s, p, cand ? 1 : 0, nR, sumCost ? 1 : 0, pri);
 }
 
 // row i of the prior -> (reduced-system row, or -1) with the 3x3 rotation map applied on the fly
@@ -3663,7 +3665,7 @@ void launchBuildNormalEquations(const DeviceProblem& p, double mu, bool initScal
   launchFinalizeNormalEquations(p, mu, initScale, s);
 }
 void launchFinalizeNormalEquations(const DeviceProblem& p, double mu, bool initScale, hipStream_t s) {
-  hipLaunchKernelGGL(k_finalize_diag, dim3((p.d + 255) / 256), dim3(256), 0, s, p, mu, initScale ? 1 : 0);
+  launch(k_finalize_diag, dim3((p.d + 255) / 256), dim3(256), 0, s, p, mu, initScale ? 1 : 0);
 }
 __global__ __launch_bounds__(256) void k_factors_only(DeviceProblem p, int nFacBlocks) {
   __shared__ int colRow[30];
@@ -3687,7 +3689,7 @@ __global__ __launch_bounds__(256) void k_scatter_staged(const unsigned char* blo
 }
 void launchScatterStaged(const void* block, int nSeg, hipStream_t s) {
   if (nSeg <= 0) return;
-  hipLaunchKernelGGL(k_scatter_staged, dim3(32, std::min(nSeg, 64)), dim3(256), 0, s, reinterpret_cast<const unsigned char*>(block), nSeg);
+  launch(k_scatter_staged, dim3(32, std::min(nSeg, 64)), dim3(256), 0, s, reinterpret_cast<const unsigned char*>(block), nSeg);
 }
 __global__ __launch_bounds__(256) void k_gather_staged(unsigned char* block, GatherArgs a) {
   const int sIdx = blockIdx.y;
@@ -3699,10 +3701,10 @@ __global__ __launch_bounds__(256) void k_gather_staged(unsigned char* block, Gat
 }
 void launchGatherStaged(void* block, const GatherArgs& a, hipStream_t s) {
   if (a.n <= 0) return;
-  hipLaunchKernelGGL(k_gather_staged, dim3(16, a.n), dim3(256), 0, s, reinterpret_cast<unsigned char*>(block), a);
+  launch(k_gather_staged, dim3(16, a.n), dim3(256), 0, s, reinterpret_cast<unsigned char*>(block), a);
 }
 void launchZeroBuild(const DeviceProblem& p, hipStream_t s) {
-  hipLaunchKernelGGL(k_zero_build, dim3((p.ldS * p.d + 255) / 256), dim3(256), 0, s, p);
+  launch(k_zero_build, dim3((p.ldS * p.d + 255) / 256), dim3(256), 0, s, p);
 }
 // zeroFirst = false: the accumulators are already clear (pack() clears them, and k_post_solve clears them again
 // for the next linearisation of the trust-region loop)
@@ -3740,17 +3742,11 @@ void launchAccumulateNormalEquations(const DeviceProblem& p, double mu, bool ini
     const dim3 grid(p.nSlabs + nFac + nPri);
     DeviceProblem pb = p;
     pb.aBlocks = plan.aBlocks ? 1 : 0;
-#define LAUNCH(MAXT, E, NWV)                                                                                        \
-  do {                                                                                                              \
-    ensureDynamicLds((const void*)k_schur_dense<MAXT, E, NWV>, ldsBytes); \
-    hipLaunchKernelGGL((k_schur_dense<MAXT, E, NWV>), grid, dim3(64 * NWV), ldsBytes, s, pb, mu, initScale ? 1 : 0, p.nSlabs, \
-                       nFac);                                                                                       \
-  } while (0)
-    if (nTr > 12) LAUNCH(17, true, 8);        // <= 16 tile rows: 136 tiles over 8 waves
-    else if (nTr > 8) LAUNCH(10, true, 8);    // <= 12 tile rows: 78 tiles
-    else if (aMfma) LAUNCH(9, true, 4);
-    else LAUNCH(9, false, 4);
-#undef LAUNCH
+    // <= 16 tile rows: 136 tiles over 8 waves; <= 12 tile rows: 78 tiles
+    if (nTr > 12) launch(k_schur_dense<17, true, 8>, grid, dim3(64 * 8), ldsBytes, s, pb, mu, initScale ? 1 : 0, p.nSlabs, nFac);
+    else if (nTr > 8) launch(k_schur_dense<10, true, 8>, grid, dim3(64 * 8), ldsBytes, s, pb, mu, initScale ? 1 : 0, p.nSlabs, nFac);
+    else if (aMfma) launch(k_schur_dense<9, true, 4>, grid, dim3(64 * 4), ldsBytes, s, pb, mu, initScale ? 1 : 0, p.nSlabs, nFac);
+    else launch(k_schur_dense<9, false, 4>, grid, dim3(64 * 4), ldsBytes, s, pb, mu, initScale ? 1 : 0, p.nSlabs, nFac);
   } else if (p.L > 0 && p.N > 0 && dC > 0 && p.schurPanels) {
     // off-diagonal pairs: two G tiles + c; diagonal pairs: one G tile + the per-wave pose blocks + c (smaller)
     const size_t ldsBytes = ((size_t)2 * kPanelRows * kDenseLd + kDenseK) * 8;
@@ -3776,12 +3772,12 @@ void launchAccumulateNormalEquations(const DeviceProblem& p, double mu, bool ini
     const bool early = sbEarlyActive(p);
     if (early) {
       lane = &sideLaneOf(s);
-      HIP_LAUNCH_OK(hipEventRecord(lane->fork, s));
-      HIP_LAUNCH_OK(hipStreamWaitEvent(lane->side, lane->fork, 0));
-      hipLaunchKernelGGL(k_factors_only, dim3(nFac + nPri), dim3(256), 0, lane->side, p, nFac);
-      HIP_LAUNCH_OK(hipEventRecord(lane->mid, lane->side));
+      HIP_OK(hipEventRecord(lane->fork, s));
+      HIP_OK(hipStreamWaitEvent(lane->side, lane->fork, 0));
+      launch(k_factors_only, dim3(nFac + nPri), dim3(256), 0, lane->side, p, nFac);
+      HIP_OK(hipEventRecord(lane->mid, lane->side));
       launchSbEarly(p, lane->side, mu, initScale);
-      HIP_LAUNCH_OK(hipEventRecord(lane->join, lane->side));
+      HIP_OK(hipEventRecord(lane->join, lane->side));
     }
     if (p.schurBlocks) {
       constexpr int NW = kBlkWaves;
@@ -3795,26 +3791,23 @@ void launchAccumulateNormalEquations(const DeviceProblem& p, double mu, bool ini
       while (nCopies > 1 && (size_t)nCopies * (dC / 6) * kBlkPoseLd * 8 > SVIN_SLOT_COPIES_KB * 1024) nCopies >>= 1;
       const size_t ldsLm = (size_t)nCopies * (dC / 6) * kBlkPoseLd * 8;
       const int nSlotBlocks = (p.nSlots + kBlkSlotsPerWorkgroup - 1) / kBlkSlotsPerWorkgroup;
-      hipLaunchKernelGGL(k_panels_landmarks, dim3((p.L + 15) / 16), dim3(256), 0, s, p, mu, initScale ? 1 : 0);
-      ensureDynamicLds((const void*)k_blocks_slots, ldsLm);
-      if (nSlotBlocks > 0) hipLaunchKernelGGL(k_blocks_slots, dim3(nSlotBlocks), dim3(256), ldsLm, s, p, nCopies);
-      ensureDynamicLds((const void*)k_schur_rows<NW>, ldsBlk);
-      if (p.nPanelBlocks > 0) hipLaunchKernelGGL((k_schur_rows<NW>), dim3(p.nPanelBlocks), dim3(64 * NW), ldsBlk, s, p);
-      if (early) HIP_LAUNCH_OK(hipStreamWaitEvent(s, lane->mid, 0));
-      if (nSlotBlocks > 0) hipLaunchKernelGGL(k_blocks_pose_reduce, dim3(dC / 6), dim3(1024), 0, s, p, nSlotBlocks);
+      launch(k_panels_landmarks, dim3((p.L + 15) / 16), dim3(256), 0, s, p, mu, initScale ? 1 : 0);
+      launch(k_blocks_slots, dim3(nSlotBlocks), dim3(256), ldsLm, s, p, nCopies);
+      launch(k_schur_rows<NW>, dim3(p.nPanelBlocks), dim3(64 * NW), ldsBlk, s, p);
+      if (early) HIP_OK(hipStreamWaitEvent(s, lane->mid, 0));
+      if (nSlotBlocks > 0) launch(k_blocks_pose_reduce, dim3(dC / 6), dim3(1024), 0, s, p, nSlotBlocks);
     } else {
-      hipLaunchKernelGGL(k_panels_landmarks, dim3((p.L + 15) / 16), dim3(256), 0, s, p, mu, initScale ? 1 : 0);
-      ensureDynamicLds((const void*)k_schur_panels<2, false, true>, ldsBytes);
-      hipLaunchKernelGGL((k_schur_panels<2, false, true>), dim3(p.nPanelBlocks), dim3(256), ldsBytes, s, p, mu, initScale ? 1 : 0, p.nPanelBlocks, nFac);
+      launch(k_panels_landmarks, dim3((p.L + 15) / 16), dim3(256), 0, s, p, mu, initScale ? 1 : 0);
+      launch(k_schur_panels<2, false, true>, dim3(p.nPanelBlocks), dim3(256), ldsBytes, s, p, mu, initScale ? 1 : 0, p.nPanelBlocks, nFac);
     }
-    if (!early && nFac + nPri > 0) hipLaunchKernelGGL(k_factors_only, dim3(nFac + nPri), dim3(256), 0, s, p, nFac);
-    hipLaunchKernelGGL(k_reduce_panel_slabs, dim3((kPanelSlab + 15) / 16, p.nPanelPairs), dim3(256), 0, s, p);
+    if (!early) launch(k_factors_only, dim3(nFac + nPri), dim3(256), 0, s, p, nFac);
+    launch(k_reduce_panel_slabs, dim3((kPanelSlab + 15) / 16, p.nPanelPairs), dim3(256), 0, s, p);
     // The join comes LAST (the slab sum touches pose rows only, the chain's kernels read speed / bias rows only) but inside this
     // function: once it returns, everything it enqueued is ordered on `s` (a later k_zero_build must not meet a chain still reading S).
     // The chain is what the main stream waits for: k_sb_factor (145 KB of LDS) and k_sb_forward (161 KB per workgroup) need EMPTY CUs
     // and get them only when k_schur_rows (two workgroups of 77 KB per CU, refilled from a queue of ~1 000) runs out -- they end with
     // it however early they are launched, whatever the stream's or the waves' priority (both measured).
-    if (early) HIP_LAUNCH_OK(hipStreamWaitEvent(s, lane->join, 0));
+    if (early) HIP_OK(hipStreamWaitEvent(s, lane->join, 0));
     return;
   } else if (p.L > 0 && p.N > 0 && dC > 0) {
     const size_t accBytes = ((size_t)dC * dC + 3 * dC) * 8;
@@ -3822,29 +3815,17 @@ void launchAccumulateNormalEquations(const DeviceProblem& p, double mu, bool ini
     const bool useLds = accBytes + stageBytes <= 150 * 1024;
     if (useLds) {
       const int grid = p.nSlabs;
-#define LAUNCH(E)                                                                                                   \
-  do {                                                                                                              \
-    ensureDynamicLds((const void*)k_schur<true, E>, accBytes + stageBytes);                                        \
-    hipLaunchKernelGGL((k_schur<true, E>), dim3(grid + nFac + nPri), dim3(256), accBytes + stageBytes, s, p, mu,   \
-                       initScale ? 1 : 0, grid, nFac);                                                              \
-  } while (0)
-      if (p.anyExtVariable) LAUNCH(true); else LAUNCH(false);
-#undef LAUNCH
+      launch(p.anyExtVariable ? k_schur<true, true> : k_schur<true, false>, dim3(grid + nFac + nPri), dim3(256), accBytes + stageBytes,
+             s, p, mu, initScale ? 1 : 0, grid, nFac);
     } else {
       (void)hipMemsetAsync(p.slabs, 0, accBytes, s);
       const int grid = min((p.L + 3) / 4, 2048);
       DeviceProblem q = p;
-#define LAUNCH(E)                                                                                                   \
-  do {                                                                                                              \
-    ensureDynamicLds((const void*)k_schur<false, E>, stageBytes); \
-    hipLaunchKernelGGL((k_schur<false, E>), dim3(grid + nFac + nPri), dim3(256), stageBytes, s, q, mu,             \
-                       initScale ? 1 : 0, grid, nFac);                                                              \
-  } while (0)
-      if (p.anyExtVariable) LAUNCH(true); else LAUNCH(false);
-#undef LAUNCH
+      launch(p.anyExtVariable ? k_schur<false, true> : k_schur<false, false>, dim3(grid + nFac + nPri), dim3(256), stageBytes, s, q,
+             mu, initScale ? 1 : 0, grid, nFac);
     }
-  } else if (nFac + nPri > 0) {
-    hipLaunchKernelGGL(k_factors_only, dim3(nFac + nPri), dim3(256), 0, s, p, nFac);
+  } else {
+    launch(k_factors_only, dim3(nFac + nPri), dim3(256), 0, s, p, nFac);
   }
   if (p.L > 0 && p.N > 0 && dC > 0) {
     const size_t accBytes = ((size_t)dC * dC + 3 * dC) * 8;
@@ -3852,7 +3833,7 @@ void launchAccumulateNormalEquations(const DeviceProblem& p, double mu, bool ini
     DeviceProblem q = p;
     if (!useLds && !p.schurDense) q.nSlabs = 1;
     const int n = dC * dC + 3 * dC;
-    hipLaunchKernelGGL(k_reduce_slabs, dim3((n + 15) / 16), dim3(256), 0, s, q);
+    launch(k_reduce_slabs, dim3((n + 15) / 16), dim3(256), 0, s, q);
   }
 }
 
@@ -6622,26 +6603,22 @@ static void launchSolveDense(const DeviceProblem& p, hipStream_t s, double mu, b
   if (cls == 0 && border > 4) {
     // the border block factorised and V, q, Lc^-1 written to the solver's global scratch by a small launch of its own
     const size_t ldsBytes = cholLdsBytes(kCholLdsMaxTiles);
-    hipLaunchKernelGGL(k_chol_border_prepare, dim3(1), dim3(kBorderPrepThreads), 0, s, p, 16 * kCholLdsMaxTiles, mu, initScale ? 1 : 0,
-                       fuseFinalize ? 1 : 0, border, p.cholL);
-    ensureDynamicLds((const void*)k_chol_solve_lds<2>, ldsBytes);
-    hipLaunchKernelGGL(k_chol_solve_lds<2>, dim3(1), dim3(kCholLdsThreads), ldsBytes, s, p, 16 * kCholLdsMaxTiles, mu, initScale ? 1 : 0,
-                       fuseFinalize ? 1 : 0, border, (const double*)p.cholL);
+    launch(k_chol_border_prepare, dim3(1), dim3(kBorderPrepThreads), 0, s, p, 16 * kCholLdsMaxTiles, mu, initScale ? 1 : 0,
+           fuseFinalize ? 1 : 0, border, p.cholL);
+    launch(k_chol_solve_lds<2>, dim3(1), dim3(kCholLdsThreads), ldsBytes, s, p, 16 * kCholLdsMaxTiles, mu, initScale ? 1 : 0,
+           fuseFinalize ? 1 : 0, border, (const double*)p.cholL);
   } else if (cls == 0 && border > 0) {
     const size_t ldsBytes = cholLdsBytes(kCholLdsMaxTiles);
-    ensureDynamicLds((const void*)k_chol_solve_lds<1>, ldsBytes);
-    hipLaunchKernelGGL(k_chol_solve_lds<1>, dim3(1), dim3(kCholLdsThreads), ldsBytes, s, p, 16 * kCholLdsMaxTiles, mu, initScale ? 1 : 0,
-                       fuseFinalize ? 1 : 0, border, (const double*)nullptr);
+    launch(k_chol_solve_lds<1>, dim3(1), dim3(kCholLdsThreads), ldsBytes, s, p, 16 * kCholLdsMaxTiles, mu, initScale ? 1 : 0,
+           fuseFinalize ? 1 : 0, border, (const double*)nullptr);
   } else if (cls == 0) {
     const size_t ldsBytes = cholLdsBytes(nT);
-    ensureDynamicLds((const void*)k_chol_solve_lds<0>, ldsBytes);
-    hipLaunchKernelGGL(k_chol_solve_lds<0>, dim3(1), dim3(kCholLdsThreads), ldsBytes, s, p, dpad, mu, initScale ? 1 : 0,
-                       fuseFinalize ? 1 : 0, 0, (const double*)nullptr);
+    launch(k_chol_solve_lds<0>, dim3(1), dim3(kCholLdsThreads), ldsBytes, s, p, dpad, mu, initScale ? 1 : 0,
+           fuseFinalize ? 1 : 0, 0, (const double*)nullptr);
   } else if (cls == 1) {
     // one workgroup, left-looking: at most 72 live tiles in LDS, finished tiles written through to p.cholL
     const size_t ldsLL = llLdsDoubles(nT) * 8;
-    ensureDynamicLds((const void*)k_chol_solve_ll, ldsLL);
-    hipLaunchKernelGGL(k_chol_solve_ll, dim3(1), dim3(kLLThreads), ldsLL, s, p, dpad, mu, initScale ? 1 : 0, fuseFinalize ? 1 : 0);
+    launch(k_chol_solve_ll, dim3(1), dim3(kLLThreads), ldsLL, s, p, dpad, mu, initScale ? 1 : 0, fuseFinalize ? 1 : 0);
   } else {
     // multi-workgroup blocked factorisation, 64-wide panels; p.cholL holds (dpad64 + 64) x dpad64 doubles, its tail
     // the 1/L_ii vector.  Behind a chain elimination the matrix is already there (k_sb_load) and only spans the kept rows.
@@ -6652,39 +6629,28 @@ static void launchSolveDense(const DeviceProblem& p, hipStream_t s, double mu, b
     int* ready = reinterpret_cast<int*>(diagF + (size_t)dp * kNB);   // (nb + 3) x nb block flags
     if (sb) {
       const int nTk = (sb->dK + 15) / 16;
-      hipLaunchKernelGGL(k_sb_load, dim3(nTk * (nTk + 1) / 2 + (sb->dK + 15) / 16), dim3(256), 0, s, p, *sb, mu, initScale ? 1 : 0,
-                         fuseFinalize ? 1 : 0, ready, (nb + 3) * nb);
+      launch(k_sb_load, dim3(nTk * (nTk + 1) / 2 + (sb->dK + 15) / 16), dim3(256), 0, s, p, *sb, mu, initScale ? 1 : 0,
+             fuseFinalize ? 1 : 0, ready, (nb + 3) * nb);
     } else {
-      hipLaunchKernelGGL(k_big_load, dim3(256), dim3(256), 0, s, p, dp, mu, initScale ? 1 : 0, fuseFinalize ? 1 : 0, ready,
-                         (nb + 3) * nb);
+      launch(k_big_load, dim3(256), dim3(256), 0, s, p, dp, mu, initScale ? 1 : 0, fuseFinalize ? 1 : 0, ready, (nb + 3) * nb);
     }
     {
       const size_t ldsTasks = ((size_t)3 * kBigBlockLds + kNB + 2) * 8;
-      ensureDynamicLds((const void*)k_big_chol_chain, ldsTasks);
       int nHelperTasks = 0;
       for (int st = 0; st < nb; ++st) nHelperTasks += std::max(nb - st - 1, 0) + ((st + 2 <= nb - 1) ? 2 : 0);
-      hipLaunchKernelGGL(k_big_chol_chain,
-                         dim3(1 + std::max(1, std::min(nHelperTasks, (nHelperTasks > kPersistWideTasks ? kPersistWideGrid : kPersistMaxGrid) - 1))),
-                         dim3(256), ldsTasks, s, p, dp,
-                         dinvG, diagF, ready);
+      launch(k_big_chol_chain,
+             dim3(1 + std::max(1, std::min(nHelperTasks, (nHelperTasks > kPersistWideTasks ? kPersistWideGrid : kPersistMaxGrid) - 1))),
+             dim3(256), ldsTasks, s, p, dp, dinvG, diagF, ready);
     }
     const size_t ldsBack = ((size_t)kBackSpan + 8 * 64 + kNB * (kNB + 1) + kNB) * 8;
     for (int c1 = dp; c1 > 0; c1 -= kBackSpan) {
       const int c0 = std::max(0, c1 - kBackSpan);
       const int nChunks = (dp - c1 + kBackSpan - 1) / kBackSpan;   // <= 63: the spare rows of the rhs block
-      if (nChunks > 0) hipLaunchKernelGGL(k_big_back_gemv, dim3((c1 - c0) / kNB, nChunks), dim3(512), 0, s, p, dp, c0, c1);
-      hipLaunchKernelGGL(k_big_back, dim3(1), dim3(512), ldsBack, s, p, dp, c0, c1, nChunks, (const double*)dinvG,
-                         (const double*)diagF);
+      launch(k_big_back_gemv, dim3((c1 - c0) / kNB, nChunks), dim3(512), 0, s, p, dp, c0, c1);
+      launch(k_big_back, dim3(1), dim3(512), ldsBack, s, p, dp, c0, c1, nChunks, (const double*)dinvG, (const double*)diagF);
     }
   }
 }
-// A refused launch (LDS limit, attribute failure) would leave a stale y_C / v_C behind that the trust-region step consumes silently
-// (ADVICE r5): the error of any launch of the solve is read back here -- hipGetLastError is thread-local and costs no synchronisation.
-static void checkSolverLaunches() {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) throw std::runtime_error(std::string("reduced-system solver launch: ") + hipGetErrorString(e));
-}
-static void launchSolveReducedUnchecked(const DeviceProblem& p, hipStream_t s, double mu, bool initScale, bool fuseFinalize);
 // Reduced pose manifolds (PoseManifold3d / 4d / 2d, PoseManifold.cpp:173-466; Map::resetParameterization, Map.cpp:513-543).  Their
 // Plus() is the 6-DoF one with some components of delta held at zero, so Ceres sees the 6-column local Jacobian with those columns
 // dropped.  Dropping columns of J drops the same rows and columns of J^T J and of every Schur complement built from it, and the
@@ -6701,21 +6667,13 @@ __global__ __launch_bounds__(256) void k_lock_rows(DeviceProblem p) {
   }
   if (threadIdx.x == 0) { p.gRed[i] = 0.0; p.gFull[i] = 0.0; p.hC[i] = 0.0; }
 }
-void launchSolveReduced(const DeviceProblem& p, hipStream_t s, double mu, bool initScale, bool fuseFinalize) {
-  (void)hipGetLastError();   // (a polling hipEventQuery / hipStreamQuery of another library -- RCCL -- leaves hipErrorNotReady behind: not ours)
-  if (p.nLocked > 0) hipLaunchKernelGGL(k_lock_rows, dim3(p.nLocked), dim3(256), 0, s, p);
-  launchSolveReducedUnchecked(p, s, mu, initScale, fuseFinalize);
-  checkSolverLaunches();
-}
 // factorisation and forward substitution of the speed / bias chain (the first two launches of the reduced solve with the chain
 // eliminated); fuseFinalize: the chain's rows get their metric and damping here
 static void launchSbChainFactor(const DeviceProblem& p, const SbElimArgs& sb, hipStream_t s, double mu, bool initScale, bool fuseFinalize) {
   const size_t ldsFactor = ((size_t)sb.n * 162 + (size_t)((sb.n + 1) / 2) * 243) * 8;
-  ensureDynamicLds((const void*)k_sb_factor, ldsFactor);
-  hipLaunchKernelGGL(k_sb_factor, dim3(1), dim3(kSbFactorThreads), ldsFactor, s, p, sb, mu, initScale ? 1 : 0, fuseFinalize ? 1 : 0);
+  launch(k_sb_factor, dim3(1), dim3(kSbFactorThreads), ldsFactor, s, p, sb, mu, initScale ? 1 : 0, fuseFinalize ? 1 : 0);
   const size_t ldsFwd = ((size_t)sb.rowsY * kSbCols + (size_t)sb.n * kSbLdsRec) * 8;
-  ensureDynamicLds((const void*)k_sb_forward, ldsFwd);
-  hipLaunchKernelGGL(k_sb_forward, dim3(sb.ldY / kSbCols), dim3(256), ldsFwd, s, p, sb);
+  launch(k_sb_forward, dim3(sb.ldY / kSbCols), dim3(256), ldsFwd, s, p, sb);
 }
 // ONE predicate for the build (which then launches the chain's kernels) and the solve (which then skips them)
 static bool sbEarlyActive(const DeviceProblem& p) {
@@ -6728,7 +6686,8 @@ static void launchSbEarly(const DeviceProblem& p, hipStream_t side, double mu, b
   SbElimArgs sb;
   if (planSbElimination(p, sb)) launchSbChainFactor(p, sb, side, mu, initScale, /*fuseFinalize=*/true);
 }
-static void launchSolveReducedUnchecked(const DeviceProblem& p, hipStream_t s, double mu, bool initScale, bool fuseFinalize) {
+void launchSolveReduced(const DeviceProblem& p, hipStream_t s, double mu, bool initScale, bool fuseFinalize) {
+  launch(k_lock_rows, dim3(p.nLocked), dim3(256), 0, s, p);
   SbElimArgs sb;
   const int elim = planSbElimination(p, sb);
   if (!elim) { launchSolveDense(p, s, mu, initScale, fuseFinalize, nullptr); return; }
@@ -6739,15 +6698,14 @@ static void launchSolveReducedUnchecked(const DeviceProblem& p, hipStream_t s, d
     launchSolveDense(p, s, mu, initScale, fuseFinalize, &sb);
   } else {
     const int nTk = (sb.dK + 15) / 16;
-    hipLaunchKernelGGL(k_sb_load, dim3(nTk * (nTk + 1) / 2 + (sb.dK + 15) / 16), dim3(256), 0, s, p, sb, mu, initScale ? 1 : 0,
-                       fuseFinalize ? 1 : 0, (int*)nullptr, 0);
+    launch(k_sb_load, dim3(nTk * (nTk + 1) / 2 + (sb.dK + 15) / 16), dim3(256), 0, s, p, sb, mu, initScale ? 1 : 0,
+           fuseFinalize ? 1 : 0, (int*)nullptr, 0);
     DeviceProblem q = p;   // the kept system as a problem of its own: rows 0 .. dK of every vector are the kept rows
     q.d = sb.dK; q.S = sb.Sout; q.ldS = sb.ldOut; q.sPadded = 1; q.gRed = sb.gOut; q.sbChain = 0;
     launchSolveDense(q, s, 0.0, false, false, nullptr);   // (metric and damping are in S' already)
   }
   const size_t ldsBackSb = ((size_t)sb.n * kSbRec + 18 * (size_t)sb.n) * 8;
-  ensureDynamicLds((const void*)k_sb_back, ldsBackSb);
-  hipLaunchKernelGGL(k_sb_back, dim3((9 * sb.n + 15) / 16), dim3(256), ldsBackSb, s, p, sb);
+  launch(k_sb_back, dim3((9 * sb.n + 15) / 16), dim3(256), ldsBackSb, s, p, sb);
 }
 
 // ================================================================ post-solve pass and dogleg step
@@ -7333,12 +7291,12 @@ void launchDoglegPrepare(const DeviceProblem& p, hipStream_t s, double fuseRadiu
   const int nLm = (p.L > 0 && p.N > 0) ? min((p.L + 15) / 16, 1024) : 0;
   const int nFac = p.F > 0 ? min((p.F + 3) / 4, 1024) : 0;
   if (nLm + nFac + 1 > kEvalSplitBlocks && !optOn(kOptNoEvalSplit)) {
-    if (p.anyExtVariable) hipLaunchKernelGGL(k_post_solve_wide<true>, dim3(nLm + nFac + 1), dim3(256), 0, s, p, nLm, nFac, fuseRadius);
-    else hipLaunchKernelGGL(k_post_solve_wide<false>, dim3(nLm + nFac + 1), dim3(256), 0, s, p, nLm, nFac, fuseRadius);
+    if (p.anyExtVariable) launch(k_post_solve_wide<true>, dim3(nLm + nFac + 1), dim3(256), 0, s, p, nLm, nFac, fuseRadius);
+    else launch(k_post_solve_wide<false>, dim3(nLm + nFac + 1), dim3(256), 0, s, p, nLm, nFac, fuseRadius);
     return;
   }
-  if (p.anyExtVariable) hipLaunchKernelGGL(k_post_solve<true>, dim3(nLm + nFac + 1), dim3(256), 0, s, p, nLm, nFac, fuseRadius);
-  else hipLaunchKernelGGL(k_post_solve<false>, dim3(nLm + nFac + 1), dim3(256), 0, s, p, nLm, nFac, fuseRadius);
+  if (p.anyExtVariable) launch(k_post_solve<true>, dim3(nLm + nFac + 1), dim3(256), 0, s, p, nLm, nFac, fuseRadius);
+  else launch(k_post_solve<false>, dim3(nLm + nFac + 1), dim3(256), 0, s, p, nLm, nFac, fuseRadius);
 }
 
 // final single-block reduction of the cost partials into SolverScalars (used when no later evaluation kernel
@@ -7349,12 +7307,12 @@ __global__ __launch_bounds__(256) void k_reduce_cost(DeviceProblem p, int nA, in
 }
 
 void launchCost(const DeviceProblem& p, hipStream_t s) {
-  hipLaunchKernelGGL(k_reduce_cost, dim3(1), dim3(256), 0, s, p, p.N > 0 ? evalGrid(p.N) : 0, p.F);
+  launch(k_reduce_cost, dim3(1), dim3(256), 0, s, p, p.N > 0 ? evalGrid(p.N) : 0, p.F);
 }
 
 void launchDoglegStep(const DeviceProblem& p, double radius, hipStream_t s) {
   const int nB = (p.nPose + p.nExt + p.nSb + p.L + 255) / 256;
-  hipLaunchKernelGGL(k_step_retract, dim3(nB), dim3(256), 0, s, p, radius);
+  launch(k_step_retract, dim3(nB), dim3(256), 0, s, p, radius);
 }
 
 // ================================================================ batched rounds (kernels.hpp: BatchSlot)
@@ -7373,44 +7331,35 @@ bool batchSupported(const DeviceProblem& p) {
 }
 void launchBatchRound(const BatchSlot* dSlots, const DeviceProblem& geom, int n, int stagesUnion, bool cand, hipStream_t s) {
   const DeviceProblem& p = geom;
-  (void)hipGetLastError();
   if (stagesUnion & kBatchFull) {
     const DenseSchurPlan plan = denseSchurPlan(p);
     const int nFac = p.F, nPri = priorAccBlocks(p);
     const dim3 grid(p.nSlabs + nFac + nPri, n);
-#define LAUNCH(MAXT, E, NWV)                                                                                        \
-  do {                                                                                                              \
-    ensureDynamicLds((const void*)k_schur_dense_batch<MAXT, E, NWV>, plan.ldsBytes);                                \
-    hipLaunchKernelGGL((k_schur_dense_batch<MAXT, E, NWV>), grid, dim3(64 * NWV), plan.ldsBytes, s, dSlots, p.nSlabs, nFac); \
-  } while (0)
-    if (plan.nTr > 12) LAUNCH(17, true, 8);
-    else if (plan.nTr > 8) LAUNCH(10, true, 8);
-    else if (plan.aMfma) LAUNCH(9, true, 4);
-    else LAUNCH(9, false, 4);
-#undef LAUNCH
+    if (plan.nTr > 12) launch(k_schur_dense_batch<17, true, 8>, grid, dim3(64 * 8), plan.ldsBytes, s, dSlots, p.nSlabs, nFac);
+    else if (plan.nTr > 8) launch(k_schur_dense_batch<10, true, 8>, grid, dim3(64 * 8), plan.ldsBytes, s, dSlots, p.nSlabs, nFac);
+    else if (plan.aMfma) launch(k_schur_dense_batch<9, true, 4>, grid, dim3(64 * 4), plan.ldsBytes, s, dSlots, p.nSlabs, nFac);
+    else launch(k_schur_dense_batch<9, false, 4>, grid, dim3(64 * 4), plan.ldsBytes, s, dSlots, p.nSlabs, nFac);
     const int nRed = p.dC * p.dC + 3 * p.dC;
-    hipLaunchKernelGGL(k_reduce_slabs_batch, dim3((nRed + 15) / 16, n), dim3(256), 0, s, dSlots);
+    launch(k_reduce_slabs_batch, dim3((nRed + 15) / 16, n), dim3(256), 0, s, dSlots);
     const int dpad = ((p.d + 15) / 16) * 16;
     const size_t ldsChol = cholLdsBytes(dpad / 16);
-    ensureDynamicLds((const void*)k_chol_solve_lds_batch<0>, ldsChol);
-    hipLaunchKernelGGL(k_chol_solve_lds_batch<0>, dim3(1, n), dim3(kCholLdsThreads), ldsChol, s, dSlots, dpad, 1, 0, (const double*)nullptr);
+    launch(k_chol_solve_lds_batch<0>, dim3(1, n), dim3(kCholLdsThreads), ldsChol, s, dSlots, dpad, 1, 0, (const double*)nullptr);
     const int nLm = min((p.L + 15) / 16, 1024);
     const int nFacP = p.F > 0 ? min((p.F + 3) / 4, 1024) : 0;
-    if (p.anyExtVariable) hipLaunchKernelGGL(k_post_solve_batch<true>, dim3(nLm + nFacP + 1, n), dim3(256), 0, s, dSlots, nLm, nFacP);
-    else hipLaunchKernelGGL(k_post_solve_batch<false>, dim3(nLm + nFacP + 1, n), dim3(256), 0, s, dSlots, nLm, nFacP);
+    if (p.anyExtVariable) launch(k_post_solve_batch<true>, dim3(nLm + nFacP + 1, n), dim3(256), 0, s, dSlots, nLm, nFacP);
+    else launch(k_post_solve_batch<false>, dim3(nLm + nFacP + 1, n), dim3(256), 0, s, dSlots, nLm, nFacP);
   }
   if (stagesUnion & kBatchReuse) {
     const int nB = (p.nPose + p.nExt + p.nSb + p.L + 255) / 256;
-    hipLaunchKernelGGL(k_step_retract_batch, dim3(nB, n), dim3(256), 0, s, dSlots);
+    launch(k_step_retract_batch, dim3(nB, n), dim3(256), 0, s, dSlots);
   }
   if (stagesUnion & kBatchEval) {
     const int nR = (p.N + 255) / 256, pri = p.priorM > 0 ? 1 : 0;
     const size_t stage = evalSplitStageBytes(p);
-    if (p.anyExtVariable) hipLaunchKernelGGL(k_eval_reproj_batch<true>, dim3(nR, n), dim3(256), stage, s, dSlots, cand ? 1 : 0);
-    else hipLaunchKernelGGL(k_eval_reproj_batch<false>, dim3(nR, n), dim3(256), stage, s, dSlots, cand ? 1 : 0);
-    hipLaunchKernelGGL(k_eval_rest_batch, dim3(p.F + pri, n), dim3(256), 0, s, dSlots, cand ? 1 : 0, nR, pri);
+    if (p.anyExtVariable) launch(k_eval_reproj_batch<true>, dim3(nR, n), dim3(256), stage, s, dSlots, cand ? 1 : 0);
+    else launch(k_eval_reproj_batch<false>, dim3(nR, n), dim3(256), stage, s, dSlots, cand ? 1 : 0);
+    launch(k_eval_rest_batch, dim3(p.F + pri, n), dim3(256), 0, s, dSlots, cand ? 1 : 0, nR, pri);
   }
-  checkSolverLaunches();
 }
 
 // ================================================================ K9: landmark quality (Estimator.cpp:902-923)
@@ -7468,8 +7417,7 @@ __global__ __launch_bounds__(256) void k_landmark_quality(DeviceProblem p, doubl
 }
 
 void launchLandmarkQuality(const DeviceProblem& p, double* quality, hipStream_t s) {
-  if (p.L == 0) return;
-  hipLaunchKernelGGL(k_landmark_quality, dim3((p.L + 15) / 16), dim3(256), 0, s, p, quality);
+  launch(k_landmark_quality, dim3((p.L + 15) / 16), dim3(256), 0, s, p, quality);
 }
 
 }  // namespace svin

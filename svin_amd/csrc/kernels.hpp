@@ -14,6 +14,10 @@
 //   normal equations   S[d][d], gRed[d], gFull[d], hC[d], per-landmark Vinv[6] bl[3] hL[3] scaleL[3]
 #pragma once
 #include <cstdint>
+#include <stdexcept>
+#include <string>
+#include <tuple>
+#include <utility>
 #include <hip/hip_runtime.h>
 #include "dmath.hpp"
 #include "options.hpp"
@@ -279,6 +283,30 @@ void launchSolveReduced(const DeviceProblem& p, hipStream_t s, double mu = 0.0, 
 // grants a kernel `bytes` of dynamic LDS (hipFuncSetAttribute) once per (device, kernel) and only ever upwards: the attribute
 // belongs to the function for the whole process, so the bookkeeping is process-wide and mutex-protected, not per handle
 void ensureDynamicLds(const void* fn, size_t bytes);
+
+// a HIP call that is not a launch: its error becomes an exception (every C entry point turns it into its error return)
+#define HIP_OK(expr)                                                                                      \
+  do {                                                                                                    \
+    const hipError_t e_ = (expr);                                                                         \
+    if (e_ != hipSuccess) throw std::runtime_error(std::string(#expr) + ": " + hipGetErrorString(e_));    \
+  } while (0)
+
+[[noreturn]] void launchFailed(const void* kernel, dim3 grid, dim3 block, size_t ldsBytes, hipError_t e);
+// The one way the library launches a kernel: the arguments converted to the kernel's parameter types, dynamic LDS granted when
+// the launch asks for any, an empty grid a no-op, and a refused launch an exception.  It reads the status hipLaunchKernel
+// returns, not the sticky hipGetLastError(): that one also holds errors of other calls on this thread (RCCL's polling leaves
+// hipErrorNotReady behind), and whoever reads it clears it for everyone else.
+template <typename... P, typename... A>
+void launch(void (*kernel)(P...), dim3 grid, dim3 block, size_t ldsBytes, hipStream_t s, A&&... args) {
+  if (grid.x == 0 || grid.y == 0 || grid.z == 0) return;
+  if (ldsBytes > 0) ensureDynamicLds((const void*)kernel, ldsBytes);
+  std::tuple<P...> params(std::forward<A>(args)...);
+  const hipError_t e = std::apply([&](P&... a) {
+    void* argv[] = {(void*)&a..., nullptr};
+    return hipLaunchKernel((const void*)kernel, grid, block, argv, ldsBytes, s);
+  }, params);
+  if (e != hipSuccess) launchFailed((const void*)kernel, grid, block, ldsBytes, e);
+}
 // doubles DeviceProblem::cholL must hold for a reduced system of d unknowns: the LDS-resident solver's spill copy, or
 // the blocked solver's (d64 + 64) x d64 matrix + 1/L_ii + factorised diagonal blocks + block-ready flags
 // (withChain: room for the speed / bias chain elimination next to either solver -- the compact kept system, the chain's records,

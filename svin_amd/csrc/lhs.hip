@@ -18,9 +18,6 @@
 //                    before) in list order, then its diagonal block of the prior's H-space matrix Ht = J^T J.
 #include "kernels.hpp"
 
-#include <stdexcept>
-#include <string>
-
 namespace svin {
 
 namespace {
@@ -204,11 +201,9 @@ __global__ __launch_bounds__(kLhsThreads) void k_lhs_blocks(DeviceProblem p, con
 
 void launchLhsAll(const DeviceProblem& p, const LhsItem* items, int nItems, const LhsBlock* blocks, int nBlocks, const int2* facs,
                   double* partial, double* out, size_t lmOut, hipStream_t s) {
-  if (nItems > 0) hipLaunchKernelGGL(k_lhs_cam, dim3(nItems), dim3(kLhsThreads), 0, s, p, items, partial);
-  if (p.L > 0) hipLaunchKernelGGL(k_lhs_landmarks, dim3((p.L + 15) / 16), dim3(256), 0, s, p, out + lmOut);
-  if (nBlocks > 0) hipLaunchKernelGGL(k_lhs_blocks, dim3(nBlocks), dim3(kLhsThreads), 0, s, p, blocks, facs, (const double*)partial, out);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) throw std::runtime_error(std::string("getLhs launch: ") + hipGetErrorString(e));
+  launch(k_lhs_cam, dim3(nItems), dim3(kLhsThreads), 0, s, p, items, partial);
+  launch(k_lhs_landmarks, dim3((p.L + 15) / 16), dim3(256), 0, s, p, out + lmOut);
+  launch(k_lhs_blocks, dim3(nBlocks), dim3(kLhsThreads), 0, s, p, blocks, facs, (const double*)partial, out);
 }
 
 }  // namespace svin

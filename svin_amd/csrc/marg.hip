@@ -22,12 +22,6 @@
 
 namespace svin {
 
-#define HIP_OK(expr)                                                                              \
-  do {                                                                                            \
-    hipError_t _e = (expr);                                                                       \
-    if (_e != hipSuccess) throw std::runtime_error(std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
-
 __device__ __forceinline__ double waveSumM(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -1074,14 +1068,12 @@ int debugSymEig(int n, const double* A, double* lam, double* X, double* deviceMs
   int* dOk = sc.dOk;
   HIP_OK(hipMemcpy(dA, A, sizeof(double) * n2, hipMemcpyHostToDevice));
   const size_t lds = symEigLdsBytes(n);
-  ensureDynamicLds((const void*)k_sym_eig_debug, lds);
   HIP_OK(hipEventCreate(&sc.e0)); HIP_OK(hipEventCreate(&sc.e1));
   const hipEvent_t e0 = sc.e0, e1 = sc.e1;
   float best = 1e30f;
   for (int rep = 0; rep < 3; ++rep) {   // (the first launch pays the code upload)
     HIP_OK(hipEventRecord(e0, 0));
-    hipLaunchKernelGGL(k_sym_eig_debug, dim3(1), dim3(1024), lds, 0, n, dA, dLam, dX, dS, dOk);
-    HIP_OK(hipGetLastError());
+    launch(k_sym_eig_debug, dim3(1), dim3(1024), lds, 0, n, dA, dLam, dX, dS, dOk);
     HIP_OK(hipEventRecord(e1, 0));
     HIP_OK(hipEventSynchronize(e1));
     float ms = 0; HIP_OK(hipEventElapsedTime(&ms, e0, e1));
@@ -1730,16 +1722,16 @@ int Window::applyMarginalizationStrategy(size_t numKeyframes, size_t numImuFrame
       launchEvalReproj(q, false, true, s);
       const dim3 camGrid(q.nPose + q.nExt, anyExtVar ? 1 + q.nCam : 1);
       if (anyExtVar) {
-        hipLaunchKernelGGL(k_marg_accum_lm<true>, dim3((Lm + 63) / 64), dim3(64), 0, s, q, md);
-        hipLaunchKernelGGL(k_marg_accum_cam<true>, camGrid, dim3(64), 0, s, q, md);
+        launch(k_marg_accum_lm<true>, dim3((Lm + 63) / 64), dim3(64), 0, s, q, md);
+        launch(k_marg_accum_cam<true>, camGrid, dim3(64), 0, s, q, md);
       } else {
-        hipLaunchKernelGGL(k_marg_accum_lm<false>, dim3((Lm + 63) / 64), dim3(64), 0, s, q, md);
-        hipLaunchKernelGGL(k_marg_accum_cam<false>, camGrid, dim3(64), 0, s, q, md);
+        launch(k_marg_accum_lm<false>, dim3((Lm + 63) / 64), dim3(64), 0, s, q, md);
+        launch(k_marg_accum_cam<false>, camGrid, dim3(64), 0, s, q, md);
       }
     }
     if (F > 0) {
       launchEvalFactors(q, false, s);
-      hipLaunchKernelGGL(k_marg_accum_factors, dim3(1), dim3(256), 0, s, q, md);
+      launch(k_marg_accum_factors, dim3(1), dim3(256), 0, s, q, md);
     }
     if (keepPre) {   // inspection: the system after M1 (svin_ba_get_marg_pre), before anything is eliminated
       HIP_OK(hipStreamSynchronize(s));
@@ -1766,9 +1758,9 @@ int Window::applyMarginalizationStrategy(size_t numKeyframes, size_t numImuFrame
     }
     // M2 landmark part
     if (Lm > 0 && m > 0) {
-      hipLaunchKernelGGL(k_marg_lm_prepare, dim3((Lm + 127) / 128), dim3(128), 0, s, md, vb);
-      hipLaunchKernelGGL(k_marg_lm_apply, dim3(m), dim3(256), 0, s, md, (const double*)vb);
-      hipLaunchKernelGGL(k_marg_lm_update, dim3(((m + 15) / 16) * ((m + 15) / 16)), dim3(64), 0, s, md);
+      launch(k_marg_lm_prepare, dim3((Lm + 127) / 128), dim3(128), 0, s, md, vb);
+      launch(k_marg_lm_apply, dim3(m), dim3(256), 0, s, md, (const double*)vb);
+      launch(k_marg_lm_update, dim3(((m + 15) / 16) * ((m + 15) / 16)), dim3(64), 0, s, md);
     }
     // M2 dense part
     if (nk > 0) {
@@ -1787,9 +1779,7 @@ int Window::applyMarginalizationStrategy(size_t numKeyframes, size_t numImuFrame
           const size_t ldsTile = margCholLdsBytes(nm);   // the certified Cholesky route of the pseudo-inverse, on tiles
           const bool tileChol = ldsTile <= kJacobiLdsLimit;
           const size_t lds = std::max(std::max(ldsEig, prodLds ? ldsProd : (size_t)0), tileChol ? ldsTile : (size_t)0);
-          if (lds) ensureDynamicLds((const void*)k_marg_dense, lds);
-          hipLaunchKernelGGL(k_marg_dense, dim3(1), dim3(1024), lds, s, da, ldsEig ? 1 : 0, prodLds ? 1 : 0, tileChol ? 1 : 0);
-          HIP_OK(hipGetLastError());   // (a refused launch would leave a garbage prior behind)
+          launch(k_marg_dense, dim3(1), dim3(1024), lds, s, da, ldsEig ? 1 : 0, prodLds ? 1 : 0, tileChol ? 1 : 0);
         }
       } else {
         HIP_OK(hipMemcpyAsync(bHk.p, bU.p, sizeof(double) * (size_t)m * m, hipMemcpyDeviceToDevice, s));
@@ -1826,19 +1816,13 @@ int Window::applyMarginalizationStrategy(size_t numKeyframes, size_t numImuFrame
         const bool chol = !want && nk <= kSymEigMaxN;
         if (chol) {
           const size_t ldsC = margCholLdsBytes(nk);
-          ensureDynamicLds((const void*)k_marg_final_chol, ldsC);
-          hipLaunchKernelGGL(k_marg_final_chol, dim3(1), dim3(1024), ldsC, s, fa);
-          HIP_OK(hipGetLastError());
+          launch(k_marg_final_chol, dim3(1), dim3(1024), ldsC, s, fa);
         }
         if (direct) {
           const size_t ldsDc = symEigLdsBytes(nk);
-          ensureDynamicLds((const void*)k_marg_final_dc, ldsDc);
-          hipLaunchKernelGGL(k_marg_final_dc, dim3(1), dim3(1024), ldsDc, s, fa, chol ? 1 : 0);
-          HIP_OK(hipGetLastError());
+          launch(k_marg_final_dc, dim3(1), dim3(1024), ldsDc, s, fa, chol ? 1 : 0);
         }
-        if (lds) ensureDynamicLds((const void*)k_marg_final, lds);
-        hipLaunchKernelGGL(k_marg_final, dim3(1), dim3(1024), lds, s, fa, mode, (mode == 4 && ldsBoth) ? 1 : 0, direct ? 1 : 0);
-        HIP_OK(hipGetLastError());
+        launch(k_marg_final, dim3(1), dim3(1024), lds, s, fa, mode, (mode == 4 && ldsBoth) ? 1 : 0, direct ? 1 : 0);
       }
     }
     };

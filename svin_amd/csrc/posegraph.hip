@@ -41,12 +41,6 @@
 namespace svin {
 namespace pg {
 
-#define PG_HIP_OK(expr)                                                                             \
-  do {                                                                                              \
-    hipError_t _e = (expr);                                                                         \
-    if (_e != hipSuccess) throw std::runtime_error(std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
-
 constexpr double kPgPi = 3.14159265358979323846;
 
 struct PgPiece {
@@ -815,7 +809,7 @@ struct Buf {
   }
   void upload(const std::vector<T>& h, hipStream_t s) {
     reserve(std::max<size_t>(h.size(), 1));
-    if (!h.empty()) PG_HIP_OK(hipMemcpyAsync(p, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice, s));
+    if (!h.empty()) HIP_OK(hipMemcpyAsync(p, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice, s));
   }
 };
 
@@ -879,9 +873,9 @@ class PoseGraph {
     if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
       throw std::runtime_error("svin_pg: no HIP device available (this backend has no CPU fallback)");
     if (device < 0 || device >= count) throw std::runtime_error("svin_pg: invalid device index");
-    PG_HIP_OK(hipSetDevice(device));
-    PG_HIP_OK(hipStreamCreate(&s_));
-    for (int i = 0; i < kPgMaxTimed; ++i) { PG_HIP_OK(hipEventCreate(&evA_[i])); PG_HIP_OK(hipEventCreate(&evB_[i])); }
+    HIP_OK(hipSetDevice(device));
+    HIP_OK(hipStreamCreate(&s_));
+    for (int i = 0; i < kPgMaxTimed; ++i) { HIP_OK(hipEventCreate(&evA_[i])); HIP_OK(hipEventCreate(&evB_[i])); }
   }
   ~PoseGraph() {
     for (int i = 0; i < kPgMaxTimed; ++i) { if (evA_[i]) (void)hipEventDestroy(evA_[i]); if (evB_[i]) (void)hipEventDestroy(evB_[i]); }
@@ -1309,11 +1303,11 @@ class PoseGraph {
     p.HS = dHS_.p; p.band = dHS_.p + (size_t)nS * nS; p.Y = p.band + bandTot; p.Sp = dSp_.p;
     p.fail = &dSol->cholFail;
     p.ticket = reinterpret_cast<int*>(dSol + 1);
-    PG_HIP_OK(hipMemsetAsync(dSol, 0, sizeof(SolverScalars) + 2 * sizeof(double), s_));
+    HIP_OK(hipMemsetAsync(dSol, 0, sizeof(SolverScalars) + 2 * sizeof(double), s_));
     {
       std::vector<double> one(nS, 1.0);
-      PG_HIP_OK(hipMemcpyAsync(ones, one.data(), sizeof(double) * nS, hipMemcpyHostToDevice, s_));
-      PG_HIP_OK(hipStreamSynchronize(s_));
+      HIP_OK(hipMemcpyAsync(ones, one.data(), sizeof(double) * nS, hipMemcpyHostToDevice, s_));
+      HIP_OK(hipStreamSynchronize(s_));
     }
     // the dense solver of the BA backend sees the separator system through a DeviceProblem view
     DeviceProblem dp;
@@ -1332,69 +1326,57 @@ class PoseGraph {
     }
     const size_t ldsFactor2 = (size_t)L2.maxRows * (BW2 + 2) * 8 + 2 * 1024;
     const size_t ldsBack2 = ((size_t)L2.maxRows * (BW2 + 2) + W2 * D + kPgPieceThreads) * 8;
-    if (nPieces2 > 0) {
-      (void)hipFuncSetAttribute(six_ ? (const void*)k_pg_piece_factor<6, 7> : (const void*)k_pg_piece_factor<4, 3>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsFactor2);
-      (void)hipFuncSetAttribute(six_ ? (const void*)k_pg_piece_back<6, 7> : (const void*)k_pg_piece_back<4, 3>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBack2);
-    }
     const int gE = (ne + 127) / 128, gN = (nn + 127) / 128;
     if (gE > kPgMaxPartials || gN > kPgMaxPartials) throw std::runtime_error("svin_pg: graph too large for the reduction scratch");
     const size_t ldsFactor = (size_t)maxRows * (BW + 2) * 8 + 2 * 512;
     const size_t ldsBack = ((size_t)maxRows * (BW + 2) + w * D + kPgPieceThreads) * 8;
-    if (nPieces > 0) {
-      (void)hipFuncSetAttribute(six_ ? (const void*)k_pg_piece_factor<6, 4> : (const void*)k_pg_piece_factor<4, 2>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsFactor);
-      (void)hipFuncSetAttribute(six_ ? (const void*)k_pg_piece_back<6, 4> : (const void*)k_pg_piece_back<4, 2>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBack);
-    }
     struct HostScal { double sc[PG_NSCAL]; SolverScalars sol; } hs;
     static_assert(sizeof(SolverScalars) % sizeof(double) == 0, "SolverScalars must pack behind the LM scalars");
     double* const sc = hs.sc;
     auto readScal = [&]() {   // the one blocking read-back of an iteration
-      PG_HIP_OK(hipMemcpyAsync(&hs, p.scal, sizeof(double) * PG_NSCAL + sizeof(SolverScalars), hipMemcpyDeviceToHost, s_));
-      PG_HIP_OK(hipStreamSynchronize(s_));
+      HIP_OK(hipMemcpyAsync(&hs, p.scal, sizeof(double) * PG_NSCAL + sizeof(SolverScalars), hipMemcpyDeviceToHost, s_));
+      HIP_OK(hipStreamSynchronize(s_));
     };
     // residuals (+ Jacobians) at the current point or the candidate; finalReduce: the launch also sums the iteration's scalars
     auto evaluate = [&](bool cand, bool withJac, bool finalReduce) {
-      if (six_) hipLaunchKernelGGL(k_pg_eval<true>, dim3(gE), dim3(128), 0, s_, p, cand ? 1 : 0, withJac ? 1 : 0, finalReduce ? gN : 0);
-      else hipLaunchKernelGGL(k_pg_eval<false>, dim3(gE), dim3(128), 0, s_, p, cand ? 1 : 0, withJac ? 1 : 0, finalReduce ? gN : 0);
+      if (six_) launch(k_pg_eval<true>, dim3(gE), dim3(128), 0, s_, p, cand ? 1 : 0, withJac ? 1 : 0, finalReduce ? gN : 0);
+      else launch(k_pg_eval<false>, dim3(gE), dim3(128), 0, s_, p, cand ? 1 : 0, withJac ? 1 : 0, finalReduce ? gN : 0);
     };
     // damped normal equations at the current linearisation -> y (tangent order, scaled space)
     auto solveNormalEquations = [&](double radius, int& nSolves) {
-      PG_HIP_OK(hipMemsetAsync(p.HS, 0, sizeof(double) * ((size_t)nS * nS + (nPieces > 0 ? workTot : 0)), s_));   // H_S | band | Y (| level 2)
-      if (six_) hipLaunchKernelGGL(k_pg_assemble<6>, dim3(gN + gE), dim3(128), 0, s_, p, radius, gN);
-      else hipLaunchKernelGGL(k_pg_assemble<4>, dim3(gN + gE), dim3(128), 0, s_, p, radius, gN);
+      HIP_OK(hipMemsetAsync(p.HS, 0, sizeof(double) * ((size_t)nS * nS + (nPieces > 0 ? workTot : 0)), s_));   // H_S | band | Y (| level 2)
+      if (six_) launch(k_pg_assemble<6>, dim3(gN + gE), dim3(128), 0, s_, p, radius, gN);
+      else launch(k_pg_assemble<4>, dim3(gN + gE), dim3(128), 0, s_, p, radius, gN);
       if (nPieces > 0) {
-        if (six_) hipLaunchKernelGGL((k_pg_piece_factor<6, 4>), dim3(nPieces), dim3(kPgPieceThreads), ldsFactor, s_, p);
-        else hipLaunchKernelGGL((k_pg_piece_factor<4, 2>), dim3(nPieces), dim3(kPgPieceThreads), ldsFactor, s_, p);
-        hipLaunchKernelGGL(k_pg_piece_schur, dim3((unsigned)tileWork.size()), dim3(256), 0, s_, p);
-        hipLaunchKernelGGL(k_pg_sep_gather, dim3((nDest * D * D + 255) / 256 + (nS + 255) / 256), dim3(256), 0, s_, p, nDest,
-                           (nDest * D * D + 255) / 256);
+        if (six_) launch(k_pg_piece_factor<6, 4>, dim3(nPieces), dim3(kPgPieceThreads), ldsFactor, s_, p);
+        else launch(k_pg_piece_factor<4, 2>, dim3(nPieces), dim3(kPgPieceThreads), ldsFactor, s_, p);
+        launch(k_pg_piece_schur, dim3((unsigned)tileWork.size()), dim3(256), 0, s_, p);
+        launch(k_pg_sep_gather, dim3((nDest * D * D + 255) / 256 + (nS + 255) / 256), dim3(256), 0, s_, p, nDest,
+               (nDest * D * D + 255) / 256);
       }
       if (nPieces2 > 0) {
-        hipLaunchKernelGGL(k_pg_l2_extract, dim3((nX * D * D + 255) / 256), dim3(256), 0, s_, p2, (const int4*)dXDst_.p,
-                           (const int2*)dXSrc_.p, nX);
-        if (six_) hipLaunchKernelGGL((k_pg_piece_factor<6, 7>), dim3(nPieces2), dim3(kPgPieceThreads), ldsFactor2, s_, p2);
-        else hipLaunchKernelGGL((k_pg_piece_factor<4, 3>), dim3(nPieces2), dim3(kPgPieceThreads), ldsFactor2, s_, p2);
-        hipLaunchKernelGGL(k_pg_piece_schur, dim3((unsigned)L2.tileWork.size()), dim3(256), 0, s_, p2);
-        hipLaunchKernelGGL(k_pg_sep_gather, dim3((L2.nDest * D * D + 255) / 256 + (nS + 255) / 256), dim3(256), 0, s_, p2, L2.nDest,
-                           (L2.nDest * D * D + 255) / 256);
+        launch(k_pg_l2_extract, dim3((nX * D * D + 255) / 256), dim3(256), 0, s_, p2, (const int4*)dXDst_.p,
+               (const int2*)dXSrc_.p, nX);
+        if (six_) launch(k_pg_piece_factor<6, 7>, dim3(nPieces2), dim3(kPgPieceThreads), ldsFactor2, s_, p2);
+        else launch(k_pg_piece_factor<4, 3>, dim3(nPieces2), dim3(kPgPieceThreads), ldsFactor2, s_, p2);
+        launch(k_pg_piece_schur, dim3((unsigned)L2.tileWork.size()), dim3(256), 0, s_, p2);
+        launch(k_pg_sep_gather, dim3((L2.nDest * D * D + 255) / 256 + (nS + 255) / 256), dim3(256), 0, s_, p2, L2.nDest,
+               (L2.nDest * D * D + 255) / 256);
       }
-      PG_HIP_OK(hipEventRecord(evA_[nSolves % kPgMaxTimed], s_));
+      HIP_OK(hipEventRecord(evA_[nSolves % kPgMaxTimed], s_));
       launchSolveReduced(dp, s_, 0.0, false, false);
-      PG_HIP_OK(hipEventRecord(evB_[nSolves % kPgMaxTimed], s_));
+      HIP_OK(hipEventRecord(evB_[nSolves % kPgMaxTimed], s_));
       ++nSolves;
       if (nPieces2 > 0) {
-        if (six_) hipLaunchKernelGGL((k_pg_piece_back<6, 7>), dim3(nPieces2), dim3(kPgPieceThreads), ldsBack2, s_, p2);
-        else hipLaunchKernelGGL((k_pg_piece_back<4, 3>), dim3(nPieces2), dim3(kPgPieceThreads), ldsBack2, s_, p2);
+        if (six_) launch(k_pg_piece_back<6, 7>, dim3(nPieces2), dim3(kPgPieceThreads), ldsBack2, s_, p2);
+        else launch(k_pg_piece_back<4, 3>, dim3(nPieces2), dim3(kPgPieceThreads), ldsBack2, s_, p2);
       }
       if (nPieces > 0) {
         const int nScatter = (nn + kPgPieceThreads - 1) / kPgPieceThreads;
-        if (six_) hipLaunchKernelGGL((k_pg_piece_back<6, 4>), dim3(nPieces + nScatter), dim3(kPgPieceThreads), ldsBack, s_, p);
-        else hipLaunchKernelGGL((k_pg_piece_back<4, 2>), dim3(nPieces + nScatter), dim3(kPgPieceThreads), ldsBack, s_, p);
+        if (six_) launch(k_pg_piece_back<6, 4>, dim3(nPieces + nScatter), dim3(kPgPieceThreads), ldsBack, s_, p);
+        else launch(k_pg_piece_back<4, 2>, dim3(nPieces + nScatter), dim3(kPgPieceThreads), ldsBack, s_, p);
       } else {
-        hipLaunchKernelGGL(k_pg_scatter_sep, dim3(gN), dim3(128), 0, s_, p);
+        launch(k_pg_scatter_sep, dim3(gN), dim3(128), 0, s_, p);
       }
     };
     int nSolves = 0;
@@ -1404,7 +1386,7 @@ class PoseGraph {
     const double min_relative_decrease = 1e-3, max_radius = 1e16, min_radius = 1e-32;
     double radius = 1e4, decrease_factor = 2.0;
     evaluate(false, true, false);
-    hipLaunchKernelGGL(k_pg_reduce, dim3(1), dim3(256), 0, s_, p, (int)PG_COST, gE, 0);
+    launch(k_pg_reduce, dim3(1), dim3(256), 0, s_, p, (int)PG_COST, gE, 0);
     readScal();
     double x_cost = sc[PG_COST];
     summary[0] = x_cost;
@@ -1413,8 +1395,8 @@ class PoseGraph {
     while (true) {
       const bool freshLinearization = needLinearize;
       if (needLinearize) {  // gradient / column norms / J^T J blocks of the current linearisation
-        if (six_) hipLaunchKernelGGL(k_pg_node<6>, dim3(gN), dim3(128), 0, s_, p, initScale ? 1 : 0);
-        else hipLaunchKernelGGL(k_pg_node<4>, dim3(gN), dim3(128), 0, s_, p, initScale ? 1 : 0);
+        if (six_) launch(k_pg_node<6>, dim3(gN), dim3(128), 0, s_, p, initScale ? 1 : 0);
+        else launch(k_pg_node<4>, dim3(gN), dim3(128), 0, s_, p, initScale ? 1 : 0);
         initScale = false;
       }
       if (iteration >= maxIter_) { termination = 1; break; }
@@ -1422,8 +1404,8 @@ class PoseGraph {
       // The step is enqueued before the gradient check's scalar is back (one read-back per iteration instead of
       // three); when the gradient test fires the step is simply not used -- Ceres would not have computed it.
       solveNormalEquations(radius, nSolves);
-      if (six_) hipLaunchKernelGGL(k_pg_model_plus<6>, dim3(gE + gN), dim3(128), 0, s_, p, gE);
-      else hipLaunchKernelGGL(k_pg_model_plus<4>, dim3(gE + gN), dim3(128), 0, s_, p, gE);
+      if (six_) launch(k_pg_model_plus<6>, dim3(gE + gN), dim3(128), 0, s_, p, gE);
+      else launch(k_pg_model_plus<4>, dim3(gE + gN), dim3(128), 0, s_, p, gE);
       evaluate(true, false, true);   // + the iteration's scalars (and the gradient max of this linearisation)
       readScal();
       if (freshLinearization && sc[PG_GRADMAX] <= gradient_tolerance) { termination = 0; break; }
@@ -1454,21 +1436,21 @@ class PoseGraph {
         radius /= decrease_factor; decrease_factor *= 2.0;
       }
     }
-    PG_HIP_OK(hipStreamSynchronize(s_));
+    HIP_OK(hipStreamSynchronize(s_));
     summary[5] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     summary[1] = x_cost; summary[2] = iteration; summary[3] = termination; summary[4] = successful;
     summary[7] = 0;
     for (int i = 0; i < std::min(nSolves, kPgMaxTimed); ++i) {   // HIP events on the solve's own stream
       float ms = 0;
-      PG_HIP_OK(hipEventElapsedTime(&ms, evA_[i], evB_[i]));
+      HIP_OK(hipEventElapsedTime(&ms, evA_[i], evB_[i]));
       summary[7] += 1e-3 * ms;
     }
     partition[5] = nR; partition[6] = std::min(nSolves, kPgMaxTimed);
     // ---- write back, drift update, keyframes after cur (PoseGraph.cpp:340-375 / :504-534)
     std::vector<double> hy(nn), ht(3 * (size_t)nn), hq(4 * (size_t)nn);
-    PG_HIP_OK(hipMemcpy(hy.data(), p.yaw, sizeof(double) * nn, hipMemcpyDeviceToHost));
-    PG_HIP_OK(hipMemcpy(ht.data(), p.t, sizeof(double) * 3 * nn, hipMemcpyDeviceToHost));
-    PG_HIP_OK(hipMemcpy(hq.data(), p.q, sizeof(double) * 4 * nn, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(hy.data(), p.yaw, sizeof(double) * nn, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(ht.data(), p.t, sizeof(double) * 3 * nn, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(hq.data(), p.q, sizeof(double) * 4 * nn, hipMemcpyDeviceToHost));
     const auto tWb0 = std::chrono::steady_clock::now();
     writeBack(hy, pitch, roll, ht, hq, kfOfLocal, cur);
     if (optOn(kOptPgTiming)) {

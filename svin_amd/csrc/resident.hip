@@ -313,22 +313,22 @@ __global__ __launch_bounds__(256) void k_fill_jobs(FillJobs f) {
 
 void launchFillJobs(const FillJobs& f, hipStream_t s) {
   if (f.n <= 0) return;
-  hipLaunchKernelGGL(k_fill_jobs, dim3(64, f.n), dim3(256), 0, s, f);
+  launch(k_fill_jobs, dim3(64, f.n), dim3(256), 0, s, f);
 }
 void launchWindowRebuild(const ResidentArgs& a, hipStream_t s) {
-  hipLaunchKernelGGL(k_window_rebuild, dim3(1), dim3(kRebuildThreads), 0, s, a);
-  if (a.wantOrder && a.Lnew > 0) hipLaunchKernelGGL(k_window_order, dim3((a.Lnew + 15) / 16), dim3(64), 0, s, a);
+  launch(k_window_rebuild, dim3(1), dim3(kRebuildThreads), 0, s, a);
+  if (a.wantOrder) launch(k_window_order, dim3((a.Lnew + 15) / 16), dim3(64), 0, s, a);
 }
 void launchWindowStoreLandmarks(int H, const int* slotOfH, const double* lm, const double* quality, double* lmHp, double* qualH,
                                 hipStream_t s) {
   if (H <= 0) return;
-  hipLaunchKernelGGL(k_window_store_landmarks, dim3((H + 255) / 256), dim3(256), 0, s, H, slotOfH, lm, quality, lmHp, qualH);
+  launch(k_window_store_landmarks, dim3((H + 255) / 256), dim3(256), 0, s, H, slotOfH, lm, quality, lmHp, qualH);
 }
 void launchWindowFinish(const FinishArgs& a, hipStream_t s) {
-  hipLaunchKernelGGL(k_window_finish, dim3(a.nLmBlocks + kFinishBlocksPerSegment * a.ga.n), dim3(256), 0, s, a);
+  launch(k_window_finish, dim3(a.nLmBlocks + kFinishBlocksPerSegment * a.ga.n), dim3(256), 0, s, a);
 }
 void launchWindowMargGather(const MargGatherArgs& a, hipStream_t s) {
-  hipLaunchKernelGGL(k_window_marg_gather, dim3(1), dim3(kRebuildThreads), 0, s, a);
+  launch(k_window_marg_gather, dim3(1), dim3(kRebuildThreads), 0, s, a);
 }
 
 }  // namespace svin

@@ -26,12 +26,6 @@ std::string& lastError() {
   return e;
 }
 
-#define HIP_OK(expr)                                                                              \
-  do {                                                                                            \
-    hipError_t _e = (expr);                                                                       \
-    if (_e != hipSuccess) throw std::runtime_error(std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
-
 // compute units of the current device (asked once)
 static int deviceComputeUnits() {
   static const int n = [] {
