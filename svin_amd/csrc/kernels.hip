@@ -3729,6 +3729,8 @@ static DenseSchurPlan denseSchurPlan(const DeviceProblem& p) {
 int schurDenseABlocks(const DeviceProblem& p) { return (p.L > 0 && p.N > 0 && p.dC > 0 && p.schurDense && denseSchurPlan(p).aBlocks) ? 1 : 0; }
 static bool sbEarlyActive(const DeviceProblem& p);                                          // (behind the chain kernels, below)
 static void launchSbEarly(const DeviceProblem& p, hipStream_t side, double mu, bool initScale);
+static std::atomic<int> gLastSchurForm{0};
+int lastSchurForm() { return gLastSchurForm.load(std::memory_order_relaxed); }
 void launchAccumulateNormalEquations(const DeviceProblem& p, double mu, bool initScale, hipStream_t s, bool zeroFirst) {
   const int dC = p.dC;
   if (zeroFirst) launchZeroBuild(p, s);
@@ -3742,6 +3744,7 @@ void launchAccumulateNormalEquations(const DeviceProblem& p, double mu, bool ini
     const dim3 grid(p.nSlabs + nFac + nPri);
     DeviceProblem pb = p;
     pb.aBlocks = plan.aBlocks ? 1 : 0;
+    gLastSchurForm.store(1000 + 10 * (nTr > 12 ? 17 : nTr > 8 ? 10 : 9) + (aMfma ? (plan.aBlocks ? 1 : 2) : 0), std::memory_order_relaxed);
     // <= 16 tile rows: 136 tiles over 8 waves; <= 12 tile rows: 78 tiles
     if (nTr > 12) launch(k_schur_dense<17, true, 8>, grid, dim3(64 * 8), ldsBytes, s, pb, mu, initScale ? 1 : 0, p.nSlabs, nFac);
     else if (nTr > 8) launch(k_schur_dense<10, true, 8>, grid, dim3(64 * 8), ldsBytes, s, pb, mu, initScale ? 1 : 0, p.nSlabs, nFac);
@@ -3770,6 +3773,7 @@ void launchAccumulateNormalEquations(const DeviceProblem& p, double mu, bool ini
     // k_blocks_pose_reduce: the latter waits for the former (event `mid`).
     SideLane* lane = nullptr;
     const bool early = sbEarlyActive(p);
+    gLastSchurForm.store(p.schurBlocks ? 2000 : 3000, std::memory_order_relaxed);
     if (early) {
       lane = &sideLaneOf(s);
       HIP_OK(hipEventRecord(lane->fork, s));
@@ -3813,6 +3817,7 @@ void launchAccumulateNormalEquations(const DeviceProblem& p, double mu, bool ini
     const size_t accBytes = ((size_t)dC * dC + 3 * dC) * 8;
     const size_t stageBytes = (size_t)4 * 64 * kStage * 8;
     const bool useLds = accBytes + stageBytes <= 150 * 1024;
+    gLastSchurForm.store(useLds ? 4000 : 4001, std::memory_order_relaxed);
     if (useLds) {
       const int grid = p.nSlabs;
       launch(p.anyExtVariable ? k_schur<true, true> : k_schur<true, false>, dim3(grid + nFac + nPri), dim3(256), accBytes + stageBytes,
@@ -3825,6 +3830,7 @@ void launchAccumulateNormalEquations(const DeviceProblem& p, double mu, bool ini
              mu, initScale ? 1 : 0, grid, nFac);
     }
   } else {
+    gLastSchurForm.store(5000, std::memory_order_relaxed);
     launch(k_factors_only, dim3(nFac + nPri), dim3(256), 0, s, p, nFac);
   }
   if (p.L > 0 && p.N > 0 && dC > 0) {

@@ -255,6 +255,11 @@ bool batchSupported(const DeviceProblem& p);   // the geometry the batched kerne
 // `stagesUnion` = OR of the slots' stages, `cand` as for launchEvalAll
 void launchBatchRound(const BatchSlot* dSlots, const DeviceProblem& geom, int n, int stagesUnion, bool cand, hipStream_t s);
 int schurDenseABlocks(const DeviceProblem& p);   // DeviceProblem::aBlocks as launchAccumulateNormalEquations chooses it
+// Which landmark-elimination form launchAccumulateNormalEquations launched last in this process (read-only inspection field,
+// svin_ba_debug_get_option("SVIN_LAST_SCHUR_FORM")): 0 none yet; 1000 + 10 MAXT + a for k_schur_dense<MAXT, ...> (a = 0: A in per-wave
+// block copies, 1: A on MFMA block-wise, 2: A on MFMA tile-wise); 2000 k_blocks_slots + k_schur_rows; 3000 k_schur_panels;
+// 4000 / 4001 pairwise k_schur with LDS slabs / global atomics; 5000 small factors only.
+int lastSchurForm();
 
 // ---- launch wrappers (kernels.hip).  `cand` selects candidate tables/buffers.
 void launchEvalReproj(const DeviceProblem& p, bool cand, bool robust, hipStream_t s);

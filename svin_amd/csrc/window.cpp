@@ -86,6 +86,7 @@ OptionTable& optionTable() {
 int debugOption(DebugOption which) { return optionTable().v[which].load(std::memory_order_relaxed); }
 int debugOptionByName(const char* name, int* value) {
   if (!name) return 0;
+  if (std::strcmp(name, "SVIN_LAST_SCHUR_FORM") == 0) { if (value) *value = lastSchurForm(); return 1; }   // read-only: not in the table
   OptionTable& t = optionTable();
   for (int k = 0; k < kOptCount; ++k)
     if (std::strcmp(t.name[k], name) == 0) { if (value) *value = t.v[k].load(std::memory_order_relaxed); return 1; }
