@@ -153,10 +153,13 @@ int svin_ba_solve_prepared(svin_ba* h, uint64_t num_iter, int verbose);
 int svin_ba_finish(svin_ba* h);
 /* SEVERAL windows at once (the reference has no counterpart: okvis::Estimator::optimize, Estimator.cpp:876-929, is one window per
  * call and ThreadedKFVio runs one estimator; SURVEY 8(e) names "independent replicas processing different windows" as the other
- * way to fill the hardware).  Handles of ONE device; windows with the same launch geometry (numbers of states, landmarks,
- * observations and factors) that the LDS-resident solver takes (reduced system of at most 176 rows, no marginalisation-only
- * restrictions) share one launch sequence per trust-region round, the window as a grid dimension; the others -- and a window
- * without a partner -- are optimised one after the other by the ordinary path.  Every window ends exactly (bit for bit) where
+ * way to fill the hardware).  Handles of ONE device; windows that agree in the numbers of states (poses, extrinsics, speed / bias
+ * blocks) and of factors, in the size and block count of the marginalisation prior, in the number of cameras and in whether
+ * extrinsics are estimated, and that the LDS-resident solver takes (reduced system of at most 176 rows, no marginalisation-only
+ * restrictions) share one launch sequence per trust-region round, the window as a grid dimension.  The numbers of LANDMARKS and
+ * OBSERVATIONS may differ from window to window -- what a front end decides anew every frame does not separate the vehicles of a
+ * fleet: every window brings the extent of each launch, the grid is the largest one, similar sizes share a lane.  The others --
+ * and a window without a partner -- are optimised one after the other by the ordinary path.  Every window ends exactly (bit for bit) where
  * svin_ba_optimize / svin_ba_solve_prepared would leave it on its own; *n_batched (may be NULL) = windows that ran in a batch.
  * solve_prepared_batch expects svin_ba_prepare on every handle (measurement form); optimize_batch = prepare, solve, finish.
  * The call owns the handles while it runs (no other thread may use them); the batched windows run on up to four streams of the

@@ -197,12 +197,18 @@ enum PartialSlot : int {
 enum Ticket : int { TK_POST = 0, TK_STEP = 1, TK_EVAL = 2 };
 // last-block-done: returns true in every thread of the block that finishes last (its loads see all other
 // blocks' partials); the summation order over the partial slots is fixed, so the result is deterministic
-__device__ __forceinline__ bool lastBlockDone(unsigned int* ticket, int* flagLds) {
+// How many blocks a launch has FOR THIS WINDOW, as an argument of the kernel bodies that count tickets, sum partials or stride
+// by it: the launch's own gridDim.x for a window on its own (GridDimX: read where it is used, the single-window kernels compile
+// to what they were), the window's extent from its slot in a batched kernel (ExtentX; batch_plan.hpp).
+struct GridDimX { __device__ __forceinline__ unsigned int operator()() const { return gridDim.x; } };
+struct ExtentX { unsigned int n; __device__ __forceinline__ unsigned int operator()() const { return n; } };
+template <class NB>
+__device__ __forceinline__ bool lastBlockDone(unsigned int* ticket, int* flagLds, NB nBlocks) {
   __threadfence();
   __syncthreads();
   if (threadIdx.x == 0) {
     const unsigned int tk = atomicAdd(ticket, 1u);
-    *flagLds = (tk == gridDim.x - 1) ? 1 : 0;
+    *flagLds = (tk == nBlocks() - 1) ? 1 : 0;
   }
   __syncthreads();
   const bool last = *flagLds != 0;
@@ -215,12 +221,13 @@ __device__ __forceinline__ bool lastBlockDone(unsigned int* ticket, int* flagLds
 // __threadfence() makes every block write back its XCD's dirty L2 lines -- megabytes of Jacobians right after K1.
 __device__ __forceinline__ void cstore(double* q, double v) { __hip_atomic_store(q, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ double cload(const double* q) { return __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ bool lastBlockDoneLight(unsigned int* ticket, int* flagLds) {
+template <class NB>
+__device__ __forceinline__ bool lastBlockDoneLight(unsigned int* ticket, int* flagLds, NB nBlocks) {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");   // this thread's cstore()s have completed
   __syncthreads();
   if (threadIdx.x == 0) {
     const unsigned int tk = atomicAdd(ticket, 1u);
-    *flagLds = (tk == gridDim.x - 1) ? 1 : 0;
+    *flagLds = (tk == nBlocks() - 1) ? 1 : 0;
   }
   __syncthreads();
   return *flagLds != 0;
@@ -1753,7 +1760,7 @@ __global__ __launch_bounds__(256) void k_eval_factors(DeviceProblem p, int cand,
   // kernel of the stream) -- saves the separate reduction launch
   if (costBlocksA >= 0) {
     __shared__ int lastFlag;
-    if (lastBlockDone(&p.tickets[TK_EVAL], &lastFlag)) {
+    if (lastBlockDone(&p.tickets[TK_EVAL], &lastFlag, GridDimX{})) {
       reduceCost(p, costBlocksA, (int)gridDim.x, sh.P);
       if (threadIdx.x == 0) p.tickets[TK_EVAL] = 0;
     }
@@ -1878,7 +1885,7 @@ __device__ __forceinline__ void k_eval_all_body(const DeviceProblem& p, int cand
   if (sumCost) {
     __shared__ int lastFlag;
     __shared__ double red4[72];
-    if (lastBlockDoneLight(&p.tickets[TK_EVAL], &lastFlag)) {   // (cost partials and costPrior are cstore()d)
+    if (lastBlockDoneLight(&p.tickets[TK_EVAL], &lastFlag, GridDimX{})) {   // (cost partials and costPrior are cstore()d)
       TRACE(19);
       reduceCost(p, nR, F, red4, (cand && p.lmDeferred) ? nR : 0);
       if (threadIdx.x == 0) p.tickets[TK_EVAL] = 0;
@@ -1922,8 +1929,11 @@ __device__ __forceinline__ void evalReprojSplitBody(const DeviceProblem& p, int 
                                   df, p.lmPrior, p.lossTab);
 }
 // blocks [0, F): the small factors, block F (hasPrior): the marginalisation prior; the block that finishes last sums the cost
-__device__ __forceinline__ void evalRestSplitBody(const DeviceProblem& p, int cand, int nR, int hasPrior, FactorShared& sh) {
-  const int F = (int)gridDim.x - hasPrior;
+// (nBlocks = F + hasPrior: the launch's gridDim.x for one window, the window's own extent in a batch; nR: the reprojection
+// partials of the launch before)
+template <class NB>
+__device__ __forceinline__ void evalRestSplitBody(const DeviceProblem& p, int cand, int nR, int hasPrior, FactorShared& sh, NB nBlocks) {
+  const int F = (int)nBlocks() - hasPrior;
   if ((int)blockIdx.x < F) {
     SVIN_ARGS(SA(p.factors), SA(p.imus), SA(p.linCand), SA(p.linCur), SA(p.poseC), SA(p.pose), SA(p.sbC), SA(p.sb), SA(p.extC), SA(p.ext),
               SA(p.poseOff), SA(p.sbOff), SA(p.extOff), SA(p.partial), SA(p.imuT), SA(p.imuMeas));
@@ -1933,7 +1943,7 @@ __device__ __forceinline__ void evalRestSplitBody(const DeviceProblem& p, int ca
   }
   __shared__ int lastFlag;
   __shared__ double red4[72];
-  if (lastBlockDoneLight(&p.tickets[TK_EVAL], &lastFlag)) {   // (cost partials and costPrior are cstore()d; the reprojection partials: previous launch)
+  if (lastBlockDoneLight(&p.tickets[TK_EVAL], &lastFlag, nBlocks)) {   // (cost partials and costPrior are cstore()d; the reprojection partials: previous launch)
     reduceCost(p, nR, F, red4, (cand && p.lmDeferred) ? nR : 0);
     if (threadIdx.x == 0) p.tickets[TK_EVAL] = 0;
   }
@@ -1942,14 +1952,15 @@ template <bool WITH_EXT>
 __global__ __launch_bounds__(256) void k_eval_reproj_batch(const BatchSlot* __restrict__ slots, int cand) {
   extern __shared__ double smem[];
   const BatchSlot& sl = batchSlot(slots);
-  if (!(sl.stages & kBatchEval)) return;
+  if (!(sl.stages & kBatchEval) || (int)blockIdx.x >= sl.ext.evalR) return;   // (beyond the window's own blocks: no partial, no store)
   evalReprojSplitBody<WITH_EXT>(sl.p, cand, smem);
 }
-__global__ __launch_bounds__(256) void k_eval_rest_batch(const BatchSlot* __restrict__ slots, int cand, int nR, int hasPrior) {
+__global__ __launch_bounds__(256) void k_eval_rest_batch(const BatchSlot* __restrict__ slots, int cand) {
   __shared__ FactorShared sh;
   const BatchSlot& sl = batchSlot(slots);
-  if (!(sl.stages & kBatchEval)) return;
-  evalRestSplitBody(sl.p, cand, nR, hasPrior, sh);
+  const int nBlocks = sl.ext.evalF + sl.ext.evalPri;
+  if (!(sl.stages & kBatchEval) || (int)blockIdx.x >= nBlocks) return;
+  evalRestSplitBody(sl.p, cand, sl.ext.evalR, sl.ext.evalPri, sh, ExtentX{(unsigned int)nBlocks});
 }
 // The same two launches for ONE window whose evaluation has more blocks than the chip has CUs (wide windows: 1 954 reprojection
 // blocks at 500 000 observations): in k_eval_all every block carries the factor blocks' LDS, one workgroup per CU.
@@ -1960,7 +1971,7 @@ __global__ __launch_bounds__(256) void k_eval_reproj_split(DeviceProblem p, int 
 }
 __global__ __launch_bounds__(256) void k_eval_rest_split(DeviceProblem p, int cand, int nR, int hasPrior) {
   __shared__ FactorShared sh;
-  evalRestSplitBody(p, cand, nR, hasPrior, sh);
+  evalRestSplitBody(p, cand, nR, hasPrior, sh, GridDimX{});
 }
 
 constexpr int kEvalSplitBlocks = 512;   // more evaluation blocks than this: reprojection blocks in a launch of their own (launchEvalAll)
@@ -1973,7 +1984,7 @@ static size_t evalSplitStageBytes(const DeviceProblem& p) {
   return (size_t)48 * 8 + (size_t)(p.nPose + p.nExt) * 7 * 8 + (size_t)p.nCam * sizeof(CameraModel) + kLossTabBytes + 64;
 }
 void launchEvalAll(const DeviceProblem& p, bool cand, bool sumCost, hipStream_t s) {
-  const int nR = (p.N + 255) / 256, pri = p.priorM > 0 ? 1 : 0;
+  const int nR = evalReprojBlockCount(p.N), pri = evalPriorBlockCount(p.priorM);   // (batch_plan.hpp: shared with the batched extents)
   if (sumCost && p.F + nR + pri > kEvalSplitBlocks && !optOn(kOptNoEvalSplit)) {
     const size_t stage = evalSplitStageBytes(p);
     // (measured, round 6: the factor blocks on the side stream beside the reprojection blocks, one cost ticket for both launches --
@@ -2052,7 +2063,7 @@ __device__ void priorAccumulateBlock(const DeviceProblem& p, int block) {
   }
 }
 __global__ __launch_bounds__(256) void k_prior_accumulate(DeviceProblem p) { priorAccumulateBlock(p, blockIdx.x); }
-static int priorAccBlocks(const DeviceProblem& p) { return (p.priorM > 0 && p.ownsCamera) ? (p.priorM * p.priorM + 255) / 256 : 0; }
+static int priorAccBlocks(const DeviceProblem& p) { return priorAccBlockCount(p.priorM, p.ownsCamera != 0); }   // (batch_plan.hpp: shared with the batched extents)
 // ================================================================ K5: normal equations + landmark Schur complement
 // generic small factors: J^T J into S (both triangles), J^T r into gRed/gFull, column norms into hC
 __device__ void factorsAccumulate(const DeviceProblem& p, int f, int* colRow) {
@@ -2767,10 +2778,12 @@ template <int MAXT, bool A_MFMA, int NW = 4>
 __global__ __launch_bounds__(64 * NW) void k_schur_dense(DeviceProblem p, double mu, int initScale, int nChunkBlocks, int nFacBlocks) { k_schur_dense_body<MAXT, A_MFMA, NW>(p, mu, initScale, nChunkBlocks, nFacBlocks); }
 // (batched form: blockIdx.y = the window of the batch, its problem and trust-region scalars from the slot table)
 template <int MAXT, bool A_MFMA, int NW = 4>
-__global__ __launch_bounds__(64 * NW, NW == 4 ? SVIN_BATCH_OCC_SCHUR : 1) void k_schur_dense_batch(const BatchSlot* __restrict__ slots, int nChunkBlocks, int nFacBlocks) {
+__global__ __launch_bounds__(64 * NW, NW == 4 ? SVIN_BATCH_OCC_SCHUR : 1) void k_schur_dense_batch(const BatchSlot* __restrict__ slots) {
   const BatchSlot& sl = batchSlot(slots);
-  if (!(sl.stages & kBatchFull)) return;
-  k_schur_dense_body<MAXT, A_MFMA, NW>(sl.p, sl.mu, sl.initScale, nChunkBlocks, nFacBlocks);
+  // the window's own [slab | factor | prior] blocks: the body takes a block's role from these two counts, and whatever lies
+  // beyond the prior's blocks leaves here
+  if (!(sl.stages & kBatchFull) || (int)blockIdx.x >= sl.ext.buildSlabs + sl.ext.buildFac + sl.ext.buildPri) return;
+  k_schur_dense_body<MAXT, A_MFMA, NW>(sl.p, sl.mu, sl.initScale, sl.ext.buildSlabs, sl.ext.buildFac);
 }
 
 
@@ -6821,7 +6834,9 @@ __device__ __forceinline__ void retractItem(const DeviceProblem& p, int i, doubl
 
 // stand-alone dogleg step + retraction (re-used linearisation after a rejected step, multi-GPU mode, wide windows);
 // the last block reduces the norms
-__device__ __forceinline__ void k_step_retract_body(const DeviceProblem& p, double radius) {
+// (nBlocks: gridDim.x of the window's own launch -- the ticket and the partial sums read it from here)
+template <class NB>
+__device__ __forceinline__ void k_step_retract_body(const DeviceProblem& p, double radius, NB nBlocks) {
   __shared__ double red[16 * 2];
   __shared__ int lastFlag;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -6832,11 +6847,11 @@ __device__ __forceinline__ void k_step_retract_body(const DeviceProblem& p, doub
   retractItem(p, i, c.cg, c.cn, acc);
   const double mine = blockSumK<2>(acc, red, -1);
   if (threadIdx.x < 2) cstore(p.partial + (size_t)(threadIdx.x == 0 ? PS_STEP : PS_XNORM) * kMaxPartials + blockIdx.x, mine);
-  if (!lastBlockDoneLight(&p.tickets[TK_STEP], &lastFlag)) return;
+  if (!lastBlockDoneLight(&p.tickets[TK_STEP], &lastFlag, nBlocks)) return;
   for (int k = 0; k < 2; ++k) {
     double s = 0;
     const double* src = p.partial + (size_t)(k == 0 ? PS_STEP : PS_XNORM) * kMaxPartials;
-    for (int j = threadIdx.x; j < (int)gridDim.x; j += blockDim.x) s += cload(src + j);
+    for (int j = threadIdx.x; j < (int)nBlocks(); j += blockDim.x) s += cload(src + j);
     acc[k] = s;
   }
   const double tot = blockSumK<2>(acc, red, -1);
@@ -6844,12 +6859,12 @@ __device__ __forceinline__ void k_step_retract_body(const DeviceProblem& p, doub
   if (threadIdx.x == 1) p.scal->xNormSq = tot;
   if (threadIdx.x == 0) p.tickets[TK_STEP] = 0;
 }
-__global__ __launch_bounds__(256) void k_step_retract(DeviceProblem p, double radius) { k_step_retract_body(p, radius); }
+__global__ __launch_bounds__(256) void k_step_retract(DeviceProblem p, double radius) { k_step_retract_body(p, radius, GridDimX{}); }
 // (batched form: blockIdx.y = the window of the batch, its problem and trust-region scalars from the slot table)
 __global__ __launch_bounds__(256) void k_step_retract_batch(const BatchSlot* __restrict__ slots) {
   const BatchSlot& sl = batchSlot(slots);
-  if (!(sl.stages & kBatchReuse)) return;
-  k_step_retract_body(sl.p, sl.radius);
+  if (!(sl.stages & kBatchReuse) || (int)blockIdx.x >= sl.ext.step) return;
+  k_step_retract_body(sl.p, sl.radius, ExtentX{(unsigned int)sl.ext.step});
 }
 
 
@@ -6870,8 +6885,10 @@ __device__ constexpr int postSlotC(int k) {
 //  factor blocks (one wave per factor): the same five sums over the rows of the small factors;
 //  last block: camera part of the norms and the marginalisation prior (H-space);
 //  whichever block finishes last reduces all partials into SolverScalars group B.
-template <bool WITH_EXT>
-__device__ __forceinline__ void k_post_solve_body(const DeviceProblem& p, int nLmBlocks, int nFacBlocks, double fuseRadius) {
+//  (nBlocks = nLmBlocks + nFacBlocks + 1: gridDim.x of the window's own launch -- the clears' stride, the ticket and the partial
+//  sums read it from here)
+template <bool WITH_EXT, class NB>
+__device__ __forceinline__ void k_post_solve_body(const DeviceProblem& p, int nLmBlocks, int nFacBlocks, double fuseRadius, NB nBlocks) {
   __shared__ double red[16 * kPostK];
   __shared__ int lastFlag;
   const int t = threadIdx.x, b = blockIdx.x;
@@ -6883,8 +6900,8 @@ __device__ __forceinline__ void k_post_solve_body(const DeviceProblem& p, int nL
   TRACE(0);
   // clear the accumulators of the next linearisation (nothing reads S / gRed / hC after the solve; gFull is
   // still needed by the last block below and is cleared there)
-  for (int i = b * blockDim.x + t; i < p.ldS * p.d; i += gridDim.x * blockDim.x) p.S[i] = 0.0;
-  for (int i = b * blockDim.x + t; i < p.d; i += gridDim.x * blockDim.x) { p.gRed[i] = 0.0; p.hC[i] = 0.0; }
+  for (int i = b * blockDim.x + t; i < p.ldS * p.d; i += nBlocks() * blockDim.x) p.S[i] = 0.0;
+  for (int i = b * blockDim.x + t; i < p.d; i += nBlocks() * blockDim.x) { p.gRed[i] = 0.0; p.hC[i] = 0.0; }
   // Staged in LDS by every block at its start: the camera-side solution vectors (tiny, read by every observation: one
   // copy instead of a dependent global load per observation; wide windows keep reading them through L2), the block ->
   // row maps, and -- because any block may turn out to be the last one, whose tail is the serial end of the
@@ -7153,7 +7170,7 @@ __device__ __forceinline__ void k_post_solve_body(const DeviceProblem& p, int nL
   const double mine = blockSumK<kPostK>(acc, red, 8);
   TRACE(11);
   if (t < kPostK) cstore(p.partial + (size_t)kPostSlot[t] * kMaxPartials + b, mine);
-  if (!lastBlockDoneLight(&p.tickets[TK_POST], &lastFlag)) return;   // partials, y_l and v_l are cstore()d
+  if (!lastBlockDoneLight(&p.tickets[TK_POST], &lastFlag, nBlocks)) return;   // partials, y_l and v_l are cstore()d
   TRACE(2);
   // The tail from here on is the serial end of the iteration: one round trip for the partials of the nine sums, then the
   // first round of landmarks with their y_l / v_l (eight per thread) in the shadow of the arithmetic.
@@ -7174,12 +7191,12 @@ __device__ __forceinline__ void k_post_solve_body(const DeviceProblem& p, int nL
   {
     double x0[kPostK];
 #pragma unroll
-    for (int k = 0; k < kPostK; ++k) x0[k] = (t < (int)gridDim.x) ? cload(p.partial + (size_t)postSlotC(k) * kMaxPartials + t) : 0.0;
+    for (int k = 0; k < kPostK; ++k) x0[k] = (t < (int)nBlocks()) ? cload(p.partial + (size_t)postSlotC(k) * kMaxPartials + t) : 0.0;
 #pragma unroll
     for (int k = 0; k < kPostK; ++k) {
       double s = x0[k];
       const double* src = p.partial + (size_t)postSlotC(k) * kMaxPartials;
-      for (int i = t + blockDim.x; i < (int)gridDim.x; i += blockDim.x) { const double x = cload(src + i); s = (k == 8) ? fmax(s, x) : s + x; }
+      for (int i = t + blockDim.x; i < (int)nBlocks(); i += blockDim.x) { const double x = cload(src + i); s = (k == 8) ? fmax(s, x) : s + x; }
       acc[k] = s;
     }
   }
@@ -7280,22 +7297,22 @@ __device__ __forceinline__ void k_post_solve_body(const DeviceProblem& p, int nL
   TRACE(7);
 }
 template <bool WITH_EXT>
-__global__ __launch_bounds__(256) void k_post_solve(DeviceProblem p, int nLmBlocks, int nFacBlocks, double fuseRadius) { k_post_solve_body<WITH_EXT>(p, nLmBlocks, nFacBlocks, fuseRadius); }
+__global__ __launch_bounds__(256) void k_post_solve(DeviceProblem p, int nLmBlocks, int nFacBlocks, double fuseRadius) { k_post_solve_body<WITH_EXT>(p, nLmBlocks, nFacBlocks, fuseRadius, GridDimX{}); }
 // (the same body held to 256 registers -- two workgroups per CU -- for grids of more blocks than the chip has CUs: wide windows)
 template <bool WITH_EXT>
-__global__ __launch_bounds__(256, 2) void k_post_solve_wide(DeviceProblem p, int nLmBlocks, int nFacBlocks, double fuseRadius) { k_post_solve_body<WITH_EXT>(p, nLmBlocks, nFacBlocks, fuseRadius); }
+__global__ __launch_bounds__(256, 2) void k_post_solve_wide(DeviceProblem p, int nLmBlocks, int nFacBlocks, double fuseRadius) { k_post_solve_body<WITH_EXT>(p, nLmBlocks, nFacBlocks, fuseRadius, GridDimX{}); }
 // (batched form: blockIdx.y = the window of the batch, its problem and trust-region scalars from the slot table)
 template <bool WITH_EXT>
-__global__ __launch_bounds__(256, SVIN_BATCH_OCC_POST) void k_post_solve_batch(const BatchSlot* __restrict__ slots, int nLmBlocks, int nFacBlocks) {
+__global__ __launch_bounds__(256, SVIN_BATCH_OCC_POST) void k_post_solve_batch(const BatchSlot* __restrict__ slots) {
   const BatchSlot& sl = batchSlot(slots);
-  if (!(sl.stages & kBatchFull)) return;
-  k_post_solve_body<WITH_EXT>(sl.p, nLmBlocks, nFacBlocks, sl.radius);
+  const int nBlocks = sl.ext.postLm + sl.ext.postFac + 1;
+  if (!(sl.stages & kBatchFull) || (int)blockIdx.x >= nBlocks) return;
+  k_post_solve_body<WITH_EXT>(sl.p, sl.ext.postLm, sl.ext.postFac, sl.radius, ExtentX{(unsigned int)nBlocks});
 }
 
 
 void launchDoglegPrepare(const DeviceProblem& p, hipStream_t s, double fuseRadius) {
-  const int nLm = (p.L > 0 && p.N > 0) ? min((p.L + 15) / 16, 1024) : 0;
-  const int nFac = p.F > 0 ? min((p.F + 3) / 4, 1024) : 0;
+  const int nLm = postLmBlockCount(p.L, p.N), nFac = postFacBlockCount(p.F);   // (batch_plan.hpp: shared with the batched extents)
   if (nLm + nFac + 1 > kEvalSplitBlocks && !optOn(kOptNoEvalSplit)) {
     if (p.anyExtVariable) launch(k_post_solve_wide<true>, dim3(nLm + nFac + 1), dim3(256), 0, s, p, nLm, nFac, fuseRadius);
     else launch(k_post_solve_wide<false>, dim3(nLm + nFac + 1), dim3(256), 0, s, p, nLm, nFac, fuseRadius);
@@ -7317,14 +7334,17 @@ void launchCost(const DeviceProblem& p, hipStream_t s) {
 }
 
 void launchDoglegStep(const DeviceProblem& p, double radius, hipStream_t s) {
-  const int nB = (p.nPose + p.nExt + p.nSb + p.L + 255) / 256;
+  const int nB = stepBlockCount(p.nPose, p.nExt, p.nSb, p.L);   // (batch_plan.hpp: shared with the batched extents)
   launch(k_step_retract, dim3(nB), dim3(256), 0, s, p, radius);
 }
 
 // ================================================================ batched rounds (kernels.hpp: BatchSlot)
-// The windows of a batch have the same launch geometry: every grid below is the one the launcher of the single window computes
-// from `geom`, with the window as blockIdx.y -- gridDim.x, which the kernels' last-block logic and partial sums read, is what it is
-// for the window on its own, and so is every reduction order: a window ends bit for bit where it ends alone.
+// The windows of a batch agree in what is computed here once per launch -- the kernel variant, the LDS sizes, the slab sum's and
+// the solver's grid (batch_plan.hpp BatchGroupFields) -- and each brings the extent of the other launches that its own launcher
+// would take (BatchSlot::ext, from the same expressions).  gridDim.x is the largest extent among the windows taking part; a
+// block at or beyond its window's extent leaves before any ticket, partial or store, and the last-block logic and the partial
+// sums read the extent where they read gridDim.x for a window on its own.  So every window has the block roles, the partial
+// indices and the reduction orders of its own launches: it ends bit for bit where it ends alone.
 bool batchSupported(const DeviceProblem& p) {
   if (!(p.L > 0 && p.N > 0 && p.dC > 0 && p.schurDense && p.d > 0)) return false;
   if (!canFuseEvaluation(p) || optOn(kOptSplitEval) || optOn(kOptNoFuseStep) || optOn(kOptNoDeferLm)) return false;
@@ -7335,36 +7355,29 @@ bool batchSupported(const DeviceProblem& p) {
   if (p.nHostFactors > 0) return false;
   return true;
 }
-void launchBatchRound(const BatchSlot* dSlots, const DeviceProblem& geom, int n, int stagesUnion, bool cand, hipStream_t s) {
+void launchBatchRound(const BatchSlot* dSlots, const DeviceProblem& geom, const BatchGrid& grid, int n, int stagesUnion, bool cand, hipStream_t s) {
   const DeviceProblem& p = geom;
   if (stagesUnion & kBatchFull) {
     const DenseSchurPlan plan = denseSchurPlan(p);
-    const int nFac = p.F, nPri = priorAccBlocks(p);
-    const dim3 grid(p.nSlabs + nFac + nPri, n);
-    if (plan.nTr > 12) launch(k_schur_dense_batch<17, true, 8>, grid, dim3(64 * 8), plan.ldsBytes, s, dSlots, p.nSlabs, nFac);
-    else if (plan.nTr > 8) launch(k_schur_dense_batch<10, true, 8>, grid, dim3(64 * 8), plan.ldsBytes, s, dSlots, p.nSlabs, nFac);
-    else if (plan.aMfma) launch(k_schur_dense_batch<9, true, 4>, grid, dim3(64 * 4), plan.ldsBytes, s, dSlots, p.nSlabs, nFac);
-    else launch(k_schur_dense_batch<9, false, 4>, grid, dim3(64 * 4), plan.ldsBytes, s, dSlots, p.nSlabs, nFac);
+    const dim3 gridB(grid.build, n);
+    if (plan.nTr > 12) launch(k_schur_dense_batch<17, true, 8>, gridB, dim3(64 * 8), plan.ldsBytes, s, dSlots);
+    else if (plan.nTr > 8) launch(k_schur_dense_batch<10, true, 8>, gridB, dim3(64 * 8), plan.ldsBytes, s, dSlots);
+    else if (plan.aMfma) launch(k_schur_dense_batch<9, true, 4>, gridB, dim3(64 * 4), plan.ldsBytes, s, dSlots);
+    else launch(k_schur_dense_batch<9, false, 4>, gridB, dim3(64 * 4), plan.ldsBytes, s, dSlots);
     const int nRed = p.dC * p.dC + 3 * p.dC;
-    launch(k_reduce_slabs_batch, dim3((nRed + 15) / 16, n), dim3(256), 0, s, dSlots);
+    launch(k_reduce_slabs_batch, dim3((nRed + 15) / 16, n), dim3(256), 0, s, dSlots);   // (every window sums its own nSlabs)
     const int dpad = ((p.d + 15) / 16) * 16;
     const size_t ldsChol = cholLdsBytes(dpad / 16);
     launch(k_chol_solve_lds_batch<0>, dim3(1, n), dim3(kCholLdsThreads), ldsChol, s, dSlots, dpad, 1, 0, (const double*)nullptr);
-    const int nLm = min((p.L + 15) / 16, 1024);
-    const int nFacP = p.F > 0 ? min((p.F + 3) / 4, 1024) : 0;
-    if (p.anyExtVariable) launch(k_post_solve_batch<true>, dim3(nLm + nFacP + 1, n), dim3(256), 0, s, dSlots, nLm, nFacP);
-    else launch(k_post_solve_batch<false>, dim3(nLm + nFacP + 1, n), dim3(256), 0, s, dSlots, nLm, nFacP);
+    if (p.anyExtVariable) launch(k_post_solve_batch<true>, dim3(grid.post, n), dim3(256), 0, s, dSlots);
+    else launch(k_post_solve_batch<false>, dim3(grid.post, n), dim3(256), 0, s, dSlots);
   }
-  if (stagesUnion & kBatchReuse) {
-    const int nB = (p.nPose + p.nExt + p.nSb + p.L + 255) / 256;
-    launch(k_step_retract_batch, dim3(nB, n), dim3(256), 0, s, dSlots);
-  }
+  if (stagesUnion & kBatchReuse) launch(k_step_retract_batch, dim3(grid.step, n), dim3(256), 0, s, dSlots);
   if (stagesUnion & kBatchEval) {
-    const int nR = (p.N + 255) / 256, pri = p.priorM > 0 ? 1 : 0;
     const size_t stage = evalSplitStageBytes(p);
-    if (p.anyExtVariable) launch(k_eval_reproj_batch<true>, dim3(nR, n), dim3(256), stage, s, dSlots, cand ? 1 : 0);
-    else launch(k_eval_reproj_batch<false>, dim3(nR, n), dim3(256), stage, s, dSlots, cand ? 1 : 0);
-    launch(k_eval_rest_batch, dim3(p.F + pri, n), dim3(256), 0, s, dSlots, cand ? 1 : 0, nR, pri);
+    if (p.anyExtVariable) launch(k_eval_reproj_batch<true>, dim3(grid.evalR, n), dim3(256), stage, s, dSlots, cand ? 1 : 0);
+    else launch(k_eval_reproj_batch<false>, dim3(grid.evalR, n), dim3(256), stage, s, dSlots, cand ? 1 : 0);
+    launch(k_eval_rest_batch, dim3(grid.evalRest, n), dim3(256), 0, s, dSlots, cand ? 1 : 0);
   }
 }
 

@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 #include "dmath.hpp"
 #include "options.hpp"
+#include "batch_plan.hpp"
 
 namespace svin {
 
@@ -237,23 +238,27 @@ struct DeviceProblem {
   const double* lossTab;   // reprojection loss table: (kind, a) per selector of the packed index; nullptr = every selector 0 (CauchyLoss(1))
 };
 
-// ---- batched solve (svin_ba_solve_prepared_batch: B independent windows of equal launch geometry through ONE launch sequence per
-// trust-region round, the window as blockIdx.y).  One slot per window, refilled by the host every round: the window's problem as
-// it stands (buffer sets swapped by its accepted steps, mailbox sequence number of this round's evaluation) and the scalars its
-// own trust region hands the kernels; `stages` says which launches of the round the window takes part in.
-enum : int { kBatchFull = 1,    // build + reduced solve + post-solve pass with the fused dogleg step (a fresh linearisation)
-             kBatchReuse = 2,   // k_step_retract only (a rejected step: smaller radius on the same Gauss-Newton / Cauchy pair)
-             kBatchEval = 4 };  // the candidate (or initial) evaluation
+// ---- batched solve (svin_ba_solve_prepared_batch: B independent windows through ONE launch sequence per trust-region round, the
+// window as blockIdx.y).  The windows of a batch agree in what the launcher computes once per launch (batch_plan.hpp
+// BatchGroupFields: reduced system, factors, prior, cameras); their landmark and observation counts may differ.  One slot per
+// window, refilled by the host every round: the window's problem as it stands (buffer sets swapped by its accepted steps,
+// mailbox sequence number of this round's evaluation), the scalars its own trust region hands the kernels, and the window's
+// OWN extent of every launch (`ext`: the grid the single-window launcher would take) -- a block finds its role from it and leaves
+// at once when blockIdx.x lies beyond it; `stages` (kBatchFull / kBatchReuse / kBatchEval) says which launches of the round the
+// window takes part in.
 struct BatchSlot {
   DeviceProblem p;
   double mu, radius;
   int initScale, stages;
+  BatchExtents ext;
 };
+inline BatchDims batchDimsOf(const DeviceProblem& p) { return BatchDims{p.L, p.N, p.F, p.nPose, p.nExt, p.nSb, p.priorM, p.ownsCamera, p.nSlabs}; }
 void releaseSideLane(hipStream_t s);   // frees the side stream / events kernels.hip keeps for solver stream `s` (before `s` is destroyed)
 bool batchSupported(const DeviceProblem& p);   // the geometry the batched kernels cover (otherwise the window is solved on its own)
-// one round for the `n` windows of dSlots (device copy of the slot table); `geom` = any window of the batch (equal geometry),
+// one round for the `n` windows of dSlots (device copy of the slot table); `geom` = any window of the batch (what the launcher reads
+// of it is equal in all of them), `grid` = gridDim.x of every launch (the largest extent among the windows taking part),
 // `stagesUnion` = OR of the slots' stages, `cand` as for launchEvalAll
-void launchBatchRound(const BatchSlot* dSlots, const DeviceProblem& geom, int n, int stagesUnion, bool cand, hipStream_t s);
+void launchBatchRound(const BatchSlot* dSlots, const DeviceProblem& geom, const BatchGrid& grid, int n, int stagesUnion, bool cand, hipStream_t s);
 int schurDenseABlocks(const DeviceProblem& p);   // DeviceProblem::aBlocks as launchAccumulateNormalEquations chooses it
 // Which landmark-elimination form launchAccumulateNormalEquations launched last in this process (read-only inspection field,
 // svin_ba_debug_get_option("SVIN_LAST_SCHUR_FORM")): 0 none yet; 1000 + 10 MAXT + a for k_schur_dense<MAXT, ...> (a = 0: A in per-wave

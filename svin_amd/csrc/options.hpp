@@ -45,6 +45,10 @@ enum DebugOption : int {
 int debugOption(DebugOption which);                        // current value (0 = off)
 int setDebugOption(const char* name, int value);           // by environment-variable name; 1, or 0 for an unknown name
 int debugOptionByName(const char* name, int* value);       // 1 and *value, or 0 for an unknown name
+// read-only inspection field "SVIN_LAST_BATCH_IDLE_PPM": of the blocks the last svin_ba_solve_prepared_batch launched in the kernels
+// whose grid differs from window to window, the share (parts per million) that left at once -- beyond their window's own extent, or
+// of a window sitting out the stage (window.cpp, batch_plan.hpp)
+int lastBatchIdlePpm();
 inline bool optOn(DebugOption which) { return debugOption(which) != 0; }
 
 }  // namespace svin

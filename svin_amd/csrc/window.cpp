@@ -87,6 +87,7 @@ int debugOption(DebugOption which) { return optionTable().v[which].load(std::mem
 int debugOptionByName(const char* name, int* value) {
   if (!name) return 0;
   if (std::strcmp(name, "SVIN_LAST_SCHUR_FORM") == 0) { if (value) *value = lastSchurForm(); return 1; }   // read-only: not in the table
+  if (std::strcmp(name, "SVIN_LAST_BATCH_IDLE_PPM") == 0) { if (value) *value = lastBatchIdlePpm(); return 1; }   // read-only (options.hpp)
   OptionTable& t = optionTable();
   for (int k = 0; k < kOptCount; ++k)
     if (std::strcmp(t.name[k], name) == 0) { if (value) *value = t.v[k].load(std::memory_order_relaxed); return 1; }
@@ -1923,7 +1924,7 @@ void Window::pack(bool solveFollows) {
   // dense Gram-matrix Schur complement on MFMA
   const bool schurDense = dC > 0 && dC + 2 <= 256 && poseIds_.size() <= (size_t)kDensePoseCap && !optOn(kOptSchurPairwise);
   if (schurDense) {
-    nSlabs = std::max(1, std::min(256, (L + 15) / 16));
+    nSlabs = denseSlabCount(L);   // (batch_plan.hpp)
     // SVIN_SLAB_CHUNKS=n: n chunks of 16 landmarks per workgroup and private slab (default 1 up to 256 workgroups)
     if (debugOption(kOptSlabChunks) > 1) nSlabs = std::max(1, std::min(nSlabs, ((L + 15) / 16 + debugOption(kOptSlabChunks) - 1) / debugOption(kOptSlabChunks)));
   }
@@ -2650,7 +2651,7 @@ void Window::swapStateSets() {
 // SURVEY 8(e)'s "independent replicas processing different windows" on ONE GPU: a 10-keyframe window keeps 1-3 % of the chip
 // busy (five launches of 10-30 us per iteration, the solver one workgroup), and eight handles on eight streams only reach
 // 1.6 x one handle -- launch rate and hardware queues.  Here the windows of a batch share the launches: per trust-region ROUND one
-// slot table goes to the device (every window's problem as it stands and the scalars of its own trust region, 816 bytes each)
+// slot table goes to the device (every window's problem as it stands, the scalars of its own trust region and its extents, some 850 bytes each)
 // and at most six launches follow with the window as blockIdx.y.  The host keeps one TrustRegionHost per window and takes each
 // window's decision from its own mailbox record exactly as solve() does; a window whose step was rejected takes the round's
 // k_step_retract launch instead of the build / solve / post-solve launches, a window that has terminated takes none.  No
@@ -2658,24 +2659,31 @@ void Window::swapStateSets() {
 // chip busy, so the builds of steps that end up rejected are work added, not latency hidden.  For the same reason issuing the initial
 // evaluation and the first round together (two slot tables, two mailbox records in flight; one host turnaround of eleven saved)
 // gains nothing: 6.8 x against 7.1 x at B = 16, 8.3 / 9.0 x at 32 / 64 either way -- measured, not kept.  The arithmetic of a window is the
-// arithmetic of solve(): same kernels bodies, same grids (gridDim.x), same reduction orders.
+// arithmetic of solve(): same kernels bodies, same grids, same reduction orders.
+// Which windows share a launch sequence, the extent of every launch per window and the cut into lanes: batch_plan.hpp.  The
+// landmark and observation counts -- what the front end decides anew every frame and on every vehicle -- do not separate windows:
+// each brings its own extents in its slot, the lanes are cut by size.
 namespace {
-struct BatchKey {
-  int v[18];
-  bool operator<(const BatchKey& o) const { return std::lexicographical_compare(v, v + 18, o.v, o.v + 18); }
-};
-BatchKey batchKeyOf(const DeviceProblem& p) {
-  // what the grids, the LDS sizes and the uniform kernel arguments of launchBatchRound are computed from (L and N themselves may
-  // differ: every kernel reads them from its window's problem)
-  return BatchKey{{p.d, p.dC, p.dCPose, (p.L + 15) / 16, (p.N + 255) / 256, p.F, p.nPose, p.nExt, p.nSb, (p.nPose + p.nExt + p.nSb + p.L + 255) / 256,
-                   p.nSlabs, p.priorM, p.anyExtVariable, p.ldS, p.sPadded, p.priorBlocks, p.nCam /* (staging area of the evaluation) */, p.schurDense}};
+BatchGroupKey batchKeyOf(const DeviceProblem& p) {
+  // what the kernel variants, the LDS sizes and the uniform kernel arguments of launchBatchRound are computed from
+  return batchGroupKey(BatchGroupFields{p.d, p.dC, p.dCPose, p.F, p.nPose, p.nExt, p.nSb, p.priorM, p.anyExtVariable, p.ldS, p.sPadded, p.priorBlocks,
+                                        p.nCam, p.schurDense});
 }
+// blocks of the extent-carrying launches of the last svin_ba_solve_prepared_batch: all of them, and those that left at once
+// (beyond their window's extent, or of a window sitting out the stage)
+std::atomic<long long> gBatchBlocksLaunched{0}, gBatchBlocksIdle{0};
 }  // namespace
+int lastBatchIdlePpm() {
+  const long long n = gBatchBlocksLaunched.load(std::memory_order_relaxed), idle = gBatchBlocksIdle.load(std::memory_order_relaxed);
+  return n > 0 ? (int)(1000000.0 * (double)idle / (double)n + 0.5) : 0;
+}
 
 int Window::solvePreparedBatch(Window* const* ws, int n, size_t numIter, bool verbose, int* nBatched) {
   if (nBatched) *nBatched = 0;
   if (n <= 0) return 1;
-  std::map<BatchKey, std::vector<Window*>> groups;
+  gBatchBlocksLaunched.store(0, std::memory_order_relaxed);
+  gBatchBlocksIdle.store(0, std::memory_order_relaxed);
+  std::map<BatchGroupKey, std::vector<Window*>> groups;
   std::vector<Window*> alone;
   for (int i = 0; i < n; ++i) {
     Window* w = ws[i];
@@ -2712,23 +2720,29 @@ static hipStream_t laneStream(int device, int k) {
   return v[(size_t)k];
 }
 
-void Window::solveBatchGroup(const std::vector<Window*>& g, size_t numIter, bool verbose) {
+void Window::solveBatchGroup(const std::vector<Window*>& group, size_t numIter, bool verbose) {
   const double tStart = nowSec();
-  const int B = (int)g.size();
-  HIP_OK(hipSetDevice(g[0]->device_));
-  for (Window* w : g) HIP_OK(hipStreamSynchronize(w->stream_));   // uploads / earlier work of every window: done before a shared stream reads them
+  const int B = (int)group.size();
+  HIP_OK(hipSetDevice(group[0]->device_));
+  for (Window* w : group) HIP_OK(hipStreamSynchronize(w->stream_));   // uploads / earlier work of every window: done before a shared stream reads them
   // LANES: the windows are cut into up to kLanes sub-batches, each with the stream and the slot table of its first window.  The
   // reduced solve (one workgroup per window, 30 us) and a re-preintegrating IMU factor (one workgroup, 50 us) are latency, not
   // work: while one lane sits in them the launches of the other lanes fill the chip.  The host serves the lanes round robin --
   // collect a lane's mailbox records, take its windows' decisions, issue its next round, go on to the next lane.
-  int nLanes = debugOption(kOptBatchLanes) > 0 ? debugOption(kOptBatchLanes) : 4;
-  nLanes = std::max(1, std::min(nLanes, B / 2));
+  // A lane's grid is as large as its largest window: the group is sorted by size and the lanes are contiguous runs of that order
+  // (batch_plan.hpp planBatchLanes; windows of equal size keep the order of the call).  `g` = the group in lane order.
+  std::vector<BatchDims> dims;
+  for (Window* w : group) dims.push_back(batchDimsOf(w->prob_));
+  const BatchLanePlan plan = planBatchLanes(dims, debugOption(kOptBatchLanes) > 0 ? debugOption(kOptBatchLanes) : 4);
+  std::vector<Window*> g;
+  for (int i : plan.order) g.push_back(group[(size_t)i]);
+  const int nLanes = (int)plan.lanes.size();
   struct Lane { int first = 0, count = 0; Window* lead = nullptr; hipStream_t s = nullptr; BatchSlot* hs = nullptr; bool cand = false, done = false; };
   std::vector<Lane> lanes((size_t)nLanes);
   for (int k = 0; k < nLanes; ++k) {
     Lane& ln = lanes[(size_t)k];
-    ln.first = (int)((long long)B * k / nLanes);
-    ln.count = (int)((long long)B * (k + 1) / nLanes) - ln.first;
+    ln.first = plan.lanes[(size_t)k].first;
+    ln.count = plan.lanes[(size_t)k].count;
     ln.lead = g[(size_t)ln.first];
     ln.s = nLanes > 1 ? laneStream(g[0]->device_, k) : ln.lead->stream_;
     ln.lead->batchSlotsDev_.reserve((size_t)ln.count);
@@ -2752,8 +2766,11 @@ void Window::solveBatchGroup(const std::vector<Window*>& g, size_t numIter, bool
     st[i].tr.maxIterations = (int)numIter;
   }
   // one round of a lane: the slots of its windows that take part -> device, the launches; false if no window takes part
+  long long blocksLaunched = 0, blocksIdle = 0;
   auto issue = [&](Lane& ln, bool cand) -> bool {
     int uni = 0;
+    BatchGrid grid;
+    long long busy = 0;
     for (int k = 0; k < ln.count; ++k) {
       const int i = ln.first + k;
       Window* w = g[i];
@@ -2770,12 +2787,17 @@ void Window::solveBatchGroup(const std::vector<Window*>& g, size_t numIter, bool
       p.lmDeferred = 0;
       sl.mu = tr.mu; sl.radius = tr.radius; sl.initScale = tr.initScale ? 1 : 0;
       sl.stages = !cand ? kBatchEval : (tr.reuse ? (kBatchReuse | kBatchEval) : (kBatchFull | kBatchEval));
+      sl.ext = batchExtentsOf(batchDimsOf(sl.p));
+      grid.include(sl.ext, sl.stages);
+      busy += batchBusyBlocks(sl.ext, sl.stages);
       uni |= sl.stages;
     }
     ln.cand = cand;
     if (!uni) return false;
     HIP_OK(hipMemcpyAsync(ln.lead->batchSlotsDev_.p, ln.hs, sizeof(BatchSlot) * (size_t)ln.count, hipMemcpyHostToDevice, ln.s));
-    launchBatchRound(ln.lead->batchSlotsDev_.p, ln.lead->prob_, ln.count, uni, cand, ln.s);
+    launchBatchRound(ln.lead->batchSlotsDev_.p, ln.lead->prob_, grid, ln.count, uni, cand, ln.s);
+    blocksLaunched += grid.blocks(uni) * ln.count;
+    blocksIdle += grid.blocks(uni) * ln.count - busy;
     return true;
   };
   auto toTr = [](const SolverScalars& r) {
@@ -2864,10 +2886,13 @@ void Window::solveBatchGroup(const std::vector<Window*>& g, size_t numIter, bool
     throw;
   }
   for (Lane& ln : lanes) HIP_OK(hipStreamSynchronize(ln.s));
+  gBatchBlocksLaunched.fetch_add(blocksLaunched, std::memory_order_relaxed);
+  gBatchBlocksIdle.fetch_add(blocksIdle, std::memory_order_relaxed);
   if (timing)
-    std::printf("[svin_ba batch] %d windows in %d lanes: %.1f us, %d lane rounds: wait %.1f us, collect %.1f us, issue %.1f us each\n", B, nLanes,
+    std::printf("[svin_ba batch] %d windows in %d lanes: %.1f us, %d lane rounds: wait %.1f us, collect %.1f us, issue %.1f us each, "
+                "%.1f %% of the launched blocks idle\n", B, nLanes,
                 1e6 * (nowSec() - tStart), nRounds, 1e6 * tWaitSum / std::max(1, nRounds), 1e6 * tCollect / std::max(1, nRounds),
-                1e6 * tIssue / std::max(1, nRounds));
+                1e6 * tIssue / std::max(1, nRounds), 100.0 * (double)blocksIdle / (double)std::max(1LL, blocksLaunched));
   for (Window* w : g) w->summary_.solve_time = nowSec() - tStart;
 }
 
