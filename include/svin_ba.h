@@ -450,6 +450,26 @@ int svin_ba_debug_reduced_solve(svin_ba* h, double mu, double* y, int cap_d);
 /* the same with the choice svin_ba_optimize makes: fuse_finalize != 0 applies the metric and the damping inside the solver's
  * load phase (the fused form every trust-region iteration runs), 0 is svin_ba_debug_reduced_solve. */
 int svin_ba_debug_reduced_solve_ex(svin_ba* h, double mu, int fuse_finalize, double* y, int cap_d);
+/* ONE trust-region iteration on a fresh linearisation with the launches svin_ba_optimize issues -- evaluation, build with damping
+ * mu (metric recomputed), reduced solve, post-solve pass, dogleg step with trust-region radius `radius`, candidate evaluation --
+ * and what the step is made of (tests of the post-solve pass and the step).  form: 0 what svin_ba_optimize chooses for this window,
+ * 1 step fused into the post-solve pass, which also moves the landmarks, 2 post-solve pass and the stand-alone step kernel (the
+ * pair a rejected step and SVIN_NO_FUSE_STEP take), 3 fused step with the landmarks moved inside the candidate evaluation.
+ * Outputs (any array may be NULL): scalars38 = the solver's scalar record after the candidate evaluation ([0] cost, [1..3] its
+ * parts, [4] |step|^2, [5] |x|^2, [6..7] spare, [8..15] gHatSq jgSq gnHatSq gDotGn jySq jvDotJy jvDotR jyDotR, [16..31] sharded
+ * gather slots, [32] gradMax, [33] failMax, [34] jdSq, [35] jdDotR, [36] dogleg step norm, [37] cholFail); y_c / v_c (d each): the
+ * Gauss-Newton and the scaled-gradient vector of the reduced system; y_l / v_l (3 L), landmark_candidates (4 L) and landmark_ids
+ * (L) in the device's landmark order; block_ids / block_kinds (0 pose, 1 extrinsics, 2 speed and biases) / block_candidates (9
+ * doubles per block, 7 used by a pose) for every block of the window, constant ones included; info8 = d, L, number of blocks, the
+ * form that ran (1 / 2 / 3), landmark and factor blocks of the post-solve launch, blocks of the step launch, the form
+ * svin_ba_optimize chooses.  commit != 0: the step is then accepted the way svin_ba_optimize accepts one and the host copies are
+ * brought up to date (the getters return the candidate).
+ * Returns 1; 0 if a capacity is too small (info8 is filled: call again with d, L and the block count); SVIN_ERR_UNSUPPORTED for a
+ * form this window cannot take (no other form runs in its place) and for a sharded handle. */
+int svin_ba_debug_trust_region_step(svin_ba* h, double mu, double radius, int form, int commit, double* scalars38, double* y_c,
+                                    double* v_c, int cap_d, double* y_l, double* v_l, double* landmark_candidates,
+                                    uint64_t* landmark_ids, int cap_landmarks, uint64_t* block_ids, int32_t* block_kinds,
+                                    double* block_candidates, int cap_blocks, int32_t* info8);
 /* Which path the handle's work took since it was created, so that no fall-back is silent: out[0] optimisations on the
  * device-resident window (per frame only the new / removed observation records travel), out[1] optimisations that
  * re-packed the whole window on the host (wide windows with their panel work lists, landmark priors, constant landmarks,

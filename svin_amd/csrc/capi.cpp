@@ -578,6 +578,17 @@ int svin_ba_debug_reduced_solve_ex(svin_ba* h, double mu, int fuse_finalize, dou
   GUARD_BEGIN return win(h).debugReducedSolve(mu, y, cap_d, fuse_finalize != 0);
   GUARD_END(SVIN_ERR_DEVICE)
 }
+int svin_ba_debug_trust_region_step(svin_ba* h, double mu, double radius, int form, int commit, double* scalars38, double* y_c,
+                                    double* v_c, int cap_d, double* y_l, double* v_l, double* landmark_candidates,
+                                    uint64_t* landmark_ids, int cap_landmarks, uint64_t* block_ids, int32_t* block_kinds,
+                                    double* block_candidates, int cap_blocks, int32_t* info8) {
+  if (!h || !info8) return SVIN_ERR_INVALID_ARG;
+  GUARD_BEGIN
+  Window::DebugStepOut o{scalars38, y_c, v_c, cap_d, y_l, v_l, landmark_candidates, landmark_ids, cap_landmarks,
+                         block_ids, block_kinds, block_candidates, cap_blocks, info8};
+  return win(h).debugTrustRegionStep(mu, radius, form, commit, o);
+  GUARD_END(SVIN_ERR_DEVICE)
+}
 int svin_ba_get_path_counters(svin_ba* h, int64_t out[4]) try {
   if (!h || !out) return SVIN_ERR_INVALID_ARG;
   const long long* c = ro(h).pathCounters();

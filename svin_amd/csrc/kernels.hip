@@ -25,6 +25,7 @@
 #include <string>
 #include <unordered_map>
 #include "tile16.hpp"
+#include "trust_region.hpp"
 
 #ifndef SVIN_BATCH_OCC_SCHUR
 #define SVIN_BATCH_OCC_SCHUR 2   // waves per SIMD the batched Schur / post-solve forms are held to (register budget 512 / n)
@@ -6731,30 +6732,7 @@ void launchSolveReduced(const DeviceProblem& p, hipStream_t s, double mu, bool i
 // traditional dogleg (ceres dogleg_strategy.cc) expressed on the un-scaled vectors:
 //   delta_i = cg * g_i/htil_i + cn * (-y_i)
 // J*delta is never formed: |J delta|^2 and (J delta).r follow from group B by linearity.
-struct DoglegCoeff { double cg, cn, stepNorm, jdSq, jdDotR; };
-__device__ __forceinline__ DoglegCoeff doglegCoefficients(double gHatSq, double jgSq, double gnHatSq, double gDotGn,
-                                                          double jySq, double jvDotJy, double jvDotR, double jyDotR,
-                                                          double radius) {
-  const double gnorm = sqrt(gHatSq), gnnorm = sqrt(gnHatSq);
-  const double alpha = gHatSq / jgSq;
-  DoglegCoeff c;
-  if (gnnorm <= radius) { c.cg = 0; c.cn = 1; c.stepNorm = gnnorm; }
-  else if (gnorm * alpha >= radius) { c.cg = -(radius / gnorm); c.cn = 0; c.stepNorm = radius; }
-  else {
-    const double b_dot_a = -alpha * gDotGn;
-    const double a_sq = (alpha * gnorm) * (alpha * gnorm);
-    const double b_minus_a_sq = a_sq - 2 * b_dot_a + gnnorm * gnnorm;
-    const double cc = b_dot_a - a_sq;
-    const double dd = sqrt(cc * cc + b_minus_a_sq * (radius * radius - a_sq));
-    const double beta = (cc <= 0) ? (dd - cc) / b_minus_a_sq : (radius * radius - a_sq) / (dd + cc);
-    c.cg = -alpha * (1.0 - beta);
-    c.cn = beta;
-    c.stepNorm = sqrt(fmax(c.cg * c.cg * gHatSq + 2 * c.cg * c.cn * gDotGn + c.cn * c.cn * gnHatSq, 0.0));
-  }
-  c.jdSq = c.cg * c.cg * jgSq - 2.0 * c.cg * c.cn * jvDotJy + c.cn * c.cn * jySq;
-  c.jdDotR = c.cg * jvDotR - c.cn * jyDotR;
-  return c;
-}
+// (DoglegCoeff / doglegCoefficients: trust_region.hpp, where a CPU test reaches the very same expressions)
 // candidate = x [+] delta for item i (variable blocks first, then landmarks); acc += |x - x_cand|^2, |x|^2
 // poseOplus (dmath.hpp) with the device exponential and one reciprocal per normalisation
 __device__ __forceinline__ void poseOplusDev(const double* x, const double* delta, double* xo) {

@@ -11,7 +11,44 @@
 #include <algorithm>
 #include <cmath>
 
+// (as in dmath.hpp: the device functions of this header are the ones the kernels call, and g++ compiles them for the CPU tests)
+#ifndef SVIN_HD
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#define SVIN_HD __host__ __device__ __forceinline__
+#else
+#define SVIN_HD inline
+#endif
+#endif
+
 namespace svin {
+
+// Coefficients of the traditional dogleg step (ceres dogleg_strategy.cc) on the un-scaled vectors, delta = cg v + cn (-y), from
+// group B of SolverScalars and the radius; |J delta|^2 and (J delta).r follow from group B by linearity.  Called by k_post_solve
+// (fused step) and k_step_retract (kernels.hip); tests/test_dogleg_host.py holds it against mpmath through the shim.
+struct DoglegCoeff { double cg, cn, stepNorm, jdSq, jdDotR; };
+SVIN_HD DoglegCoeff doglegCoefficients(double gHatSq, double jgSq, double gnHatSq, double gDotGn,
+                                       double jySq, double jvDotJy, double jvDotR, double jyDotR, double radius) {
+  const double gnorm = sqrt(gHatSq), gnnorm = sqrt(gnHatSq);
+  const double alpha = gHatSq / jgSq;
+  DoglegCoeff c;
+  if (gnnorm <= radius) { c.cg = 0; c.cn = 1; c.stepNorm = gnnorm; }
+  else if (gnorm * alpha >= radius) { c.cg = -(radius / gnorm); c.cn = 0; c.stepNorm = radius; }
+  else {
+    const double b_dot_a = -alpha * gDotGn;
+    const double a_sq = (alpha * gnorm) * (alpha * gnorm);
+    const double b_minus_a_sq = a_sq - 2 * b_dot_a + gnnorm * gnnorm;
+    const double cc = b_dot_a - a_sq;
+    const double dd = sqrt(cc * cc + b_minus_a_sq * (radius * radius - a_sq));
+    const double beta = (cc <= 0) ? (dd - cc) / b_minus_a_sq : (radius * radius - a_sq) / (dd + cc);
+    c.cg = -alpha * (1.0 - beta);
+    c.cn = beta;
+    c.stepNorm = sqrt(fmax(c.cg * c.cg * gHatSq + 2 * c.cg * c.cn * gDotGn + c.cn * c.cn * gnHatSq, 0.0));
+  }
+  c.jdSq = c.cg * c.cg * jgSq - 2.0 * c.cg * c.cn * jvDotJy + c.cn * c.cn * jySq;
+  c.jdDotR = c.cg * jvDotR - c.cn * jyDotR;
+  return c;
+}
 
 // the fields of SolverScalars the host reads (kernels.hpp); rank-invariant in sharded mode
 struct TrScalars {

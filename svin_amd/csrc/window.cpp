@@ -3109,6 +3109,88 @@ int Window::debugReducedSolve(double mu, double* y, int capD, bool fuseFinalize)
   HIP_OK(hipStreamSynchronize(stream_));
   return p.d;
 }
+// inspection hook: ONE trust-region iteration on a fresh linearisation, with the launches solve() issues -- build, reduced solve,
+// post-solve pass, dogleg step in the requested form, candidate evaluation -- and everything the step is made of read back, for
+// the tests to hold against a long-double reference (tests/helpers/step_reference.py).  form: 0 what solve() chooses for this
+// window, 1 the fused step with the landmarks moved by k_post_solve's tail, 2 k_post_solve without a radius + k_step_retract,
+// 3 the fused step with the landmarks moved by the candidate evaluation.  A form the window cannot take is an error, never another form.
+int Window::debugTrustRegionStep(double mu, double radius, int form, int commit, const DebugStepOut& o) {
+  distNative_ = false;
+  if (form < 0 || form > 3 || !(radius > 0.0) || !o.info) return -1 /* SVIN_ERR_INVALID_ARG */;
+  if (world_ > 1 || rcclComm_) return -4 /* SVIN_ERR_UNSUPPORTED */;   // (the sharded step has all-reduces between these launches: solve() only)
+  pack();
+  DeviceProblem& p = prob_;
+  hipStream_t s = stream_;
+  const int nBlk = (int)(poseIds_.size() + extIds_.size() + sbIds_.size());
+  // the choice of solve()
+  const bool deferPossible = canFuseEvaluation(p) && !optOn(kOptSplitEval) && !optOn(kOptNoDeferLm) && p.L > 0 && p.N > 0;
+  const bool small = (p.nPose + p.nExt + p.nSb + p.L) <= 16384;
+  const bool fuseStep = !optOn(kOptNoFuseStep) && (small || deferPossible);
+  const int chosen = fuseStep ? (deferPossible ? 3 : 1) : 2;
+  const int run = form == 0 ? chosen : form;
+  o.info[0] = p.d; o.info[1] = p.L; o.info[2] = nBlk; o.info[3] = run;
+  o.info[4] = postLmBlockCount(p.L, p.N); o.info[5] = postFacBlockCount(p.F); o.info[6] = stepBlockCount(p.nPose, p.nExt, p.nSb, p.L);
+  o.info[7] = chosen;
+  if (p.d + 3 * p.L == 0) return -4 /* SVIN_ERR_UNSUPPORTED */;
+  if (run == 3 && !deferPossible) return -4 /* SVIN_ERR_UNSUPPORTED */;
+  if (run == 1 && !small) return -4 /* SVIN_ERR_UNSUPPORTED */;   // (one workgroup moves every landmark: solve() never asks that of more)
+  if (p.d > o.capD || p.L > o.capL || nBlk > o.capBlocks) return 0;   // sizes only
+  {
+    struct SbEarlyGuard { DeviceProblem& q; ~SbEarlyGuard() { q.sideLane = 0; q.lmDeferred = 0; } } guard{p};
+    p.sideLane = optOn(kOptNoSbEarly) ? 0 : 1;
+    evaluateAll(false, s);
+    launchAccumulateNormalEquations(p, mu, true, s, /*zeroFirst=*/true);
+    launchSolveReduced(p, s, mu, true, /*fuseFinalize=*/true);
+    p.lmDeferred = run == 3 ? 1 : 0;
+    launchDoglegPrepare(p, s, run == 2 ? -1.0 : radius);
+    if (run == 2) launchDoglegStep(p, radius, s);
+    evaluateAll(true, s);
+    p.lmDeferred = 0;
+  }
+  const SolverScalars sc = readScalars();
+  HIP_OK(hipStreamSynchronize(s));
+  if (o.scalars) {
+    static_assert(sizeof(SolverScalars) == 38 * sizeof(double), "svin_ba_debug_trust_region_step lays the record out as 38 doubles");
+    std::memcpy(o.scalars, &sc, 37 * sizeof(double));
+    o.scalars[37] = (double)sc.cholFail;
+  }
+  if (p.d > 0) {
+    if (o.yC) HIP_OK(hipMemcpy(o.yC, p.yC, sizeof(double) * p.d, hipMemcpyDeviceToHost));
+    if (o.vC) HIP_OK(hipMemcpy(o.vC, p.vC, sizeof(double) * p.d, hipMemcpyDeviceToHost));
+  }
+  if (p.L > 0) {
+    if (o.yL) HIP_OK(hipMemcpy(o.yL, p.yL, sizeof(double) * 3 * p.L, hipMemcpyDeviceToHost));
+    if (o.vL) HIP_OK(hipMemcpy(o.vL, p.vL, sizeof(double) * 3 * p.L, hipMemcpyDeviceToHost));
+    if (o.lmCand) HIP_OK(hipMemcpy(o.lmCand, p.lmC, sizeof(double) * 4 * p.L, hipMemcpyDeviceToHost));
+    if (o.lmIds) {   // device order: observationIds()
+      int l = 0;
+      if (residentUsed_) { for (const Landmark* lp : lmByHandle_) if (lp && !lp->obs.empty() && l < p.L) o.lmIds[l++] = lp->id; }
+      else for (uint64_t id : lmIds_) if (l < p.L) o.lmIds[l++] = id;
+      if (l != p.L) throw std::logic_error("debugTrustRegionStep: landmark table and device count disagree");
+    }
+  }
+  if (o.blockCand) {
+    std::vector<double> hPose(poseIds_.size() * 7), hExt(extIds_.size() * 7), hSb(sbIds_.size() * 9);
+    if (!hPose.empty()) HIP_OK(hipMemcpy(hPose.data(), p.poseC, sizeof(double) * hPose.size(), hipMemcpyDeviceToHost));
+    if (!hExt.empty()) HIP_OK(hipMemcpy(hExt.data(), p.extC, sizeof(double) * hExt.size(), hipMemcpyDeviceToHost));
+    if (!hSb.empty()) HIP_OK(hipMemcpy(hSb.data(), p.sbC, sizeof(double) * hSb.size(), hipMemcpyDeviceToHost));
+    int k = 0;
+    auto put = [&](uint64_t id, int kind, const double* x, int len) {
+      if (o.blockIds) o.blockIds[k] = id;
+      if (o.blockKind) o.blockKind[k] = kind;
+      for (int a = 0; a < 9; ++a) o.blockCand[9 * k + a] = a < len ? x[a] : 0.0;
+      ++k;
+    };
+    for (size_t i = 0; i < poseIds_.size(); ++i) put(poseIds_[i], 0, &hPose[7 * i], 7);
+    for (size_t i = 0; i < extIds_.size(); ++i) put(extIds_[i], 1, &hExt[7 * i], 7);
+    for (size_t i = 0; i < sbIds_.size(); ++i) put(sbIds_[i], 2, &hSb[9 * i], 9);
+  }
+  if (commit) {   // an accepted step of solve(), then what optimize() does behind its solve
+    swapStateSets();
+    downloadStates();
+  }
+  return 1;
+}
 // inspection hook: doubles [off, off + count) of the reduced-system solver's scratch buffer (the factor, the eliminated chain's
 // records and Y: layout in kernels.hip, launchSolveReduced) after the last solve
 int Window::debugPeekSolverScratch(uint64_t off, uint64_t count, double* out) {

@@ -335,6 +335,15 @@ class Window {
   const long long* pathCounters() const { return pathCounters_; }
   int debugReducedSolve(double mu, double* y, int capD, bool fuseFinalize = false);
   int debugPeekSolverScratch(uint64_t off, uint64_t count, double* out);
+  // one trust-region iteration with everything the step is made of read back (window.cpp); the arrays may be null
+  struct DebugStepOut {
+    double* scalars;                               // 38: SolverScalars after the candidate evaluation, cholFail last
+    double *yC, *vC; int capD;                     // d each
+    double *yL, *vL, *lmCand; uint64_t* lmIds; int capL;   // 3 L, 3 L, 4 L, L: device landmark order
+    uint64_t* blockIds; int32_t* blockKind; double* blockCand; int capBlocks;   // pose, extrinsics, speed / bias slots: 9 doubles each
+    int32_t* info;                                 // 8: d, L, blocks, form that ran, post-solve landmark / factor blocks, step blocks, solve()'s form
+  };
+  int debugTrustRegionStep(double mu, double radius, int form, int commit, const DebugStepOut& out);
   int getPrior(double* H, double* b0, double* J, double* e0, uint64_t* ids, int32_t* ord, int32_t* mdim,
                int32_t* nBlocks, int capM);
   int describeBlock(uint64_t id, uint64_t* frame, int32_t* kind, int32_t* index) const;

@@ -56,7 +56,7 @@ EXPORTS = [
     "svin_ba_set_camera_sensor_states", "svin_ba_set_landmark", "svin_ba_num_frames", "svin_ba_num_landmarks",
     "svin_ba_current_keyframe_id", "svin_ba_current_frame_id", "svin_ba_frame_id_by_age", "svin_ba_is_keyframe",
     "svin_ba_is_in_imu_window", "svin_ba_frame_ids", "svin_ba_landmark_ids", "svin_ba_imu_propagation",
-    "svin_ba_eval_reprojection", "svin_ba_observation_ids", "svin_ba_eval_factors", "svin_ba_linearize", "svin_ba_debug_reduced_solve", "svin_ba_debug_reduced_solve_ex", "svin_ba_debug_set_switch", "svin_ba_debug_set_option", "svin_ba_debug_get_option", "svin_ba_debug_sym_eig", "svin_ba_get_path_counters", "svin_ba_wait_idle", "svin_ba_debug_peek_solver_scratch",
+    "svin_ba_eval_reprojection", "svin_ba_observation_ids", "svin_ba_eval_factors", "svin_ba_linearize", "svin_ba_debug_reduced_solve", "svin_ba_debug_reduced_solve_ex", "svin_ba_debug_trust_region_step", "svin_ba_debug_set_switch", "svin_ba_debug_set_option", "svin_ba_debug_get_option", "svin_ba_debug_sym_eig", "svin_ba_get_path_counters", "svin_ba_wait_idle", "svin_ba_debug_peek_solver_scratch",
     "svin_ba_get_prior", "svin_ba_describe_block", "svin_ba_bench_jacobian_eval", "svin_ba_bench_jacobian_eval_b2b", "svin_ba_set_pack_mode", "svin_ba_debug_csr", "svin_ba_residual_info",
     "svin_ba_map_add_parameter_block", "svin_ba_set_parameter_block", "svin_ba_map_remove_parameter_block", "svin_ba_map_add_pose_error",
     "svin_ba_map_add_speed_and_bias_error", "svin_ba_map_add_relative_pose_error", "svin_ba_map_add_reprojection_error",
@@ -165,6 +165,7 @@ def load_library():
     sig("svin_ba_linearize", i32, vp, f64, pd, pd, pu64, pi32, pi32, i32, pd)
     sig("svin_ba_debug_reduced_solve", i32, vp, f64, pd, i32)
     sig("svin_ba_debug_reduced_solve_ex", i32, vp, f64, i32, pd, i32)
+    sig("svin_ba_debug_trust_region_step", i32, vp, f64, f64, i32, i32, pd, pd, pd, i32, pd, pd, pd, pu64, i32, pu64, pi32, pd, i32, pi32)
     sig("svin_ba_debug_set_switch", i32, C.c_char_p, i32)
     sig("svin_ba_debug_set_option", i32, C.c_char_p, i32)
     sig("svin_ba_debug_get_option", i32, C.c_char_p, pi32)
@@ -789,6 +790,36 @@ class Estimator:
         y = np.zeros(cap)
         d = self._check(self.L.svin_ba_debug_reduced_solve_ex(self.h, float(mu), 1 if fused else 0, _d(y), cap), "debug_reduced_solve")
         return y[:d].copy()
+
+    SCALAR_FIELDS = ("cost", "costReproj", "costFactors", "costPrior", "stepNormSq", "xNormSq", "spareA0", "spareA1",
+                     "gHatSq", "jgSq", "gnHatSq", "gDotGn", "jySq", "jvDotJy", "jvDotR", "jyDotR")
+    STEP_FORM_SOLVE, STEP_FORM_FUSED, STEP_FORM_SEPARATE, STEP_FORM_DEFERRED = 0, 1, 2, 3
+
+    def debug_trust_region_step(self, mu, radius, form=0, commit=False):
+        """one trust-region iteration as optimize() runs it (include/svin_ba.h: svin_ba_debug_trust_region_step) -> dict with the
+        scalar record by field name (`scalars`), y_C, v_C, y_L, v_L, lm_ids, lm_cand, block_ids, block_kind, block_cand (list of
+        arrays of 7 / 9), form (the one that ran), form_solve (the one optimize() chooses), post_lm_blocks, post_fac_blocks,
+        step_blocks.  A form the window cannot take raises."""
+        info = np.zeros(8, np.int32)
+        rc = self.L.svin_ba_debug_trust_region_step(self.h, float(mu), float(radius), int(form), 0, None, None, None, 0, None, None,
+                                                    None, None, 0, None, None, None, 0, info.ctypes.data_as(pi32))
+        if rc < 0:
+            self._check(rc, "debug_trust_region_step")
+        d, L, nb = int(info[0]), int(info[1]), int(info[2])
+        sc, yC, vC = np.zeros(38), np.zeros(max(d, 1)), np.zeros(max(d, 1))
+        yL, vL, lmC, lm_ids = np.zeros((max(L, 1), 3)), np.zeros((max(L, 1), 3)), np.zeros((max(L, 1), 4)), np.zeros(max(L, 1), np.uint64)
+        bids, bkind, bc = np.zeros(max(nb, 1), np.uint64), np.zeros(max(nb, 1), np.int32), np.zeros((max(nb, 1), 9))
+        rc = self.L.svin_ba_debug_trust_region_step(self.h, float(mu), float(radius), int(form), 1 if commit else 0, _d(sc), _d(yC), _d(vC), d,
+                                                    _d(yL), _d(vL), _d(lmC), lm_ids.ctypes.data_as(pu64), L, bids.ctypes.data_as(pu64),
+                                                    bkind.ctypes.data_as(pi32), _d(bc), nb, info.ctypes.data_as(pi32))
+        if self._check(rc, "debug_trust_region_step") != 1:
+            raise RuntimeError("debug_trust_region_step: sizes changed between two calls")
+        scal = dict(zip(self.SCALAR_FIELDS, sc[:16]))
+        scal.update(gather=sc[16:32].copy(), gradMax=sc[32], failMax=sc[33], jdSq=sc[34], jdDotR=sc[35], doglegStepNorm=sc[36], cholFail=int(sc[37]))
+        return dict(scalars=scal, d=d, L=L, y_C=yC[:d].copy(), v_C=vC[:d].copy(), y_L=yL[:L].copy(), v_L=vL[:L].copy(), lm_ids=lm_ids[:L].copy(),
+                    lm_cand=lmC[:L].copy(), block_ids=bids[:nb].copy(), block_kind=bkind[:nb].copy(),
+                    block_cand=[bc[i, :9 if bkind[i] == 2 else 7].copy() for i in range(nb)], form=int(info[3]), form_solve=int(info[7]),
+                    post_lm_blocks=int(info[4]), post_fac_blocks=int(info[5]), step_blocks=int(info[6]))
 
     def path_counters(self):
         """dict(resident_solves, host_pack_solves, device_gathered_marginalisations, host_assembled_marginalisations)"""

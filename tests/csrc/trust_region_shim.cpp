@@ -1,6 +1,6 @@
 // C entry points over svin_amd/csrc/trust_region.hpp (the host decisions of Window::solve) for tests/test_trust_region_host.py:
 // the state machine is HIP-free, so its rules are checked on the CPU -- including that two ranks fed the same all-reduced
-// numbers take the same decisions whatever their rank-local fields hold.
+// numbers take the same decisions whatever their rank-local fields hold.  Also the one device function of that header.
 #include "../../svin_amd/csrc/trust_region.hpp"
 
 extern "C" {
@@ -24,5 +24,11 @@ void tr_state(void* h, double* out) {
   auto* t = static_cast<svin::TrustRegionHost*>(h);
   out[0] = t->radius; out[1] = t->mu; out[2] = t->x_cost; out[3] = t->reuse; out[4] = t->initScale; out[5] = t->invalid;
   out[6] = t->iteration; out[7] = t->successful; out[8] = t->termination; out[9] = t->muAfterAccept();
+}
+// the dogleg coefficients the kernels compute (k_post_solve, k_step_retract): in = gHatSq jgSq gnHatSq gDotGn jySq jvDotJy jvDotR
+// jyDotR radius, out = cg cn stepNorm jdSq jdDotR  (tests/test_dogleg_host.py)
+void tr_dogleg(const double* in, double* out) {
+  const svin::DoglegCoeff c = svin::doglegCoefficients(in[0], in[1], in[2], in[3], in[4], in[5], in[6], in[7], in[8]);
+  out[0] = c.cg; out[1] = c.cn; out[2] = c.stepNorm; out[3] = c.jdSq; out[4] = c.jdDotR;
 }
 }

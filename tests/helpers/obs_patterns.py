@@ -161,6 +161,43 @@ def design(P, L, rig="euroc", seed=1, fixed_frame=None, wide=False, sparse_pairs
     return d
 
 
+def keep_tracks(spec, tracks):
+    """reduce a full window to exactly the planned observations"""
+    P = spec.P
+    key = (spec.obs_lm * P + spec.obs_frame) * 2 + spec.obs_cam
+    want = np.array(sorted((l * P + f) * 2 + c for l, t in tracks.items() for f, c in t), np.int64)
+    keep = np.isin(key, want)
+    assert keep.sum() == len(want), "a planned observation is not in the window"
+    for name in ("obs_lm", "obs_frame", "obs_cam", "obs_uv", "obs_size"):
+        setattr(spec, name, getattr(spec, name)[keep])
+    assert np.all(np.bincount(spec.obs_lm, minlength=spec.L) == [len(tracks[l]) for l in range(spec.L)])
+
+
+def design_track_lengths(P=17, lengths=(15, 16, 17, 31, 32, 33, 34), n_more=9, seed=1):
+    """narrow window whose first landmarks have tracks of exactly the given numbers of observations (the post-solve pass gives a
+    landmark sixteen lanes, each keeping its first observation in registers: one lane short, all lanes once, one lane twice, ...
+    two lanes a third time), followed by n_more landmarks with three to six; every pose is observed"""
+    assert max(lengths) <= 2 * P
+    L = len(lengths) + n_more
+    spec = full_window(P, L, "euroc", seed)
+    every = sorted((f, c) for f in range(P) for c in (0, 1))
+    tracks = {l: every[:n] for l, n in enumerate(lengths)}
+    for k in range(n_more):
+        tracks[len(lengths) + k] = every[(5 * k) % (2 * P - 6):][:3 + k % 4]
+    keep_tracks(spec, tracks)
+    assert set(spec.obs_frame.tolist()) == set(range(P))
+    return Design(spec=spec, tracks=tracks, roles={"lengths": list(range(len(lengths)))})
+
+
+def design_three_observations(L, P=3, seed=1):
+    """L landmarks with three observations each on P = 3 poses (one per pose, cameras alternating): the smallest window with a
+    given landmark count that can be linearised without damping"""
+    spec = full_window(P, L, "euroc", seed)
+    tracks = {l: [(f, (l + f) % 2) for f in range(P)] for l in range(L)}
+    keep_tracks(spec, tracks)
+    return Design(spec=spec, tracks=tracks, roles={"three": list(range(L))})
+
+
 def slots_of(d):
     """per landmark with observations on variable poses: sorted block indices (one slot per distinct variable pose)"""
     spec = d.spec

@@ -56,8 +56,9 @@ inverse plus 3 rows_l for the sum that forms V_l, up to ~800 for a track of 2 P 
 eps = 2^-52 (np.finfo(np.float64).eps).  The same bound with the long-double eps holds for this reference itself:
 its error is at most (eps_ld / eps) tol = 2^-11 tol, which `assemble` asserts to be below tol / 1000.
 
-Not covered by what is compared through this helper: the batched form (k_schur_dense_batch), the sharded path, windows with
-a marginalisation prior, and the landmark back-substitution in k_post_solve.
+Not covered by what is compared through this helper or through step_reference.py (the post-solve pass and the dogleg step, which
+build on it): the batched Schur form (k_schur_dense_batch), the sharded path, and a marginalisation prior away from its
+linearisation point (`prior` below is the prior AT that point).
 """
 import numpy as np
 
@@ -114,11 +115,15 @@ def _kappa(Vd):
     return float("inf") if not w[0] > 0 else float(w[-1] / w[0])
 
 
-def assemble(records, blocks, mu, dtype=LD):
+def assemble(records, blocks, mu, dtype=LD, prior=None):
     """records: iterable of (r, [(key, J), ...]) or (r, [(key, J), ...], cost_term); key = (kind, id), kind one of "p" pose,
     "e" extrinsics, "s" speed / bias, "l" landmark (at most one landmark per record); J is len(r) x (6 | 6 | 9 | 3).  A record's
     cost term is 0.5 |r|^2 unless given (a robustified residual's is 0.5 rho).
     blocks: [(key, offset, dim)] of the variable camera-side blocks, in the order and at the offsets of the system to compare with.
+    prior: None or (H, b0, c0, columns): the marginalisation prior as the quadratic form the device adds at the prior's linearisation
+    point -- H into A (and its diagonal into hC), b0 into the gradient, c0 into the cost; columns[i] = the row of the system that
+    row i of the prior belongs to, or -1 (a constant block).  One term per entry, M = |H|, |b0|.  A prior away from its
+    linearisation point (M3 != I, dchi != 0) is not covered.
     Returns a dict: S, g, cost (dtype), d, per landmark V / b / kappa (dicts by landmark id), M_S / n_S / M_g / n_g, the
     conditioning sums K_S / K_g, tol_S / tol_g / tol_cost (float64 arrays) and ref_ratio (the reference's own error / tol)."""
     T = dtype
@@ -160,6 +165,19 @@ def assemble(records, blocks, mu, dtype=LD):
             ng[idx] += m
         if lm is not None:
             by_lm.setdefault(lm, []).append((idx, Jc, Jl, r))
+    if prior is not None:
+        pc = np.asarray(prior[3])
+        sel = np.nonzero(pc >= 0)[0]
+        ix = np.ix_(pc[sel], pc[sel])
+        Hp, bp = np.asarray(prior[0], T)[np.ix_(sel, sel)], np.asarray(prior[1], T)[sel]
+        A[ix] += Hp
+        MA[ix] += np.abs(Hp)
+        nS[ix] += 1
+        gA[pc[sel]] += bp
+        Mg[pc[sel]] += np.abs(bp)
+        ng[pc[sel]] += 1
+        cost += T(prior[2])
+        n_cost += 1
     S, g = A.copy(), gA.copy()
     MS = MA.copy()
     KS, Kg = np.zeros((d, d), T), np.zeros(d, T)
