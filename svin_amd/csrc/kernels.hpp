@@ -22,11 +22,11 @@
 #include "dmath.hpp"
 #include "options.hpp"
 #include "batch_plan.hpp"
+#include "pack_plan.hpp"
 
 namespace svin {
 
 constexpr int kMaxCams = 8;
-constexpr int kDensePoseCap = 256;   // k_schur_dense stages the pose -> row map of at most this many poses in LDS
 constexpr int kPriorCam = 15;   // camera field of a packed index that marks a landmark-prior pseudo-observation (HomogeneousPointError)
 
 // packed per-observation index: pose slot (12 bit) | ext slot (12 bit) | camera (4 bit) | loss selector (4 bit, an entry of the
@@ -122,26 +122,8 @@ struct ScalarMailbox {
 constexpr int kCholFailSync = 4 | 8;
 constexpr int kScalGroupA = 0, kScalGroupB = 8, kScalGather = 16, kScalGatherSlots = 16;  // offsets (doubles) of the all-reduced groups
 
-// wide windows: 16-landmark chunks one workgroup of k_schur_panels works through (the host builds the work list: Window::pack).
-// Config #4 on one GPU, 8 / 12 / 16: k_schur_panels 523 / 545 / 551 us, k_reduce_panel_slabs (one 74 KB slab per workgroup) 45 / 25 /
-// 19 us -- a wash on one GPU, and a rank of an 8-GPU run has an eighth of the chunks: 8 keeps its ~210 workgroups from becoming ~105.
-#ifndef SVIN_PANEL_CHUNKS
-#define SVIN_PANEL_CHUNKS 8
-#endif
-constexpr int kPanelChunksPerBlock = SVIN_PANEL_CHUNKS;
-// block-pair form (round 6): entries (landmark x panel pair) per workgroup of k_schur_rows, its waves (the host deals the block
-// rows of a panel pair to them), records a batch stages in LDS (x 20 doubles = 160 bytes: two buffers of 36.8 KB, two workgroups
-// per CU; the last record of a buffer is never staged: all zero, the B operand of the padding pairs), pair words per wave and batch
-constexpr int kBlkMinWordsPerBlock = 1024;    // pair words per workgroup, at least (Window::pack cuts the work list by words)
-constexpr int kBlkWaves = 8;
-constexpr int kBlkBatchRecs = 230;
-constexpr int kBlkBatchWords = 128;
-constexpr int kBlkRec = 18;                   // doubles per slot record: E_la (6 x 3), rec[6 k + row]
-#ifndef SVIN_SLOTS_PER_WG
-#define SVIN_SLOTS_PER_WG 1024
-#endif
-constexpr int kBlkSlotsPerWorkgroup = SVIN_SLOTS_PER_WG;   // slots (one thread each, four trips) per workgroup of k_blocks_slots
-constexpr int kBlkMaxPoseBlocks = 512;      // the per-pose accumulators of k_blocks_slots live in LDS (28 doubles per pose block)
+// kPanelChunksPerBlock, kBlk* (the work lists of the wide-window Schur kernels) and kDensePoseCap: pack_plan.hpp, with the host
+// code that builds those lists
 
 struct DeviceProblem {
   // sizes
@@ -170,7 +152,7 @@ struct DeviceProblem {
   const int* slotObs;                        // observation numbers
   const int* slotLm;                         // per slot: its landmark
   double* slotRec;                           // per slot kBlkRec doubles, written once per build: E = (sum Jp^T Jl) L^-T (kernels.hip)
-  // work list of k_schur_rows (host-built, Window::pack): panelWork.z / .w = first batch / batches of the workgroup
+  // work list of k_schur_rows (host-built, pack_plan.hpp buildSchurRowsWorkList): panelWork.z / .w = first batch / batches of the workgroup
   const int4* blkOwn;                        // per workgroup: the two block rows of wave w in bytes 2 w, 2 w + 1 (255: none)
   const int2* blkBatch;                      // per batch: first entry of blkRecSlot, records
   const int4* blkWaveTab;                    // per (batch, wave): first pair word, pair words of its first / second row (multiples of 8, together at most kBlkBatchWords)

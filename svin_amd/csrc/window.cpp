@@ -2,6 +2,7 @@
 // /root/reference/okvis_ros/okvis/okvis_ceres/src/Estimator.cpp unless another file is named.
 #include "window.hpp"
 #include "trust_region.hpp"
+#include "pack_plan.hpp"
 #include <array>
 #include <atomic>
 #include <cstdint>
@@ -1579,6 +1580,80 @@ void Window::flushStaged(const std::vector<StagedCopy>& pending, hipStream_t s) 
   launchScatterStaged(stageDev_.p, (int)pending.size(), s);
 }
 
+// The host arrays of one pack(), filled step by step.  They live to the end of pack(): the staged copies keep pointers into
+// them until flushStaged has copied the block -- the planner's results (slots, work lists) included, which are moved in here
+// and never copied.
+struct PackHost {
+  // state tables and the block -> reduced-row maps
+  std::vector<double> hPose, hExt, hSb;
+  std::vector<int> hPoseOff, hExtOff, hSbOff;
+  std::vector<int> hLocked;   // blocks on a reduced manifold: the reduced-system rows of their held tangent directions (kernels.hip k_lock_rows)
+  int d = 0, dCPose = 0, dC = 0;
+  bool anyExtVar = false, phantom = false;
+  int phantomSlot = 0;
+  // landmarks + observations (landmark-major; empty on the resident path)
+  bool resident = false;
+  std::vector<double> hLmPrior;   // 12 doubles per HomogeneousPointError: measurement xyz, sqrt information (row-major)
+  std::vector<double> hLm, hUv, hW;
+  std::vector<int> hLmPtr, hObsLm;
+  std::vector<uint32_t> hIdx;
+  int L = 0, N = 0;
+  // factors and prior
+  std::vector<DevFactor> hFac;
+  std::vector<DevImu> hImu;
+  std::vector<uint32_t> hImuT;
+  std::vector<double> hImuM;
+  int F = 0;
+  std::vector<PriorBlock> hPb;
+  int priorM = 0, sbChain = 0;
+  // the plan (pack_plan.hpp)
+  SchurForm form{};
+  std::vector<int> hObsOrder;
+  SchurSlots slots;
+  SchurRowsWorkList rows;
+  SchurPanelsWorkList panels;
+  // device side
+  std::vector<int> hPoseSlotOfH, hExtSlotOfH;   // this frame's slot of every pose / extrinsics block handle (the resident observation records name blocks by handle)
+  int sS = 0;                                   // row stride of S
+};
+
+namespace {
+struct SlotCache {
+  const std::unordered_map<uint64_t, int>& map;
+  std::vector<uint64_t> ids;
+  std::vector<int> slots;
+  explicit SlotCache(const std::unordered_map<uint64_t, int>& m) : map(m) {
+    if (m.size() <= 64)
+      for (const auto& kv : m) { ids.push_back(kv.first); slots.push_back(kv.second); }
+  }
+  int at(uint64_t id) const {
+    for (size_t i = 0; i < ids.size(); ++i)
+      if (ids[i] == id) return slots[i];
+    return map.at(id);
+  }
+};
+
+// Which Schur form the window takes and what its kernels are told to do (pack_plan.hpp; the options and the CU count are read here, once)
+void planSchur(PackHost& a, int nPoseSlots) {
+  a.form = chooseSchurForm(a.dC, a.L, a.N, nPoseSlots, a.anyExtVar, optOn(kOptSchurPairwise), optOn(kOptPanelsOld), debugOption(kOptSlabChunks));
+  if (a.form.schurPanels && a.resident) throw std::logic_error("resident window needs a panel work list");
+  // (the resident path sorts on the device: k_window_rebuild, phase 4)
+  if (a.form.orderObs && !a.resident) a.hObsOrder = chunkObservationOrder(a.hLmPtr, a.hIdx, a.L, nPoseSlots);
+  if (a.form.schurBlocks) {
+    a.slots = buildSchurSlots(a.hLmPtr, a.hIdx, a.hPoseOff, a.L);
+    a.rows = buildSchurRowsWorkList(a.slots, a.dC, a.L, deviceComputeUnits(), debugOption(kOptBlkRounds), !optOn(kOptNoRowSplit));
+    const SchurRowsWorkList& w = a.rows;
+    if (!w.fits) throw std::logic_error("k_schur_rows work list: an entry does not fit a batch");
+    if (optOn(kOptPackTiming))
+      std::printf("[svin_ba pack] k_schur_rows work list: %d workgroups, %zu batches, %zu pair words; the busiest wave of a batch has %.2f x the mean, of a workgroup %.2f x\n",
+                  w.nPanelBlocks, w.batch.size() / 2 - 3, w.balAll, w.balAll ? (double)kBlkWaves * (double)w.balMax / (double)w.balAll : 0.0,
+                  w.balWgAll ? (double)kBlkWaves * (double)w.balWgMax / (double)w.balWgAll : 0.0);
+  } else if (a.form.schurPanels) {
+    a.panels = buildSchurPanelsWorkList(a.hLmPtr, a.hIdx, a.hPoseOff, a.dC, a.L);
+  }
+}
+}  // namespace
+
 void Window::pack(bool solveFollows) {
   quiesce();
   // the qualities of the last solve: a new solve replaces them before anybody can look; any other caller (inspection hooks,
@@ -1586,6 +1661,42 @@ void Window::pack(bool solveFollows) {
   if (solveFollows) qualityPending_ = false;
   else flushPendingQuality();
   const double tPack0 = nowSec();
+  PackHost a;   // (lives to the end: the staged copies point into it until flushStaged)
+  packNumberSlots(a);
+  packLandmarks(a);
+  packFactors(a);
+  // ---- device allocation + upload
+  const double tPack1 = nowSec();
+  hipStream_t s = stream_;
+  planSchur(a, (int)poseIds_.size());
+  // every host array of the window goes into one pinned block behind a segment table: one DMA, one scatter kernel
+  // (18 separate pageable copies cost ~70 us of enqueueing and ~70 us of draining per pack())
+  std::vector<StagedCopy> pending;
+  packReserveAndStage(a, pending);
+  ResidentArgs ra;
+  std::memset(&ra, 0, sizeof(ra));
+  if (a.resident) flushResident(s, a.form.orderObs, pending, ra);   // stages the delta; the rebuild kernel follows the scatter
+  flushStaged(pending, s);
+  if (solveFollows && a.resident) HIP_OK(hipEventRecord(evUploaded_, s));   // (the side stream of the early IMU pre-integration waits for the tables)
+  if (a.resident) {
+    addLog_.clear(); remLog_.clear(); setLog_.clear();   // (copied into the staged block by flushStaged)
+    ++epoch_;
+    ra.nPoseSlots = (int)poseIds_.size();
+    ra.obsIdx = dObsIdx_.p; ra.lm = dLm_.p; ra.obsOrder = dObsOrder_.p;
+    ra.poseSlotOfH = res_.poseSlotOfH.p; ra.extSlotOfH = res_.extSlotOfH.p;
+    launchWindowRebuild(ra, s);
+  }
+  packFillProblem(a);
+  if (solveFollows) packEarlyImu(a);
+  if (optOn(kOptPackTiming)) {
+    const double tPack2 = nowSec();
+    HIP_OK(hipStreamSynchronize(s));
+    std::printf("[pack] host graph -> arrays %.1f us, allocation + enqueue %.1f us, drain %.1f us\n", 1e6 * (tPack1 - tPack0),
+                1e6 * (tPack2 - tPack1), 1e6 * (nowSec() - tPack2));
+  }
+}
+
+void Window::packNumberSlots(PackHost& a) {
   poseIds_.clear(); extIds_.clear(); sbIds_.clear(); lmIds_.clear(); factorIds_.clear();
   poseSlot_.clear(); extSlot_.clear(); sbSlot_.clear();
   for (const auto& kv : states_) {
@@ -1605,8 +1716,7 @@ void Window::pack(bool solveFollows) {
     for (const auto& kv : blocks_) {
       const Block& b = kv.second;
       if (b.residuals.empty() && b.nObs == 0) continue;   // (a variable block outside every frame: added through the Map interface)
-      const bool known = (b.kind == B_POSE) ? poseSlot_.count(b.id) : (b.kind == B_EXT ? extSlot_.count(b.id) : sbSlot_.count(b.id));
-      if (!known) orphans.push_back(b.id);
+      if (!slotMapOf(b.kind).count(b.id)) orphans.push_back(b.id);
     }
     std::sort(orphans.begin(), orphans.end());
     for (uint64_t id : orphans) {
@@ -1617,11 +1727,12 @@ void Window::pack(bool solveFollows) {
     }
   }
   if (poseIds_.size() > 4095 || extIds_.size() > 4095) throw std::runtime_error("window too wide for the packed index");
-  std::vector<double> hPose(poseIds_.size() * 7), hExt(std::max<size_t>(extIds_.size(), 1) * 7), hSb(sbIds_.size() * 9);
-  std::vector<int> hPoseOff(poseIds_.size()), hExtOff(std::max<size_t>(extIds_.size(), 1), -1), hSbOff(sbIds_.size());
+  std::vector<double>&hPose = a.hPose, &hExt = a.hExt, &hSb = a.hSb;
+  std::vector<int>&hPoseOff = a.hPoseOff, &hExtOff = a.hExtOff, &hSbOff = a.hSbOff;
+  hPose.resize(poseIds_.size() * 7); hExt.resize(std::max<size_t>(extIds_.size(), 1) * 7); hSb.resize(sbIds_.size() * 9);
+  hPoseOff.resize(poseIds_.size()); hExtOff.assign(std::max<size_t>(extIds_.size(), 1), -1); hSbOff.resize(sbIds_.size());
   redBlockIds_.clear(); redBlockOff_.clear();
   int d = 0;
-  bool anyExtVar = false;
   for (size_t i = 0; i < poseIds_.size(); ++i) {
     const Block& b = blocks_.at(poseIds_[i]);
     std::memcpy(&hPose[7 * i], b.x, 7 * sizeof(double));
@@ -1635,28 +1746,27 @@ void Window::pack(bool solveFollows) {
   bool anyVariable = d > 0;
   for (uint64_t id : extIds_) anyVariable |= !blocks_.at(id).fixed;
   for (uint64_t id : sbIds_) anyVariable |= !blocks_.at(id).fixed;
-  const bool phantom = !anyVariable && (numObs_ + numLandmarkPriors_) > 0;
-  const int phantomSlot = (int)poseIds_.size();
-  if (phantom) {
+  a.phantom = !anyVariable && (numObs_ + numLandmarkPriors_) > 0;
+  a.phantomSlot = (int)poseIds_.size();
+  if (a.phantom) {
     const double ident[7] = {0, 0, 0, 0, 0, 0, 1};
     hPose.insert(hPose.end(), ident, ident + 7);
     hPoseOff.push_back(d);
     d += 6;
   }
-  const int dCPose = d;
+  a.dCPose = d;
   for (size_t i = 0; i < extIds_.size(); ++i) {
     const Block& b = blocks_.at(extIds_[i]);
     std::memcpy(&hExt[7 * i], b.x, 7 * sizeof(double));
     if (b.fixed) hExtOff[i] = -1;
-    else { hExtOff[i] = d; redBlockIds_.push_back(b.id); redBlockOff_.push_back(d); d += 6; anyExtVar = true; }
+    else { hExtOff[i] = d; redBlockIds_.push_back(b.id); redBlockOff_.push_back(d); d += 6; a.anyExtVar = true; }
   }
-  const int dC = d;
+  a.dC = d;
   // blocks on a reduced manifold: the reduced-system rows of their held tangent directions (kernels.hip k_lock_rows)
-  std::vector<int> hLocked;
   for (size_t k = 0; k < redBlockIds_.size(); ++k) {
     const Block& b = blocks_.at(redBlockIds_[k]);
-    for (int a = 0; a < 6; ++a)
-      if ((b.lock >> a) & 1) hLocked.push_back(redBlockOff_[k] + a);
+    for (int t = 0; t < 6; ++t)
+      if ((b.lock >> t) & 1) a.hLocked.push_back(redBlockOff_[k] + t);
   }
   for (size_t i = 0; i < sbIds_.size(); ++i) {
     const Block& b = blocks_.at(sbIds_[i]);
@@ -1664,12 +1774,16 @@ void Window::pack(bool solveFollows) {
     if (b.fixed) hSbOff[i] = -1;
     else { hSbOff[i] = d; redBlockIds_.push_back(b.id); redBlockOff_.push_back(d); d += 9; }
   }
-  // landmarks + observations (landmark-major).  Two ways to the same arrays: the device-resident window takes this frame's
-  // delta and rebuilds its CSR on the device (resident.hpp); the host path below walks the whole graph and uploads everything
-  // (wide windows with their panel work lists, landmark priors, sharded mode, and the reference the tests hold the resident
-  // path against).  Both list the landmarks with observations in HANDLE order, the observations in insertion order.
+  a.d = d;
+}
+
+// landmarks + observations (landmark-major).  Two ways to the same arrays: the device-resident window takes this frame's
+// delta and rebuilds its CSR on the device (resident.hpp); the host path below walks the whole graph and uploads everything
+// (wide windows with their panel work lists, landmark priors, sharded mode, and the reference the tests hold the resident
+// path against).  Both list the landmarks with observations in HANDLE order, the observations in insertion order.
+void Window::packLandmarks(PackHost& a) {
   const bool resident = useResident();
-  residentUsed_ = resident;
+  a.resident = residentUsed_ = resident;
   if (!resident) {
     syncLandmarks();         // the host graph becomes the authority again ...
     invalidateResident();    // ... and the device copy is rebuilt from it when the window next qualifies
@@ -1678,65 +1792,33 @@ void Window::pack(bool solveFollows) {
   if (!resident)
     for (const Landmark* lm : lmByHandle_)
       if (lm && (!lm->obs.empty() || !lm->priors.empty())) { ++nLmObs; nObs += lm->obs.size() + 2 * lm->priors.size(); }
-  std::vector<double> hLmPrior;   // 12 doubles per HomogeneousPointError: measurement xyz, sqrt information (row-major)
-  std::vector<double> hLm(4 * nLmObs), hUv(2 * nObs), hW(nObs);
-  std::vector<int> hLmPtr(resident ? 0 : nLmObs + 1), hObsLm(nObs);
-  std::vector<uint32_t> hIdx(nObs);
+  std::vector<double>&hLmPrior = a.hLmPrior, &hLm = a.hLm, &hUv = a.hUv, &hW = a.hW;
+  std::vector<int>&hLmPtr = a.hLmPtr, &hObsLm = a.hObsLm;
+  std::vector<uint32_t>& hIdx = a.hIdx;
+  hLm.resize(4 * nLmObs); hUv.resize(2 * nObs); hW.resize(nObs);
+  hLmPtr.resize(resident ? 0 : nLmObs + 1); hObsLm.resize(nObs);
+  hIdx.resize(nObs);
   lmIds_.resize(nLmObs);
-  struct SlotCache {
-    const std::unordered_map<uint64_t, int>& map;
-    std::vector<uint64_t> ids;
-    std::vector<int> slots;
-    explicit SlotCache(const std::unordered_map<uint64_t, int>& m) : map(m) {
-      if (m.size() <= 64)
-        for (const auto& kv : m) { ids.push_back(kv.first); slots.push_back(kv.second); }
-    }
-    int at(uint64_t id) const {
-      for (size_t i = 0; i < ids.size(); ++i)
-        if (ids[i] == id) return slots[i];
-      return map.at(id);
-    }
-  };
-  const SlotCache poseCache(poseSlot_), extCache(extSlot_);
-  // landmark order of the CSR: handle order (creation order; id order when ids grow with time, as the reference's IdProvider
-  // makes them); for wide windows sorted by visibility signature (below), so that a chunk of 16 consecutive landmarks
-  // touches few 96-row panels of the camera matrix and the same tile rows inside them (k_schur_panels work list)
-  std::vector<const Landmark*> lmOrder;
   if (!resident) {
+    const SlotCache poseCache(poseSlot_), extCache(extSlot_);
+    // landmark order of the CSR: handle order (creation order; id order when ids grow with time, as the reference's IdProvider
+    // makes them); for wide windows sorted by visibility signature (pack_plan.hpp), so that a chunk of 16 consecutive landmarks
+    // touches few 96-row panels of the camera matrix and the same tile rows inside them (k_schur_panels work list)
+    std::vector<const Landmark*> lmOrder;
     lmOrder.reserve(nLmObs);
     for (const Landmark* lm : lmByHandle_)
       if (lm && (!lm->obs.empty() || !lm->priors.empty())) lmOrder.push_back(lm);
     if (poseIds_.size() > (size_t)kResidentPoseCap) {
-      // Wide windows (k_schur_panels): order by VISIBILITY SIGNATURE -- the set of 16-row tiles of the camera matrix a landmark's
-      // observations write to (first tile, last tile, then the bit pattern) -- so that the 16 landmarks of a chunk hit the same
-      // tile rows and the kernel's step masks drop whole products.  A product step (tile row, tile column, 4 columns of G) runs
-      // when both tile rows hold something in those columns; modelled on the host (tools/panel_order_model.py) for the bench
-      // window of configs[3]: executed / algorithmic MFMA flops 9.28 ordered by first pose (measured 9.3), 7.84 by (first, last)
-      // pose, 6.30 by signature.  The rest is granularity: a landmark there sees 9 poses scattered over a span of 28 (its 55 rows
-      // live in ~8 tiles of 16), which no order of the landmarks changes.
-      struct Key { int first, last; uint64_t lo, hi; const Landmark* lm; };
-      std::vector<Key> keyed;
-      keyed.reserve(lmOrder.size());
+      std::vector<int> offPtr(1, 0), offs;   // per landmark: the reduced-row offsets of its observing poses
+      offPtr.reserve(lmOrder.size() + 1); offs.reserve(nObs);
       for (const Landmark* lm : lmOrder) {
-        Key k{INT32_MAX, -1, 0, 0, lm};
-        for (const Observation& ob : lm->obs) {
-          const int off = hPoseOff[poseCache.at(ob.poseId)];
-          if (off < 0) continue;
-          for (int tr : {off >> 4, (off + 5) >> 4}) {
-            k.first = std::min(k.first, tr); k.last = std::max(k.last, tr);
-            if (tr < 64) k.lo |= 1ull << tr; else if (tr < 128) k.hi |= 1ull << (tr - 64);
-          }
-        }
-        if (k.last < 0) k.first = 0;
-        keyed.push_back(k);
+        for (const Observation& ob : lm->obs) offs.push_back(a.hPoseOff[poseCache.at(ob.poseId)]);
+        offPtr.push_back((int)offs.size());
       }
-      std::stable_sort(keyed.begin(), keyed.end(), [](const Key& a, const Key& b) {
-        if (a.first != b.first) return a.first < b.first;
-        if (a.last != b.last) return a.last < b.last;
-        if (a.hi != b.hi) return a.hi < b.hi;
-        return a.lo < b.lo;
-      });
-      for (size_t i = 0; i < keyed.size(); ++i) lmOrder[i] = keyed[i].lm;
+      const std::vector<int> perm = orderLandmarksBySignature(offPtr, offs);
+      std::vector<const Landmark*> sorted(lmOrder.size());
+      for (size_t i = 0; i < perm.size(); ++i) sorted[i] = lmOrder[perm[i]];
+      lmOrder.swap(sorted);
     }
     size_t slot = 0, o = 0;
     hLmPtr[0] = 0;
@@ -1769,18 +1851,16 @@ void Window::pack(bool solveFollows) {
       hLmPtr[++slot] = (int)o;
     }
   }
-  const int L = resident ? (int)numLmObserved_ : (int)lmIds_.size(), N = resident ? (int)numObs_ : (int)hObsLm.size();
-  // factors
-  std::vector<DevFactor> hFac;
+  a.L = resident ? (int)numLmObserved_ : (int)lmIds_.size();
+  a.N = resident ? (int)numObs_ : (int)hObsLm.size();
+}
+
+void Window::packFactors(PackHost& a) {
+  std::vector<DevFactor>& hFac = a.hFac;
+  std::vector<DevImu>& hImu = a.hImu;
+  std::vector<uint32_t>& hImuT = a.hImuT;
+  std::vector<double>& hImuM = a.hImuM;
   hostFactors_.clear();
-  std::vector<DevImu> hImu;
-  std::vector<uint32_t> hImuT;
-  std::vector<double> hImuM;
-  auto blkKindSlot = [&](uint64_t id, int& kind, int& slot) {
-    const Block& b = blocks_.at(id);
-    kind = b.kind;
-    slot = (b.kind == B_POSE) ? poseSlot_.at(id) : (b.kind == B_EXT ? extSlot_.at(id) : sbSlot_.at(id));
-  };
   // sharded mode: the small factors are dealt to the ranks by creation number (factors are created in frame order: IMU factor
   // k -> k+1, the priors of a frame, its relative-extrinsics and sonar / depth terms); every rank still holds all states
   for (auto& kv : factors_) {
@@ -1790,7 +1870,10 @@ void Window::pack(bool solveFollows) {
     std::memset(&df, 0, sizeof(df));
     df.kind = f.kind; df.nblk = f.nblk; df.m = f.m; df.imuIndex = -1;
     df.lossKind = f.lossKind; df.lossScale = f.lossScale;
-    for (int b = 0; b < f.nblk; ++b) blkKindSlot(f.blocks[b], df.blkKind[b], df.blkSlot[b]);
+    for (int b = 0; b < f.nblk; ++b) {
+      df.blkKind[b] = blocks_.at(f.blocks[b]).kind;
+      df.blkSlot[b] = slotMapOf(df.blkKind[b]).at(f.blocks[b]);
+    }
     std::memcpy(df.meas, f.meas, sizeof(df.meas));
     std::memcpy(df.aux, f.aux, sizeof(df.aux));
     std::memcpy(df.sqrtInfo, f.sqrtInfo, sizeof(df.sqrtInfo));
@@ -1809,449 +1892,145 @@ void Window::pack(bool solveFollows) {
     factorIds_.push_back(f.id);
     hFac.push_back(df);
   }
-  hPoseOffKeep_ = hPoseOff; hExtOffKeep_ = hExtOff; hSbOffKeep_ = hSbOff;
-  if (phantom) {
+  hPoseOffKeep_ = a.hPoseOff; hExtOffKeep_ = a.hExtOff; hSbOffKeep_ = a.hSbOff;
+  if (a.phantom) {
     DevFactor df;
     std::memset(&df, 0, sizeof(df));
     df.kind = F_POSE_PRIOR; df.nblk = 1; df.m = 6; df.imuIndex = -1; df.lossScale = 1.0;
-    df.blkKind[0] = B_POSE; df.blkSlot[0] = phantomSlot;
+    df.blkKind[0] = B_POSE; df.blkSlot[0] = a.phantomSlot;
     df.meas[6] = 1.0;
     for (int k = 0; k < 6; ++k) df.sqrtInfo[k * 6 + k] = 1.0;
     hFac.push_back(df);   // (not in factorIds_: the inspection hooks report the graph's factors)
   }
-  const int F = (int)hFac.size();
+  a.F = (int)hFac.size();
   // prior
-  std::vector<PriorBlock> hPb;
-  int priorM = 0;
   if (hasPrior_) {
-    priorM = priorM_;
+    a.priorM = priorM_;
     for (const PriorBlockHost& pb : priorBlocks_) {
       PriorBlock q;
       std::memset(&q, 0, sizeof(q));
       q.kind = pb.kind;
-      q.slot = (pb.kind == B_POSE) ? poseSlot_.at(pb.id) : (pb.kind == B_EXT ? extSlot_.at(pb.id) : sbSlot_.at(pb.id));
+      q.slot = slotMapOf(pb.kind).at(pb.id);
       q.ord = pb.ord; q.mdim = pb.mdim;
       std::memcpy(q.lin, pb.lin, sizeof(q.lin));
-      hPb.push_back(q);
+      a.hPb.push_back(q);
     }
   }
-  // Do the variable speed / bias blocks form a chain behind the kept rows -- every factor (of ANY rank: the all-reduced system
-  // holds them all) and the prior tying two of them only ties neighbours in the order of the rows?  Then the wide-window solver
-  // eliminates them ahead of its blocked Cholesky (kernels.hip, k_sb_factor ...).
-  int sbChain = 0;
-  {
-    std::vector<int> chainPos(sbIds_.size(), -1);
-    int n = 0;
-    bool ok = true;
-    for (size_t i = 0; i < sbIds_.size(); ++i)
-      if (hSbOff[i] >= 0) { ok = ok && hSbOff[i] == dC + 9 * n; chainPos[i] = n++; }
-    auto neighbours = [&](const int* pos, int cnt) {
-      for (int x = 0; x < cnt; ++x)
-        for (int y = x + 1; y < cnt; ++y) ok = ok && std::abs(pos[x] - pos[y]) == 1;
-    };
-    for (const auto& kv : factors_) {
-      int pos[4], cnt = 0;
-      for (int b = 0; b < kv.second.nblk; ++b) {
-        const Block& blk = blocks_.at(kv.second.blocks[b]);
-        if (blk.kind != B_POSE && blk.kind != B_EXT && !blk.fixed) pos[cnt++] = chainPos[sbSlot_.at(blk.id)];
-      }
-      neighbours(pos, cnt);
+  a.sbChain = packSpeedBiasChain(a);
+}
+
+// the chain test of the variable speed / bias blocks (pack_plan.hpp speedBiasChainLength) over the factors of ANY rank and the prior
+int Window::packSpeedBiasChain(const PackHost& a) const {
+  std::vector<int> facPtr(1, 0), facSlots, priorSlots;
+  for (const auto& kv : factors_) {
+    for (int b = 0; b < kv.second.nblk; ++b) {
+      const Block& blk = blocks_.at(kv.second.blocks[b]);
+      if (blk.kind != B_POSE && blk.kind != B_EXT && !blk.fixed) facSlots.push_back(sbSlot_.at(blk.id));
     }
-    if (hasPrior_) {
-      std::vector<int> pos;
-      for (const PriorBlockHost& pb : priorBlocks_)
-        if (pb.kind != B_POSE && pb.kind != B_EXT && chainPos[sbSlot_.at(pb.id)] >= 0) pos.push_back(chainPos[sbSlot_.at(pb.id)]);
-      neighbours(pos.data(), (int)pos.size());
-    }
-    if (ok && d == dC + 9 * n) sbChain = n;
+    facPtr.push_back((int)facSlots.size());
   }
-  // ---- device allocation + upload
-  const double tPack1 = nowSec();
+  if (hasPrior_)
+    for (const PriorBlockHost& pb : priorBlocks_)
+      if (pb.kind != B_POSE && pb.kind != B_EXT && a.hSbOff[sbSlot_.at(pb.id)] >= 0) priorSlots.push_back(sbSlot_.at(pb.id));
+  return speedBiasChainLength(a.hSbOff, a.dC, a.d, facPtr, facSlots, priorSlots);
+}
+
+// Device buffers grow to what the window needs; every host array is queued in `pending` (sources stay in `a`).  The order of the
+// upload() calls is the layout of the staged block.
+void Window::packReserveAndStage(PackHost& a, std::vector<StagedCopy>& pending) {
   hipStream_t s = stream_;
-  // every host array of the window goes into one pinned block behind a segment table: one DMA, one scatter kernel
-  // (18 separate pageable copies cost ~70 us of enqueueing and ~70 us of draining per pack())
-  std::vector<StagedCopy> pending;
+  const int d = a.d, dC = a.dC, L = a.L, N = a.N, F = a.F;
   auto upload = [&](auto& buf, const auto& host, hipStream_t) {
     using T = typename std::remove_reference<decltype(host)>::type::value_type;
     buf.reserve(std::max<size_t>(host.size() + 16 / sizeof(T) + 1, 1));   // room for the 16-byte rounding of the copy
     if (!host.empty()) pending.push_back({host.data(), sizeof(T) * host.size(), buf.p});
   };
-  upload(dPose_, hPose, s); upload(dExt_, hExt, s); upload(dSb_, hSb, s);
-  dPoseC_.reserve(std::max<size_t>(hPose.size(), 1)); dExtC_.reserve(std::max<size_t>(hExt.size(), 1));
-  dSbC_.reserve(std::max<size_t>(hSb.size(), 1)); dLmC_.reserve(std::max<size_t>((size_t)4 * L, 1));
-  upload(dPoseOff_, hPoseOff, s); upload(dExtOff_, hExtOff, s); upload(dSbOff_, hSbOff, s);
-  if (!hLocked.empty()) upload(dLockedRows_, hLocked, s);
+  upload(dPose_, a.hPose, s); upload(dExt_, a.hExt, s); upload(dSb_, a.hSb, s);
+  dPoseC_.reserve(std::max<size_t>(a.hPose.size(), 1)); dExtC_.reserve(std::max<size_t>(a.hExt.size(), 1));
+  dSbC_.reserve(std::max<size_t>(a.hSb.size(), 1)); dLmC_.reserve(std::max<size_t>((size_t)4 * L, 1));
+  upload(dPoseOff_, a.hPoseOff, s); upload(dExtOff_, a.hExtOff, s); upload(dSbOff_, a.hSbOff, s);
+  if (!a.hLocked.empty()) upload(dLockedRows_, a.hLocked, s);
   upload(dCams_, cameras_, s);
   if (nLoss_ > 1) upload(dLossTab_, lossTab_, s);
-  ResidentArgs ra;
-  std::memset(&ra, 0, sizeof(ra));
-  // this frame's slot of every pose / extrinsics block handle (the resident observation records name blocks by handle)
-  std::vector<int> hPoseSlotOfH, hExtSlotOfH;
-  if (resident) {
-    hPoseSlotOfH.assign(std::max(nextBlockH_[B_POSE], 1), -1); hExtSlotOfH.assign(std::max(nextBlockH_[B_EXT], 1), -1);
-    for (size_t i = 0; i < poseIds_.size(); ++i) hPoseSlotOfH[blocks_.at(poseIds_[i]).handle] = (int)i;
-    for (size_t i = 0; i < extIds_.size(); ++i) hExtSlotOfH[blocks_.at(extIds_[i]).handle] = (int)i;
-    upload(res_.poseSlotOfH, hPoseSlotOfH, s); upload(res_.extSlotOfH, hExtSlotOfH, s);
+  if (a.resident) {
+    a.hPoseSlotOfH.assign(std::max(nextBlockH_[B_POSE], 1), -1); a.hExtSlotOfH.assign(std::max(nextBlockH_[B_EXT], 1), -1);
+    for (size_t i = 0; i < poseIds_.size(); ++i) a.hPoseSlotOfH[blocks_.at(poseIds_[i]).handle] = (int)i;
+    for (size_t i = 0; i < extIds_.size(); ++i) a.hExtSlotOfH[blocks_.at(extIds_[i]).handle] = (int)i;
+    upload(res_.poseSlotOfH, a.hPoseSlotOfH, s); upload(res_.extSlotOfH, a.hExtSlotOfH, s);
     dLm_.reserve(std::max<size_t>((size_t)4 * L, 1)); dObsIdx_.reserve(std::max<size_t>(N, 1));
   } else {
-    upload(dLm_, hLm, s);
-    upload(dLmPtr_, hLmPtr, s); upload(dObsLm_, hObsLm, s); upload(dObsUv_, hUv, s); upload(dObsW_, hW, s);
-    upload(dObsIdx_, hIdx, s);
-    upload(dLmPrior_, hLmPrior, s);
+    upload(dLm_, a.hLm, s);
+    upload(dLmPtr_, a.hLmPtr, s); upload(dObsLm_, a.hObsLm, s); upload(dObsUv_, a.hUv, s); upload(dObsW_, a.hW, s);
+    upload(dObsIdx_, a.hIdx, s);
+    upload(dLmPrior_, a.hLmPrior, s);
   }
   for (int k = 0; k < 2; ++k) { dLin_[k].reserve(std::max<size_t>((size_t)32 * N, 1)); dFacLin_[k].reserve(std::max(F, 1)); }
-  upload(dFactors_, hFac, s); upload(dImus_, hImu, s); upload(dImuT_, hImuT, s); upload(dImuM_, hImuM, s);
+  upload(dFactors_, a.hFac, s); upload(dImus_, a.hImu, s); upload(dImuT_, a.hImuT, s); upload(dImuM_, a.hImuM, s);
   if (hasPrior_) {
-    upload(dPriorBlk_, hPb, s);  // Ht / bp / c0 stay where the marginalisation kernels left them (margBuf_.bOut)
-    dPriorScratch_.reserve((size_t)6 * priorM + 18 * hPb.size() + 16);
+    upload(dPriorBlk_, a.hPb, s);  // Ht / bp / c0 stay where the marginalisation kernels left them (margBuf_.bOut)
+    dPriorScratch_.reserve((size_t)6 * a.priorM + 18 * a.hPb.size() + 16);
   }
-  const int dpad = ((d + 15) / 16) * 16;
   // S and the camera-side vectors share one allocation: [S | gRed | gFull | hC | ...] is all-reduced as one message
-  const int sS = ((std::max(d, 1) + 15) / 16) * 16;   // row stride of S: whole 128-byte lines per 16-column tile segment
+  const int sS = a.sS = ((std::max(d, 1) + 15) / 16) * 16;   // row stride of S: whole 128-byte lines per 16-column tile segment
   dS_.reserve((size_t)sS * sS + (size_t)12 * std::max(d, 1) + 64);   // sS rows as well: the solver reads whole tiles without clamping
   dLmVec_.reserve((size_t)(6 + 3 * 7 + 9) * std::max(L, 1));
-  {
-    const size_t dp64 = ((size_t)d + 63) / 64 * 64;  // multi-workgroup solver: (dp64 + 64) x dp64 matrix + 1/L_ii + diagonal factors
-    dChol_.reserve(std::max<size_t>(solveReducedScratchDoubles(d, true), 1));
-  }
+  dChol_.reserve(std::max<size_t>(solveReducedScratchDoubles(d, true), 1));
   dPartial_.reserve((size_t)16 * 4096);
   dScal_.reserve(1);
   dQuality_.reserve(std::max(L, 1));
-  const size_t slabSize = (size_t)dC * dC + 3 * dC;
-  const bool useLds = slabSize * 8 + (size_t)4 * 64 * 34 * 8 <= 150 * 1024;
-  int nSlabs = 1;
-  // windows whose camera block fits 16 x 16 MFMA tiles (dC <= 254, e.g. 42 poses or 10 poses with per-frame extrinsics):
-  // dense Gram-matrix Schur complement on MFMA
-  const bool schurDense = dC > 0 && dC + 2 <= 256 && poseIds_.size() <= (size_t)kDensePoseCap && !optOn(kOptSchurPairwise);
-  if (schurDense) {
-    nSlabs = denseSlabCount(L);   // (batch_plan.hpp)
-    // SVIN_SLAB_CHUNKS=n: n chunks of 16 landmarks per workgroup and private slab (default 1 up to 256 workgroups)
-    if (debugOption(kOptSlabChunks) > 1) nSlabs = std::max(1, std::min(nSlabs, ((L + 15) / 16 + debugOption(kOptSlabChunks) - 1) / debugOption(kOptSlabChunks)));
+  if (a.form.orderObs && a.resident) dObsOrder_.reserve((size_t)N);   // counting sort per chunk on the device (k_window_rebuild, phase 4)
+  if (a.form.orderObs && !a.resident) upload(dObsOrder_, a.hObsOrder, s);
+  if (a.form.schurBlocks) {
+    const SchurSlots& sl = a.slots;
+    const SchurRowsWorkList& w = a.rows;
+    upload(dSlotPtr_, sl.slotPtr, s); upload(dSlotBlk_, sl.slotBlk, s); upload(dSlotObsPtr_, sl.slotObsPtr, s); upload(dSlotObs_, sl.slotObs, s);
+    upload(dSlotLm_, sl.slotLm, s);
+    dSlotRec_.reserve(std::max<size_t>(sl.slotBlk.size() * kBlkRec, 1));
+    dBlkPartial_.reserve(std::max<size_t>(((sl.slotBlk.size() + kBlkSlotsPerWorkgroup - 1) / kBlkSlotsPerWorkgroup) * (size_t)(dC / 6) * 34, 1));
+    upload(dBlkPairs_, w.pairWords, s); upload(dBlkBatch_, w.batch, s); upload(dBlkWaveTab_, w.waveTab, s); upload(dBlkRecSlot_, w.recSlot, s);
+    upload(dPanelWork_, w.panelWork, s); upload(dPanelChunks_, w.blkOwn, s); upload(dPanelPairPtr_, w.panelPairPtr, s);
+    dSlabs_.reserve(std::max<size_t>((size_t)w.nPanelBlocks * (96 * 96 + 3 * 96), 1));
+  } else if (a.form.schurPanels) {
+    const SchurPanelsWorkList& w = a.panels;
+    upload(dPanelWork_, w.panelWork, s); upload(dPanelChunks_, w.panelChunks, s); upload(dPanelPairPtr_, w.panelPairPtr, s);
+    dSlabs_.reserve(std::max<size_t>((size_t)w.nPanelBlocks * (96 * 96 + 3 * 96), 1));
+  } else {
+    dSlabs_.reserve(std::max<size_t>(((size_t)dC * dC + 3 * dC) * a.form.nSlabs, 1));
   }
-  else if (useLds) nSlabs = std::max(1, std::min(256, (L + 7) / 8));
-  // dense Schur with the A part on MFMA (variable extrinsics, or more than 8 tile rows): within every chunk of 16
-  // landmarks the observations are visited pose by pose, so that a batch only touches a few tile rows (counting sort)
-  std::vector<int> hObsOrder;
-  const bool orderObs = schurDense && (anyExtVar || (dC + 2 + 15) / 16 > 8) && N > 0;
-  if (orderObs && resident) dObsOrder_.reserve((size_t)N);   // counting sort per chunk on the device (k_window_rebuild, phase 4)
-  if (orderObs && !resident) {
-    hObsOrder.resize(N);
-    std::vector<int> cnt;
-    for (int l0 = 0; l0 < L; l0 += 16) {
-      const int oBeg = hLmPtr[l0], oEnd = hLmPtr[std::min(L, l0 + 16)];
-      cnt.assign(poseIds_.size() + 2, 0);
-      for (int o = oBeg; o < oEnd; ++o) cnt[(hIdx[o] & 0xfff) + 1]++;
-      for (size_t k = 1; k < cnt.size(); ++k) cnt[k] += cnt[k - 1];
-      for (int o = oBeg; o < oEnd; ++o) hObsOrder[oBeg + cnt[hIdx[o] & 0xfff]++] = o;
-    }
-    upload(dObsOrder_, hObsOrder, s);
-  }
-  // wide windows with fixed extrinsics: Gram-matrix Schur complement per pair of 96-row panels (k_schur_panels).
-  // Work list: every chunk of 16 landmarks goes to all panel pairs (I >= J) inside the row range its observations touch.
-  const bool schurPanels = !schurDense && !anyExtVar && dC > 0 && L > 0 && !optOn(kOptSchurPairwise);
-  std::vector<int> hPanelWork, hPanelChunks, hPanelPairPtr;
-  int nPanelBlocks = 0, nPanelPairs = 0;
-  // Round 6: the block-pair form (k_schur_blocks) is what runs unless SVIN_PANELS_OLD keeps the tile form (k_schur_panels).  Its
-  // SLOTS -- one per (landmark, distinct variable pose), ascending with the pose inside a landmark, each with the list of its
-  // observations (two for a stereo pair) -- are structure, built here once per pack(); k_blocks_slots writes a 24-double record
-  // per slot and build.  A pose block index has to fit 16 bits.
-  const bool schurBlocks = schurPanels && !optOn(kOptPanelsOld) && dC / 6 <= kBlkMaxPoseBlocks;
-  std::vector<uint32_t> hPairWords;
-  std::vector<int> hSlotPtr, hSlotObsPtr, hSlotObs, hSlotLm, hEntries, hBatch, hWaveTab, hRecSlot;   // (staged uploads copy from these when the block is flushed: they live to the end of pack())
-  std::vector<unsigned short> hSlotBlk;
-  if (schurBlocks) {
-    hSlotPtr.resize((size_t)L + 1); hSlotObs.reserve(N); hSlotBlk.reserve(N); hSlotObsPtr.reserve((size_t)N + 1);
-    std::vector<std::pair<int, int>> seen;   // (pose block, observation) of one landmark
-    for (int l = 0; l < L; ++l) {
-      hSlotPtr[l] = (int)hSlotBlk.size();
-      seen.clear();
-      for (int o = hLmPtr[l]; o < hLmPtr[l + 1]; ++o) {
-        const int off = hPoseOff[hIdx[o] & 0xfff];
-        if (off >= 0) seen.emplace_back(off / 6, o);
-      }
-      std::stable_sort(seen.begin(), seen.end(), [](const std::pair<int, int>& a, const std::pair<int, int>& b) { return a.first < b.first; });
-      for (size_t k = 0; k < seen.size(); ++k) {
-        if (k == 0 || seen[k].first != seen[k - 1].first) { hSlotBlk.push_back((unsigned short)seen[k].first); hSlotObsPtr.push_back((int)hSlotObs.size()); hSlotLm.push_back(l); }
-        hSlotObs.push_back(seen[k].second);
-      }
-    }
-    hSlotPtr[L] = (int)hSlotBlk.size();
-    hSlotObsPtr.push_back((int)hSlotObs.size());
-    upload(dSlotPtr_, hSlotPtr, s); upload(dSlotBlk_, hSlotBlk, s); upload(dSlotObsPtr_, hSlotObsPtr, s); upload(dSlotObs_, hSlotObs, s);
-    upload(dSlotLm_, hSlotLm, s);
-    dSlotRec_.reserve(std::max<size_t>(hSlotBlk.size() * kBlkRec, 1));
-    dBlkPartial_.reserve(std::max<size_t>(((hSlotBlk.size() + kBlkSlotsPerWorkgroup - 1) / kBlkSlotsPerWorkgroup) * (size_t)(dC / 6) * 34, 1));
-    // work list: per panel pair (I >= J; a panel is 16 pose blocks = 96 rows) the landmarks with slots in both panels, as ENTRIES
-    // (first slot and count in either panel -- the slots of a panel are a run, they ascend with the pose), cut into workgroups of
-    // pair words (below); the pairs in the order k_reduce_panel_slabs expects (panelPairPtr)
-    const int nPan = (dC + 95) / 96;
-    nPanelPairs = nPan * (nPan + 1) / 2;
-    std::vector<std::vector<int>> lists(nPanelPairs);   // four ints per entry: first slot in I, in J, counts, landmark
-    std::vector<int> runPanel, runFirst, runCount;
-    for (int l = 0; l < L; ++l) {
-      runPanel.clear(); runFirst.clear(); runCount.clear();
-      for (int sl = hSlotPtr[l]; sl < hSlotPtr[l + 1]; ++sl) {
-        const int pan = hSlotBlk[sl] / 16;
-        if (runPanel.empty() || runPanel.back() != pan) { runPanel.push_back(pan); runFirst.push_back(sl); runCount.push_back(1); }
-        else ++runCount.back();
-      }
-      for (size_t a = 0; a < runPanel.size(); ++a)
-        for (size_t b = 0; b <= a; ++b) {
-          std::vector<int>& li = lists[runPanel[a] * (runPanel[a] + 1) / 2 + runPanel[b]];
-          li.insert(li.end(), {runFirst[a], runFirst[b], runCount[a] | (runCount[b] << 8), l});
-        }
-    }
-    // ... and for k_schur_rows (kernels.hip), per panel pair: the sixteen block rows dealt to the kernel's eight waves (two each, by
-    // their pair counts, heaviest first, per workgroup), the entries cut into workgroups by pair words and those into BATCHES (records
-    // staged in LDS at a time: at most kBlkBatchRecs, and at most kBlkBatchWords pair words per wave), and per batch and wave the
-    // PAIR WORDS (pairWord below) in the order the wave works through them, its first row's, then
-    // its second row's, each sorted by A record (entry, slot in I); the run of an A record is padded to an even length and a row's
-    // words to whole eights with pairs whose B operand is the zero record (the kernel takes the A record of words 2 j, 2 j + 1 from
-    // word 2 j, and words 2 j, 2 j + 1 must name two accumulators).  A diagonal pair takes the blocks on and below the block diagonal.
-    // Workgroups: cut by PAIR WORDS (an entry of a pair of different panels has 17 pairs on the bench window of configs[3], one of a
-    // diagonal pair 12), so many that SVIN_BLK_ROUNDS (default 2) workgroups per place run one after the other -- two places per
-    // CU.  (900 workgroups of 256 entries: 181 us; one round of equal entry counts: 233 us, the heaviest workgroup is the kernel.)
-    // (pair word: twice the accumulator's number | byte offset of the B record in its LDS buffer << 8 | A record << 24 -- what the
-    // kernel needs with the fewest scalar instructions; a staged record is 160 bytes)
-    auto pairWord = [](int recA, int recB, int pb) { return (uint32_t)(2 * pb) | ((uint32_t)(recB * 160) << 8) | ((uint32_t)recA << 24); };
-    static_assert(kBlkBatchRecs <= 256 && kBlkBatchRecs * 160 < 65536, "pair word fields");
-    auto entryWords = [&](const int* en, bool dg) {
-      const int nA = en[2] & 0xff, nB = en[2] >> 8;
-      int wds = 0;
-      for (int ka = 0; ka < nA; ++ka) wds += ((dg ? ka + 1 : nB) + 1) & ~1;
-      return wds;
-    };
-    size_t wordsPerWg = 0;
-    {
-      size_t total = 0;
-      for (int I = 0; I < nPan; ++I)
-        for (int J = 0; J <= I; ++J) {
-          const std::vector<int>& li = lists[I * (I + 1) / 2 + J];
-          for (size_t e = 0; e < li.size() / 4; ++e) total += entryWords(&li[4 * e], I == J);
-        }
-      const int rounds = debugOption(kOptBlkRounds) > 0 ? debugOption(kOptBlkRounds) : 2;
-      const size_t places = (size_t)std::max(1, rounds * 2 * deviceComputeUnits() - nPanelPairs);
-      wordsPerWg = std::max<size_t>(kBlkMinWordsPerBlock, (total + places - 1) / places);
-    }
-    hPanelPairPtr.push_back(0);
-    size_t balWgMax = 0, balWgAll = 0, balAll = 0, balMax = 0;   // pair words of the busiest wave / of all waves: per workgroup, per batch (a barrier pair per batch)
-    for (int I = 0; I < nPan; ++I)
-      for (int J = 0; J <= I; ++J) {
-        const std::vector<int>& li = lists[I * (I + 1) / 2 + J];
-        const size_t nEnt = li.size() / 4;
-        const bool dg = I == J;
-        for (size_t k = 0; k < nEnt;) {
-          size_t kEnd = k, wgWords = 0;
-          while (kEnd < nEnt && wgWords < wordsPerWg) wgWords += entryWords(&li[4 * kEnd++], dg);
-          // The workgroup's block rows dealt to the sixteen accumulator sets of its eight waves (two each).  Rows no landmark of the
-          // list touches get none; the sets that are left go to the heaviest rows as a SECOND set (the row's runs are then shared
-          // between two waves -- by the lighter wave of the moment, below -- and k_schur_rows adds both sets into the slab image:
-          // two terms, so the sum does not depend on their order).  Sets heaviest first, to the wave with the least so far.
-          // (round 6, measured on the bench window: one set per row and rows dealt by load left the busiest wave of a batch with
-          //  1.59 x the mean number of pair words and the busiest wave of a workgroup with 1.24 x; rows r, r + 8 to wave r: 1.71;
-          //  entries re-ordered round robin by the wave they load most: 1.57)
-          long rowLoad[16] = {0};
-          for (size_t e = k; e < kEnd; ++e) {
-            const int fa = li[4 * e], nA = li[4 * e + 2] & 0xff, nB = li[4 * e + 2] >> 8;
-            for (int ka = 0; ka < nA; ++ka) rowLoad[hSlotBlk[fa + ka] - 16 * I] += ((dg ? ka + 1 : nB) + 1) & ~1;
-          }
-          int nOwn[16] = {0}, ownerWave[16][2], ownerSel[16][2], ownRows[kBlkWaves][2];
-          long waveLoad[kBlkWaves] = {0};
-          for (int wvv = 0; wvv < kBlkWaves; ++wvv) ownRows[wvv][0] = ownRows[wvv][1] = 255;
-          {
-            int mult[16], sets = 0;
-            for (int r = 0; r < 16; ++r) { mult[r] = rowLoad[r] > 0 ? 1 : 0; sets += mult[r]; }
-            const bool split = !optOn(kOptNoRowSplit);
-            while (split && sets < 2 * kBlkWaves) {
-              int best = -1;
-              for (int r = 0; r < 16; ++r)
-                if (mult[r] == 1 && rowLoad[r] >= 16 && (best < 0 || rowLoad[r] > rowLoad[best])) best = r;
-              if (best < 0) break;
-              mult[best] = 2; ++sets;
-            }
-            struct Unit { int row; long load; };
-            std::vector<Unit> units;
-            for (int r = 0; r < 16; ++r)
-              for (int c = 0; c < mult[r]; ++c) units.push_back(Unit{r, rowLoad[r] / mult[r]});
-            std::stable_sort(units.begin(), units.end(), [](const Unit& a, const Unit& b) { return a.load > b.load; });
-            for (const Unit& u : units) {
-              int best = -1;
-              for (int wvv = 0; wvv < kBlkWaves; ++wvv) {
-                if (ownRows[wvv][1] != 255) continue;
-                if (nOwn[u.row] == 1 && ownerWave[u.row][0] == wvv) continue;   // (the two sets of a row: two waves)
-                if (best < 0 || waveLoad[wvv] < waveLoad[best]) best = wvv;
-              }
-              if (best < 0) continue;   // (only the second set of a row can be left over: the row keeps its first)
-              const int sel = ownRows[best][0] == 255 ? 0 : 1;
-              ownRows[best][sel] = u.row;
-              ownerWave[u.row][nOwn[u.row]] = best; ownerSel[u.row][nOwn[u.row]] = sel; ++nOwn[u.row];
-              waveLoad[best] += u.load;
-            }
-          }
-          {
-            long mx = 0, sum = 0;
-            for (int wvv = 0; wvv < kBlkWaves; ++wvv) { mx = std::max(mx, waveLoad[wvv]); sum += waveLoad[wvv]; }
-            balWgMax += (size_t)mx; balWgAll += (size_t)sum;
-          }
-          int ownWords[4] = {0, 0, 0, 0};
-          for (int wvv = 0; wvv < kBlkWaves; ++wvv)
-            ownWords[wvv >> 1] |= (ownRows[wvv][0] | (ownRows[wvv][1] << 8)) << (16 * (wvv & 1));
-          const int firstBatch = (int)(hBatch.size() / 2);
-          size_t e = k;
-          while (e < kEnd) {
-            std::vector<uint32_t> words[kBlkWaves][2];   // per wave and owned row
-            const int firstRec = (int)hRecSlot.size();
-            int recs = 0;
-            for (; e < kEnd; ++e) {
-              const int fa = li[4 * e], fb = li[4 * e + 1], nA = li[4 * e + 2] & 0xff, nB = li[4 * e + 2] >> 8;
-              const int need = nA + (dg ? 0 : nB);
-              if (recs + need > kBlkBatchRecs - 1) break;
-              int add[kBlkWaves] = {0};   // (every run of an A record is padded to an even number of words)
-              int pick[64];               // which of its row's sets the run of slot ka goes to: the wave with fewer words in this batch
-              for (int ka = 0; ka < nA; ++ka) {
-                const int row = hSlotBlk[fa + ka] - 16 * I;
-                int c = 0;
-                if (nOwn[row] == 2) {
-                  const int w0 = ownerWave[row][0], w1 = ownerWave[row][1];
-                  const size_t l0 = words[w0][0].size() + words[w0][1].size() + (size_t)add[w0], l1 = words[w1][0].size() + words[w1][1].size() + (size_t)add[w1];
-                  c = l1 < l0 ? 1 : 0;
-                }
-                pick[ka] = c;
-                add[ownerWave[row][c]] += ((dg ? ka + 1 : nB) + 1) & ~1;
-              }
-              bool fits = true;
-              for (int wvv = 0; wvv < kBlkWaves; ++wvv) fits = fits && (int)(words[wvv][0].size() + words[wvv][1].size()) + add[wvv] <= kBlkBatchWords - 12;
-              if (!fits) break;
-              const int recA0 = recs, recB0 = dg ? recs : recs + nA;
-              for (int ka = 0; ka < nA; ++ka) hRecSlot.push_back(fa + ka);
-              if (!dg) for (int kb = 0; kb < nB; ++kb) hRecSlot.push_back(fb + kb);
-              recs += need;
-              for (int ka = 0; ka < nA; ++ka) {
-                const int row = hSlotBlk[fa + ka] - 16 * I;
-                std::vector<uint32_t>& wl = words[ownerWave[row][pick[ka]]][ownerSel[row][pick[ka]]];
-                const int cnt = dg ? ka + 1 : nB;
-                int pb = 0;
-                for (int kb = 0; kb < cnt; ++kb) {
-                  pb = hSlotBlk[fb + kb] - 16 * J;
-                  wl.push_back(pairWord(recA0 + ka, recB0 + kb, pb));
-                }
-                // (padding word of the run: the zero record as B, an accumulator other than its partner's)
-                if (cnt & 1) wl.push_back(pairWord(recA0 + ka, kBlkBatchRecs - 1, (pb + 1) & 15));
-              }
-            }
-            if (recs == 0) throw std::logic_error("k_schur_rows work list: an entry does not fit a batch");
-            hBatch.insert(hBatch.end(), {firstRec, recs});
-            {
-              size_t mx = 0;
-              for (int wvv = 0; wvv < kBlkWaves; ++wvv) { const size_t n = words[wvv][0].size() + words[wvv][1].size(); balAll += n; mx = std::max(mx, n); }
-              balMax += mx;
-            }
-            for (int wvv = 0; wvv < kBlkWaves; ++wvv) {
-              for (int sel = 0; sel < 2; ++sel)   // (a row's words in eights: padding words in twos -- both operands the zero record, two accumulators)
-                while (words[wvv][sel].size() % 8) {
-                  words[wvv][sel].push_back(pairWord(kBlkBatchRecs - 1, kBlkBatchRecs - 1, 0));
-                  words[wvv][sel].push_back(pairWord(kBlkBatchRecs - 1, kBlkBatchRecs - 1, 1));
-                }
-              hWaveTab.insert(hWaveTab.end(), {(int)hPairWords.size(), (int)words[wvv][0].size(), (int)words[wvv][1].size(), 0});
-              hPairWords.insert(hPairWords.end(), words[wvv][0].begin(), words[wvv][0].end());
-              hPairWords.insert(hPairWords.end(), words[wvv][1].begin(), words[wvv][1].end());
-            }
-          }
-          hPanelWork.insert(hPanelWork.end(), {I, J, firstBatch, (int)(hBatch.size() / 2) - firstBatch});
-          hEntries.insert(hEntries.end(), ownWords, ownWords + 4);   // (blkOwn: one int4 per workgroup)
-          ++nPanelBlocks;
-          k = kEnd;
-        }
-        hPanelPairPtr.push_back(nPanelBlocks);
-      }
-    if (optOn(kOptPackTiming))
-      std::printf("[svin_ba pack] k_schur_rows work list: %d workgroups, %zu batches, %zu pair words; the busiest wave of a batch has %.2f x the mean, of a workgroup %.2f x\n",
-                  nPanelBlocks, hBatch.size() / 2, balAll, balAll ? (double)kBlkWaves * (double)balMax / (double)balAll : 0.0,
-                  balWgAll ? (double)kBlkWaves * (double)balWgMax / (double)balWgAll : 0.0);
-    hPairWords.resize(hPairWords.size() + 128, 0u);   // (a wave requests its words in 64s)
-    hBatch.resize(hBatch.size() + 2 * 3, 0); hWaveTab.resize(hWaveTab.size() + (size_t)4 * kBlkWaves * 3, 0);   // (the kernel reads descriptors three batches ahead, unconditionally)
-    upload(dBlkPairs_, hPairWords, s); upload(dBlkBatch_, hBatch, s); upload(dBlkWaveTab_, hWaveTab, s); upload(dBlkRecSlot_, hRecSlot, s);
-    upload(dPanelWork_, hPanelWork, s); upload(dPanelChunks_, hEntries, s); upload(dPanelPairPtr_, hPanelPairPtr, s);
-    dSlabs_.reserve(std::max<size_t>((size_t)nPanelBlocks * (96 * 96 + 3 * 96), 1));
-  }
-  if (schurPanels && !schurBlocks) {
-    constexpr int kRows = 96, kChunk = 16, kPerBlock = kPanelChunksPerBlock;
-    const int nPan = (dC + kRows - 1) / kRows;
-    nPanelPairs = nPan * (nPan + 1) / 2;
-    std::vector<std::vector<int>> lists(nPanelPairs);
-    const int nChunks = (L + kChunk - 1) / kChunk;
-    for (int c = 0; c < nChunks; ++c) {
-      int lo = INT32_MAX, hi = -1;
-      const int o0 = hLmPtr[c * kChunk], o1 = hLmPtr[std::min(L, (c + 1) * kChunk)];
-      for (int o = o0; o < o1; ++o) {
-        const int off = hPoseOff[hIdx[o] & 0xfff];
-        if (off < 0) continue;
-        lo = std::min(lo, off); hi = std::max(hi, off);
-      }
-      // a chunk without variable poses still has to produce V^-1, b, htil for its landmarks: give it to pair (0, 0)
-      const int pLo = hi < 0 ? 0 : lo / kRows, pHi = hi < 0 ? 0 : hi / kRows;
-      for (int I = pLo; I <= pHi; ++I)
-        for (int J = pLo; J <= I; ++J) lists[I * (I + 1) / 2 + J].push_back(c);
-    }
-    hPanelPairPtr.push_back(0);
-    for (int I = 0; I < nPan; ++I)
-      for (int J = 0; J <= I; ++J) {
-        const std::vector<int>& li = lists[I * (I + 1) / 2 + J];
-        for (size_t k = 0; k < li.size(); k += kPerBlock) {
-          const int cnt = (int)std::min<size_t>(kPerBlock, li.size() - k);
-          hPanelWork.insert(hPanelWork.end(), {I, J, (int)hPanelChunks.size(), cnt});
-          hPanelChunks.insert(hPanelChunks.end(), li.begin() + k, li.begin() + k + cnt);
-          ++nPanelBlocks;
-        }
-        hPanelPairPtr.push_back(nPanelBlocks);
-      }
-    upload(dPanelWork_, hPanelWork, s); upload(dPanelChunks_, hPanelChunks, s); upload(dPanelPairPtr_, hPanelPairPtr, s);
-    dSlabs_.reserve(std::max<size_t>((size_t)nPanelBlocks * (kRows * kRows + 3 * kRows), 1));
-  } else if (!schurPanels) {
-    dSlabs_.reserve(std::max<size_t>(slabSize * nSlabs, 1));
-  }
-
   // the accumulators start clear (the trust-region loop never launches k_zero_build: k_post_solve re-clears them); the clears
   // ride in the scatter launch of the staged block
-  const int sSq = ((std::max(d, 1) + 15) / 16) * 16;
-  pending.push_back({nullptr, sizeof(double) * ((size_t)sSq * sSq + (size_t)12 * std::max(d, 1)), dS_.p});
+  pending.push_back({nullptr, sizeof(double) * ((size_t)sS * sS + (size_t)12 * std::max(d, 1)), dS_.p});
   pending.push_back({nullptr, sizeof(SolverScalars), dScal_.p});
   pending.push_back({nullptr, sizeof(double) * 16 * 4096, dPartial_.p});
-  if (hasPrior_) pending.push_back({nullptr, sizeof(double) * (6 * (size_t)priorM + 18 * hPb.size()), dPriorScratch_.p});
-  if (schurPanels && resident) throw std::logic_error("resident window needs a panel work list");
-  if (resident) flushResident(s, orderObs, pending, ra);   // stages the delta; the rebuild kernel follows the scatter
-  flushStaged(pending, s);
-  if (solveFollows && resident) HIP_OK(hipEventRecord(evUploaded_, s));   // (the side stream of the early IMU pre-integration waits for the tables)
-  if (resident) {
-    addLog_.clear(); remLog_.clear(); setLog_.clear();   // (copied into the staged block by flushStaged)
-    ++epoch_;
-    ra.nPoseSlots = (int)poseIds_.size();
-    ra.obsIdx = dObsIdx_.p; ra.lm = dLm_.p; ra.obsOrder = dObsOrder_.p;
-    ra.poseSlotOfH = res_.poseSlotOfH.p; ra.extSlotOfH = res_.extSlotOfH.p;
-    launchWindowRebuild(ra, s);
-  }
+  if (hasPrior_) pending.push_back({nullptr, sizeof(double) * (6 * (size_t)a.priorM + 18 * a.hPb.size()), dPriorScratch_.p});
+}
 
+void Window::packFillProblem(const PackHost& a) {
+  const int d = a.d, dC = a.dC, L = a.L, N = a.N, priorM = a.priorM, sS = a.sS;
+  const bool resident = a.resident, schurBlocks = a.form.schurBlocks;
   DeviceProblem& p = prob_;
   std::memset(&p, 0, sizeof(p));
-  p.nPose = (int)(hPose.size() / 7); p.nExt = (int)std::max<size_t>(extIds_.size(), 1); p.nSb = (int)sbIds_.size();
-  p.L = L; p.N = N; p.F = F; p.nImu = (int)hImu.size(); p.d = d; p.dC = dC; p.nCam = (int)cameras_.size();
-  p.priorM = priorM; p.priorBlocks = (int)hPb.size(); p.anyExtVariable = anyExtVar ? 1 : 0;
+  p.nPose = (int)(a.hPose.size() / 7); p.nExt = (int)std::max<size_t>(extIds_.size(), 1); p.nSb = (int)sbIds_.size();
+  p.L = L; p.N = N; p.F = a.F; p.nImu = (int)a.hImu.size(); p.d = d; p.dC = dC; p.nCam = (int)cameras_.size();
+  p.priorM = priorM; p.priorBlocks = (int)a.hPb.size(); p.anyExtVariable = a.anyExtVar ? 1 : 0;
   p.ownsCamera = (world_ <= 1 || rank_ == 0) ? 1 : 0;
   p.rank = (world_ <= 1 && rcclComm_ && optOn(kOptForceDistributed)) ? -1 : rank_;   // -1: one-rank communicator exercising the sharded path
   p.world = world_;
   if (!p.ownsCamera) p.priorM = 0;   // the prior is evaluated and accumulated on one rank only
   p.pose = dPose_.p; p.ext = dExt_.p; p.sb = dSb_.p; p.lm = dLm_.p;
-  p.obsOrder = orderObs ? dObsOrder_.p : nullptr;
-  p.dCPose = dCPose;
-  p.lockedRows = hLocked.empty() ? nullptr : dLockedRows_.p; p.nLocked = (int)hLocked.size();
+  p.obsOrder = a.form.orderObs ? dObsOrder_.p : nullptr;
+  p.dCPose = a.dCPose;
+  p.lockedRows = a.hLocked.empty() ? nullptr : dLockedRows_.p; p.nLocked = (int)a.hLocked.size();
   p.nHostFactors = (int)hostFactors_.size();
   p.poseC = dPoseC_.p; p.extC = dExtC_.p; p.sbC = dSbC_.p; p.lmC = dLmC_.p;
   p.poseOff = dPoseOff_.p; p.extOff = dExtOff_.p; p.sbOff = dSbOff_.p;
   p.cams = dCams_.p;
   p.lossTab = nLoss_ > 1 ? dLossTab_.p : nullptr;
-  p.schurDense = schurDense ? 1 : 0;
-  p.schurPanels = schurPanels ? 1 : 0; p.nPanelBlocks = nPanelBlocks; p.nPanelPairs = nPanelPairs;
-  p.schurBlocks = schurBlocks ? 1 : 0; p.nSlots = (int)hSlotBlk.size();
+  p.schurDense = a.form.schurDense ? 1 : 0;
+  p.schurPanels = a.form.schurPanels ? 1 : 0;
+  p.nPanelBlocks = schurBlocks ? a.rows.nPanelBlocks : a.panels.nPanelBlocks;
+  p.nPanelPairs = schurBlocks ? a.rows.nPanelPairs : a.panels.nPanelPairs;
+  p.schurBlocks = schurBlocks ? 1 : 0; p.nSlots = (int)a.slots.slotBlk.size();
   p.slotPtr = dSlotPtr_.p; p.slotBlk = dSlotBlk_.p; p.slotObsPtr = dSlotObsPtr_.p; p.slotObs = dSlotObs_.p; p.slotLm = dSlotLm_.p; p.slotRec = dSlotRec_.p;
   p.blkOwn = reinterpret_cast<const int4*>(dPanelChunks_.p); p.blkPartial = dBlkPartial_.p; p.blkPairs = dBlkPairs_.p;
   p.blkBatch = reinterpret_cast<const int2*>(dBlkBatch_.p); p.blkWaveTab = reinterpret_cast<const int4*>(dBlkWaveTab_.p); p.blkRecSlot = dBlkRecSlot_.p;
@@ -2278,7 +2057,7 @@ void Window::pack(bool solveFollows) {
     double* ps = dPriorScratch_.p;
     p.priorDchi = ps; p.priorGrad = ps + priorM; p.priorDchiC = ps + 2 * priorM; p.priorGradC = ps + 3 * priorM;
     p.priorMv = ps + 4 * priorM; p.priorMy = ps + 5 * priorM;
-    p.priorM3 = ps + 6 * priorM; p.priorM3C = p.priorM3 + 9 * hPb.size();
+    p.priorM3 = ps + 6 * priorM; p.priorM3C = p.priorM3 + 9 * a.hPb.size();
   }
   const int dd = std::max(d, 1);
   // accumulators start clear: the trust-region loop never launches k_zero_build (k_post_solve re-clears them)
@@ -2293,35 +2072,29 @@ void Window::pack(bool solveFollows) {
   p.Vinv = dLmVec_.p; p.bl = dLmVec_.p + 6 * LL; p.hL = dLmVec_.p + 9 * LL; p.scaleL = dLmVec_.p + 12 * LL;
   p.yL = dLmVec_.p + 15 * LL; p.deltaL = dLmVec_.p + 18 * LL; p.vL = dLmVec_.p + 21 * LL;
   p.lmFactor = dLmVec_.p + 27 * LL;
-  p.sbChain = sbChain;
-  p.slabs = dSlabs_.p; p.nSlabs = nSlabs;
+  p.sbChain = a.sbChain;
+  p.slabs = dSlabs_.p; p.nSlabs = a.form.nSlabs;
   p.cholL = dChol_.p;
   p.scal = dScal_.p;
   p.partial = dPartial_.p;
   p.tickets = reinterpret_cast<unsigned int*>(dPartial_.p + (size_t)14 * 4096);  // zeroed with the partials
   static_assert(sizeof(SolverScalars) % 16 == 0, "cleared in 16-byte words by the scatter kernel");
-  // optimize() on the resident path: a factor that still has to be pre-integrated (the frame's new ImuError, redo_ = true,
-  // ImuError.cpp:739) is evaluated once on a side stream while the main stream rebuilds the observation table -- the two
-  // do not depend on each other, and the ~40 us integration chain is otherwise the first thing the solve waits for.  The
-  // results of this evaluation are discarded (the solve's first evaluation repeats it, now without the integration); only
-  // the pre-integration state stays.  Not in prepare(): there the upload is outside the measured region and the solve is not.
-  const bool noEarlyImu = optOn(kOptNoEarlyImu);
-  if (solveFollows && resident && !noEarlyImu && F > 0) {
-    bool anyRedo = false;
-    for (const DevImu& im : hImu) anyRedo |= im.redo != 0;
-    if (anyRedo) {
-      HIP_OK(hipStreamWaitEvent(stream2_, evUploaded_, 0));
-      launchEvalFactors(p, false, stream2_, false);
-      HIP_OK(hipEventRecord(evImuReady_, stream2_));
-      HIP_OK(hipStreamWaitEvent(s, evImuReady_, 0));
-    }
-  }
-  if (optOn(kOptPackTiming)) {
-    const double tPack2 = nowSec();
-    HIP_OK(hipStreamSynchronize(s));
-    std::printf("[pack] host graph -> arrays %.1f us, allocation + enqueue %.1f us, drain %.1f us\n", 1e6 * (tPack1 - tPack0),
-                1e6 * (tPack2 - tPack1), 1e6 * (nowSec() - tPack2));
-  }
+}
+
+// optimize() on the resident path: a factor that still has to be pre-integrated (the frame's new ImuError, redo_ = true,
+// ImuError.cpp:739) is evaluated once on a side stream while the main stream rebuilds the observation table -- the two
+// do not depend on each other, and the ~40 us integration chain is otherwise the first thing the solve waits for.  The
+// results of this evaluation are discarded (the solve's first evaluation repeats it, now without the integration); only
+// the pre-integration state stays.  Not in prepare(): there the upload is outside the measured region and the solve is not.
+void Window::packEarlyImu(const PackHost& a) {
+  if (!a.resident || optOn(kOptNoEarlyImu) || a.F <= 0) return;
+  bool anyRedo = false;
+  for (const DevImu& im : a.hImu) anyRedo |= im.redo != 0;
+  if (!anyRedo) return;
+  HIP_OK(hipStreamWaitEvent(stream2_, evUploaded_, 0));
+  launchEvalFactors(prob_, false, stream2_, false);
+  HIP_OK(hipEventRecord(evImuReady_, stream2_));
+  HIP_OK(hipStreamWaitEvent(stream_, evImuReady_, 0));
 }
 
 void Window::downloadStates() {

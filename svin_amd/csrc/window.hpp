@@ -37,6 +37,8 @@ struct TimeStamp {
   uint32_t sec = 0, nsec = 0;
 };
 
+struct PackHost;   // the host arrays of one pack() (window.cpp)
+
 struct ExtrinsicsSigmas {
   double abs_t = 0, abs_r = 0, rel_t = 0, rel_r = 0;
 };
@@ -408,6 +410,15 @@ class Window {
   // staged upload of pack(): pinned host block + its device twin (segment table first), see launchScatterStaged
   struct StagedCopy { const void* src; size_t bytes; void* dst; };
   void flushStaged(const std::vector<StagedCopy>& pending, hipStream_t s);
+  // the steps of pack(), in order (the planning between packFactors and packReserveAndStage is pack_plan.hpp)
+  void packNumberSlots(PackHost& a);       // state slots (with the orphan blocks and the phantom pose), state tables, reduced-row maps
+  void packLandmarks(PackHost& a);         // landmarks + observations on the host path
+  void packFactors(PackHost& a);           // factors, prior blocks, the speed / bias chain test
+  int packSpeedBiasChain(const PackHost& a) const;
+  void packReserveAndStage(PackHost& a, std::vector<StagedCopy>& pending);   // device buffers; every upload queued in `pending`
+  void packFillProblem(const PackHost& a);   // prob_
+  void packEarlyImu(const PackHost& a);      // optimize() on the resident path: the pre-integration on the side stream
+  const std::unordered_map<uint64_t, int>& slotMapOf(int kind) const { return kind == B_POSE ? poseSlot_ : (kind == B_EXT ? extSlot_ : sbSlot_); }
   unsigned char* stageHost_ = nullptr;
   size_t stageHostCap_ = 0;
   DevBuf<unsigned char> stageDev_;
