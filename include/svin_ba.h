@@ -337,10 +337,23 @@ uint64_t svin_ba_map_add_depth_error(svin_ba* h, uint64_t pose_block, double dep
 typedef int (*svin_cost_function)(void* user, const double* const* parameters, double* residuals, double** jacobians_minimal);
 uint64_t svin_ba_map_add_host_residual(svin_ba* h, const uint64_t* block_ids, int n_blocks, int residual_dim, svin_cost_function fn, void* user);
 /* ReprojectionError<geometry of camera cam_idx>(uv, information) under CauchyLoss(1) on (pose, landmark, extrinsics)
- * (ReprojectionErrorBase.hpp:50-54, Estimator.cpp:69).  information: 2 x 2 row-major, a positive multiple of the identity
- * (the device stores one weight per residual, as Estimator::addObservation's 64 / size^2 * I needs). */
+ * (ReprojectionErrorBase.hpp:50-54, Estimator.cpp:69).  information: 2 x 2 row-major, any finite, symmetric
+ * (information[1] == information[2]) positive-definite matrix; the error is weighted by the transposed Cholesky factor
+ * S = L^T, information = L L^T (ReprojectionErrorBase::setInformation).  Anything else returns 0 with a svin_ba_last_error text.
+ * A multiple of the identity (Estimator::addObservation's 64 / size^2 * I) is stored as one weight per residual and takes the
+ * same device path as before.  Any other matrix is stored as S = (s00, s01, s11) beside the observation; a window that holds at
+ * least one such residual is packed by the host (svin_ba_get_path_counters out[1], its marginalisation jobs out[3]) until the
+ * last one is removed or set back to a multiple of the identity.  It is solved, batched, marginalised and answered by get_lhs
+ * like any other window.  Landmark-sharded mode has no code of its own for this: the weight is folded into the residual and its
+ * Jacobians by the evaluation kernels of every rank and never leaves them.  svin_ba_debug_csr's w reports +-s00. */
 uint64_t svin_ba_map_add_reprojection_error(svin_ba* h, uint64_t pose_block, uint64_t landmark_id, uint64_t extrinsics_block,
                                             uint64_t cam_idx, const double uv[2], const double information[4]);
+/* ReprojectionErrorBase::setInformation / information() of a reprojection residual, from svin_ba_add_observation(s) or
+ * svin_ba_map_add_reprojection_error alike (same conditions on the matrix as above; s * I returns the residual to the one-weight
+ * form).  1; SVIN_ERR_NOT_FOUND for an unknown residual; SVIN_ERR_UNSUPPORTED for a residual that is not a reprojection error
+ * (a HomogeneousPointError included); SVIN_ERR_INVALID_ARG for a bad matrix. */
+int svin_ba_map_set_reprojection_information(svin_ba* h, uint64_t residual_id, const double information[4]);
+int svin_ba_map_get_reprojection_information(svin_ba* h, uint64_t residual_id, double information[4]);
 /* Map::removeResidualBlock for any residual of the graph (Map.cpp:467-492) */
 int svin_ba_map_remove_residual_block(svin_ba* h, uint64_t residual_id);
 /* The loss function of a residual (Map::addResidualBlock's loss_function): SVIN_LOSS_NONE (ceres::TrivialLoss, or NULL),

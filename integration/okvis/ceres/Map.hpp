@@ -191,7 +191,8 @@ class Map {
     return record(svin_ba_add_homogeneous_point_error(h_, x0->id(), meas, e->informationRowMajor()), e, {x0});
   }
   /// ReprojectionError<GEOMETRY>(geometry, cameraId, measurement, information) on (T_WS, hp_W, T_SC) (TestMap.cpp:104-108,
-  /// Estimator::addObservation) under NULL / TrivialLoss (none), CauchyLoss(a) or HuberLoss(a).  information: a multiple of the identity.
+  /// Estimator::addObservation) under NULL / TrivialLoss (none), CauchyLoss(a) or HuberLoss(a).  information: any symmetric positive-definite 2x2 matrix
+  /// (ReprojectionErrorBase::setInformation); NULL when the backend refuses it.
   template <class GEOMETRY_T>
   ::ceres::ResidualBlockId addResidualBlock(std::shared_ptr<ReprojectionError<GEOMETRY_T> > e, ::ceres::LossFunction* loss,
                                             std::shared_ptr<okvis::ceres::ParameterBlock> pose, std::shared_ptr<okvis::ceres::ParameterBlock> point,

@@ -744,6 +744,16 @@ int svin_ba_map_get_residual_loss(svin_ba* h, uint64_t rid, int* kind, double* s
   GUARD_BEGIN return lossCode(ro(h).getResidualLoss(rid, kind, scale));
   GUARD_END(SVIN_ERR_DEVICE)
 }
+int svin_ba_map_set_reprojection_information(svin_ba* h, uint64_t rid, const double information[4]) {
+  if (!h) return SVIN_ERR_INVALID_ARG;
+  GUARD_BEGIN return win(h).setReprojectionInformation(rid, information);
+  GUARD_END(SVIN_ERR_DEVICE)
+}
+int svin_ba_map_get_reprojection_information(svin_ba* h, uint64_t rid, double information[4]) {
+  if (!h) return SVIN_ERR_INVALID_ARG;
+  GUARD_BEGIN return ro(h).getReprojectionInformation(rid, information);
+  GUARD_END(SVIN_ERR_DEVICE)
+}
 int svin_ba_get_lhs(svin_ba* h, uint64_t block_id, double* H, int cap) {
   if (!h || (!H && cap > 0)) return SVIN_ERR_INVALID_ARG;
   GUARD_BEGIN return h->w.getLhs(block_id, H, cap);

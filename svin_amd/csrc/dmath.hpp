@@ -238,12 +238,29 @@ SVIN_HD void projectHomogeneous(const CameraModel& c, double hx, double hy, doub
 }
 
 // ---------------------------------------------------------------- reprojection residual
-// Inputs: pose T_WS (7), landmark hp_W (4), extrinsics T_SC (7), measurement uv, isotropic
-// square-root information w (= sqrt(64/size^2), Estimator.hpp:64-67).
-// Outputs (all already multiplied by w): r(2), Jp 2x6, Jl 2x3, Je 2x6 (row-major).  Invalid
+// Square-root information of a reprojection residual (ReprojectionErrorBase::setInformation): S = L^T of information = L L^T,
+// the unblocked LLT reading the LOWER triangle (row-major index 2) as Eigen does.  S = (s00, s01, s11), upper triangular.
+// false: an entry is not finite or the matrix is not positive definite (S is then unspecified).  Host-side data preparation.
+inline bool reprojSqrtInformation(const double* info, double* S) {
+  const double i00 = info[0], i10 = info[2], i11 = info[3];
+  if (!std::isfinite(i00) || !std::isfinite(i10) || !std::isfinite(i11) || !(i00 > 0.0)) return false;
+  const double l00 = std::sqrt(i00), l10 = i10 / l00, t = i11 - l10 * l10;
+  if (!(t > 0.0)) return false;
+  S[0] = l00; S[1] = l10; S[2] = std::sqrt(t);
+  return std::isfinite(S[0]) && std::isfinite(S[1]) && std::isfinite(S[2]);
+}
+// what a caller may hand over as an information matrix: finite, symmetric, positive definite (S as above)
+inline bool reprojInformationValid(const double* info, double* S) {
+  return std::isfinite(info[1]) && info[1] == info[2] && reprojSqrtInformation(info, S);
+}
+// Inputs: pose T_WS (7), landmark hp_W (4), extrinsics T_SC (7), measurement uv and the square-root information:
+// isotropic w (= sqrt(64/size^2), Estimator.hpp:64-67) or the upper-triangular S = (s00, s01, s11) of any 2x2 information.
+// Outputs (all already multiplied by the square-root information): r(2), Jp 2x6, Jl 2x3, Je 2x6 (row-major).  Invalid
 // points (|w_C|>1e-8 and z_C<0.2) keep their residual but get zero Jacobians (:140-147).
-SVIN_HD void reprojEval(const CameraModel& cam, const double* T_WS, const double* hpW, const double* T_SC, double u,
-                        double v, double w, double* r, double* Jp, double* Jl, double* Je) {
+// GENERAL = false: s00 is the scalar w and s01, s11 are not read -- the arithmetic of the isotropic form, operation for operation.
+template <bool GENERAL>
+SVIN_HD void reprojEvalCore(const CameraModel& cam, const double* T_WS, const double* hpW, const double* T_SC, double u,
+                            double v, double s00, double s01, double s11, double* r, double* Jp, double* Jl, double* Je) {
   const Mat3 C_WS = quatToR(Quat{T_WS[3], T_WS[4], T_WS[5], T_WS[6]});
   const Mat3 C_SC = quatToR(Quat{T_SC[3], T_SC[4], T_SC[5], T_SC[6]});
   const double hw = hpW[3];
@@ -254,8 +271,14 @@ SVIN_HD void reprojEval(const CameraModel& cam, const double* T_WS, const double
   const Vec3 pC = rotateT(C_SC, dS);
   double kx, ky, J3[6];
   projectHomogeneous(cam, pC.x, pC.y, pC.z, hw, kx, ky, J3);
-  r[0] = w * (u - kx);
-  r[1] = w * (v - ky);
+  if (GENERAL) {   // r = S (uv - projection)
+    const double e0 = u - kx, e1 = v - ky;
+    r[0] = s00 * e0 + s01 * e1;
+    r[1] = s11 * e1;
+  } else {
+    r[0] = s00 * (u - kx);
+    r[1] = s00 * (v - ky);
+  }
   bool valid = true;
   if (fabs(hw) > 1.0e-8) {
     if (pC.z / hw < 0.2) valid = false;
@@ -267,7 +290,11 @@ SVIN_HD void reprojEval(const CameraModel& cam, const double* T_WS, const double
   }
   // weighted projection Jacobian (2x3), the homogeneous column of Jh is zero
   double Jw[6];
-  for (int i = 0; i < 6; ++i) Jw[i] = w * J3[i];
+  if (GENERAL) {   // Jw = S J3
+    for (int i = 0; i < 3; ++i) { Jw[i] = s00 * J3[i] + s01 * J3[3 + i]; Jw[3 + i] = s11 * J3[3 + i]; }
+  } else {
+    for (int i = 0; i < 6; ++i) Jw[i] = s00 * J3[i];
+  }
   // A = Jw * C_CS  (2x3),  C_CS = C_SC^T  ->  A[i][j] = sum_k Jw[i][k] C_SC[j][k]
   double A[6];
   for (int i = 0; i < 2; ++i)
@@ -295,6 +322,14 @@ SVIN_HD void reprojEval(const CameraModel& cam, const double* T_WS, const double
     Je[i * 6 + 4] = -(a2 * dS.x - a0 * dS.z);
     Je[i * 6 + 5] = -(a0 * dS.y - a1 * dS.x);
   }
+}
+SVIN_HD void reprojEval(const CameraModel& cam, const double* T_WS, const double* hpW, const double* T_SC, double u,
+                        double v, double w, double* r, double* Jp, double* Jl, double* Je) {
+  reprojEvalCore<false>(cam, T_WS, hpW, T_SC, u, v, w, 0.0, w, r, Jp, Jl, Je);
+}
+SVIN_HD void reprojEval(const CameraModel& cam, const double* T_WS, const double* hpW, const double* T_SC, double u,
+                        double v, double s00, double s01, double s11, double* r, double* Jp, double* Jl, double* Je) {
+  reprojEvalCore<true>(cam, T_WS, hpW, T_SC, u, v, s00, s01, s11, r, Jp, Jl, Je);
 }
 
 // Cauchy(1) loss (ceres loss_function.cc) on s = |r|^2: rho, rho', rho''

@@ -251,15 +251,13 @@ int svin_host_reprojection_error(int model, const double intr[4], const double* 
   cam.fu = intr[0]; cam.fv = intr[1]; cam.cu = intr[2]; cam.cv = intr[3];
   for (int i = 0; i < n_dist; ++i) cam.k[i] = dist[i];
   cam.model = model;
-  // unweighted residual and Jacobians, then the 2x2 square-root information L^T of information = L L^T
-  // (ReprojectionErrorBase::setInformation: Eigen LLT, upper factor)
+  // the 2x2 square-root information S = L^T of information = L L^T (ReprojectionErrorBase::setInformation: Eigen LLT, upper
+  // factor), then the device's own general form of the residual (dmath.hpp): r = S e, Jw = S J3 ahead of the rotation chain
+  double S[3];
+  if (!svin::reprojSqrtInformation(information, S)) return SVIN_ERR_INVALID_ARG;
+  const double l00 = S[0], l10 = S[1], l11 = S[2];
   double r[2], Jp[12], Jl[6], Je[12];
-  svin::reprojEval(cam, T_WS, hp_W, T_SC, uv[0], uv[1], 1.0, r, Jp, Jl, Je);
-  const double i00 = information[0], i10 = 0.5 * (information[1] + information[2]), i11 = information[3];
-  if (!(i00 > 0)) return SVIN_ERR_INVALID_ARG;
-  const double l00 = std::sqrt(i00), l10 = i10 / l00, t = i11 - l10 * l10;
-  if (!(t > 0)) return SVIN_ERR_INVALID_ARG;
-  const double l11 = std::sqrt(t);
+  svin::reprojEval(cam, T_WS, hp_W, T_SC, uv[0], uv[1], l00, l10, l11, r, Jp, Jl, Je);
   // W = L^T = [l00 l10; 0 l11]
   auto weight = [&](double* M, int cols) {
     for (int c = 0; c < cols; ++c) {
@@ -268,7 +266,6 @@ int svin_host_reprojection_error(int model, const double intr[4], const double* 
       M[cols + c] = l11 * b;
     }
   };
-  weight(r, 1); weight(Jp, 6); weight(Jl, 3); weight(Je, 6);
   residual[0] = r[0]; residual[1] = r[1];
   if (J_pose_min) std::memcpy(J_pose_min, Jp, sizeof(Jp));
   if (J_lm_min) std::memcpy(J_lm_min, Jl, sizeof(Jl));

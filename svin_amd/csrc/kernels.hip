@@ -441,7 +441,8 @@ struct LmDefer {   // passed BY VALUE (through a pointer it lands in scratch and
   double* stepPartial = nullptr;
   double* xPartial = nullptr;
 };
-template <bool ROBUST, bool WITH_EXT>
+// GENERAL: `obsS` may be set (DeviceProblem::obsS, stride `stride`); the kernels compiled without it never read the pointer
+template <bool ROBUST, bool WITH_EXT, bool GENERAL = false>
 __device__ __forceinline__ void evalReprojBlock(int block, double* smem, double* red, int N, int nPose, int nExt, int nCam,
                                                 const double* __restrict__ pose, const double* __restrict__ ext,
                                                 const double* __restrict__ lm, const CameraModel* __restrict__ cams,
@@ -450,7 +451,8 @@ __device__ __forceinline__ void evalReprojBlock(int block, double* smem, double*
                                                 double* __restrict__ r, double* __restrict__ Jp, double* __restrict__ Jl,
                                                 double* __restrict__ Je, double* __restrict__ costPartial, size_t stride,
                                                 const LmDefer df = LmDefer(), const double* __restrict__ lmPrior = nullptr,
-                                                const double* __restrict__ lossTab = nullptr) {
+                                                const double* __restrict__ lossTab = nullptr,
+                                                const double* __restrict__ obsS = nullptr) {
   double* sPose = smem;                      // nPose*7
   double* sExt = sPose + nPose * 7;          // nExt*7
   CameraModel* sCam = reinterpret_cast<CameraModel*>(sExt + nExt * 7);  // nCam
@@ -513,6 +515,8 @@ __device__ __forceinline__ void evalReprojBlock(int block, double* smem, double*
       rr[1] = jl[3] * e0 + jl[4] * e1 + jl[5] * e2;
 #pragma unroll
       for (int k = 0; k < 12; ++k) { jp[k] = 0.0; je[k] = 0.0; }
+    } else if (GENERAL && obsS) {
+      reprojEval(sCam[cs], sPose + ps * 7, hpw, sExt + es * 7, uv.x, uv.y, obsS[i], obsS[stride + i], obsS[2 * stride + i], rr, jp, jl, je);
     } else {
       reprojEval(sCam[cs], sPose + ps * 7, hpw, sExt + es * 7, uv.x, uv.y, w, rr, jp, jl, je);
     }
@@ -570,7 +574,7 @@ __device__ __forceinline__ void evalReprojBlock(int block, double* smem, double*
   }
 }
 
-template <bool ROBUST, bool WITH_EXT>
+template <bool ROBUST, bool WITH_EXT, bool GENERAL = false>
 __global__ __launch_bounds__(128) void k_eval_reproj(int N, int nPose, int nExt, int nCam, const double* __restrict__ pose,
                                                      const double* __restrict__ ext, const double* __restrict__ lm,
                                                      const CameraModel* __restrict__ cams,
@@ -579,11 +583,12 @@ __global__ __launch_bounds__(128) void k_eval_reproj(int N, int nPose, int nExt,
                                                      double* __restrict__ r, double* __restrict__ Jp,
                                                      double* __restrict__ Jl, double* __restrict__ Je,
                                                      double* __restrict__ costPartial, size_t stride,
-                                                     const double* __restrict__ lmPrior, const double* __restrict__ lossTab) {
+                                                     const double* __restrict__ lmPrior, const double* __restrict__ lossTab,
+                                                     const double* __restrict__ obsS) {
   extern __shared__ double smem[];
   __shared__ double red[4];
-  evalReprojBlock<ROBUST, WITH_EXT>(blockIdx.x, smem, red, N, nPose, nExt, nCam, pose, ext, lm, cams, obsUv, obsW, obsIdx,
-                                    obsLm, r, Jp, Jl, Je, costPartial, stride, LmDefer(), lmPrior, lossTab);
+  evalReprojBlock<ROBUST, WITH_EXT, GENERAL>(blockIdx.x, smem, red, N, nPose, nExt, nCam, pose, ext, lm, cams, obsUv, obsW, obsIdx,
+                                             obsLm, r, Jp, Jl, Je, costPartial, stride, LmDefer(), lmPrior, lossTab, obsS);
 }
 
 static int evalGrid(int N) { return (N + 127) / 128; }
@@ -600,10 +605,13 @@ void launchEvalReproj(const DeviceProblem& p, bool cand, bool robust, hipStream_
   double* Jl = cand ? p.JlCand : p.JlCur;
   double* Je = cand ? p.JeCand : p.JeCur;
   double* cp = p.partial + (size_t)PS_COST_REPROJ * kMaxPartials;
-  const auto kernel = robust ? (p.anyExtVariable ? k_eval_reproj<true, true> : k_eval_reproj<true, false>)
-                              : (p.anyExtVariable ? k_eval_reproj<false, true> : k_eval_reproj<false, false>);
+  auto kernel = robust ? (p.anyExtVariable ? k_eval_reproj<true, true> : k_eval_reproj<true, false>)
+                        : (p.anyExtVariable ? k_eval_reproj<false, true> : k_eval_reproj<false, false>);
+  if (p.obsS)
+    kernel = robust ? (p.anyExtVariable ? k_eval_reproj<true, true, true> : k_eval_reproj<true, false, true>)
+                    : (p.anyExtVariable ? k_eval_reproj<false, true, true> : k_eval_reproj<false, false, true>);
   launch(kernel, dim3(grid), dim3(128), smem, s, p.N, p.nPose, p.nExt, p.nCam, pose, ext, lm, p.cams, p.obsUv, p.obsW, p.obsIdx,
-         p.obsLm, r, Jp, Jl, Je, cp, (size_t)p.N, p.lmPrior, p.lossTab);
+         p.obsLm, r, Jp, Jl, Je, cp, (size_t)p.N, p.lmPrior, p.lossTab, p.obsS);
 }
 
 // Jacobian-evaluation roofline kernel on `copies` independent replicas of the window (HBM-resident
@@ -618,11 +626,11 @@ void launchEvalReprojBatched(const DeviceProblem& p, int copies, double* rOut, d
   if (p.anyExtVariable)
     launch(k_eval_reproj<true, true>, dim3(grid), dim3(128), smem, s, NB, p.nPose, p.nExt, p.nCam, p.pose,
            p.ext, p.lm, p.cams, p.obsUv, p.obsW, p.obsIdx, p.obsLm, rOut, JpOut, JlOut, JeOut,
-           (double*)nullptr, (size_t)NB, p.lmPrior, (const double*)nullptr);
+           (double*)nullptr, (size_t)NB, p.lmPrior, (const double*)nullptr, (const double*)nullptr);
   else
     launch(k_eval_reproj<true, false>, dim3(grid), dim3(128), smem, s, NB, p.nPose, p.nExt, p.nCam,
            p.pose, p.ext, p.lm, p.cams, p.obsUv, p.obsW, p.obsIdx, p.obsLm, rOut, JpOut, JlOut, JeOut,
-           (double*)nullptr, (size_t)NB, p.lmPrior, (const double*)nullptr);
+           (double*)nullptr, (size_t)NB, p.lmPrior, (const double*)nullptr, (const double*)nullptr);
 }
 
 // ================================================================ K2: small factors (one workgroup each)
@@ -1847,7 +1855,7 @@ void launchEvalPrior(const DeviceProblem& p, bool cand, hipStream_t s, bool sumC
 // take tens of microseconds), blocks [F, F + nR) the reprojection residuals with 256 observations each, side by side
 // in one launch, plus one block for the marginalisation prior (hasPrior); the block that finishes last sums the cost
 // (sumCost) and publishes the scalars.
-template <bool WITH_EXT>
+template <bool WITH_EXT, bool GENERAL>
 __device__ __forceinline__ void k_eval_all_body(const DeviceProblem& p, int cand, int nR, int sumCost, int hasPrior) {
   __shared__ FactorShared sh;
   const int F = (int)gridDim.x - nR - hasPrior;
@@ -1876,11 +1884,11 @@ __device__ __forceinline__ void k_eval_all_body(const DeviceProblem& p, int cand
       df.stepPartial = p.partial + (size_t)PS_STEP * kMaxPartials;
       df.xPartial = p.partial + (size_t)PS_XNORM * kMaxPartials;
     }
-    evalReprojBlock<true, WITH_EXT>(blockIdx.x - F, smem + 48, smem, p.N, p.nPose, p.nExt, p.nCam, cand ? p.poseC : p.pose,
+    evalReprojBlock<true, WITH_EXT, GENERAL>(blockIdx.x - F, smem + 48, smem, p.N, p.nPose, p.nExt, p.nCam, cand ? p.poseC : p.pose,
                                     cand ? p.extC : p.ext, defer ? p.lm : (cand ? p.lmC : p.lm), p.cams, p.obsUv, p.obsW, p.obsIdx, p.obsLm,
                                     cand ? p.rCand : p.rCur, cand ? p.JpCand : p.JpCur, cand ? p.JlCand : p.JlCur,
                                     cand ? p.JeCand : p.JeCur, p.partial + (size_t)PS_COST_REPROJ * kMaxPartials, (size_t)p.N,
-                                    df, p.lmPrior, p.lossTab);
+                                    df, p.lmPrior, p.lossTab, GENERAL ? p.obsS : nullptr);
   }
   TRACE(18);
   if (sumCost) {
@@ -1894,8 +1902,8 @@ __device__ __forceinline__ void k_eval_all_body(const DeviceProblem& p, int cand
     }
   }
 }
-template <bool WITH_EXT>
-__global__ __launch_bounds__(256) void k_eval_all(DeviceProblem p, int cand, int nR, int sumCost, int hasPrior) { k_eval_all_body<WITH_EXT>(p, cand, nR, sumCost, hasPrior); }
+template <bool WITH_EXT, bool GENERAL = false>
+__global__ __launch_bounds__(256) void k_eval_all(DeviceProblem p, int cand, int nR, int sumCost, int hasPrior) { k_eval_all_body<WITH_EXT, GENERAL>(p, cand, nR, sumCost, hasPrior); }
 // The slot of this block's window.  The table is written by the host's copy before the launch and by nothing afterwards, so it is
 // read through the CONSTANT address space like the kernel arguments it replaces: every field stays a scalar load the compiler may
 // repeat wherever it likes.  Through a plain global pointer the loads behind the first barrier go through the vector memory path
@@ -1909,7 +1917,7 @@ __device__ __forceinline__ const BatchSlot& batchSlot(const BatchSlot* slots) {
 // grid the reprojection blocks are what fills the chip, so they get a kernel of their own (staging area only, registers of
 // evalReprojBlock alone) and the factor / prior blocks follow with the cost sum.  Same device functions, same partial slots,
 // same summation order as k_eval_all: a window's numbers do not change.
-template <bool WITH_EXT>
+template <bool WITH_EXT, bool GENERAL>
 __device__ __forceinline__ void evalReprojSplitBody(const DeviceProblem& p, int cand, double* smem) {
   SVIN_ARGS(SA(p.poseC), SA(p.pose), SA(p.extC), SA(p.ext), SA(p.lm), SA(p.lmC), SA(p.cams), SA(p.obsUv), SA(p.obsW), SA(p.obsIdx),
             SA(p.obsLm), SA(p.rCand), SA(p.JpCand), SA(p.JlCand), SA(p.partial), SA(p.scal), SA(p.vL), SA(p.yL), SA(p.lmPtr), SA(p.N),
@@ -1923,11 +1931,11 @@ __device__ __forceinline__ void evalReprojSplitBody(const DeviceProblem& p, int 
     df.stepPartial = p.partial + (size_t)PS_STEP * kMaxPartials;
     df.xPartial = p.partial + (size_t)PS_XNORM * kMaxPartials;
   }
-  evalReprojBlock<true, WITH_EXT>(blockIdx.x, smem + 48, smem, p.N, p.nPose, p.nExt, p.nCam, cand ? p.poseC : p.pose,
+  evalReprojBlock<true, WITH_EXT, GENERAL>(blockIdx.x, smem + 48, smem, p.N, p.nPose, p.nExt, p.nCam, cand ? p.poseC : p.pose,
                                   cand ? p.extC : p.ext, defer ? p.lm : (cand ? p.lmC : p.lm), p.cams, p.obsUv, p.obsW, p.obsIdx, p.obsLm,
                                   cand ? p.rCand : p.rCur, cand ? p.JpCand : p.JpCur, cand ? p.JlCand : p.JlCur,
                                   cand ? p.JeCand : p.JeCur, p.partial + (size_t)PS_COST_REPROJ * kMaxPartials, (size_t)p.N,
-                                  df, p.lmPrior, p.lossTab);
+                                  df, p.lmPrior, p.lossTab, GENERAL ? p.obsS : nullptr);
 }
 // blocks [0, F): the small factors, block F (hasPrior): the marginalisation prior; the block that finishes last sums the cost
 // (nBlocks = F + hasPrior: the launch's gridDim.x for one window, the window's own extent in a batch; nR: the reprojection
@@ -1949,12 +1957,12 @@ __device__ __forceinline__ void evalRestSplitBody(const DeviceProblem& p, int ca
     if (threadIdx.x == 0) p.tickets[TK_EVAL] = 0;
   }
 }
-template <bool WITH_EXT>
+template <bool WITH_EXT, bool GENERAL = false>
 __global__ __launch_bounds__(256) void k_eval_reproj_batch(const BatchSlot* __restrict__ slots, int cand) {
   extern __shared__ double smem[];
   const BatchSlot& sl = batchSlot(slots);
   if (!(sl.stages & kBatchEval) || (int)blockIdx.x >= sl.ext.evalR) return;   // (beyond the window's own blocks: no partial, no store)
-  evalReprojSplitBody<WITH_EXT>(sl.p, cand, smem);
+  evalReprojSplitBody<WITH_EXT, GENERAL>(sl.p, cand, smem);
 }
 __global__ __launch_bounds__(256) void k_eval_rest_batch(const BatchSlot* __restrict__ slots, int cand) {
   __shared__ FactorShared sh;
@@ -1965,10 +1973,10 @@ __global__ __launch_bounds__(256) void k_eval_rest_batch(const BatchSlot* __rest
 }
 // The same two launches for ONE window whose evaluation has more blocks than the chip has CUs (wide windows: 1 954 reprojection
 // blocks at 500 000 observations): in k_eval_all every block carries the factor blocks' LDS, one workgroup per CU.
-template <bool WITH_EXT>
+template <bool WITH_EXT, bool GENERAL = false>
 __global__ __launch_bounds__(256) void k_eval_reproj_split(DeviceProblem p, int cand) {
   extern __shared__ double smem[];
-  evalReprojSplitBody<WITH_EXT>(p, cand, smem);
+  evalReprojSplitBody<WITH_EXT, GENERAL>(p, cand, smem);
 }
 __global__ __launch_bounds__(256) void k_eval_rest_split(DeviceProblem p, int cand, int nR, int hasPrior) {
   __shared__ FactorShared sh;
@@ -1994,12 +2002,18 @@ void launchEvalAll(const DeviceProblem& p, bool cand, bool sumCost, hipStream_t 
     //  reprojection blocks instead of behind them -- the side chain then ends before the main one needs it, but the reprojection
     //  launch takes 41 us instead of 27 next to it: 0.65 again.  A side stream of the highest priority changes nothing either: the
     //  one workgroup of k_sb_factor / the few of k_sb_forward run 4-5 x slower next to k_schur_rows whatever the queue says.)
-    if (p.anyExtVariable) launch(k_eval_reproj_split<true>, dim3(nR), dim3(256), stage, s, p, cand ? 1 : 0);
+    if (p.obsS) {   // a window with general information matrices: the kernels that read obsS
+      if (p.anyExtVariable) launch(k_eval_reproj_split<true, true>, dim3(nR), dim3(256), stage, s, p, cand ? 1 : 0);
+      else launch(k_eval_reproj_split<false, true>, dim3(nR), dim3(256), stage, s, p, cand ? 1 : 0);
+    } else if (p.anyExtVariable) launch(k_eval_reproj_split<true>, dim3(nR), dim3(256), stage, s, p, cand ? 1 : 0);
     else launch(k_eval_reproj_split<false>, dim3(nR), dim3(256), stage, s, p, cand ? 1 : 0);
     launch(k_eval_rest_split, dim3(p.F + pri), dim3(256), 0, s, p, cand ? 1 : 0, nR, pri);
     return;
   }
-  if (p.anyExtVariable)
+  if (p.obsS) {
+    if (p.anyExtVariable) launch(k_eval_all<true, true>, dim3(p.F + nR + pri), dim3(256), 0, s, p, cand ? 1 : 0, nR, sumCost ? 1 : 0, pri);
+    else launch(k_eval_all<false, true>, dim3(p.F + nR + pri), dim3(256), 0, s, p, cand ? 1 : 0, nR, sumCost ? 1 : 0, pri);
+  } else if (p.anyExtVariable)
     launch(k_eval_all<true>, dim3(p.F + nR + pri), dim3(256), 0, s, p, cand ? 1 : 0, nR, sumCost ? 1 : 0, pri);
   else
     launch(k_eval_all<false>, dim3(p.F + nR + pri), dim3(256), 0, s, p, cand ? 1 : 0, nR, sumCost ? 1 : 0, pri);
@@ -7333,7 +7347,8 @@ bool batchSupported(const DeviceProblem& p) {
   if (p.nHostFactors > 0) return false;
   return true;
 }
-void launchBatchRound(const BatchSlot* dSlots, const DeviceProblem& geom, const BatchGrid& grid, int n, int stagesUnion, bool cand, hipStream_t s) {
+void launchBatchRound(const BatchSlot* dSlots, const DeviceProblem& geom, const BatchGrid& grid, int n, int stagesUnion, bool cand, hipStream_t s,
+                      bool anyObsS) {
   const DeviceProblem& p = geom;
   if (stagesUnion & kBatchFull) {
     const DenseSchurPlan plan = denseSchurPlan(p);
@@ -7353,7 +7368,10 @@ void launchBatchRound(const BatchSlot* dSlots, const DeviceProblem& geom, const 
   if (stagesUnion & kBatchReuse) launch(k_step_retract_batch, dim3(grid.step, n), dim3(256), 0, s, dSlots);
   if (stagesUnion & kBatchEval) {
     const size_t stage = evalSplitStageBytes(p);
-    if (p.anyExtVariable) launch(k_eval_reproj_batch<true>, dim3(grid.evalR, n), dim3(256), stage, s, dSlots, cand ? 1 : 0);
+    if (anyObsS) {   // every block reads its own slot's obsS: a window without one takes the scalar arithmetic there as well
+      if (p.anyExtVariable) launch(k_eval_reproj_batch<true, true>, dim3(grid.evalR, n), dim3(256), stage, s, dSlots, cand ? 1 : 0);
+      else launch(k_eval_reproj_batch<false, true>, dim3(grid.evalR, n), dim3(256), stage, s, dSlots, cand ? 1 : 0);
+    } else if (p.anyExtVariable) launch(k_eval_reproj_batch<true>, dim3(grid.evalR, n), dim3(256), stage, s, dSlots, cand ? 1 : 0);
     else launch(k_eval_reproj_batch<false>, dim3(grid.evalR, n), dim3(256), stage, s, dSlots, cand ? 1 : 0);
     launch(k_eval_rest_batch, dim3(grid.evalRest, n), dim3(256), 0, s, dSlots, cand ? 1 : 0);
   }
@@ -7364,6 +7382,9 @@ void launchBatchRound(const BatchSlot* dSlots, const DeviceProblem& geom, const 
 // eigenvalues by cyclic Jacobi, quality = sqrt(lmin)/sqrt(lmax) (0 if lmin < 1e-12).
 // 16 lanes per landmark, one observation per lane and turn (a thread per landmark walked its ~10 observations serially:
 // 23 us for 2 000 landmarks)
+// GENERAL: the window holds general 2x2 information matrices (p.obsS set); chosen at launch, so that the one-weight kernel keeps
+// its registers (168 VGPRs, three waves per SIMD; both forms in one body: 194 and two)
+template <bool GENERAL>
 __global__ __launch_bounds__(256) void k_landmark_quality(DeviceProblem p, double* __restrict__ quality) {
   const int l = blockIdx.x * 16 + (threadIdx.x >> 4), gl = threadIdx.x & 15;
   if (l >= p.L) return;   // whole 16-lane rows leave together
@@ -7379,8 +7400,12 @@ __global__ __launch_bounds__(256) void k_landmark_quality(DeviceProblem p, doubl
       const bool second = p.obsUv[2 * (size_t)o + 1] != 0.0;
       for (int k = 0; k < 3; ++k) { jl[k] = pr[3 + (second ? 6 : 0) + k]; jl[3 + k] = second ? 0.0 : pr[6 + k]; }
     } else {
-      reprojEval(p.cams[(idx >> 24) & 0xf], p.pose + (size_t)(idx & 0xfff) * 7, hpw, p.ext + (size_t)((idx >> 12) & 0xfff) * 7,
-                 p.obsUv[2 * (size_t)o], p.obsUv[2 * (size_t)o + 1], fabs(p.obsW[o]), rr, jp, jl, je);   // (Map::getLhs does not ask whether the block is constant)
+      if (GENERAL)
+        reprojEval(p.cams[(idx >> 24) & 0xf], p.pose + (size_t)(idx & 0xfff) * 7, hpw, p.ext + (size_t)((idx >> 12) & 0xfff) * 7,
+                   p.obsUv[2 * (size_t)o], p.obsUv[2 * (size_t)o + 1], p.obsS[o], p.obsS[(size_t)p.N + o], p.obsS[2 * (size_t)p.N + o], rr, jp, jl, je);
+      else
+        reprojEval(p.cams[(idx >> 24) & 0xf], p.pose + (size_t)(idx & 0xfff) * 7, hpw, p.ext + (size_t)((idx >> 12) & 0xfff) * 7,
+                   p.obsUv[2 * (size_t)o], p.obsUv[2 * (size_t)o + 1], fabs(p.obsW[o]), rr, jp, jl, je);   // (Map::getLhs does not ask whether the block is constant)
     }
     a00 += jl[0] * jl[0] + jl[3] * jl[3]; a01 += jl[0] * jl[1] + jl[3] * jl[4]; a02 += jl[0] * jl[2] + jl[3] * jl[5];
     a11 += jl[1] * jl[1] + jl[4] * jl[4]; a12 += jl[1] * jl[2] + jl[4] * jl[5]; a22 += jl[2] * jl[2] + jl[5] * jl[5];
@@ -7414,7 +7439,8 @@ __global__ __launch_bounds__(256) void k_landmark_quality(DeviceProblem p, doubl
 }
 
 void launchLandmarkQuality(const DeviceProblem& p, double* quality, hipStream_t s) {
-  launch(k_landmark_quality, dim3((p.L + 15) / 16), dim3(256), 0, s, p, quality);
+  if (p.obsS) launch(k_landmark_quality<true>, dim3((p.L + 15) / 16), dim3(256), 0, s, p, quality);
+  else launch(k_landmark_quality<false>, dim3((p.L + 15) / 16), dim3(256), 0, s, p, quality);
 }
 
 }  // namespace svin

@@ -218,6 +218,11 @@ struct DeviceProblem {
   // which is what the trust-region loop does anyway.
   int sideLane;
   const double* lossTab;   // reprojection loss table: (kind, a) per selector of the packed index; nullptr = every selector 0 (CauchyLoss(1))
+  // General 2x2 information on reprojection residuals: the upper-triangular square-root information S = (s00, s01, s11) of every
+  // observation, component-major with stride N like the Jacobian arrays (obsS[c * N + o]).  nullptr = every observation is
+  // isotropic: the evaluation reads obsW alone and takes the scalar arithmetic.  When set, |obsW| = s00 and only its sign
+  // (constant landmark) is read.  Host-packed windows only (the device-resident window's records carry one weight).
+  const double* obsS;
 };
 
 // ---- batched solve (svin_ba_solve_prepared_batch: B independent windows through ONE launch sequence per trust-region round, the
@@ -240,7 +245,9 @@ bool batchSupported(const DeviceProblem& p);   // the geometry the batched kerne
 // one round for the `n` windows of dSlots (device copy of the slot table); `geom` = any window of the batch (what the launcher reads
 // of it is equal in all of them), `grid` = gridDim.x of every launch (the largest extent among the windows taking part),
 // `stagesUnion` = OR of the slots' stages, `cand` as for launchEvalAll
-void launchBatchRound(const BatchSlot* dSlots, const DeviceProblem& geom, const BatchGrid& grid, int n, int stagesUnion, bool cand, hipStream_t s);
+// `anyObsS`: a window of the batch has DeviceProblem::obsS set (the reprojection blocks then run the kernel that can read it)
+void launchBatchRound(const BatchSlot* dSlots, const DeviceProblem& geom, const BatchGrid& grid, int n, int stagesUnion, bool cand, hipStream_t s,
+                      bool anyObsS = false);
 int schurDenseABlocks(const DeviceProblem& p);   // DeviceProblem::aBlocks as launchAccumulateNormalEquations chooses it
 // Which landmark-elimination form launchAccumulateNormalEquations launched last in this process (read-only inspection field,
 // svin_ba_debug_get_option("SVIN_LAST_SCHUR_FORM")): 0 none yet; 1000 + 10 MAXT + a for k_schur_dense<MAXT, ...> (a = 0: A in per-wave

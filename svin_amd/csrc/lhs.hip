@@ -35,15 +35,21 @@ __device__ __forceinline__ void lhsWaveSync() {
 __host__ __device__ __forceinline__ int lhsSym6(int a, int c) { return a * 6 - a * (a - 1) / 2 + (c - a); }
 
 // one observation's J^T J (both rows) into the upper triangle `acc`: the pose part (POSE) or the extrinsics part
-template <bool POSE>
+// GENERAL (here and below): the window holds general 2x2 information matrices (p.obsS set); chosen at launch, so that the
+// one-weight kernels keep their registers
+template <bool POSE, bool GENERAL>
 __device__ __forceinline__ void lhsObservation(const DeviceProblem& p, int o, double (&acc)[21]) {
   const uint32_t idx = p.obsIdx[o];
   const double4 hp = reinterpret_cast<const double4*>(p.lm)[p.obsLm[o]];
   const double hpw[4] = {hp.x, hp.y, hp.z, hp.w};
   const double2 uv = reinterpret_cast<const double2*>(p.obsUv)[o];
   double rr[2], jp[12], jl[6], je[12];
-  reprojEval(p.cams[(idx >> 24) & 0xf], p.pose + (size_t)(idx & 0xfff) * 7, hpw, p.ext + (size_t)((idx >> 12) & 0xfff) * 7, uv.x,
-             uv.y, fabs(p.obsW[o]), rr, jp, jl, je);
+  if (GENERAL)   // general 2x2 information: S = (s00, s01, s11), component-major with stride N
+    reprojEval(p.cams[(idx >> 24) & 0xf], p.pose + (size_t)(idx & 0xfff) * 7, hpw, p.ext + (size_t)((idx >> 12) & 0xfff) * 7, uv.x,
+               uv.y, p.obsS[o], p.obsS[(size_t)p.N + o], p.obsS[2 * (size_t)p.N + o], rr, jp, jl, je);
+  else
+    reprojEval(p.cams[(idx >> 24) & 0xf], p.pose + (size_t)(idx & 0xfff) * 7, hpw, p.ext + (size_t)((idx >> 12) & 0xfff) * 7, uv.x,
+               uv.y, fabs(p.obsW[o]), rr, jp, jl, je);
   const double* J = POSE ? jp : je;
   int k = 0;
 #pragma unroll
@@ -52,7 +58,7 @@ __device__ __forceinline__ void lhsObservation(const DeviceProblem& p, int o, do
     for (int c = a; c < 6; ++c) acc[k++] += J[a] * J[c] + J[6 + a] * J[6 + c];
 }
 
-template <bool POSE>
+template <bool POSE, bool GENERAL>
 __device__ __forceinline__ void lhsScan(const DeviceProblem& p, uint32_t want, int b0, int b1, int* q, double (&acc)[21]) {
   const int lane = threadIdx.x & 63;
   const int shift = POSE ? 0 : 12;
@@ -75,7 +81,7 @@ __device__ __forceinline__ void lhsScan(const DeviceProblem& p, uint32_t want, i
       qn += __popcll(mask);
       if (qn >= 64) {
         lhsWaveSync();
-        lhsObservation<POSE>(p, q[lane], acc);
+        lhsObservation<POSE, GENERAL>(p, q[lane], acc);
         const int rest = qn - 64;
         const int moved = lane < rest ? q[64 + lane] : 0;
         lhsWaveSync();
@@ -86,9 +92,10 @@ __device__ __forceinline__ void lhsScan(const DeviceProblem& p, uint32_t want, i
     }
   }
   lhsWaveSync();
-  if (lane < qn) lhsObservation<POSE>(p, q[lane], acc);
+  if (lane < qn) lhsObservation<POSE, GENERAL>(p, q[lane], acc);
 }
 
+template <bool GENERAL>
 __global__ __launch_bounds__(kLhsThreads) void k_lhs_cam(DeviceProblem p, const LhsItem* __restrict__ items,
                                                          double* __restrict__ partial) {
   __shared__ int queue[kLhsWaves][128];
@@ -100,8 +107,8 @@ __global__ __launch_bounds__(kLhsThreads) void k_lhs_cam(DeviceProblem p, const 
   double acc[21];
 #pragma unroll
   for (int k = 0; k < 21; ++k) acc[k] = 0.0;
-  if (it.key < p.nPose) lhsScan<true>(p, (uint32_t)it.key, b0, b1, queue[wave], acc);
-  else lhsScan<false>(p, (uint32_t)(it.key - p.nPose), b0, b1, queue[wave], acc);
+  if (it.key < p.nPose) lhsScan<true, GENERAL>(p, (uint32_t)it.key, b0, b1, queue[wave], acc);
+  else lhsScan<false, GENERAL>(p, (uint32_t)(it.key - p.nPose), b0, b1, queue[wave], acc);
   // fixed-order reduction: lanes by a shuffle tree, then the four waves in order
 #pragma unroll
   for (int k = 0; k < 21; ++k) {
@@ -119,6 +126,7 @@ __global__ __launch_bounds__(kLhsThreads) void k_lhs_cam(DeviceProblem p, const 
   }
 }
 
+template <bool GENERAL>
 __global__ __launch_bounds__(256) void k_lhs_landmarks(DeviceProblem p, double* __restrict__ out) {
   const int l = blockIdx.x * 16 + (threadIdx.x >> 4), gl = threadIdx.x & 15;
   if (l >= p.L) return;   // whole 16-lane rows leave together
@@ -134,8 +142,12 @@ __global__ __launch_bounds__(256) void k_lhs_landmarks(DeviceProblem p, double* 
       const bool second = p.obsUv[2 * (size_t)o + 1] != 0.0;
       for (int k = 0; k < 3; ++k) { jl[k] = pr[3 + (second ? 6 : 0) + k]; jl[3 + k] = second ? 0.0 : pr[6 + k]; }
     } else {
-      reprojEval(p.cams[(idx >> 24) & 0xf], p.pose + (size_t)(idx & 0xfff) * 7, hpw, p.ext + (size_t)((idx >> 12) & 0xfff) * 7,
-                 p.obsUv[2 * (size_t)o], p.obsUv[2 * (size_t)o + 1], fabs(p.obsW[o]), rr, jp, jl, je);
+      if (GENERAL)
+        reprojEval(p.cams[(idx >> 24) & 0xf], p.pose + (size_t)(idx & 0xfff) * 7, hpw, p.ext + (size_t)((idx >> 12) & 0xfff) * 7,
+                   p.obsUv[2 * (size_t)o], p.obsUv[2 * (size_t)o + 1], p.obsS[o], p.obsS[(size_t)p.N + o], p.obsS[2 * (size_t)p.N + o], rr, jp, jl, je);
+      else
+        reprojEval(p.cams[(idx >> 24) & 0xf], p.pose + (size_t)(idx & 0xfff) * 7, hpw, p.ext + (size_t)((idx >> 12) & 0xfff) * 7,
+                   p.obsUv[2 * (size_t)o], p.obsUv[2 * (size_t)o + 1], fabs(p.obsW[o]), rr, jp, jl, je);
     }
     a[0] += jl[0] * jl[0] + jl[3] * jl[3]; a[1] += jl[0] * jl[1] + jl[3] * jl[4]; a[2] += jl[0] * jl[2] + jl[3] * jl[5];
     a[3] += jl[1] * jl[1] + jl[4] * jl[4]; a[4] += jl[1] * jl[2] + jl[4] * jl[5]; a[5] += jl[2] * jl[2] + jl[5] * jl[5];
@@ -201,8 +213,13 @@ __global__ __launch_bounds__(kLhsThreads) void k_lhs_blocks(DeviceProblem p, con
 
 void launchLhsAll(const DeviceProblem& p, const LhsItem* items, int nItems, const LhsBlock* blocks, int nBlocks, const int2* facs,
                   double* partial, double* out, size_t lmOut, hipStream_t s) {
-  launch(k_lhs_cam, dim3(nItems), dim3(kLhsThreads), 0, s, p, items, partial);
-  launch(k_lhs_landmarks, dim3((p.L + 15) / 16), dim3(256), 0, s, p, out + lmOut);
+  if (p.obsS) {
+    launch(k_lhs_cam<true>, dim3(nItems), dim3(kLhsThreads), 0, s, p, items, partial);
+    launch(k_lhs_landmarks<true>, dim3((p.L + 15) / 16), dim3(256), 0, s, p, out + lmOut);
+  } else {
+    launch(k_lhs_cam<false>, dim3(nItems), dim3(kLhsThreads), 0, s, p, items, partial);
+    launch(k_lhs_landmarks<false>, dim3((p.L + 15) / 16), dim3(256), 0, s, p, out + lmOut);
+  }
   launch(k_lhs_blocks, dim3(nBlocks), dim3(kLhsThreads), 0, s, p, blocks, facs, (const double*)partial, out);
 }
 

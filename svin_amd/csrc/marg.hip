@@ -1281,7 +1281,7 @@ int Window::applyMarginalizationStrategy(size_t numKeyframes, size_t numImuFrame
     ++rit;
   }
   // the job: residuals to linearise (copied out of the graph as they are removed) and blocks to marginalise
-  struct JobObs { Observation o; uint64_t lmId, extId; };
+  struct JobObs { Observation o; uint64_t lmId, extId; double S[3]; };   // S: the square-root information of a general observation (o.general)
   std::vector<Factor> jobFactors;
   std::vector<JobObs> jobObs;
   std::vector<uint64_t> toMarginalize;
@@ -1444,7 +1444,12 @@ int Window::applyMarginalizationStrategy(size_t numKeyframes, size_t numImuFrame
               lmOrder.push_back(lm.id);
               if (!deviceJob) lmLin[lm.id].assign(lm.hp, lm.hp + 4);
             }
-            if (!deviceJob) jobObs.push_back({ob, lm.id, extIdOf(ob)});
+            if (!deviceJob) {
+              JobObs jo{ob, lm.id, extIdOf(ob), {0.0, 0.0, 0.0}};
+              if (const ObsInformation* gi = generalInformation(ob)) { jo.S[0] = gi->S[0]; jo.S[1] = gi->S[1]; jo.S[2] = gi->S[2]; }   // (detachObsRecord drops the entry)
+              else jo.o.general = 0;
+              jobObs.push_back(jo);
+            }
             ++nJobObs;
           }
           detachObsRecord(lm, ob);
@@ -1521,9 +1526,18 @@ int Window::applyMarginalizationStrategy(size_t numKeyframes, size_t numImuFrame
       for (const auto& kv : sPose) jobPoseSlot[blocks_.at(kv.first).handle] = kv.second;
       for (const auto& kv : sExt) jobExtSlot[blocks_.at(kv.first).handle] = kv.second;
     }
+    // DeviceProblem::obsS of the job (3 N, component-major): only when one of its observations has a general information matrix
+    bool generalOn = false;
+    for (const JobObs& jo : jobObs) generalOn = generalOn || jo.o.general;
+    std::vector<double> hS(generalOn ? 3 * jobObs.size() : 0);
     for (const JobObs& jo : jobObs) {
       hUv.push_back(jo.o.uv[0]); hUv.push_back(jo.o.uv[1]);
       hW.push_back(obsWeight(jo.o.size));
+      if (generalOn) {
+        const size_t o = hW.size() - 1, n = jobObs.size();
+        const double w = hW.back();
+        hS[o] = jo.o.general ? jo.S[0] : w; hS[n + o] = jo.o.general ? jo.S[1] : 0.0; hS[2 * n + o] = jo.o.general ? jo.S[2] : w;
+      }
       const int es = sExt.count(jo.extId) ? sExt.at(jo.extId) : 0;
       hIdx.push_back(packObs(sPose.at(jo.o.poseId), es, jo.o.cam, jo.o.loss));
       hObsLm.push_back(sLm.at(jo.lmId));
@@ -1604,6 +1618,7 @@ int Window::applyMarginalizationStrategy(size_t numKeyframes, size_t numImuFrame
         if (!host.empty()) pending.push_back({host.data(), sizeof(T) * host.size(), buf.p});
       };
       stage(bPose, hPose); stage(bExt, hExt); stage(bSb, hSb); stage(bLm, hLm); stage(bUv, hUv); stage(bW, hW);
+      if (generalOn) stage(mb.bS, hS);
       stage(bOP, oPose); stage(bOE, oExt); stage(bOS, oSb); stage(bLmPtr, hLmPtr); stage(bObsLm, hObsLm); stage(bIdx, hIdx);
       stage(bFac, hFac); stage(bImu, hImu); stage(bImuT, hImuT); stage(bImuM, hImuM);
       stage(dCams_, cameras_);
@@ -1645,7 +1660,7 @@ int Window::applyMarginalizationStrategy(size_t numKeyframes, size_t numImuFrame
     const int margEig = debugOption(kOptMargEig);   // read HERE, on the caller's thread: the job may be issued by the enqueue thread
     // the host tables the staged block is filled from must outlive this call when the job is issued by the enqueue thread
     struct JobTables {
-      std::vector<double> hPose, hExt, hSb, hLm, hUv, hW, hImuM;
+      std::vector<double> hPose, hExt, hSb, hLm, hUv, hW, hS, hImuM;
       std::vector<int> oPose, oExt, oSb, hObsLm, hLmPtr, idxLists, jobPoseSlot, jobExtSlot;
       std::vector<uint32_t> hIdx, hImuT;
       std::vector<DevFactor> hFac;
@@ -1660,7 +1675,7 @@ int Window::applyMarginalizationStrategy(size_t numKeyframes, size_t numImuFrame
     double** dbgScalPtr = runInline ? &dbgScal : nullptr;
     // (explicit captures: the job buffers are reached through `this` -- a by-value capture of the DevBuf aliases above would copy,
     // and later free, the buffers themselves; lmOrder / dense / toMarginalize are only read by the inline inspection path)
-    auto launchJob = [this, tables, pendingPtr, lossOn, N, Lm, m, F, nk, nm, mm, L3, n2k, oldPriorM, oldPrior, anyExtVar, deviceJob, nPoseJ, nExtJ,
+    auto launchJob = [this, tables, pendingPtr, lossOn, generalOn, N, Lm, m, F, nk, nm, mm, L3, n2k, oldPriorM, oldPrior, anyExtVar, deviceJob, nPoseJ, nExtJ,
                       nSbJ, nImuJ, nCamJ, keepPre, margEig, dbgScalPtr, s, &lmOrder, &dense, &toMarginalize]() {
       MargBuffers& mb = margBuf_;
       auto &bPose = mb.bPose, &bExt = mb.bExt, &bSb = mb.bSb, &bLm = mb.bLm, &bUv = mb.bUv, &bW = mb.bW, &bLin = mb.bLin,
@@ -1708,6 +1723,7 @@ int Window::applyMarginalizationStrategy(size_t numKeyframes, size_t numImuFrame
     q.poseOff = bOP.p; q.extOff = bOE.p; q.sbOff = bOS.p;
     q.cams = dCams_.p;
     q.lossTab = lossOn ? dLossTab_.p : nullptr;
+    q.obsS = generalOn ? mb.bS.p : nullptr;
     q.lmPtr = bLmPtr.p; q.obsUv = bUv.p; q.obsW = bW.p; q.obsIdx = bIdx.p; q.obsLm = bObsLm.p;
     q.rCur = bLin.p; q.JpCur = bLin.p + (size_t)2 * N; q.JlCur = bLin.p + (size_t)14 * N; q.JeCur = bLin.p + (size_t)20 * N;
     q.factors = bFac.p; q.linCur = bFacLin.p; q.linCand = bFacLin.p;
@@ -1828,7 +1844,7 @@ int Window::applyMarginalizationStrategy(size_t numKeyframes, size_t numImuFrame
     };
     // move the host tables behind the staged pointers into the job (a vector's storage does not move with it)
     tables->hPose = std::move(hPose); tables->hExt = std::move(hExt); tables->hSb = std::move(hSb); tables->hLm = std::move(hLm);
-    tables->hUv = std::move(hUv); tables->hW = std::move(hW); tables->hImuM = std::move(hImuM);
+    tables->hUv = std::move(hUv); tables->hW = std::move(hW); tables->hS = std::move(hS); tables->hImuM = std::move(hImuM);
     tables->oPose = std::move(oPose); tables->oExt = std::move(oExt); tables->oSb = std::move(oSb); tables->hObsLm = std::move(hObsLm);
     tables->hLmPtr = std::move(hLmPtr); tables->idxLists = std::move(idxLists); tables->jobPoseSlot = std::move(jobPoseSlot);
     tables->jobExtSlot = std::move(jobExtSlot); tables->hIdx = std::move(hIdx); tables->hImuT = std::move(hImuT);

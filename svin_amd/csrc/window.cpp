@@ -1,6 +1,7 @@
 // svin_amd host core (see window.hpp).  Reference line numbers cite
 // /root/reference/okvis_ros/okvis/okvis_ceres/src/Estimator.cpp unless another file is named.
 #include "window.hpp"
+#include "../../include/svin_ba.h"
 #include "trust_region.hpp"
 #include "pack_plan.hpp"
 #include <array>
@@ -316,6 +317,7 @@ void Window::detachObsRecord(Landmark& lm, const Observation& o) {
   if (Block* b = blockByHandle_[B_POSE][o.poseH]) b->nObs--;
   if (Block* b = blockByHandle_[B_EXT][o.extH]) b->nObs--;
   obsRes2Lm_.erase(o.resId);
+  if (o.general) obsInfo_.erase(o.resId);
   if (residentValid_) {   // the device copy learns about it with the next flush (resident.hpp)
     if (o.pendEpoch == epoch_) addLog_[o.pendIdx].lmH = -1;   // never got there: withdrawn
     else remLog_.push_back(WinRem{lm.handle, (uint32_t)o.resId});
@@ -939,16 +941,18 @@ void Window::evaluateHostFactors(bool cand, hipStream_t s) {
   }
 }
 // ReprojectionError<GEOMETRY>(geometry of camera `cam`, uv, information) with CauchyLoss(1) on (pose, landmark, extrinsics):
-// what Estimator::addObservation creates, with the blocks named by the caller.  The device kernels store ONE weight per
-// residual (Estimator only ever passes 64 / size^2 * I), so the information has to be a multiple of the identity.
+// what Estimator::addObservation creates, with the blocks named by the caller.  A multiple of the identity is stored as ONE weight
+// (what Estimator passes: 64 / size^2 * I); any other symmetric positive-definite matrix goes to the side table obsInfo_.
 uint64_t Window::mapAddReprojectionError(uint64_t poseBlock, uint64_t landmark, uint64_t extBlock, uint64_t cam, const double* uv,
                                          const double* information4) {
   uint64_t hnd = 0;
   if (!uv || !information4 || cam >= cameras_.size() || !lmIndex_.find(landmark, &hnd)) return 0;
-  if (information4[1] != 0.0 || information4[2] != 0.0 || information4[0] != information4[3] || !(information4[0] > 0.0)) {
-    lastError() = "map_add_reprojection_error: the information matrix must be a positive multiple of the identity";
+  ObsInformation gi;
+  if (!reprojInformationValid(information4, gi.S)) {
+    lastError() = "map_add_reprojection_error: the information matrix must be finite, symmetric and positive definite";
     return 0;
   }
+  const bool isotropic = information4[1] == 0.0 && information4[0] == information4[3];
   Block *pb = findBlock(poseBlock), *eb = findBlock(extBlock);
   if (!pb || !eb || pb == eb || pb->kind != B_POSE) return 0;
   if (eb->kind == B_POSE) {
@@ -971,7 +975,64 @@ uint64_t Window::mapAddReprojectionError(uint64_t poseBlock, uint64_t landmark, 
   Landmark& lm = *lmByHandle_[(size_t)hnd];
   // (no duplicate rule at this level: Map::addResidualBlock accepts any number of residuals on the same blocks; the key point
   // index of the record is the residual id it is about to get)
-  return addObservationRecord(lm, pb, eb, cam, nextResId_, uv, -std::sqrt(information4[0]));
+  if (isotropic) return addObservationRecord(lm, pb, eb, cam, nextResId_, uv, -std::sqrt(information4[0]));
+  // the device-resident window's records carry one weight: a window with a general matrix is packed by the host (useResident)
+  if (residentValid_) { quiesce(); invalidateResident(); }
+  const uint64_t rid = addObservationRecord(lm, pb, eb, cam, nextResId_, uv, -gi.S[0]);
+  if (!rid) return 0;
+  gi.info[0] = information4[0]; gi.info[1] = information4[2]; gi.info[2] = information4[3];
+  lm.obs.back().general = 1;
+  obsInfo_[rid] = gi;
+  return rid;
+}
+int Window::setReprojectionInformation(uint64_t resId, const double* information4) {
+  const int rk = residualKind(resId);
+  if (rk < 0) return SVIN_ERR_NOT_FOUND;
+  if (rk != 100) return SVIN_ERR_UNSUPPORTED;   // (HomogeneousPointError included: its information is 3x3 and set when it is added)
+  ObsInformation gi;
+  if (!information4 || !reprojInformationValid(information4, gi.S)) return SVIN_ERR_INVALID_ARG;
+  quiesce();
+  uint64_t node = 0;
+  obsRes2Lm_.find(resId, &node);
+  Landmark& lm = *reinterpret_cast<Landmark*>((uintptr_t)node);
+  Observation* ob = nullptr;
+  for (Observation& o : lm.obs)
+    if (o.resId == resId) ob = &o;
+  if (!ob) return SVIN_ERR_NOT_FOUND;
+  const bool isotropic = information4[1] == 0.0 && information4[0] == information4[3];
+  const double size = isotropic ? -std::sqrt(information4[0]) : -gi.S[0];
+  if (isotropic && !ob->general && obsWeight(ob->size) == -size) return 1;   // nothing changes (the record keeps its key point size)
+  // the device-resident copy holds the old weight: it is rebuilt from the graph at the next pack() that qualifies
+  if (residentValid_) invalidateResident();
+  if (ob->general && isotropic) { obsInfo_.erase(resId); ob->general = 0; }
+  ob->size = size;
+  if (!isotropic) {
+    gi.info[0] = information4[0]; gi.info[1] = information4[2]; gi.info[2] = information4[3];
+    ob->general = 1;
+    obsInfo_[resId] = gi;
+  }
+  lastObsSize_ = 0.0;   // (addObservationRecord's one-entry weight cache is keyed by `size`)
+  return 1;
+}
+int Window::getReprojectionInformation(uint64_t resId, double* information4) const {
+  const int rk = residualKind(resId);
+  if (rk < 0) return SVIN_ERR_NOT_FOUND;
+  if (rk != 100) return SVIN_ERR_UNSUPPORTED;
+  if (!information4) return SVIN_ERR_INVALID_ARG;
+  uint64_t node = 0;
+  obsRes2Lm_.find(resId, &node);
+  const Landmark& lm = *reinterpret_cast<const Landmark*>((uintptr_t)node);
+  for (const Observation& o : lm.obs)
+    if (o.resId == resId) {
+      if (const ObsInformation* gi = generalInformation(o)) {
+        information4[0] = gi->info[0]; information4[1] = information4[2] = gi->info[1]; information4[3] = gi->info[2];
+      } else {
+        const double w = obsWeight(o.size);
+        information4[0] = information4[3] = w * w; information4[1] = information4[2] = 0.0;
+      }
+      return 1;
+    }
+  return SVIN_ERR_NOT_FOUND;
 }
 int Window::mapRemoveResidualBlock(uint64_t resId) {   // Map.cpp:467-492
   if (obsRes2Lm_.count(resId)) return removeObservationById(resId);
@@ -1390,7 +1451,7 @@ void Window::waitIdle() {
 bool Window::useResident() const {   // (called by pack() once the state tables are known)
   const bool forceHost = optOn(kOptHostPack);
   return packMode_ == 0 && !forceHost && world_ <= 1 && rcclComm_ == nullptr && numLandmarkPriors_ == 0 && numFixedLandmarks_ == 0 &&
-         poseIds_.size() <= (size_t)kResidentPoseCap;
+         obsInfo_.empty() && poseIds_.size() <= (size_t)kResidentPoseCap;   // (a general information matrix: the host packs obsS)
 }
 void Window::invalidateResident() {
   syncLandmarks();
@@ -1595,6 +1656,7 @@ struct PackHost {
   bool resident = false;
   std::vector<double> hLmPrior;   // 12 doubles per HomogeneousPointError: measurement xyz, sqrt information (row-major)
   std::vector<double> hLm, hUv, hW;
+  std::vector<double> hS;         // DeviceProblem::obsS (3 N, component-major); empty unless the window holds a general information matrix
   std::vector<int> hLmPtr, hObsLm;
   std::vector<uint32_t> hIdx;
   int L = 0, N = 0;
@@ -1796,6 +1858,9 @@ void Window::packLandmarks(PackHost& a) {
   std::vector<int>&hLmPtr = a.hLmPtr, &hObsLm = a.hObsLm;
   std::vector<uint32_t>& hIdx = a.hIdx;
   hLm.resize(4 * nLmObs); hUv.resize(2 * nObs); hW.resize(nObs);
+  const bool general = !resident && !obsInfo_.empty();
+  std::vector<double>& hS = a.hS;
+  if (general) hS.resize(3 * nObs);
   hLmPtr.resize(resident ? 0 : nLmObs + 1); hObsLm.resize(nObs);
   hIdx.resize(nObs);
   lmIds_.resize(nLmObs);
@@ -1830,6 +1895,11 @@ void Window::packLandmarks(PackHost& a) {
         hUv[2 * o] = ob.uv[0]; hUv[2 * o + 1] = ob.uv[1];
         // information = I * 64/size^2 ; sqrt information = its (scalar) Cholesky factor
         hW[o] = lm.fixed ? -obsWeight(ob.size) : obsWeight(ob.size);
+        if (general) {   // S = (s00, s01, s11); an isotropic observation is w I (the general form then gives the scalar form's numbers)
+          const ObsInformation* gi = generalInformation(ob);
+          const double w = obsWeight(ob.size);
+          hS[o] = gi ? gi->S[0] : w; hS[nObs + o] = gi ? gi->S[1] : 0.0; hS[2 * nObs + o] = gi ? gi->S[2] : w;
+        }
         hIdx[o] = packObs(poseCache.at(ob.poseId), extCache.at(extIdOf(ob)), ob.cam, ob.loss);
         hObsLm[o] = (int)slot;
         ++o;
@@ -1843,6 +1913,7 @@ void Window::packLandmarks(PackHost& a) {
         for (int part = 0; part < 2; ++part) {
           hUv[2 * o] = k; hUv[2 * o + 1] = (double)part;
           hW[o] = 1.0;
+          if (general) { hS[o] = 1.0; hS[nObs + o] = 0.0; hS[2 * nObs + o] = 1.0; }   // (not read: the pseudo-observation has its own S)
           hIdx[o] = packObs(0, 0, kPriorCam);
           hObsLm[o] = (int)slot;
           ++o;
@@ -1962,6 +2033,7 @@ void Window::packReserveAndStage(PackHost& a, std::vector<StagedCopy>& pending) 
     upload(dLm_, a.hLm, s);
     upload(dLmPtr_, a.hLmPtr, s); upload(dObsLm_, a.hObsLm, s); upload(dObsUv_, a.hUv, s); upload(dObsW_, a.hW, s);
     upload(dObsIdx_, a.hIdx, s);
+    if (!a.hS.empty()) upload(dObsS_, a.hS, s);
     upload(dLmPrior_, a.hLmPrior, s);
   }
   for (int k = 0; k < 2; ++k) { dLin_[k].reserve(std::max<size_t>((size_t)32 * N, 1)); dFacLin_[k].reserve(std::max(F, 1)); }
@@ -2038,6 +2110,7 @@ void Window::packFillProblem(const PackHost& a) {
   p.lmPtr = dLmPtr_.p; p.obsUv = dObsUv_.p; p.obsW = dObsW_.p; p.obsIdx = dObsIdx_.p; p.obsLm = dObsLm_.p;
   if (resident) { p.lmPtr = res_.lmPtr[res_.cur].p; p.obsUv = res_.uv[res_.cur].p; p.obsW = res_.w[res_.cur].p; p.obsLm = res_.obsLm[res_.cur].p; }
   p.lmPrior = dLmPrior_.p;
+  p.obsS = a.hS.empty() ? nullptr : dObsS_.p;
   curSet_ = 0;
   auto setLin = [&](int set, double*& r, double*& Jp, double*& Jl, double*& Je) {
     double* base = dLin_[set].p;
@@ -2542,6 +2615,7 @@ void Window::solveBatchGroup(const std::vector<Window*>& group, size_t numIter, 
   long long blocksLaunched = 0, blocksIdle = 0;
   auto issue = [&](Lane& ln, bool cand) -> bool {
     int uni = 0;
+    bool anyObsS = false;   // a window of the lane holds general information matrices: the reprojection blocks take the kernel that reads obsS
     BatchGrid grid;
     long long busy = 0;
     for (int k = 0; k < ln.count; ++k) {
@@ -2557,6 +2631,7 @@ void Window::solveBatchGroup(const std::vector<Window*>& group, size_t numIter, 
       p.lmDeferred = (cand && st[i].deferLm && !tr.reuse) ? 1 : 0;
       p.aBlocks = schurDenseABlocks(p);
       sl.p = p;
+      anyObsS = anyObsS || p.obsS != nullptr;
       p.lmDeferred = 0;
       sl.mu = tr.mu; sl.radius = tr.radius; sl.initScale = tr.initScale ? 1 : 0;
       sl.stages = !cand ? kBatchEval : (tr.reuse ? (kBatchReuse | kBatchEval) : (kBatchFull | kBatchEval));
@@ -2568,7 +2643,7 @@ void Window::solveBatchGroup(const std::vector<Window*>& group, size_t numIter, 
     ln.cand = cand;
     if (!uni) return false;
     HIP_OK(hipMemcpyAsync(ln.lead->batchSlotsDev_.p, ln.hs, sizeof(BatchSlot) * (size_t)ln.count, hipMemcpyHostToDevice, ln.s));
-    launchBatchRound(ln.lead->batchSlotsDev_.p, ln.lead->prob_, grid, ln.count, uni, cand, ln.s);
+    launchBatchRound(ln.lead->batchSlotsDev_.p, ln.lead->prob_, grid, ln.count, uni, cand, ln.s, anyObsS);
     blocksLaunched += grid.blocks(uni) * ln.count;
     blocksIdle += grid.blocks(uni) * ln.count - busy;
     return true;
@@ -3169,6 +3244,7 @@ int Window::benchJacobianEval(int copies, int iters, double* meanMs, double* byt
   }
   DeviceProblem q = p;
   q.obsUv = bUv.p; q.obsW = bW.p; q.obsIdx = bIdx.p; q.obsLm = bObsLm.p; q.lm = bLm.p;
+  q.obsS = nullptr;   // (the roofline replicas take the one-weight form)
   double* r = bOut.p;
   double* Jp = r + 2 * NB;
   double* Jl = Jp + 12 * NB;

@@ -68,6 +68,8 @@ struct Observation {
   uint16_t poseH = 0, extH = 0;           // Block::handle of the pose and the extrinsics block (the extrinsics id: Window::extIdOf)
   uint8_t cam = 0;
   uint8_t loss = 0;                       // entry of the window's reprojection loss table (0: CauchyLoss(1)); packObs bits 28-31
+  uint8_t general = 0;                    // 1: a general 2x2 information matrix; its square root lives in Window::obsInfo_ (by resId)
+                                          // and `size` holds -s00, so that obsWeight() is the first diagonal entry
 };
 static_assert(sizeof(Observation) == 64, "Observation is meant to fill one cache line");
 // square-root information of a reprojection residual: Estimator::addObservation passes 64 / size^2 * I (implementation/
@@ -168,7 +170,7 @@ struct DevBuf {
 
 // device buffers of the marginalisation job (marg.hip), kept across calls
 struct MargBuffers {
-  DevBuf<double> bPose, bExt, bSb, bLm, bUv, bW, bLin, bU, bW2, bV, bVec, bScratch, bImuM, bPartial, bHk, bOut;
+  DevBuf<double> bPose, bExt, bSb, bLm, bUv, bW, bS, bLin, bU, bW2, bV, bVec, bScratch, bImuM, bPartial, bHk, bOut;
   DevBuf<int> bOP, bOE, bOS, bLmPtr, bObsLm, bIdxList, bFlag;
   DevBuf<uint32_t> bIdx, bImuT;
   DevBuf<DevFactor> bFac;
@@ -288,6 +290,18 @@ class Window {
   // included).  1, or -2 unknown residual, -3 unsupported (prior, landmark prior, full loss table, sharded mode), -5 invalid argument
   int setResidualLoss(uint64_t resId, int kind, double scale);
   int getResidualLoss(uint64_t resId, int* kind, double* scale) const;
+  // ReprojectionErrorBase::setInformation / information() of a reprojection residual (row-major 2x2; finite, symmetric, positive
+  // definite).  A multiple of the identity keeps (or returns the observation to) the one-weight storage.  1, SVIN_ERR_NOT_FOUND,
+  // SVIN_ERR_UNSUPPORTED (not a reprojection residual), SVIN_ERR_INVALID_ARG.
+  int setReprojectionInformation(uint64_t resId, const double* information4);
+  int getReprojectionInformation(uint64_t resId, double* information4) const;
+  // observations with a general 2x2 information matrix: S = (s00, s01, s11) upper triangular and the matrix as given (00, 10, 11)
+  struct ObsInformation { double S[3]; double info[3]; };
+  const ObsInformation* generalInformation(const Observation& o) const {
+    if (!o.general) return nullptr;
+    auto it = obsInfo_.find(o.resId);
+    return it == obsInfo_.end() ? nullptr : &it->second;
+  }
   bool hasNonDefaultLoss() const;   // a reprojection residual off CauchyLoss(1) or a factor with a loss (sharded mode refuses both)
   // kind, residual dimension and the ambient dimensions of the blocks of a list of residuals in one call (what the shim's
   // Map::residuals / errorInterfacePtr need per residual: sizes and type, ErrorInterface::residualDim / parameterBlockDim)
@@ -559,6 +573,10 @@ class Window {
   int nLoss_ = 1;
   DevBuf<double> dLossTab_;
   DevBuf<double> dObsUv_, dObsW_;
+  // side table of the general information matrices (Observation stays one cache line); an entry leaves with its observation
+  // (detachObsRecord).  While it is non-empty the window is packed by the host, which fills DeviceProblem::obsS (dObsS_)
+  std::unordered_map<uint64_t, ObsInformation> obsInfo_;
+  DevBuf<double> dObsS_;
   DevBuf<uint32_t> dObsIdx_;
   DevBuf<double> dLin_[2];  // r(2N) Jp(12N) Jl(6N) Je(12N) each
   DevBuf<DevFactor> dFactors_;

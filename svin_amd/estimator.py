@@ -78,6 +78,7 @@ EXPORTS = [
     "svin_ba_get_all_landmark_observations", "svin_ba_bench_allreduce", "svin_ba_get_marg_pre", "svin_ba_get_marg_pre_blocks",
     "svin_ba_get_lhs", "svin_ba_get_lhs_blocks", "svin_ba_get_lhs_pass_count",
     "svin_ba_map_set_residual_loss", "svin_ba_map_get_residual_loss",
+    "svin_ba_map_set_reprojection_information", "svin_ba_map_get_reprojection_information",
 ]
 
 # residual loss functions (svin_ba_map_set_residual_loss): ceres::TrivialLoss, CauchyLoss(a), HuberLoss(a)
@@ -180,6 +181,8 @@ def load_library():
     sig("svin_ba_get_lhs_pass_count", C.c_int64, vp)
     sig("svin_ba_map_set_residual_loss", i32, vp, u64, i32, C.c_double)
     sig("svin_ba_map_get_residual_loss", i32, vp, u64, C.POINTER(C.c_int32), pd)
+    sig("svin_ba_map_set_reprojection_information", i32, vp, u64, pd)
+    sig("svin_ba_map_get_reprojection_information", i32, vp, u64, pd)
     sig("svin_ba_bench_jacobian_eval", i32, vp, i32, i32, pd, pd)
     sig("svin_ba_bench_jacobian_eval_b2b", i32, vp, i32, i32, pd, pd, pd)
     sig("svin_ba_set_pack_mode", i32, vp, i32)
@@ -1021,6 +1024,18 @@ class Estimator:
         k, a = C.c_int32(), np.zeros(1)
         self._check(self.L.svin_ba_map_get_residual_loss(self.h, rid, C.byref(k), _d(a)), "map_get_residual_loss")
         return int(k.value), float(a[0])
+
+    def map_set_reprojection_information(self, rid, information):
+        """svin_ba_map_set_reprojection_information: any finite, symmetric, positive-definite 2x2 information matrix on a
+        reprojection residual (add_observation or map_add_reprojection_error).  Raises on an error code."""
+        i = np.ascontiguousarray(information, np.float64).reshape(4)
+        return self._check(self.L.svin_ba_map_set_reprojection_information(self.h, rid, _d(i)), "map_set_reprojection_information") == 1
+
+    def map_get_reprojection_information(self, rid):
+        """the 2x2 information matrix of a reprojection residual"""
+        i = np.zeros(4)
+        self._check(self.L.svin_ba_map_get_reprojection_information(self.h, rid, _d(i)), "map_get_reprojection_information")
+        return i.reshape(2, 2)
 
     def residual_info(self, rids):
         """[(kind, residual dimension, [block dimensions])] for a list of residual ids (one call)"""
