@@ -3755,8 +3755,9 @@ static DenseSchurPlan denseSchurPlan(const DeviceProblem& p) {
   return q;
 }
 int schurDenseABlocks(const DeviceProblem& p) { return (p.L > 0 && p.N > 0 && p.dC > 0 && p.schurDense && denseSchurPlan(p).aBlocks) ? 1 : 0; }
-static bool sbEarlyActive(const DeviceProblem& p);                                          // (behind the chain kernels, below)
-static void launchSbEarly(const DeviceProblem& p, hipStream_t side, double mu, bool initScale);
+static ReducedSolvePlan solvePlanOf(const DeviceProblem& p);                                // (behind the solver kernels, below)
+static bool sbEarlyActive(const DeviceProblem& p, const ReducedSolvePlan& q);
+static void launchSbEarly(const DeviceProblem& p, const ReducedSolvePlan& q, hipStream_t side, double mu, bool initScale);
 static std::atomic<int> gLastSchurForm{0};
 int lastSchurForm() { return gLastSchurForm.load(std::memory_order_relaxed); }
 void launchAccumulateNormalEquations(const DeviceProblem& p, double mu, bool initScale, hipStream_t s, bool zeroFirst) {
@@ -3800,7 +3801,8 @@ void launchAccumulateNormalEquations(const DeviceProblem& p, double mu, bool ini
     // critical path.  The pose blocks of S receive the factors' atomic adds AND the plain read-modify-writes of
     // k_blocks_pose_reduce: the latter waits for the former (event `mid`).
     SideLane* lane = nullptr;
-    const bool early = sbEarlyActive(p);
+    const ReducedSolvePlan solvePlan = solvePlanOf(p);   // (the plan the solve of this iteration computes as well)
+    const bool early = sbEarlyActive(p, solvePlan);
     gLastSchurForm.store(p.schurBlocks ? 2000 : 3000, std::memory_order_relaxed);
     if (early) {
       lane = &sideLaneOf(s);
@@ -3808,7 +3810,7 @@ void launchAccumulateNormalEquations(const DeviceProblem& p, double mu, bool ini
       HIP_OK(hipStreamWaitEvent(lane->side, lane->fork, 0));
       launch(k_factors_only, dim3(nFac + nPri), dim3(256), 0, lane->side, p, nFac);
       HIP_OK(hipEventRecord(lane->mid, lane->side));
-      launchSbEarly(p, lane->side, mu, initScale);
+      launchSbEarly(p, solvePlan, lane->side, mu, initScale);
       HIP_OK(hipEventRecord(lane->join, lane->side));
     }
     if (p.schurBlocks) {
@@ -3876,16 +3878,10 @@ void launchAccumulateNormalEquations(const DeviceProblem& p, double mu, bool ini
 // C/D: col=l&15, row=(l>>4)+4*reg.  The matrix is padded to a multiple of 16 with an identity tail so that every tile is full.
 // LDS-resident variant for dpad <= 176: the lower triangle lives in LDS as 16x17 tiles (tile (I,J), I>=J at
 // index I(I+1)/2+J), so the whole factorisation and both triangular solves run at LDS latency.
-constexpr int kTile = 16 * kPanelLd;  // doubles per tile
 __device__ __forceinline__ double* tileAt(double* base, int I, int J) { return base + (size_t)(I * (I + 1) / 2 + J) * kTile; }
 
 constexpr int kCholLdsThreads = 512;  // 8 waves (16 waves measured slower: LDS pressure, the diagonal block is the critical path)
-constexpr int kCholFlagInts = 48;
-#ifdef SVIN_CHOL_TIMING
-constexpr int kCholBorderOff = 240;   // (doubles behind the flags: the timing build's stamp buffer comes first)
-#else
-constexpr int kCholBorderOff = 0;
-#endif
+// (kCholFlagInts and the other sizes the launch planning shares with the kernels: solve_plan.hpp)
 // Flags of the barrier-free factorisation (LDS ints, monotonic counters, written by exactly one wave each):
 //   fl[0]       pivotDone  number of diagonal tiles whose factor D(kb) and 1/L_ii are in LDS
 //   fl[1 + I]   xReady[I]  number of block columns for which the panel tile X(I, .) of tile row I is stored
@@ -3955,11 +3951,7 @@ __device__ __forceinline__ int cholFlagWaitAll(int* f, int n, int v, int lane, i
 // V = Lc^-1 B, q = C^-1 g2, Lc^-1 are written to `bscr` by k_chol_border_prepare, one small launch ahead (a 22 x 22 Cholesky per lane
 // is not an option); here every tile takes up to six products with V read from there (L2), the right-hand side g1 - B^T q, and at the
 // end y2 = q - Lc^-T (V y1).
-constexpr int kBorderMaxRows = 24, kBorderMaxQ = kBorderMaxRows / 4, kBorderLdV = 176;
-// layout of the border scratch (doubles): V [32 x 176] | Lc^-1 [32 x 32, row-major, lower] | q [32] | g1 - B^T q [176] | tile-column mask [16]
-constexpr int kBorderMP = 32, kBorderOffLinv = kBorderMP * kBorderLdV, kBorderOffQ = kBorderOffLinv + kBorderMP * kBorderMP,
-              kBorderOffG = kBorderOffQ + kBorderMP /* g1 - B^T q, 176 */, kBorderOffMask = kBorderOffG + kBorderLdV /* 16: tile column J of V is not zero */,
-              kBorderScratchDoubles = kBorderOffMask + 16;
+constexpr int kBorderMaxQ = kBorderMaxRows / 4;   // (layout of the border scratch, kBorderOff*: solve_plan.hpp)
 template <int kBorder>
 __device__ __forceinline__ void k_chol_solve_lds_body(const DeviceProblem& p, int dpad, double mu, int initScale, int fuseFinalize, int border, const double* bscr) {
   extern __shared__ double smem[];
@@ -4827,7 +4819,7 @@ __device__ __forceinline__ void k_chol_solve_lds_body(const DeviceProblem& p, in
   if (t < d) { p.yC[t] = rhs[t]; p.vC[t] = gFullMine / htil[t]; }  // Gauss-Newton solution + steepest-descent direction
   if constexpr (kBorder == 2) {
     // y2 = q - Lc^-T (V y1): the rows of V y1 dealt over the waves, then one thread per border row
-    double* bord = reinterpret_cast<double*>(fl + kCholFlagInts) + kCholBorderOff;
+    double* bord = reinterpret_cast<double*>(fl + kCholFlagInts) + kCholTimingDoubles;   // (the timing build's stamp buffer comes first)
 #pragma unroll
     for (int kk = 0; kk < 3; ++kk) {
       double acc = 0;
@@ -4847,7 +4839,7 @@ __device__ __forceinline__ void k_chol_solve_lds_body(const DeviceProblem& p, in
   }
   if constexpr (kBorder == 1) {
     // y2 = q - C^-1 (B y1): row a of B y1 on wave a, then one thread per border row
-    double* bord = reinterpret_cast<double*>(fl + kCholFlagInts) + kCholBorderOff;
+    double* bord = reinterpret_cast<double*>(fl + kCholFlagInts) + kCholTimingDoubles;   // (the timing build's stamp buffer comes first)
     if (wave < 4) {
       double acc = 0;
 #pragma unroll
@@ -4896,9 +4888,7 @@ __global__ __launch_bounds__(kCholLdsThreads) __attribute__((amdgpu_waves_per_eu
 // Blocked Cholesky over 64x64 blocks on many workgroups (d > 272, wide windows).  The right-hand side rides along as one
 // extra row block below the matrix, so the forward substitution falls out of the block solves; k_big_back finishes with
 // the backward substitution.
-constexpr int kNB = 64;
-constexpr int kBigTileLd = kPanelLd;                 // 16 x 17 LDS tiles
-constexpr int kBigBlockLds = 16 * 16 * kBigTileLd;   // a 64x64 block as 4x4 tiles
+// (kNB = 64, kBigTileLd, kBigBlockLds and the layout of the matrix in p.cholL -- bigMatrixDoubles, bigRhsOff, bigPartialOff: solve_plan.hpp)
 
 // global (row-major, leading dimension ld) 64x64 block <-> 4x4 LDS tiles, 256 threads,
 // through agent-scope relaxed atomics (sc1: the access itself is coherent across the XCDs' L2s), for blocks
@@ -5032,7 +5022,7 @@ __global__ __launch_bounds__(256) void k_big_load(DeviceProblem p, int dpad, dou
                                                   int nReady) {
   const int d = p.d;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < nReady; i += gridDim.x * blockDim.x) ready[i] = 0;
-  const size_t total = (size_t)(dpad + kNB) * dpad;
+  const size_t total = bigMatrixDoubles(dpad);
   for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
     const int gi = (int)(idx / dpad), gj = (int)(idx - (size_t)gi * dpad);
     double x = 0.0;
@@ -5060,11 +5050,8 @@ __global__ __launch_bounds__(256) void k_big_load(DeviceProblem p, int dpad, dou
 // (k_big_chol_chain below; its predecessors -- a launch pair per 64-wide panel, then plain block tasks without the
 // critical-path workgroup -- are in the history of this file.)
 constexpr int kSpinMax = 1 << 20;
-// Workgroups of one solve: all must be co-resident (1 per CU: 104 KB of LDS each).  120 leaves room for a second
-// solve of another handle / stream on the same GPU (2 x 120 <= 256 CUs); roots with more than kPersistWideTasks
-// block tasks (> ~2000 unknowns) take the whole chip.  Beyond that the bounded waits turn a would-be deadlock into
-// a flagged failure.
-constexpr int kPersistMaxGrid = 120, kPersistWideGrid = 256, kPersistWideTasks = 512;
+// The workgroups of one solve must all be co-resident (kPersistMaxGrid / kPersistWideGrid, solve_plan.hpp); beyond that the
+// bounded waits turn a would-be deadlock into a flagged failure.
 __device__ __forceinline__ bool pollReady(const int* f) {
   for (int it = 0; it < kSpinMax; ++it) {
     if (__hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) return true;
@@ -5296,11 +5283,10 @@ __global__ __launch_bounds__(256) void k_big_chol_chain(DeviceProblem p, int dpa
 // are a plain matrix-vector product spread over many workgroups (k_big_back_gemv: partial sums per 512-row chunk,
 // kept in the unused rows 1.. of the right-hand-side block, summed in fixed order); the triangle inside the
 // super-panel is one workgroup (k_big_back).
-constexpr int kBackSpan = 512;
 __global__ __launch_bounds__(512) void k_big_back_gemv(DeviceProblem p, int dpad, int c0, int c1) {
   __shared__ double part[8 * 64];
   double* M = p.cholL;
-  const double* y = M + (size_t)dpad * dpad;
+  const double* y = M + bigRhsOff(dpad);
   const int t = threadIdx.x, c = t & 63, stripe = t >> 6;
   const int col = c0 + 64 * blockIdx.x + c;
   const int i0 = c1 + kBackSpan * blockIdx.y, i1 = min(dpad, i0 + kBackSpan);
@@ -5312,7 +5298,7 @@ __global__ __launch_bounds__(512) void k_big_back_gemv(DeviceProblem p, int dpad
     double acc = 0;
 #pragma unroll
     for (int k = 0; k < 8; ++k) acc += part[k * 64 + t];
-    M[(size_t)(dpad + 1 + blockIdx.y) * dpad + col] = acc;
+    M[bigPartialOff(dpad, blockIdx.y) + col] = acc;
   }
 }
 __global__ __launch_bounds__(512) void k_big_back(DeviceProblem p, int dpad, int c0, int c1, int nChunks, const double* dinvG,
@@ -5326,8 +5312,8 @@ __global__ __launch_bounds__(512) void k_big_back(DeviceProblem p, int dpad, int
   const int t = threadIdx.x, d = p.d;
   double* M = p.cholL;
   for (int i = c0 + t; i < c1; i += blockDim.x) {
-    double v = M[(size_t)dpad * dpad + i];
-    for (int k = 0; k < nChunks; ++k) v -= M[(size_t)(dpad + 1 + k) * dpad + i];
+    double v = M[bigRhsOff(dpad) + i];
+    for (int k = 0; k < nChunks; ++k) v -= M[bigPartialOff(dpad, k) + i];
     y[i] = v;
   }
   __syncthreads();
@@ -5384,7 +5370,7 @@ __global__ __launch_bounds__(512) void k_big_back(DeviceProblem p, int dpad, int
     __syncthreads();
   }
   for (int i = c0 + t; i < c1; i += blockDim.x) {
-    M[(size_t)dpad * dpad + i] = y[i];   // the solved part of y, read by the super-panels before this one
+    M[bigRhsOff(dpad) + i] = y[i];   // the solved part of y, read by the super-panels before this one
     if (i < d) { p.yC[i] = y[i]; p.vC[i] = p.gFull[i] / p.htilC[i]; }  // + steepest-descent direction
   }
 }
@@ -5420,8 +5406,17 @@ struct SbElimArgs {
   int ldOut;    // leading dimension (= rows) of Sout: dK rounded up to 16, zero beyond dK
   double *Sout, *gOut;
 };
-constexpr int kSbRec = 264, kSbG = 0, kSbFlo = 88, kSbFhi = 176;   // 9x9 row-major each (16-byte aligned starts)
-constexpr int kSbMaxChain = 64;                                    // k_sb_factor keeps the whole chain in LDS
+// (kSbRec, kSbG / kSbFlo / kSbFhi, kSbMaxChain, kSbLdsRec, kSbCols: solve_plan.hpp, with the plan that fills these fields)
+static SbElimArgs sbElimArgs(const ReducedSolvePlan& q, double* base) {
+  SbElimArgs a{};
+  a.n = q.n; a.dK = q.dK; a.dp = q.dpK; a.ldY = q.ldY; a.rowsY = q.rowsY;
+  a.Lf = base + q.Lf.off; a.Y = base + q.Y.off; a.tvec = base + q.tvec.off;
+  a.counter = reinterpret_cast<int*>(base + q.counter.off);
+  a.compact = q.chainMode == 2 ? 1 : 0;
+  a.ldOut = q.ldOut;
+  if (a.compact) { a.Sout = base + q.compactS.off; a.gOut = base + q.compactG.off; }
+  return a;
+}
 
 // 1 / sqrt(s) to the last bits: the hardware estimate (v_rsq_f64, ~2^-26) refined by a third-order and a second-order step
 __device__ __forceinline__ double rsqrtRefined(double s) {
@@ -5474,7 +5469,6 @@ __device__ __forceinline__ void inverseColumn9(const double* Lp, int j, double* 
   for (int i = 0; i < 9; ++i) Gout[i * 9 + j] = X[i];
 }
 
-constexpr int kSbLdsRec = 243;   // records in LDS: G | F_lo | F_hi back to back (an odd stride: eight blocks per wave, eight banks apart)
 constexpr int kSbFactorThreads = 576;   // 9 x 64: a level of 32 eliminations has 576 column tasks and 576 row tasks
 __global__ __launch_bounds__(kSbFactorThreads) void k_sb_factor(DeviceProblem p, SbElimArgs a, double mu, int initScale, int fuseFinalize) {
   extern __shared__ double smem[];
@@ -5624,7 +5618,6 @@ __global__ __launch_bounds__(kSbFactorThreads) void k_sb_factor(DeviceProblem p,
 #undef SBT
 }
 
-constexpr int kSbCols = 8;   // records in LDS: G | F_lo | F_hi back to back (an odd stride: eight blocks per wave, eight banks apart)
 __global__ __launch_bounds__(256) void k_sb_forward(DeviceProblem p, SbElimArgs a) {
   extern __shared__ double smem[];
   double* w = smem;                                   // [rowsY][8]
@@ -5736,7 +5729,7 @@ __global__ __launch_bounds__(256) void k_sb_load(DeviceProblem p, SbElimArgs a, 
   const int ldM = a.compact ? a.ldOut : dp;
   for (int i = blockIdx.x * blockDim.x + t; i < nReady; i += gridDim.x * blockDim.x) ready[i] = 0;
   // everything outside the tiles and the right-hand side row: identity padding, zero scratch rows (the compact matrix is all tiles)
-  const size_t total = a.compact ? 0 : (size_t)(dp + kNB) * dp;
+  const size_t total = a.compact ? 0 : bigMatrixDoubles(dp);
   for (size_t idx = (size_t)blockIdx.x * blockDim.x + t; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
     const int gi = (int)(idx / dp), gj = (int)(idx - (size_t)gi * dp);
     if (gi < 16 * nT && gj < 16 * nT) continue;
@@ -5807,7 +5800,7 @@ __global__ __launch_bounds__(256) void k_sb_load(DeviceProblem p, SbElimArgs a, 
       double tot = 0.0;
 #pragma unroll
       for (int k = 0; k < 16; ++k) tot += red[k * 16 + t];
-      (a.compact ? a.gOut : M + (size_t)dp * dp)[j] = p.gRed[j] - tot;
+      (a.compact ? a.gOut : M + bigRhsOff(dp))[j] = p.gRed[j] - tot;
     }
   }
 }
@@ -5925,9 +5918,7 @@ constexpr int kLLThreads = 512;
 #ifdef SVIN_LL_TIMING
 __device__ int g_llCount;
 #endif
-__host__ __device__ constexpr int llHalf(int nT) { return (nT + 1) / 2; }
-__host__ __device__ constexpr int llSlots(int nT) { return (nT - llHalf(nT)) * llHalf(nT); }
-__host__ __device__ constexpr size_t llLdsDoubles(int nT) { return (size_t)llSlots(nT) * 256 + 2 * 256 + 16 * kPanelLd + 16 + 2 * 16 * nT; }
+// (llHalf, llSlots, llLdsDoubles: solve_plan.hpp)
 // (branch-free on purpose: as a chain of conditionals the compiler turns every slot lookup of the update loops into three
 // scalar branches)
 __host__ __device__ __forceinline__ int llSlot(int I, int j, int h) {
@@ -6566,122 +6557,54 @@ __global__ __launch_bounds__(kBorderPrepThreads) void k_chol_border_prepare(Devi
 #endif
 }
 
-// LDS bytes of k_chol_solve_lds for nT tile rows (+ kBorderMP doubles of the border variants)
-static size_t cholLdsBytes(int nT) {
-#ifdef SVIN_CHOL_TIMING
-  return ((size_t)nT * (nT + 1) / 2 * kTile + 3 * 16 * nT) * 8 + kCholFlagInts * 4 + 240 * 8 + kBorderMP * 8;
-#else
-  return ((size_t)nT * (nT + 1) / 2 * kTile + 3 * 16 * nT) * 8 + kCholFlagInts * 4 + kBorderMP * 8;
-#endif
+// The plan of p's reduced solve (solve_plan.hpp): the route, the regions of p.cholL, the grid and the LDS of every launch.  The
+// switches are read from the option table here: the planner itself reads none.  Build and solve of an iteration see the same p
+// and the same switches, hence the same plan.
+static ReducedSolvePlan solvePlanOf(const DeviceProblem& p) {
+  return planReducedSolve(SolveDims{p.d, p.dC, p.sbChain, p.sPadded}, SolveSwitches{optOn(kOptNoLL), optOn(kOptNoSbElim), optOn(kOptNoLdsBorder)});
 }
-constexpr int kCholLdsMaxTiles = 11;   // tile rows of the largest system LDS holds (156 KB)
-// rows beyond the LDS-resident solver's eleven tile rows that it eliminates while loading (k_chol_solve_lds<true>); needs the window's padded S
-static int cholBorderRows(int d, bool padded) {
-  const int m = d - 16 * kCholLdsMaxTiles;
-  return (padded && m >= 1 && m <= kBorderMaxRows && !optOn(kOptNoLdsBorder)) ? m : 0;
-}
-static int solverClass(int d, bool padded = false) {   // 0 = LDS-resident, 1 = left-looking in one workgroup, 2 = blocked over many workgroups
-  const int nT = (d + 15) / 16;
-  if (cholLdsBytes(nT) <= 156 * 1024 || cholBorderRows(d, padded) > 0) return 0;
-  if (nT >= 12 && nT <= 17 && !optOn(kOptNoLL)) return 1;
-  return 2;
-}
-// Whether (and where in p.cholL) the speed / bias chain is eliminated ahead of the dense solve: 0 = no, 1 = the kept rows go
-// to the blocked solver's matrix (k_sb_load writes it instead of k_big_load), 2 = the kept system is small enough for one of
-// the single-workgroup solvers: k_sb_load writes it as a compact padded matrix S' + right-hand side g', which that solver
-// takes through a DeviceProblem view.  A system the LDS-resident solver takes whole is left alone (14 us at d = 150: the
-// elimination's four launches cost more), and so is a chain of fewer than 8 blocks ahead of the blocked solver.
-static int planSbElimination(const DeviceProblem& p, SbElimArgs& a) {
-  if (optOn(kOptNoSbElim) || p.sbChain < 2 || p.sbChain > kSbMaxChain || p.dC < 16 || p.dC + 9 * p.sbChain != p.d) return 0;
-  if (solverClass(p.d, p.sPadded != 0) == 0) return 0;
-  // Measured (tools/sb_elim_time.py, reduced solve with / without): d = 180 66 / 64 us, 240: 73 / 91, 270: 85 / 113, 360: 99 / 183,
-  // 600: 185 / 313, 960: 289 / 476 -- the four launches cost ~45 us before they gain anything, so short chains stay with the
-  // dense solvers.  (Tried and dropped: eliminating only the last blocks of a chain in ONE fused launch so that a system a few
-  // rows over the LDS-resident solver's limit drops into it: 39 + 35 + 10 us against the left-looking solver's 70.  d = 177 .. 180
-  // is now the LDS-resident solver's own border variant; the stereo_rig_v2 sliding window is d = 198.)
-  const int mode = solverClass(p.dC) == 2 ? 1 : 2;
-  // (the compact form needed 16 blocks until the end of round 5, when the kept rows went to the left-looking solver more often than
-  //  not; with the LDS-resident solver taking up to 200 rows a chain of 8 pays: config #3 -- chain of 10, 180 kept rows -- 112.6 -> 83.6 us,
-  //  d = 210 / 225 (chains of 14 / 15) 80.9 -> 65.2 / 90.2 -> 65.6)
-  if (p.sbChain < 8) return 0;
-  a.n = p.sbChain; a.dK = p.dC;
-  a.dp = ((a.dK + kNB - 1) / kNB) * kNB;
-  a.ldY = ((a.dK + 1 + 15) / 16) * 16;
-  a.rowsY = ((9 * a.n + 3) / 4) * 4;
-  a.compact = mode == 2 ? 1 : 0;
-  size_t off0;
-  if (mode == 1) {
-    const size_t nb = a.dp / kNB;
-    off0 = (size_t)(a.dp + kNB) * a.dp + a.dp + (size_t)a.dp * kNB + ((nb + 3) * nb + 1) / 2 + 2;
-    off0 = (off0 + 1) & ~(size_t)1;
-    a.Sout = nullptr; a.gOut = nullptr; a.ldOut = 0;
-  } else {
-    const size_t dpadK = ((size_t)a.dK + 15) / 16 * 16;
-    a.ldOut = (int)dpadK;
-    a.Sout = p.cholL + dpadK * dpadK;      // behind the kept solver's own spill / write-through area
-    a.gOut = a.Sout + dpadK * dpadK;
-    off0 = 2 * dpadK * dpadK + dpadK;
-  }
-  a.Lf = p.cholL + off0;
-  a.Y = a.Lf + (size_t)a.n * kSbRec;
-  a.tvec = a.Y + (size_t)a.rowsY * a.ldY;
-  a.counter = reinterpret_cast<int*>(a.tvec + a.rowsY);
-  return off0 + (size_t)a.n * kSbRec + (size_t)a.rowsY * a.ldY + a.rowsY + 2 <= solveReducedScratchDoubles(p.d, true) ? mode : 0;
-}
-// the dense solve of p's system (or, with `sb`, of the kept rows the chain elimination left in the blocked solver's matrix)
-static void launchSolveDense(const DeviceProblem& p, hipStream_t s, double mu, bool initScale, bool fuseFinalize, const SbElimArgs* sb) {
-  const int dpad = ((p.d + 15) / 16) * 16;
-  const int nT = dpad / 16;
-  const int cls = solverClass(p.d, p.sPadded != 0);
-  const int border = cholBorderRows(p.d, p.sPadded != 0);
-  if (cls == 0 && border > 4) {
-    // the border block factorised and V, q, Lc^-1 written to the solver's global scratch by a small launch of its own
-    const size_t ldsBytes = cholLdsBytes(kCholLdsMaxTiles);
-    launch(k_chol_border_prepare, dim3(1), dim3(kBorderPrepThreads), 0, s, p, 16 * kCholLdsMaxTiles, mu, initScale ? 1 : 0,
-           fuseFinalize ? 1 : 0, border, p.cholL);
-    launch(k_chol_solve_lds<2>, dim3(1), dim3(kCholLdsThreads), ldsBytes, s, p, 16 * kCholLdsMaxTiles, mu, initScale ? 1 : 0,
-           fuseFinalize ? 1 : 0, border, (const double*)p.cholL);
-  } else if (cls == 0 && border > 0) {
-    const size_t ldsBytes = cholLdsBytes(kCholLdsMaxTiles);
-    launch(k_chol_solve_lds<1>, dim3(1), dim3(kCholLdsThreads), ldsBytes, s, p, 16 * kCholLdsMaxTiles, mu, initScale ? 1 : 0,
-           fuseFinalize ? 1 : 0, border, (const double*)nullptr);
-  } else if (cls == 0) {
-    const size_t ldsBytes = cholLdsBytes(nT);
-    launch(k_chol_solve_lds<0>, dim3(1), dim3(kCholLdsThreads), ldsBytes, s, p, dpad, mu, initScale ? 1 : 0,
-           fuseFinalize ? 1 : 0, 0, (const double*)nullptr);
-  } else if (cls == 1) {
-    // one workgroup, left-looking: at most 72 live tiles in LDS, finished tiles written through to p.cholL
-    const size_t ldsLL = llLdsDoubles(nT) * 8;
-    launch(k_chol_solve_ll, dim3(1), dim3(kLLThreads), ldsLL, s, p, dpad, mu, initScale ? 1 : 0, fuseFinalize ? 1 : 0);
-  } else {
-    // multi-workgroup blocked factorisation, 64-wide panels; p.cholL holds (dpad64 + 64) x dpad64 doubles, its tail
-    // the 1/L_ii vector.  Behind a chain elimination the matrix is already there (k_sb_load) and only spans the kept rows.
-    const int dp = sb ? sb->dp : ((p.d + kNB - 1) / kNB) * kNB;
-    double* dinvG = p.cholL + (size_t)(dp + kNB) * dp;
-    double* diagF = dinvG + dp;   // per panel the factorised 64x64 diagonal block (dp x 64)
-    const int nb = dp / kNB;
-    int* ready = reinterpret_cast<int*>(diagF + (size_t)dp * kNB);   // (nb + 3) x nb block flags
-    if (sb) {
-      const int nTk = (sb->dK + 15) / 16;
-      launch(k_sb_load, dim3(nTk * (nTk + 1) / 2 + (sb->dK + 15) / 16), dim3(256), 0, s, p, *sb, mu, initScale ? 1 : 0,
-             fuseFinalize ? 1 : 0, ready, (nb + 3) * nb);
-    } else {
-      launch(k_big_load, dim3(256), dim3(256), 0, s, p, dp, mu, initScale ? 1 : 0, fuseFinalize ? 1 : 0, ready, (nb + 3) * nb);
+// the dense solve of plan q: of p's own system, of the compact kept system (p is then the view of it), or, with `sb`, of the kept
+// rows the chain elimination leaves in the blocked solver's matrix
+static void launchSolveDense(const DeviceProblem& p, const ReducedSolvePlan& q, hipStream_t s, double mu, bool initScale, bool fuseFinalize,
+                             const SbElimArgs* sb) {
+  const int init = initScale ? 1 : 0, fuse = fuseFinalize ? 1 : 0;
+  switch (q.route) {
+    case kRouteLdsBorderPrepared: {
+      // the border block factorised and V, q, Lc^-1 written to the solver's global scratch by a small launch of its own
+      double* bscr = p.cholL + q.borderScr.off;
+      launch(k_chol_border_prepare, dim3(q.borderPrepare.grid), dim3(kBorderPrepThreads), q.borderPrepare.ldsBytes, s, p, q.dpad, mu, init, fuse,
+             q.border, bscr);
+      launch(k_chol_solve_lds<2>, dim3(q.cholLds.grid), dim3(kCholLdsThreads), q.cholLds.ldsBytes, s, p, q.dpad, mu, init, fuse, q.border,
+             (const double*)bscr);
+      break;
     }
-    {
-      const size_t ldsTasks = ((size_t)3 * kBigBlockLds + kNB + 2) * 8;
-      int nHelperTasks = 0;
-      for (int st = 0; st < nb; ++st) nHelperTasks += std::max(nb - st - 1, 0) + ((st + 2 <= nb - 1) ? 2 : 0);
-      launch(k_big_chol_chain,
-             dim3(1 + std::max(1, std::min(nHelperTasks, (nHelperTasks > kPersistWideTasks ? kPersistWideGrid : kPersistMaxGrid) - 1))),
-             dim3(256), ldsTasks, s, p, dp, dinvG, diagF, ready);
-    }
-    const size_t ldsBack = ((size_t)kBackSpan + 8 * 64 + kNB * (kNB + 1) + kNB) * 8;
-    for (int c1 = dp; c1 > 0; c1 -= kBackSpan) {
-      const int c0 = std::max(0, c1 - kBackSpan);
-      const int nChunks = (dp - c1 + kBackSpan - 1) / kBackSpan;   // <= 63: the spare rows of the rhs block
-      launch(k_big_back_gemv, dim3((c1 - c0) / kNB, nChunks), dim3(512), 0, s, p, dp, c0, c1);
-      launch(k_big_back, dim3(1), dim3(512), ldsBack, s, p, dp, c0, c1, nChunks, (const double*)dinvG, (const double*)diagF);
+    case kRouteLdsBorderLoad:
+      launch(k_chol_solve_lds<1>, dim3(q.cholLds.grid), dim3(kCholLdsThreads), q.cholLds.ldsBytes, s, p, q.dpad, mu, init, fuse, q.border,
+             (const double*)nullptr);
+      break;
+    case kRouteLdsWhole:
+      launch(k_chol_solve_lds<0>, dim3(q.cholLds.grid), dim3(kCholLdsThreads), q.cholLds.ldsBytes, s, p, q.dpad, mu, init, fuse, 0,
+             (const double*)nullptr);
+      break;
+    case kRouteLeftLooking:
+      // one workgroup, left-looking: at most 72 live tiles in LDS, finished tiles written through to p.cholL
+      launch(k_chol_solve_ll, dim3(q.cholLL.grid), dim3(kLLThreads), q.cholLL.ldsBytes, s, p, q.dpad, mu, init, fuse);
+      break;
+    case kRouteBlocked: {
+      // multi-workgroup blocked factorisation, 64-wide panels.  Behind a chain elimination the matrix is written by k_sb_load and
+      // only spans the kept rows.
+      double* dinvG = p.cholL + q.dinvG.off;
+      double* diagF = p.cholL + q.diagF.off;
+      int* ready = reinterpret_cast<int*>(p.cholL + q.ready.off);
+      if (sb) launch(k_sb_load, dim3(q.sbLoad.grid), dim3(256), q.sbLoad.ldsBytes, s, p, *sb, mu, init, fuse, ready, bigReadyInts(q.nb));
+      else launch(k_big_load, dim3(q.bigLoad.grid), dim3(256), q.bigLoad.ldsBytes, s, p, q.dp, mu, init, fuse, ready, bigReadyInts(q.nb));
+      launch(k_big_chol_chain, dim3(q.bigChain.grid), dim3(256), q.bigChain.ldsBytes, s, p, q.dp, dinvG, diagF, ready);
+      for (int k = 0; k < q.nBackPanels; ++k) {
+        const BackPanel b = backPanel(q.dp, k);
+        launch(k_big_back_gemv, dim3(b.blocks, b.nChunks), dim3(512), 0, s, p, q.dp, b.c0, b.c1);
+        launch(k_big_back, dim3(1), dim3(512), q.bigBackLdsBytes, s, p, q.dp, b.c0, b.c1, b.nChunks, (const double*)dinvG, (const double*)diagF);
+      }
+      break;
     }
   }
 }
@@ -6703,43 +6626,37 @@ __global__ __launch_bounds__(256) void k_lock_rows(DeviceProblem p) {
 }
 // factorisation and forward substitution of the speed / bias chain (the first two launches of the reduced solve with the chain
 // eliminated); fuseFinalize: the chain's rows get their metric and damping here
-static void launchSbChainFactor(const DeviceProblem& p, const SbElimArgs& sb, hipStream_t s, double mu, bool initScale, bool fuseFinalize) {
-  const size_t ldsFactor = ((size_t)sb.n * 162 + (size_t)((sb.n + 1) / 2) * 243) * 8;
-  launch(k_sb_factor, dim3(1), dim3(kSbFactorThreads), ldsFactor, s, p, sb, mu, initScale ? 1 : 0, fuseFinalize ? 1 : 0);
-  const size_t ldsFwd = ((size_t)sb.rowsY * kSbCols + (size_t)sb.n * kSbLdsRec) * 8;
-  launch(k_sb_forward, dim3(sb.ldY / kSbCols), dim3(256), ldsFwd, s, p, sb);
+static void launchSbChainFactor(const DeviceProblem& p, const ReducedSolvePlan& q, const SbElimArgs& sb, hipStream_t s, double mu, bool initScale,
+                                bool fuseFinalize) {
+  launch(k_sb_factor, dim3(q.sbFactor.grid), dim3(kSbFactorThreads), q.sbFactor.ldsBytes, s, p, sb, mu, initScale ? 1 : 0, fuseFinalize ? 1 : 0);
+  launch(k_sb_forward, dim3(q.sbForward.grid), dim3(256), q.sbForward.ldsBytes, s, p, sb);
 }
-// ONE predicate for the build (which then launches the chain's kernels) and the solve (which then skips them)
-static bool sbEarlyActive(const DeviceProblem& p) {
-  if (!(p.sideLane != 0 && p.L > 0 && p.N > 0 && p.dC > 0 && !p.schurDense && p.schurPanels && p.schurBlocks && p.nLocked == 0)) return false;
-  if (p.F + priorAccBlocks(p) <= 0) return false;
-  SbElimArgs sb;
-  return planSbElimination(p, sb) != 0;
+// ONE predicate for the build (which then launches the chain's kernels on the side stream) and the solve (which then skips them)
+static bool sbEarlyActive(const DeviceProblem& p, const ReducedSolvePlan& q) {
+  return q.chainMode != 0 && p.sideLane != 0 && p.L > 0 && p.N > 0 && p.dC > 0 && !p.schurDense && p.schurPanels && p.schurBlocks && p.nLocked == 0 &&
+         p.F + priorAccBlocks(p) > 0;
 }
-static void launchSbEarly(const DeviceProblem& p, hipStream_t side, double mu, bool initScale) {
-  SbElimArgs sb;
-  if (planSbElimination(p, sb)) launchSbChainFactor(p, sb, side, mu, initScale, /*fuseFinalize=*/true);
+static void launchSbEarly(const DeviceProblem& p, const ReducedSolvePlan& q, hipStream_t side, double mu, bool initScale) {
+  launchSbChainFactor(p, q, sbElimArgs(q, p.cholL), side, mu, initScale, /*fuseFinalize=*/true);
 }
 void launchSolveReduced(const DeviceProblem& p, hipStream_t s, double mu, bool initScale, bool fuseFinalize) {
   launch(k_lock_rows, dim3(p.nLocked), dim3(256), 0, s, p);
-  SbElimArgs sb;
-  const int elim = planSbElimination(p, sb);
-  if (!elim) { launchSolveDense(p, s, mu, initScale, fuseFinalize, nullptr); return; }
-  // (p.sideLane: the build of this iteration has run them already, with this mu and initScale -- launchAccumulateNormalEquations)
-  if (p.sideLane != 0 && sbEarlyActive(p) && !fuseFinalize) throw std::logic_error("sbEarly without the fused finalisation");
-  if (!sbEarlyActive(p)) launchSbChainFactor(p, sb, s, mu, initScale, fuseFinalize);
-  if (elim == 1) {
-    launchSolveDense(p, s, mu, initScale, fuseFinalize, &sb);
+  const ReducedSolvePlan q = solvePlanOf(p);
+  if (!q.chainMode) { launchSolveDense(p, q, s, mu, initScale, fuseFinalize, nullptr); return; }
+  const SbElimArgs sb = sbElimArgs(q, p.cholL);
+  // (early: the build of this iteration has run them already, with this mu and initScale -- launchAccumulateNormalEquations)
+  const bool early = sbEarlyActive(p, q);
+  if (early && !fuseFinalize) throw std::logic_error("sbEarly without the fused finalisation");
+  if (!early) launchSbChainFactor(p, q, sb, s, mu, initScale, fuseFinalize);
+  if (q.chainMode == 1) {
+    launchSolveDense(p, q, s, mu, initScale, fuseFinalize, &sb);
   } else {
-    const int nTk = (sb.dK + 15) / 16;
-    launch(k_sb_load, dim3(nTk * (nTk + 1) / 2 + (sb.dK + 15) / 16), dim3(256), 0, s, p, sb, mu, initScale ? 1 : 0,
-           fuseFinalize ? 1 : 0, (int*)nullptr, 0);
-    DeviceProblem q = p;   // the kept system as a problem of its own: rows 0 .. dK of every vector are the kept rows
-    q.d = sb.dK; q.S = sb.Sout; q.ldS = sb.ldOut; q.sPadded = 1; q.gRed = sb.gOut; q.sbChain = 0;
-    launchSolveDense(q, s, 0.0, false, false, nullptr);   // (metric and damping are in S' already)
+    launch(k_sb_load, dim3(q.sbLoad.grid), dim3(256), q.sbLoad.ldsBytes, s, p, sb, mu, initScale ? 1 : 0, fuseFinalize ? 1 : 0, (int*)nullptr, 0);
+    DeviceProblem v = p;   // the kept system as a problem of its own: rows 0 .. dK of every vector are the kept rows
+    v.d = sb.dK; v.S = sb.Sout; v.ldS = sb.ldOut; v.sPadded = 1; v.gRed = sb.gOut; v.sbChain = 0;
+    launchSolveDense(v, q, s, 0.0, false, false, nullptr);   // (metric and damping are in S' already)
   }
-  const size_t ldsBackSb = ((size_t)sb.n * kSbRec + 18 * (size_t)sb.n) * 8;
-  launch(k_sb_back, dim3((9 * sb.n + 15) / 16), dim3(256), ldsBackSb, s, p, sb);
+  launch(k_sb_back, dim3(q.sbBack.grid), dim3(256), q.sbBack.ldsBytes, s, p, sb);
 }
 
 // ================================================================ post-solve pass and dogleg step
@@ -7341,7 +7258,7 @@ bool batchSupported(const DeviceProblem& p) {
   if (!(p.L > 0 && p.N > 0 && p.dC > 0 && p.schurDense && p.d > 0)) return false;
   if (!canFuseEvaluation(p) || optOn(kOptSplitEval) || optOn(kOptNoFuseStep) || optOn(kOptNoDeferLm)) return false;
   if ((p.nPose + p.nExt + p.nSb + p.L) > 16384) return false;            // (the fused dogleg step of k_post_solve)
-  if (solverClass(p.d, p.sPadded != 0) != 0 || cholBorderRows(p.d, p.sPadded != 0) != 0) return false;   // LDS-resident solver, no border
+  if (!batchedSolverTakes(solvePlanOf(p))) return false;   // the whole system on the LDS-resident solver: no border, no chain elimination
   if (priorAccBlocks(p) > 0 && !p.ownsCamera) return false;
   if (p.nLocked > 0) return false;   // (reduced pose manifolds: k_lock_rows has no batched form)
   if (p.nHostFactors > 0) return false;
@@ -7359,9 +7276,9 @@ void launchBatchRound(const BatchSlot* dSlots, const DeviceProblem& geom, const 
     else launch(k_schur_dense_batch<9, false, 4>, gridB, dim3(64 * 4), plan.ldsBytes, s, dSlots);
     const int nRed = p.dC * p.dC + 3 * p.dC;
     launch(k_reduce_slabs_batch, dim3((nRed + 15) / 16, n), dim3(256), 0, s, dSlots);   // (every window sums its own nSlabs)
-    const int dpad = ((p.d + 15) / 16) * 16;
-    const size_t ldsChol = cholLdsBytes(dpad / 16);
-    launch(k_chol_solve_lds_batch<0>, dim3(1, n), dim3(kCholLdsThreads), ldsChol, s, dSlots, dpad, 1, 0, (const double*)nullptr);
+    const ReducedSolvePlan q = solvePlanOf(p);
+    if (!batchedSolverTakes(q)) throw std::logic_error("launchBatchRound: a window batchSupported refuses");
+    launch(k_chol_solve_lds_batch<0>, dim3(q.cholLds.grid, n), dim3(kCholLdsThreads), q.cholLds.ldsBytes, s, dSlots, q.dpad, 1, 0, (const double*)nullptr);
     if (p.anyExtVariable) launch(k_post_solve_batch<true>, dim3(grid.post, n), dim3(256), 0, s, dSlots);
     else launch(k_post_solve_batch<false>, dim3(grid.post, n), dim3(256), 0, s, dSlots);
   }

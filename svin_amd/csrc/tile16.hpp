@@ -3,6 +3,7 @@
 // kernels.hip in round 5 (the certified Cholesky route of the prior, k_marg_final_chol, factorises its diagonal tiles with it).
 #pragma once
 #include <hip/hip_runtime.h>
+#include "tile_dims.hpp"   // kPanelLd
 
 namespace svin {
 
@@ -21,7 +22,6 @@ __device__ __forceinline__ double rsqrtNewton(double x) {
   e = __builtin_fma(-h * y, y, 0.5);
   return __builtin_fma(y, e, y);
 }
-constexpr int kPanelLd = 17;  // leading dimension of the 16x16 LDS tiles of the dense solvers
 __device__ __forceinline__ void allGatherRows(double v, double (&out)[4]) {
   const unsigned lo = (unsigned)__double2loint(v), hi = (unsigned)__double2hiint(v);
   const auto l16 = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);  // rows [v0 v0 v2 v2], [v1 v1 v3 v3]

@@ -3040,7 +3040,7 @@ int Window::debugTrustRegionStep(double mu, double radius, int form, int commit,
   return 1;
 }
 // inspection hook: doubles [off, off + count) of the reduced-system solver's scratch buffer (the factor, the eliminated chain's
-// records and Y: layout in kernels.hip, launchSolveReduced) after the last solve
+// records and Y: layout in solve_plan.hpp, ReducedSolvePlan) after the last solve
 int Window::debugPeekSolverScratch(uint64_t off, uint64_t count, double* out) {
   quiesce();
   if (!prob_.cholL || off + count > solveReducedScratchDoubles(prob_.d, true)) return 0;

@@ -98,6 +98,24 @@ def test_mixed_geometries_fall_into_groups_and_singles(gpu_lib):
     assert estimator.optimize_batch([], 3) == 0
 
 
+def test_windows_whose_chain_is_eliminated_are_not_batched(gpu_lib):
+    """14 keyframes: a reduced system of 210 rows whose speed / bias chain is eliminated first, the 84 kept rows then go to the
+    LDS-resident solver.  The batched solver has no chain form and would take the 210 rows as they are: such windows are solved
+    one by one (0 batched), each where it ends alone"""
+    from svin_amd import estimator
+    specs = [dict(seed=11, P=14, L=300, n_obs=3000), dict(seed=12, P=14, L=300, n_obs=3000)]
+    alone = []
+    for c in specs:
+        est, fids, lids = build(**c)
+        est.optimize(4)
+        alone.append(states_of(est, fids, lids))
+    batch = [build(**c) for c in specs]
+    assert estimator.optimize_batch([b[0] for b in batch], 4) == 0
+    for k, (est, fids, lids) in enumerate(batch):
+        for a, b in zip(states_of(est, fids, lids), alone[k]):
+            assert np.array_equal(a, b), (k, float(np.max(np.abs(a - b))))
+
+
 def test_batch_of_sliding_windows_with_marginalisation_priors(gpu_lib):
     """windows in SVIn's operating mode: fed frame by frame, optimised and marginalised after every frame -- each carries a
     marginalisation prior (the prior block of the batched evaluation, the prior's blocks of the batched build) and fixed-lag

@@ -3,6 +3,7 @@ system svin_ba_linearize returns and compares every intermediate the kernels lea
 F_hi, Y, the reduced matrix, t) -- says which kernel went wrong first.   python tools/dbg/sb_elim_dbg.py [P]"""
 import os
 import sys
+import tempfile
 
 import numpy as np
 
@@ -21,36 +22,26 @@ H = np.tril(lin["S"]) + np.tril(lin["S"], -1).T
 g = lin["g"]
 d = lin["d"]
 n = P
-assert n >= 16, "chains shorter than 16 blocks are not eliminated (planSbElimination): nothing to compare"
 dK = d - 9 * n
 y_dev = est.debug_reduced_solve(mu)
 y_ref = np.linalg.solve(H, g)
 print("d", d, "dK", dK, "n", n, "device vs host", np.abs(y_dev - y_ref).max() / np.abs(y_ref).max())
 
-# scratch layout (planSbElimination)
-def solver_class(dd):
-    nT = (dd + 15) // 16
-    if (nT * (nT + 1) // 2 * 16 * 17 + 3 * 16 * nT) * 8 + 48 * 4 <= 156 * 1024:
-        return 0
-    return 1 if 12 <= nT <= 17 else 2
-
-
-dp = (dK + 63) // 64 * 64
-nb = dp // 64
-ldY = (dK + 1 + 15) // 16 * 16
-rowsY = (9 * n + 3) // 4 * 4
-compact = solver_class(dK) < 2
-if compact:
-    dpadK = (dK + 15) // 16 * 16
-    off0 = 2 * dpadK * dpadK + dpadK
-else:
-    off0 = (dp + 64) * dp + dp + dp * 64 + ((nb + 3) * nb + 1) // 2 + 2
-    off0 = (off0 + 1) & ~1
-print("kept system: class", solver_class(dK), "(compact)" if compact else "(blocked)")
-REC = 264
-Lf = est.debug_peek_solver_scratch(off0, n * REC).reshape(n, REC)
-Y = est.debug_peek_solver_scratch(off0 + n * REC, rowsY * ldY).reshape(rowsY, ldY)
-tv = est.debug_peek_solver_scratch(off0 + n * REC + rowsY * ldY, rowsY)
+# scratch layout: the plan the launchers walk (svin_amd/csrc/solve_plan.hpp through the tests' shim; the window's S is padded)
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))), "tests", "helpers"))
+import solve_plan_lib as spl                    # noqa: E402
+with tempfile.TemporaryDirectory() as tmp:
+    shim = spl.build_shim(tmp)
+    plan = spl.plan_one(shim, d, dC=dK, n=n, padded=1)
+    consts = spl.constants(shim)
+assert plan["chainMode"] != 0, "this chain is not eliminated (solve_plan.hpp chainModeOf): nothing to compare"
+compact = plan["chainMode"] == 2
+rowsY, ldY, dpadK = plan["rowsY"], plan["ldY"], plan["ldOut"]
+print("kept system: route", spl.ROUTES[plan["route"]], "(compact)" if compact else "(blocked)")
+REC, FLO, FHI = consts["kSbRec"], consts["kSbFlo"], consts["kSbFhi"]
+Lf = est.debug_peek_solver_scratch(plan["Lf_off"], n * REC).reshape(n, REC)
+Y = est.debug_peek_solver_scratch(plan["Y_off"], rowsY * ldY).reshape(rowsY, ldY)
+tv = est.debug_peek_solver_scratch(plan["tvec_off"], rowsY)
 
 # numpy replay (tools/chain_elim_replay.py: the same level schedule and per-block quantities as the kernels)
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -63,8 +54,8 @@ for s_ in cr.levels(n):
         level[b] = s_
 for b in range(n):
     eg = np.abs(Lf[b, 0:81].reshape(9, 9) - G[b]).max() / np.abs(G[b]).max()
-    el = np.abs(Lf[b, 88:169].reshape(9, 9) - Flo[b]).max() / max(np.abs(Flo[b]).max(), 1e-300)
-    eh = np.abs(Lf[b, 176:257].reshape(9, 9) - Fhi[b]).max() / max(np.abs(Fhi[b]).max(), 1e-300)
+    el = np.abs(Lf[b, FLO:FLO + 81].reshape(9, 9) - Flo[b]).max() / max(np.abs(Flo[b]).max(), 1e-300)
+    eh = np.abs(Lf[b, FHI:FHI + 81].reshape(9, 9) - Fhi[b]).max() / max(np.abs(Fhi[b]).max(), 1e-300)
     if max(eg, el, eh) > 1e-9 or not np.isfinite(eg + el + eh):
         print("record of block %d (level s = %d): G %.2e F_lo %.2e F_hi %.2e" % (b, level[b], eg, el, eh))
 print("records compared")
@@ -74,10 +65,10 @@ print("Y: max abs diff %.3e of %.3e; worst row %d col %d; pad rows zero: %s; nan
       (np.nanmax(eY), np.abs(w).max(), *np.unravel_index(np.nanargmax(eY), eY.shape), bool(np.all(Y[9 * n:] == 0)), int(np.isnan(Y).sum())))
 Mref = H[:dK, :dK] - w[:, :dK].T @ w[:, :dK]
 if compact:
-    M = est.debug_peek_solver_scratch(dpadK * dpadK, dpadK * dpadK).reshape(dpadK, dpadK)
+    M = est.debug_peek_solver_scratch(plan["compactS_off"], dpadK * dpadK).reshape(dpadK, dpadK)
     print("compact kept matrix: max rel diff %.3e; zero beyond dK: %s" % (np.abs(M[:dK, :dK] - Mref).max() / np.abs(Mref).max(),
           bool(np.all(M[dK:] == 0) and np.all(M[:, dK:] == 0))))
-    gk_dev = est.debug_peek_solver_scratch(2 * dpadK * dpadK, dK)
+    gk_dev = est.debug_peek_solver_scratch(plan["compactG_off"], dK)
     print("compact right-hand side: %.3e" % (np.abs(gk_dev - (g[:dK] - w[:, :dK].T @ w[:, dK])).max() / np.abs(g[:dK]).max()))
 gk = g[:dK] - w[:, :dK].T @ w[:, dK]
 xk = np.linalg.solve(Mref, gk)
