@@ -142,7 +142,11 @@ int svin_ba_optimize(svin_ba* h, uint64_t num_iter, uint64_t num_threads_ignored
 int svin_ba_wait_idle(svin_ba* h);
 int svin_ba_set_optimization_time_limit(svin_ba* h, double time_limit, int min_iterations);    /* :932-951 */
 /* Estimator::applyMarginalizationStrategy :495-814; removed landmark ids are written to
- * removed_ids (capacity cap), *n_removed receives the full count. */
+ * removed_ids (capacity cap), *n_removed receives the full count.  A constant landmark is treated like any other by the policy
+ * (it is removed, and listed in removed_ids, when the reference removes it); its linearised observations contribute their pose /
+ * extrinsics terms to the prior and no landmark columns (MarginalizationError.cpp:156, :343, :367).  Refused with an error and
+ * nothing changed: a landmark under a HomogeneousPointError, or -- on a landmark-sharded handle -- a constant landmark, observed
+ * from a frame that leaves. */
 int svin_ba_apply_marginalization_strategy(svin_ba* h, uint64_t num_keyframes, uint64_t num_imu_frames,
                                            uint64_t* removed_ids, int cap, int* n_removed);
 /* optimize() split in three for measurement with HBM-resident inputs: prepare = pack + upload the window,
@@ -245,8 +249,9 @@ int svin_ba_landmark_ids(svin_ba* h, uint64_t* ids, int cap);   /* returns the n
  * speed/bias: svin_ba_describe_block tells which), landmark ids.  Residual ids: what add_observation returned, the
  * ids of the non-reprojection factors (svin_ba_eval_factors lists them) and of the marginalisation prior. */
 int svin_ba_parameter_block_exists(svin_ba* h, uint64_t block_id);                    /* Map::parameterBlockExists */
-/* Map::setParameterBlockConstant / Variable (src/Map.cpp:495-510) on any block, landmarks included (a window with a constant
- * landmark is packed by the host and cannot marginalise a frame that sees it); unknown id: 0 */
+/* Map::setParameterBlockConstant / Variable (src/Map.cpp:495-510) on any block, landmarks included.  A constant landmark is how
+ * a caller anchors the window to a map it trusts: it never moves, its observations keep constraining the poses, the window stays
+ * device-resident (the flag travels with the next svin_ba_optimize's delta) and marginalises as usual; unknown id: 0 */
 int svin_ba_set_parameter_block_constant(svin_ba* h, uint64_t block_id, int constant);
 int svin_ba_is_parameter_block_constant(svin_ba* h, uint64_t block_id);               /* ParameterBlock::fixed() */
 /* Map::resetParameterization (src/Map.cpp:513-543) with the values of Map::Parameterization (include/okvis/ceres/Map.hpp:97-105):
@@ -485,10 +490,14 @@ int svin_ba_debug_trust_region_step(svin_ba* h, double mu, double radius, int fo
                                     double* block_candidates, int cap_blocks, int32_t* info8);
 /* Which path the handle's work took since it was created, so that no fall-back is silent: out[0] optimisations on the
  * device-resident window (per frame only the new / removed observation records travel), out[1] optimisations that
- * re-packed the whole window on the host (wide windows with their panel work lists, landmark priors, constant landmarks,
- * sharded mode, svin_ba_set_pack_mode), out[2] marginalisation jobs whose observation tables were gathered on the device,
+ * re-packed the whole window on the host (wide windows with their panel work lists, landmark priors, general information
+ * matrices, sharded mode, svin_ba_set_pack_mode -- NOT constant landmarks: they stay on the resident path), out[2] marginalisation jobs whose observation tables were gathered on the device,
  * out[3] jobs whose tables the host assembled.  Returns 1. */
 int svin_ba_get_path_counters(svin_ba* h, int64_t out[4]);
+/* Landmark handles (inspection): out[0] = the handle range in use -- the size of the resident window's per-handle tables; handles are
+ * creation numbers, and when the live landmarks have become a small part of the range the next svin_ba_optimize renumbers them
+ * in id order and rebuilds the device copy from the graph --, out[1] = landmarks in the graph.  Returns 1. */
+int svin_ba_debug_landmark_handles(svin_ba* h, int32_t out[2]);
 /* the eigen-solver of the marginalisation prior (M3, MarginalizationError.cpp:725-758: Eigen::SelfAdjointEigenSolver there;
  * here Householder tridiagonalisation + divide and conquer in one workgroup, svin_amd/csrc/symeig.hpp) on an arbitrary
  * symmetric matrix A (n x n, row-major, n <= 128), on the current HIP device: eigenvalues ascending, eigenvectors[i * n + j] =
@@ -523,7 +532,9 @@ int svin_ba_get_prior(svin_ba* h, double* H, double* b0, double* J, double* e0, 
  * src/MarginalizationError.cpp:126-397) and BEFORE marginalizeOut, kept only when SVIN_MARG_KEEP_PRE is set in the
  * environment (inspection: lets a test arbitrate M1 and M2 / M3 separately): H = [U W; W^T blockdiag(V)], b = [ba; bb] with
  * U m x m (dense blocks, old prior first), W m x 3 n_landmarks, V 3x3 per landmark; marg_rows[i] = 1 for the dense rows that
- * are marginalised.  *m / *n_landmarks always receive the sizes; returns 1 when the arrays were filled (capacities suffice). */
+ * are marginalised.  A linearised CONSTANT landmark is listed with its 3 columns like any other; its V block, its columns of W
+ * and its part of bb are exact zeros (the reference gives it no columns at all).
+ * *m / *n_landmarks always receive the sizes; returns 1 when the arrays were filled (capacities suffice). */
 int svin_ba_get_marg_pre(svin_ba* h, int32_t* m, int32_t* n_landmarks, double* U, double* ba, double* W, double* V,
                          double* bb, int32_t* marg_rows, int cap_m, int cap_landmarks);
 /* ... and its ordering: the dense blocks (id, first row, number of rows; 0 rows = a fixed block) and the landmark ids in the
@@ -534,10 +545,11 @@ int svin_ba_get_marg_pre_blocks(svin_ba* h, uint64_t* dense_ids, int32_t* dense_
 int svin_ba_describe_block(svin_ba* h, uint64_t block_id, uint64_t* frame_id, int32_t* kind, int32_t* index);
 
 /* ---- device-resident window (design in svin_amd/csrc/resident.hpp).  A narrow window (<= 42 pose blocks, one
- * GPU, no HomogeneousPointError) keeps its landmark-major observation table on the device from frame to frame: optimize()
+ * GPU, no HomogeneousPointError, no general information matrix; constant landmarks are fine) keeps its landmark-major observation table on the device from frame to frame: optimize()
  * sends the observations added / removed since the last call and one kernel rebuilds the table (the reference re-reads
  * its four hash containers, Map.cpp:341-376, :467-492).  mode 0 (default): resident whenever the window qualifies;
- * mode 1: always the host path (graph -> arrays on the host, full upload) -- the form the tests compare the resident one with. */
+ * mode 1: always the host path (graph -> arrays on the host, full upload) -- the form the tests compare the resident one with,
+ * windows with constant landmarks included (both write the same tables: a negative weight on such a landmark's observations). */
 int svin_ba_set_pack_mode(svin_ba* h, int mode);
 /* inspection: builds the device tables exactly as optimize() would and copies the observation CSR back: sizes first (call
  * with null arrays), then lm_ptr[L + 1], obs_lm[N], obs_idx[N] (pose slot | extrinsics slot << 12 | camera << 24), uv[2 N],

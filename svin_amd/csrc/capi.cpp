@@ -595,6 +595,11 @@ int svin_ba_get_path_counters(svin_ba* h, int64_t out[4]) try {
   for (int i = 0; i < 4; ++i) out[i] = c[i];
   return 1;
 } CATCH_ALL(SVIN_ERR_DEVICE)
+int svin_ba_debug_landmark_handles(svin_ba* h, int32_t out[2]) try {
+  if (!h || !out) return SVIN_ERR_INVALID_ARG;
+  ro(h).landmarkHandles(out);
+  return 1;
+} CATCH_ALL(SVIN_ERR_DEVICE)
 int svin_ba_debug_sym_eig(int n, const double* A, double* eigenvalues, double* eigenvectors, double* device_ms) {
   if (!A || !eigenvalues || !eigenvectors) return SVIN_ERR_INVALID_ARG;
   GUARD_BEGIN return svin::debugSymEig(n, A, eigenvalues, eigenvectors, device_ms);

@@ -440,10 +440,19 @@ static size_t jacobiLdsBytesGOnly(int n) {
 // ---------------------------------------------------------------- M2: landmark part (:557-619)
 // per landmark: p_b from diag(V), V' = V/(p_b p_b^T), (V')^+ by 3x3 eigendecomposition with tolerance
 // eps*3*lmax, N = D_b^-1 U_e diag(sqrt(1/l)|0);  Mu = W_l N (m x 3) overwrites W_l; vb = N N^T bb_l.
+// A landmark with V = 0 (a constant one) leaves the stage with N = 0, vb = 0: it takes nothing out of U and ba.
 __global__ void k_marg_lm_prepare(MargDev md, double* vb) {
   const int l = blockIdx.x * blockDim.x + threadIdx.x;
   if (l >= md.Lm) return;
   const double* V = md.V + 9 * (size_t)l;
+  if (V[0] == 0.0 && V[4] == 0.0 && V[8] == 0.0) {
+    // a constant landmark (every Jl of it is zero, so V, W's columns and bb are exact zeros): N = 0 and vb = 0, stated here and
+    // not left to the 3x3 eigen-solver (a positive semi-definite V with a zero diagonal is zero: the general branch below
+    // gives the same N)
+    for (int a = 0; a < 3; ++a) vb[3 * l + a] = 0.0;
+    for (int k = 0; k < 9; ++k) md.V[9 * (size_t)l + k] = 0.0;   // N
+    return;
+  }
   double pb[3];
   for (int a = 0; a < 3; ++a) pb[a] = (V[a * 4] > 1.0e-9) ? sqrt(V[a * 4]) : 1.0e-3;
   double Vs[9];
@@ -1241,7 +1250,11 @@ int Window::applyMarginalizationStrategy(size_t numKeyframes, size_t numImuFrame
   for (const auto& kv : blocks_)
     if (kv.second.lock != 0)
       throw std::runtime_error("applyMarginalizationStrategy: a pose block on a reduced manifold (Pose3d / Pose4d / Pose2d) is in the window");
-  if (numLandmarkPriors_ > 0 || numFixedLandmarks_ > 0) {
+  // A constant landmark is marginalised like any other (the policy loop of Estimator.cpp:671-766 never asks): its linearised
+  // observations enter the job with the negative weight, so their landmark Jacobian is zero (MarginalizationError.cpp:156 gives a
+  // fixed block zero columns, :343 / :367 skip it).  Landmark-sharded handles keep refusing it.
+  const bool refuseFixedLm = numFixedLandmarks_ > 0 && (world_ > 1 || rcclComm_ != nullptr);
+  if (numLandmarkPriors_ > 0 || refuseFixedLm) {
     // Landmarks that carry a HomogeneousPointError stay out of the marginalisation: the reference's policy loop assumes
     // every residual of a landmark is a ReprojectionError (Estimator.cpp:689-698) and never meets one, because Estimator
     // adds none.  Observed from a frame that is about to leave, such a landmark cannot be handled: refuse before anything
@@ -1253,10 +1266,12 @@ int Window::applyMarginalizationStrategy(size_t numKeyframes, size_t numImuFrame
       else kept++;
     }
     for (const auto& kv : landmarks_) {
-      if (kv.second.priors.empty() && !kv.second.fixed) continue;
+      if (kv.second.priors.empty() && !(refuseFixedLm && kv.second.fixed)) continue;
       for (const Observation& o : kv.second.obs)
         if (std::find(leaving.begin(), leaving.end(), o.poseId) != leaving.end()) {
-          lastError() = "applyMarginalizationStrategy: a landmark with a HomogeneousPointError, or a constant one, is observed from a frame that leaves the window";
+          lastError() = kv.second.priors.empty()
+                            ? "applyMarginalizationStrategy: a constant landmark of a landmark-sharded handle is observed from a frame that leaves the window"
+                            : "applyMarginalizationStrategy: a landmark with a HomogeneousPointError is observed from a frame that leaves the window";
           return -1;
         }
     }
@@ -1281,7 +1296,7 @@ int Window::applyMarginalizationStrategy(size_t numKeyframes, size_t numImuFrame
     ++rit;
   }
   // the job: residuals to linearise (copied out of the graph as they are removed) and blocks to marginalise
-  struct JobObs { Observation o; uint64_t lmId, extId; double S[3]; };   // S: the square-root information of a general observation (o.general)
+  struct JobObs { Observation o; uint64_t lmId, extId; double S[3]; bool lmFixed; };   // S: the square-root information of a general observation (o.general)
   std::vector<Factor> jobFactors;
   std::vector<JobObs> jobObs;
   std::vector<uint64_t> toMarginalize;
@@ -1344,7 +1359,7 @@ int Window::applyMarginalizationStrategy(size_t numKeyframes, size_t numImuFrame
   bool landmarksDone = false;
   // The job's observation tables come out of the device-resident CSR when it mirrors the graph as it is now (nothing was
   // added or removed since the last solve); otherwise they are assembled here from the records the policy removes.
-  const bool deviceJob = residentValid_ && residentUsed_ && addLog_.empty() && remLog_.empty() && setLog_.empty() && res_.N == (int)numObs_;
+  const bool deviceJob = residentValid_ && residentUsed_ && addLog_.empty() && remLog_.empty() && setLog_.empty() && constLog_.empty() && res_.N == (int)numObs_;
   ++pathCounters_[deviceJob ? 2 : 3];
   if (!deviceJob) syncLandmarks();   // the linearisation points of the marginalised landmarks are read from the host graph
   std::vector<unsigned char> poseClass;
@@ -1412,7 +1427,7 @@ int Window::applyMarginalizationStrategy(size_t numKeyframes, size_t numImuFrame
       const double tl1 = nowSec();
       for (int h : cand) {
         Landmark& lm = *lmByHandle_[h];
-        if (!lm.priors.empty() || lm.fixed) continue;   // see the guard at the top
+        if (!lm.priors.empty() || (refuseFixedLm && lm.fixed)) continue;   // see the guard at the top
         if (lm.obs.empty()) {
           removed.push_back(lm.id);
           eraseLandmark(lm);
@@ -1445,7 +1460,7 @@ int Window::applyMarginalizationStrategy(size_t numKeyframes, size_t numImuFrame
               if (!deviceJob) lmLin[lm.id].assign(lm.hp, lm.hp + 4);
             }
             if (!deviceJob) {
-              JobObs jo{ob, lm.id, extIdOf(ob), {0.0, 0.0, 0.0}};
+              JobObs jo{ob, lm.id, extIdOf(ob), {0.0, 0.0, 0.0}, lm.fixed};
               if (const ObsInformation* gi = generalInformation(ob)) { jo.S[0] = gi->S[0]; jo.S[1] = gi->S[1]; jo.S[2] = gi->S[2]; }   // (detachObsRecord drops the entry)
               else jo.o.general = 0;
               jobObs.push_back(jo);
@@ -1532,10 +1547,10 @@ int Window::applyMarginalizationStrategy(size_t numKeyframes, size_t numImuFrame
     std::vector<double> hS(generalOn ? 3 * jobObs.size() : 0);
     for (const JobObs& jo : jobObs) {
       hUv.push_back(jo.o.uv[0]); hUv.push_back(jo.o.uv[1]);
-      hW.push_back(obsWeight(jo.o.size));
+      const double w = obsWeight(jo.o.size);
+      hW.push_back(jo.lmFixed ? -w : w);   // (the sign Window::pack() and the resident CSR give a constant landmark's observations)
       if (generalOn) {
         const size_t o = hW.size() - 1, n = jobObs.size();
-        const double w = hW.back();
         hS[o] = jo.o.general ? jo.S[0] : w; hS[n + o] = jo.o.general ? jo.S[1] : 0.0; hS[2 * n + o] = jo.o.general ? jo.S[2] : w;
       }
       const int es = sExt.count(jo.extId) ? sExt.at(jo.extId) : 0;

@@ -55,6 +55,7 @@ __global__ __launch_bounds__(kRebuildThreads) void k_window_rebuild(ResidentArgs
     for (int k = 0; k < 4; ++k) a.lmHp[4 * (size_t)s.h + k] = s.hp[k];
     if (s.setQuality) a.qualH[s.h] = s.quality;
   }
+  for (int i = t; i < a.nConst; i += nt) a.constH[a.consts[i].h] = (unsigned char)a.consts[i].constant;   // (records of one handle carry one value)
   if (a.valuesOnly)
     for (int h = a.Hprev + t; h < a.H; h += nt) a.slotOfHNew[h] = -1;
   for (int i = t; i < a.nRem; i += nt) {
@@ -149,7 +150,9 @@ __global__ __launch_bounds__(kRebuildThreads) void k_window_rebuild(ResidentArgs
       a.uvNew[2 * (size_t)(j + 1)] = u; a.uvNew[2 * (size_t)(j + 1) + 1] = v;
       a.wNew[j + 1] = w; a.hndNew[j + 1] = hn; a.seqNew[j + 1] = sq;
     }
+    const double sign = (a.fixW && a.constH[h]) ? -1.0 : 1.0;
     for (int o = beg; o < end; ++o) {
+      if (a.fixW) a.wNew[o] = copysign(a.wNew[o], sign);   // the magnitude stays: constant -> variable brings the weight back
       const uint32_t hn = a.hndNew[o];
       const int ps = a.poseSlotOfH[hn & 0xfff], es = a.extSlotOfH[(hn >> 12) & 0xfff];
       if (ps < 0 || es < 0) atomicOr(&err, 16);   // (reported at the end; the record stays addressable: slot 0)

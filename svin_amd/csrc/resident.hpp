@@ -7,11 +7,12 @@
 // and ONE single-workgroup kernel rebuilds the CSR in place of Window::pack()'s host pass and full upload:
 //
 //   phase 0  tombstones (a removed observation is looked up in its landmark's segment of the old CSR), per-landmark
-//            counts, landmark points set by the host
+//            counts, landmark points and constant flags set by the host
 //   phase 1  exclusive scan over the landmark handles: CSR slot of every landmark that still has observations, lmPtr
 //   phase 2  surviving observations keep their order inside their landmark; the new ones follow in insertion order
 //   phase 3  packed (pose slot | extrinsics slot | camera) indices from the stable block handles through this frame's
-//            slot tables, landmark points gathered by slot, per-chunk pose ordering for the dense Schur kernels
+//            slot tables, landmark points gathered by slot, the sign of the weights of constant landmarks, per-chunk pose
+//            ordering for the dense Schur kernels
 //
 // Landmarks are addressed by a HANDLE (their creation number, renumbered in id order when the handle space has become
 // sparse); the CSR lists the landmarks with at least one observation in handle order, the observations of a landmark in
@@ -38,6 +39,7 @@ struct WinAdd {          // a new observation (Estimator::addObservation)
 };
 struct WinRem { int lmH; uint32_t seq; };                 // a removed observation
 struct WinLmSet { int h, setQuality; double hp[4]; double quality; };   // new landmark / Estimator::setLandmark
+struct WinLmConst { int h, constant; };                   // Map::setParameterBlockConstant / Variable on a landmark: the flag as the graph holds it now
 
 struct ResidentArgs {
   int nAdd, nRem, nSet, H;        // delta sizes; handles in use: [0, H)
@@ -47,6 +49,12 @@ struct ResidentArgs {
                                   // "new" name the same set), only landmark points, slot-packed indices and the order are refreshed;
                                   // handles [Hprev, H) are new landmarks without observations
   const WinAdd* adds; const WinRem* rems; const WinLmSet* sets;
+  // Constant landmarks: one byte per handle (constH) that lives on the device like the landmark points, changed by the records of
+  // this flush.  The CSR's weight carries the flag as its SIGN, the way Window::pack() writes it: copysign(|w|, -1) for an
+  // observation of a constant landmark, |w| otherwise (kernels.hip evalReprojBlock turns a negative weight into a zero landmark
+  // Jacobian).  fixW: the window holds a constant landmark or a flag changed -- only then phase 3 touches the weights at all.
+  int nConst, fixW;
+  const WinLmConst* consts; unsigned char* constH;
   // old CSR (read) / new CSR (written): the two sets take turns
   const int* lmPtrOld; const int* handleOfSlotOld; const int* slotOfHOld;
   const double* uvOld; const double* wOld; const uint32_t* hndOld; const uint32_t* seqOld; const int* obsLmOld;

@@ -1150,9 +1150,14 @@ int Window::setParameterBlockConstant(uint64_t id, bool constant) {
     uint64_t hnd = 0;
     if (!lmIndex_.find(id, &hnd)) return 0;
     // a constant landmark (okvis::Estimator never makes one; Map-level callers and the reference's TestMap do): its observations
-    // are packed with a negative weight, which the evaluation turns into a zero landmark Jacobian.  Such windows take the host path.
+    // are packed with a negative weight, which the evaluation turns into a zero landmark Jacobian.  The device-resident window
+    // learns about the flag with the next flush (resident.hpp: WinLmConst).
     Landmark& lm = *lmByHandle_[(size_t)hnd];
-    if (lm.fixed != constant) { lm.fixed = constant; numFixedLandmarks_ += constant ? 1 : -1; }
+    if (lm.fixed != constant) {
+      lm.fixed = constant;
+      numFixedLandmarks_ += constant ? 1 : -1;
+      if (residentValid_) constLog_.push_back(WinLmConst{lm.handle, constant ? 1 : 0});
+    }
     return 1;
   }
   b->fixed = constant;
@@ -1450,13 +1455,13 @@ void Window::waitIdle() {
 // ------------------------------------------------------------------------------------------ device-resident window
 bool Window::useResident() const {   // (called by pack() once the state tables are known)
   const bool forceHost = optOn(kOptHostPack);
-  return packMode_ == 0 && !forceHost && world_ <= 1 && rcclComm_ == nullptr && numLandmarkPriors_ == 0 && numFixedLandmarks_ == 0 &&
+  return packMode_ == 0 && !forceHost && world_ <= 1 && rcclComm_ == nullptr && numLandmarkPriors_ == 0 &&
          obsInfo_.empty() && poseIds_.size() <= (size_t)kResidentPoseCap;   // (a general information matrix: the host packs obsS)
 }
 void Window::invalidateResident() {
   syncLandmarks();
   residentValid_ = false;
-  addLog_.clear(); remLog_.clear(); setLog_.clear();
+  addLog_.clear(); remLog_.clear(); setLog_.clear(); constLog_.clear();
   ++epoch_;
 }
 // Handles are creation numbers and are never re-used, so the per-handle tables grow with the landmarks ever created.  When
@@ -1530,10 +1535,11 @@ void Window::flushResident(hipStream_t s, bool wantOrder, std::vector<StagedCopy
   const bool full = !residentValid_;
   if (full) {
     if ((size_t)nextLmHandle_ > std::max<size_t>(4096, 2 * landmarks_.size())) renumberLandmarkHandles();
-    addLog_.clear(); remLog_.clear(); setLog_.clear();
+    addLog_.clear(); remLog_.clear(); setLog_.clear(); constLog_.clear();
     ++epoch_;
     for (Landmark* lm : lmByHandle_) {
       if (!lm) continue;
+      if (lm->fixed) constLog_.push_back(WinLmConst{lm->handle, 1});   // (the flags come from the graph: the table below starts from zero)
       WinLmSet st;
       st.h = lm->handle; st.setQuality = 1; st.quality = lm->quality;
       std::memcpy(st.hp, lm->hp, sizeof(st.hp));
@@ -1558,7 +1564,9 @@ void Window::flushResident(hipStream_t s, bool wantOrder, std::vector<StagedCopy
   R.cnt.growKeep(Hc, R.H, s); R.addsH.growKeep(Hc, R.H, s); R.addCur.growKeep(Hc, R.H, s);
   R.lmHp.growKeep(4 * Hc, 4 * (size_t)R.H, s); R.qualH.growKeep(Hc, R.H, s);
   R.slotOfH[cur].growKeep(Hc, R.H, s);
+  R.constH.growKeep(Hc, R.H, s);
   if (full) {
+    HIP_OK(hipMemsetAsync(R.constH.p, 0, R.constH.cap, s));
     HIP_OK(hipMemsetAsync(R.cnt.p, 0, sizeof(int) * R.cnt.cap, s));
     HIP_OK(hipMemsetAsync(R.addsH.p, 0, sizeof(int) * R.addsH.cap, s));
     HIP_OK(hipMemsetAsync(R.addCur.p, 0, sizeof(int) * R.addCur.cap, s));
@@ -1574,7 +1582,13 @@ void Window::flushResident(hipStream_t s, bool wantOrder, std::vector<StagedCopy
     buf.reserve(std::max<size_t>(host.size() + 16 / sizeof(T) + 1, 1));
     if (!host.empty()) pending.push_back({host.data(), sizeof(T) * host.size(), buf.p});
   };
-  stage(R.adds, addLog_); stage(R.rems, remLog_); stage(R.sets, setLog_);
+  // a landmark whose flag went back and forth since the last flush has several records: all of them carry what the graph says now
+  // (the kernel handles the records in parallel); a landmark erased since keeps its record, its handle is never read again
+  for (WinLmConst& c : constLog_) {
+    const Landmark* lm = lmByHandle_[(size_t)c.h];
+    c.constant = (lm && lm->fixed) ? 1 : 0;
+  }
+  stage(R.adds, addLog_); stage(R.rems, remLog_); stage(R.sets, setLog_); stage(R.consts, constLog_);
   if (!resStatus_) {
     HIP_OK(hipHostMalloc(reinterpret_cast<void**>(&resStatus_), 64, hipHostMallocMapped));
     *resStatus_ = 0;
@@ -1585,6 +1599,8 @@ void Window::flushResident(hipStream_t s, bool wantOrder, std::vector<StagedCopy
   ra.Nold = R.N; ra.Lold = R.L; ra.Nnew = (int)N; ra.Lnew = (int)L;
   ra.wantOrder = wantOrder ? 1 : 0;
   ra.adds = R.adds.p; ra.rems = R.rems.p; ra.sets = R.sets.p;
+  ra.nConst = (int)constLog_.size(); ra.consts = R.consts.p; ra.constH = R.constH.p;
+  ra.fixW = (numFixedLandmarks_ > 0 || !constLog_.empty()) ? 1 : 0;
   ra.lmPtrOld = R.lmPtr[cur].p; ra.handleOfSlotOld = R.handleOfSlot[cur].p; ra.slotOfHOld = R.slotOfH[cur].p;
   ra.uvOld = R.uv[cur].p; ra.wOld = R.w[cur].p; ra.hndOld = R.hnd[cur].p; ra.seqOld = R.seq[cur].p; ra.obsLmOld = R.obsLm[cur].p;
   ra.obsLm = R.obsLm[nxt].p;
@@ -1741,7 +1757,7 @@ void Window::pack(bool solveFollows) {
   flushStaged(pending, s);
   if (solveFollows && a.resident) HIP_OK(hipEventRecord(evUploaded_, s));   // (the side stream of the early IMU pre-integration waits for the tables)
   if (a.resident) {
-    addLog_.clear(); remLog_.clear(); setLog_.clear();   // (copied into the staged block by flushStaged)
+    addLog_.clear(); remLog_.clear(); setLog_.clear(); constLog_.clear();   // (copied into the staged block by flushStaged)
     ++epoch_;
     ra.nPoseSlots = (int)poseIds_.size();
     ra.obsIdx = dObsIdx_.p; ra.lm = dLm_.p; ra.obsOrder = dObsOrder_.p;

@@ -349,6 +349,7 @@ class Window {
                 double* cost);
   void waitIdle();
   const long long* pathCounters() const { return pathCounters_; }
+  void landmarkHandles(int32_t out[2]) const { out[0] = nextLmHandle_; out[1] = (int32_t)landmarks_.size(); }
   int debugReducedSolve(double mu, double* y, int capD, bool fuseFinalize = false);
   int debugPeekSolverScratch(uint64_t off, uint64_t count, double* out);
   // one trust-region iteration with everything the step is made of read back (window.cpp); the arrays may be null
@@ -466,6 +467,7 @@ class Window {
   std::vector<WinAdd> addLog_;
   std::vector<WinRem> remLog_;
   std::vector<WinLmSet> setLog_;
+  std::vector<WinLmConst> constLog_;   // landmarks whose constant flag was set since the last flush
   uint32_t epoch_ = 1;         // identifies the add log an Observation::pendIdx refers to
   int packMode_ = 0;
   bool residentValid_ = false; // the device holds the window as of the last flush; the logs describe what changed since
@@ -482,10 +484,11 @@ class Window {
     DevBuf<double> uv[2], w[2], lmHp, qualH;
     DevBuf<uint32_t> hnd[2], seq[2];
     DevBuf<int> lmPtr[2], handleOfSlot[2], slotOfH[2], obsLm[2], cnt, addsH, addCur, poseSlotOfH, extSlotOfH, margScratch;
-    DevBuf<unsigned char> live, poseClass;
+    DevBuf<unsigned char> live, poseClass, constH;
     DevBuf<WinAdd> adds;
     DevBuf<WinRem> rems;
     DevBuf<WinLmSet> sets;
+    DevBuf<WinLmConst> consts;
     int cur = 0, N = 0, L = 0, H = 0;
   };
   mutable Resident res_;

@@ -56,7 +56,7 @@ EXPORTS = [
     "svin_ba_set_camera_sensor_states", "svin_ba_set_landmark", "svin_ba_num_frames", "svin_ba_num_landmarks",
     "svin_ba_current_keyframe_id", "svin_ba_current_frame_id", "svin_ba_frame_id_by_age", "svin_ba_is_keyframe",
     "svin_ba_is_in_imu_window", "svin_ba_frame_ids", "svin_ba_landmark_ids", "svin_ba_imu_propagation",
-    "svin_ba_eval_reprojection", "svin_ba_observation_ids", "svin_ba_eval_factors", "svin_ba_linearize", "svin_ba_debug_reduced_solve", "svin_ba_debug_reduced_solve_ex", "svin_ba_debug_trust_region_step", "svin_ba_debug_set_switch", "svin_ba_debug_set_option", "svin_ba_debug_get_option", "svin_ba_debug_sym_eig", "svin_ba_get_path_counters", "svin_ba_wait_idle", "svin_ba_debug_peek_solver_scratch",
+    "svin_ba_eval_reprojection", "svin_ba_observation_ids", "svin_ba_eval_factors", "svin_ba_linearize", "svin_ba_debug_reduced_solve", "svin_ba_debug_reduced_solve_ex", "svin_ba_debug_trust_region_step", "svin_ba_debug_set_switch", "svin_ba_debug_set_option", "svin_ba_debug_get_option", "svin_ba_debug_sym_eig", "svin_ba_get_path_counters", "svin_ba_debug_landmark_handles", "svin_ba_wait_idle", "svin_ba_debug_peek_solver_scratch",
     "svin_ba_get_prior", "svin_ba_describe_block", "svin_ba_bench_jacobian_eval", "svin_ba_bench_jacobian_eval_b2b", "svin_ba_set_pack_mode", "svin_ba_debug_csr", "svin_ba_residual_info",
     "svin_ba_map_add_parameter_block", "svin_ba_set_parameter_block", "svin_ba_map_remove_parameter_block", "svin_ba_map_add_pose_error",
     "svin_ba_map_add_speed_and_bias_error", "svin_ba_map_add_relative_pose_error", "svin_ba_map_add_reprojection_error",
@@ -172,6 +172,7 @@ def load_library():
     sig("svin_ba_debug_get_option", i32, C.c_char_p, pi32)
     sig("svin_ba_debug_sym_eig", i32, i32, pd, pd, pd, pd)
     sig("svin_ba_get_path_counters", i32, vp, C.POINTER(C.c_int64))
+    sig("svin_ba_debug_landmark_handles", i32, vp, pi32)
     sig("svin_ba_wait_idle", i32, vp)
     sig("svin_ba_debug_peek_solver_scratch", i32, vp, u64, u64, pd)
     sig("svin_ba_get_prior", i32, vp, pd, pd, pd, pd, pu64, pi32, pi32, pi32, i32)
@@ -830,6 +831,12 @@ class Estimator:
         self._check(self.L.svin_ba_get_path_counters(self.h, out), "path_counters")
         return dict(resident_solves=out[0], host_pack_solves=out[1], device_gathered_marginalisations=out[2],
                     host_assembled_marginalisations=out[3])
+
+    def landmark_handles(self):
+        """(handle range in use, landmarks in the graph): the range shrinks to the landmark count when the handles are renumbered"""
+        out = (C.c_int32 * 2)()
+        self._check(self.L.svin_ba_debug_landmark_handles(self.h, out), "landmark_handles")
+        return int(out[0]), int(out[1])
 
     @staticmethod
     def debug_sym_eig(A):
