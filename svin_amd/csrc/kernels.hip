@@ -153,8 +153,11 @@ extern "C" void svin_debug_trace(unsigned long long* out, int reset) {
   (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_trace), 128 * 8);
 }
 #define TRACE(k) tracePoint(k)
+// stamp once the value v has arrived (the empty asm makes the wave wait for the load behind it)
+#define TRACE_AFTER(k, v) do { asm volatile("" ::"v"(v)); tracePoint(k); } while (0)
 #else
 #define TRACE(k) ((void)0)
+#define TRACE_AFTER(k, v) ((void)0)
 #endif
 
 // side stream of a solver stream (one per device and stream, created on first use, kept for the life of the process) with the
@@ -2081,10 +2084,33 @@ __global__ __launch_bounds__(256) void k_prior_accumulate(DeviceProblem p) { pri
 static int priorAccBlocks(const DeviceProblem& p) { return priorAccBlockCount(p.priorM, p.ownsCamera != 0); }   // (batch_plan.hpp: shared with the batched extents)
 // ================================================================ K5: normal equations + landmark Schur complement
 // generic small factors: J^T J into S (both triangles), J^T r into gRed/gFull, column norms into hC
-__device__ void factorsAccumulate(const DeviceProblem& p, int f, int* colRow) {
+// STAGED (the factor blocks of k_schur_dense, whose launch brings the LDS): J and r of the factor are copied to LDS with ONE round of
+// loads -- colRow is then followed by kFactorStage doubles -- and the products below read them there; the other callers walk them
+// out of global memory, up to 15 dependent steps per entry.  Same products, same k order, same atomics.
+constexpr int kFactorColRow = 32;                 // ints reserved for colRow (30 used)
+constexpr int kFactorStage = 15 * 30 + 15;        // doubles behind them: J, r
+template <bool STAGED>
+__device__ __forceinline__ void factorsAccumulate(const DeviceProblem& p, int f, int* colRow) {
   const FactorLin& lin = p.linCur[f];
+  double* Js = reinterpret_cast<double*>(colRow + kFactorColRow);
+  double* rs = Js + 15 * 30;
+  double jv0 = 0, jv1 = 0, rv = 0;
+  const int i0 = threadIdx.x, i1 = threadIdx.x + blockDim.x;
+  if (STAGED) {   // addresses that depend on nothing loaded: these requests leave with the scalar loads of m, ncols, dim, off
+    jv0 = lin.J[min(i0, 15 * 30 - 1)];
+    jv1 = lin.J[min(i1, 15 * 30 - 1)];
+    rv = lin.r[min(i0, 14)];
+  }
   const int m = lin.m, nc = lin.ncols;
   const double sc2 = lin.sc * lin.sc;
+  if (STAGED) {
+    if (i0 < m * nc) Js[i0] = jv0;
+    if (i1 < m * nc) Js[i1] = jv1;
+    for (int i = i1 + blockDim.x; i < m * nc; i += blockDim.x) Js[i] = lin.J[i];   // (a workgroup of fewer than 225 threads)
+    if (i0 < m) rs[i0] = rv;
+  }
+  auto Jat = [&](int i) { return STAGED ? Js[i] : lin.J[i]; };
+  auto rat = [&](int k) { return STAGED ? rs[k] : lin.r[k]; };
   // column -> reduced row map (colRow: 30 ints of LDS)
   if (threadIdx.x < 30) {
     int c = threadIdx.x, row = -1, base = 0;
@@ -2100,13 +2126,13 @@ __device__ void factorsAccumulate(const DeviceProblem& p, int f, int* colRow) {
     const int ra = colRow[a], rb = colRow[b];
     if (ra < 0 || rb < 0) continue;
     double s = 0;
-    for (int k = 0; k < m; ++k) s += lin.J[k * nc + a] * lin.J[k * nc + b];
+    for (int k = 0; k < m; ++k) s += Jat(k * nc + a) * Jat(k * nc + b);
     s *= sc2;   // the loss corrector (1 without a loss)
     atomicAdd(&p.S[(size_t)ra * p.ldS + rb], s);
     if (a == b) {
       atomicAdd(&p.hC[ra], s);
       double g = 0;
-      for (int k = 0; k < m; ++k) g += lin.J[k * nc + a] * lin.r[k];
+      for (int k = 0; k < m; ++k) g += Jat(k * nc + a) * rat(k);
       g *= sc2;
       atomicAdd(&p.gRed[ra], g);
       atomicAdd(&p.gFull[ra], g);
@@ -2124,7 +2150,7 @@ __global__ __launch_bounds__(256) void k_schur(DeviceProblem p, double mu, int i
   extern __shared__ double smem[];
   if ((int)blockIdx.x >= nSchurBlocks) {
     const int e = blockIdx.x - nSchurBlocks;
-    if (e < nFacBlocks) factorsAccumulate(p, e, reinterpret_cast<int*>(smem));
+    if (e < nFacBlocks) factorsAccumulate<false>(p, e, reinterpret_cast<int*>(smem));
     else priorAccumulateBlock(p, e - nFacBlocks);
     return;
   }
@@ -2392,10 +2418,13 @@ __device__ __forceinline__ void k_schur_dense_body(const DeviceProblem& p, doubl
   const int t = threadIdx.x, b = blockIdx.x;
   if (b >= nChunkBlocks) {
     const int e = b - nChunkBlocks;
-    if (e < nFacBlocks) factorsAccumulate(p, e, reinterpret_cast<int*>(smem));
-    else priorAccumulateBlock(p, e - nFacBlocks);
+    TRACE(24);
+    static_assert((size_t)16 * kDenseLd * sizeof(double) >= kFactorColRow * sizeof(int) + kFactorStage * sizeof(double), "the smallest launch (one tile row) holds a factor's staging area");
+    if (e < nFacBlocks) { factorsAccumulate<true>(p, e, reinterpret_cast<int*>(smem)); TRACE(29); }
+    else { priorAccumulateBlock(p, e - nFacBlocks); TRACE(30); }
     return;
   }
+  TRACE(24);
   SVIN_ARGS(SA(p.lmPtr), SA(p.poseOff), SA(p.rCur), SA(p.JlCur), SA(p.JpCur), SA(p.obsIdx), SA(p.scaleL), SA(p.Vinv), SA(p.bl), SA(p.hL),
             SA(p.slabs), SA(p.scal), SA(p.L), SA(p.N), SA(p.dC), SA(p.nPose), SA(p.anyExtVariable), SA(p.aBlocks), SA(p.dCPose));
   const size_t N = (size_t)p.N;
@@ -2538,6 +2567,7 @@ __device__ __forceinline__ void k_schur_dense_body(const DeviceProblem& p, doubl
     const int l = (t < 256) ? chunk * kDenseLm + grp : p.L;
     if (l < p.L) {
       const int start = p.lmPtr[l], n = p.lmPtr[l + 1] - start;
+      TRACE_AFTER(25, n);
       // everything this lane needs of its first observation (a landmark rarely has more than 16) is requested in ONE round
       // trip: residual, landmark Jacobian, packed indices and the pose Jacobian of the second pass below
       const bool has0 = gl < n;
@@ -2554,6 +2584,7 @@ __device__ __forceinline__ void k_schur_dense_body(const DeviceProblem& p, doubl
 #pragma unroll
         for (int k = 0; k < 12; ++k) pjp[k] = p.JpCur[k * N + o0];
       }
+      TRACE_AFTER(26, pjp[11]);
       // V = sum Jl^T Jl, b = sum Jl^T r over the landmark's observations (16 lanes)
       double v00 = 0, v01 = 0, v02 = 0, v11 = 0, v12 = 0, v22 = 0, b0 = 0, b1 = 0, b2 = 0;
       for (int i = gl; i < n; i += 16) {
@@ -2668,6 +2699,7 @@ __device__ __forceinline__ void k_schur_dense_body(const DeviceProblem& p, doubl
       }
     }
     __syncthreads();
+    TRACE(27);
 #ifdef SVIN_SCHUR_TIMING
     const long long qc2 = __builtin_readcyclecounter();
     qdL += qc2 - qc1;
@@ -2781,6 +2813,7 @@ __device__ __forceinline__ void k_schur_dense_body(const DeviceProblem& p, doubl
       }
     }
   }
+  TRACE(28);
 #ifdef SVIN_SCHUR_TIMING
   if (b == 0 && t == 0) {
     double* dbg = p.partial + (size_t)15 * 4096 + 16;
@@ -3608,6 +3641,7 @@ constexpr int kSlabParts = 16;
 __device__ __forceinline__ void k_reduce_slabs_body(const DeviceProblem& p) {
   __shared__ double part[256];
   SVIN_ARGS(SA(p.slabs), SA(p.S), SA(p.gRed), SA(p.gFull), SA(p.hC), SA(p.nSlabs), SA(p.dC), SA(p.ldS));
+  TRACE(31);
   const int dC = p.dC;
   const size_t slabSize = (size_t)dC * dC + 3 * dC;
   const int e = threadIdx.x & 15, q = threadIdx.x >> 4;
@@ -3641,6 +3675,7 @@ __device__ __forceinline__ void k_reduce_slabs_body(const DeviceProblem& p) {
   }
   part[threadIdx.x] = (s0 + s1) + (s2 + s3);
   __syncthreads();
+  TRACE(32);
   if (q == 0 && work) {
     double s = 0;
 #pragma unroll
@@ -3655,6 +3690,7 @@ __device__ __forceinline__ void k_reduce_slabs_body(const DeviceProblem& p) {
       else p.hC[v - 2 * dC] += s;
     }
   }
+  TRACE(33);
 }
 __global__ __launch_bounds__(256) void k_reduce_slabs(DeviceProblem p) { k_reduce_slabs_body(p); }
 // (batched form: blockIdx.y = the window of the batch, its problem and trust-region scalars from the slot table)
@@ -3697,7 +3733,7 @@ void launchFinalizeNormalEquations(const DeviceProblem& p, double mu, bool initS
 }
 __global__ __launch_bounds__(256) void k_factors_only(DeviceProblem p, int nFacBlocks) {
   __shared__ int colRow[30];
-  if ((int)blockIdx.x < nFacBlocks) factorsAccumulate(p, blockIdx.x, colRow);
+  if ((int)blockIdx.x < nFacBlocks) factorsAccumulate<false>(p, blockIdx.x, colRow);
   else priorAccumulateBlock(p, blockIdx.x - nFacBlocks);
 }
 // one workgroup per (segment, 16 KB slice): 16-byte copies from the staged block to the arrays' own allocations
