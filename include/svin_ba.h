@@ -468,6 +468,13 @@ int svin_ba_debug_reduced_solve(svin_ba* h, double mu, double* y, int cap_d);
 /* the same with the choice svin_ba_optimize makes: fuse_finalize != 0 applies the metric and the damping inside the solver's
  * load phase (the fused form every trust-region iteration runs), 0 is svin_ba_debug_reduced_solve. */
 int svin_ba_debug_reduced_solve_ex(svin_ba* h, double mu, int fuse_finalize, double* y, int cap_d);
+/* read-only: what the LAST build of the normal equations (svin_ba_linearize, svin_ba_debug_reduced_solve, svin_ba_optimize) left on
+ * the device beside S and g -- g_full and h_c (d each; after svin_ba_linearize as its finalising pass leaves them), per landmark
+ * in device order Vinv (6), b_l (3), h_l (3), scale_l (3) -- and how often each IMU factor has re-integrated on the device so far
+ * (ImuError::redo, in the order of svin_ba_eval_factors' IMU factors).  Launches nothing.  sizes3 = d, L, number of IMU factors;
+ * an array whose capacity is too small (or that is NULL) is not written.  Returns 1. */
+int svin_ba_debug_build_arrays(svin_ba* h, double* g_full, double* h_c, int cap_d, double* v_inv, double* b_l, double* h_l,
+                               double* scale_l, int cap_landmarks, int32_t* imu_redo_counters, int cap_imu, int32_t* sizes3);
 /* ONE trust-region iteration on a fresh linearisation with the launches svin_ba_optimize issues -- evaluation, build with damping
  * mu (metric recomputed), reduced solve, post-solve pass, dogleg step with trust-region radius `radius`, candidate evaluation --
  * and what the step is made of (tests of the post-solve pass and the step).  form: 0 what svin_ba_optimize chooses for this window,

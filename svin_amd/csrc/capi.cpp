@@ -578,6 +578,12 @@ int svin_ba_debug_reduced_solve_ex(svin_ba* h, double mu, int fuse_finalize, dou
   GUARD_BEGIN return win(h).debugReducedSolve(mu, y, cap_d, fuse_finalize != 0);
   GUARD_END(SVIN_ERR_DEVICE)
 }
+int svin_ba_debug_build_arrays(svin_ba* h, double* g_full, double* h_c, int cap_d, double* v_inv, double* b_l, double* h_l,
+                               double* scale_l, int cap_landmarks, int32_t* imu_redo_counters, int cap_imu, int32_t* sizes3) {
+  if (!h || !sizes3) return SVIN_ERR_INVALID_ARG;
+  GUARD_BEGIN return win(h).debugBuildArrays(g_full, h_c, cap_d, v_inv, b_l, h_l, scale_l, cap_landmarks, imu_redo_counters, cap_imu, sizes3);
+  GUARD_END(SVIN_ERR_DEVICE)
+}
 int svin_ba_debug_trust_region_step(svin_ba* h, double mu, double radius, int form, int commit, double* scalars38, double* y_c,
                                     double* v_c, int cap_d, double* y_l, double* v_l, double* landmark_candidates,
                                     uint64_t* landmark_ids, int cap_landmarks, uint64_t* block_ids, int32_t* block_kinds,

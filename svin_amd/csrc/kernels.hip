@@ -444,6 +444,137 @@ struct LmDefer {   // passed BY VALUE (through a pointer it lands in scratch and
   double* stepPartial = nullptr;
   double* xPartial = nullptr;
 };
+// A value the compiler may not look through: what is computed from it, and what it is computed from, are compiled apart.  The
+// functions below are inlined into two kernels whose results must agree bit for bit (k_eval_all's reprojection blocks, the chunk
+// blocks of k_eval_build).  Floating-point contraction runs over whatever expression the inlined code has become in its
+// surroundings -- a product feeding a sum of the caller, an output the caller does not use -- so the inputs and outputs of the
+// shared arithmetic are closed off and each of the two copies is compiled as the same expression.
+__device__ __forceinline__ void fpFence(double& x) { asm volatile("" : "+v"(x)); }
+// x1 y1 + x2 y2 as the compiler contracts that expression where nothing surrounds it -- fma(x1, y1, x2 * y2) -- and closed off.
+// The chunk blocks of k_eval_build spell their per-observation sums with it: the loops around them differ from those of
+// k_schur_dense (which peels the loaded first observation off), and with them what the contraction makes of `acc += a b + c d`.
+__device__ __forceinline__ double dot2Fenced(double x1, double y1, double x2, double y2) {
+  double t = x2 * y2;
+  fpFence(t);
+  t = __builtin_fma(x1, y1, t);
+  fpFence(t);
+  return t;
+}
+// the landmark half of the fused step for one landmark, x_cand = x + (cg v_l - cn y_l): the arithmetic of retractItem.  ONE
+// function for the evaluation's reprojection blocks and the chunk blocks of k_eval_build, which form the same candidate
+__device__ __forceinline__ void lmDeferredStep(const double (&hpw)[4], double cg, double cn, const double* __restrict__ vL,
+                                               const double* __restrict__ yL, int lmi, double (&xo)[4]) {
+#pragma unroll
+  for (int k = 0; k < 3; ++k) xo[k] = hpw[k] + (cg * vL[3 * lmi + k] - cn * yL[3 * lmi + k]);
+  xo[3] = hpw[3] + 0.0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) fpFence(xo[k]);
+}
+// the tables every reprojection residual reads, staged in LDS: poses, extrinsics, camera models, loss table
+// ((nPose + nExt) * 7 doubles + nCam camera models + 2 kMaxLosses doubles); the caller's barrier follows
+struct ReprojTables { double* sPose; double* sExt; CameraModel* sCam; double* sLoss; };
+template <bool ROBUST>
+__device__ __forceinline__ ReprojTables stageReprojTables(double* smem, int nPose, int nExt, int nCam, const double* __restrict__ pose,
+                                                          const double* __restrict__ ext, const CameraModel* __restrict__ cams,
+                                                          const double* __restrict__ lossTab) {
+  ReprojTables tb;
+  tb.sPose = smem;                           // nPose*7
+  tb.sExt = tb.sPose + nPose * 7;            // nExt*7
+  tb.sCam = reinterpret_cast<CameraModel*>(tb.sExt + nExt * 7);  // nCam
+  tb.sLoss = reinterpret_cast<double*>(tb.sCam + nCam);          // 2 kMaxLosses (lossTab only: kLossTabBytes)
+  for (int i = threadIdx.x; i < nPose * 7; i += blockDim.x) tb.sPose[i] = pose[i];
+  for (int i = threadIdx.x; i < nExt * 7; i += blockDim.x) tb.sExt[i] = ext[i];
+  {
+    const double* src = reinterpret_cast<const double*>(cams);
+    double* dst = reinterpret_cast<double*>(tb.sCam);
+    for (int i = threadIdx.x; i < nCam * (int)(sizeof(CameraModel) / 8); i += blockDim.x) dst[i] = src[i];
+  }
+  if (ROBUST && lossTab)
+    for (int i = threadIdx.x; i < 2 * kMaxLosses; i += blockDim.x) tb.sLoss[i] = lossTab[i];
+  return tb;
+}
+// One observation `i` at the landmark `hpw`: residual and Jacobians as every consumer of the solve takes them -- square-root
+// information, loss corrector and the zero landmark Jacobian of a constant landmark applied -- and its share of the cost.
+// Shared by the evaluation's reprojection blocks, which store the values, and the chunk blocks of k_eval_build, which eliminate
+// the landmark from them at once: the two must agree bit for bit.
+template <bool ROBUST, bool WITH_EXT, bool GENERAL>
+__device__ __forceinline__ double reprojObservation(uint32_t idx, double2 uv, double wRaw, const double (&hpwIn)[4], size_t i, size_t stride,
+                                                    const ReprojTables& tb, const double* __restrict__ lmPrior,
+                                                    const double* __restrict__ lossTab, const double* __restrict__ obsS,
+                                                    double (&rr)[2], double (&jp)[12], double (&jl)[6], double (&je)[12]) {
+  double hpw[4] = {hpwIn[0], hpwIn[1], hpwIn[2], hpwIn[3]};
+#pragma unroll
+  for (int k = 0; k < 4; ++k) fpFence(hpw[k]);
+  fpFence(uv.x); fpFence(uv.y); fpFence(wRaw);
+  const int ps = idx & 0xfff, es = (idx >> 12) & 0xfff, cs = (idx >> 24) & 0xf;
+  // a NEGATIVE weight marks an observation of a landmark that is held constant (Map::setParameterBlockConstant on a
+  // HomogeneousPointParameterBlock, TestMap.cpp:93): the residual and the pose / extrinsics Jacobians are the usual ones, the
+  // landmark Jacobian is written as zero -- V_l, b_l and the landmark's columns of the Schur complement then vanish exactly and
+  // its step is zero, without a second code path in any kernel downstream
+  const bool lmConstant = wRaw < 0.0;
+  const double w = fabs(wRaw);
+  double cost;
+  const bool isPrior = cs == kPriorCam;
+  if (isPrior) {
+    // HomogeneousPointError (HomogeneousPointError.cpp:77-117) as two pseudo-observations of its landmark: e = lm - meas
+    // (first three components), r = S e with S the upper-triangular square-root information; uv = (index into the
+    // prior table, part): part 0 carries rows 0 and 1 of S, part 1 row 2 and a zero row.  No loss function.
+    const double* pr = lmPrior + 12 * (int)uv.x;
+    const bool second = uv.y != 0.0;
+    const double e0 = hpw[0] - pr[0], e1 = hpw[1] - pr[1], e2 = hpw[2] - pr[2];
+    const double* Sa = pr + 3 + (second ? 6 : 0);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { jl[k] = Sa[k]; jl[3 + k] = second ? 0.0 : pr[6 + k]; }
+    rr[0] = jl[0] * e0 + jl[1] * e1 + jl[2] * e2;
+    rr[1] = jl[3] * e0 + jl[4] * e1 + jl[5] * e2;
+#pragma unroll
+    for (int k = 0; k < 12; ++k) { jp[k] = 0.0; je[k] = 0.0; }
+  } else if (GENERAL && obsS) {
+    reprojEval(tb.sCam[cs], tb.sPose + ps * 7, hpw, tb.sExt + es * 7, uv.x, uv.y, obsS[i], obsS[stride + i], obsS[2 * stride + i], rr, jp, jl, je);
+  } else {
+    reprojEval(tb.sCam[cs], tb.sPose + ps * 7, hpw, tb.sExt + es * 7, uv.x, uv.y, w, rr, jp, jl, je);
+  }
+  const double s = rr[0] * rr[0] + rr[1] * rr[1];
+  if (ROBUST && !isPrior) {
+    // Ceres Corrector: rho'' <= 0 for every loss the window takes -> residual and Jacobian scale by sqrt(rho').  Without a loss
+    // table every observation has CauchyLoss(1); with one, the selector in bits 28-31 of the packed index picks its entry
+    double rho0, rho1, rho2;
+    if (lossTab) {
+      const int sel = (int)(idx >> 28);
+      residualLoss((int)tb.sLoss[2 * sel], tb.sLoss[2 * sel + 1], s, rho0, rho1);
+    } else {
+      cauchyLoss(s, rho0, rho1, rho2);
+    }
+    cost = 0.5 * rho0;
+    const double sc = sqrt(rho1);
+    rr[0] *= sc; rr[1] *= sc;
+#pragma unroll
+    for (int k = 0; k < 12; ++k) jp[k] *= sc;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) jl[k] *= sc;
+    if (WITH_EXT) {
+#pragma unroll
+      for (int k = 0; k < 12; ++k) je[k] *= sc;
+    }
+  } else {
+    cost = 0.5 * s;
+  }
+  if (lmConstant) {
+#pragma unroll
+    for (int k = 0; k < 6; ++k) jl[k] = 0.0;
+  }
+  // every output is used as far as the compiler can tell, in both kernels (the chunk blocks' first pass reads r and Jl only)
+  fpFence(rr[0]); fpFence(rr[1]); fpFence(cost);
+#pragma unroll
+  for (int k = 0; k < 12; ++k) fpFence(jp[k]);
+#pragma unroll
+  for (int k = 0; k < 6; ++k) fpFence(jl[k]);
+  if (WITH_EXT) {
+#pragma unroll
+    for (int k = 0; k < 12; ++k) fpFence(je[k]);
+  }
+  return cost;
+}
 // GENERAL: `obsS` may be set (DeviceProblem::obsS, stride `stride`); the kernels compiled without it never read the pointer
 template <bool ROBUST, bool WITH_EXT, bool GENERAL = false>
 __device__ __forceinline__ void evalReprojBlock(int block, double* smem, double* red, int N, int nPose, int nExt, int nCam,
@@ -456,43 +587,22 @@ __device__ __forceinline__ void evalReprojBlock(int block, double* smem, double*
                                                 const LmDefer df = LmDefer(), const double* __restrict__ lmPrior = nullptr,
                                                 const double* __restrict__ lossTab = nullptr,
                                                 const double* __restrict__ obsS = nullptr) {
-  double* sPose = smem;                      // nPose*7
-  double* sExt = sPose + nPose * 7;          // nExt*7
-  CameraModel* sCam = reinterpret_cast<CameraModel*>(sExt + nExt * 7);  // nCam
-  double* sLoss = reinterpret_cast<double*>(sCam + nCam);               // 2 kMaxLosses (lossTab only: kLossTabBytes)
-  for (int i = threadIdx.x; i < nPose * 7; i += blockDim.x) sPose[i] = pose[i];
-  for (int i = threadIdx.x; i < nExt * 7; i += blockDim.x) sExt[i] = ext[i];
-  {
-    const double* src = reinterpret_cast<const double*>(cams);
-    double* dst = reinterpret_cast<double*>(sCam);
-    for (int i = threadIdx.x; i < nCam * (int)(sizeof(CameraModel) / 8); i += blockDim.x) dst[i] = src[i];
-  }
-  if (ROBUST && lossTab)
-    for (int i = threadIdx.x; i < 2 * kMaxLosses; i += blockDim.x) sLoss[i] = lossTab[i];
+  const ReprojTables tb = stageReprojTables<ROBUST>(smem, nPose, nExt, nCam, pose, ext, cams, lossTab);
   __syncthreads();
   const int i = block * blockDim.x + threadIdx.x;
   double cost = 0, stepSq = 0, xSq = 0;
   if (i < N) {
     const uint32_t idx = obsIdx[i];
-    const int ps = idx & 0xfff, es = (idx >> 12) & 0xfff, cs = (idx >> 24) & 0xf;
     const double2 uv = reinterpret_cast<const double2*>(obsUv)[i];
-    // a NEGATIVE weight marks an observation of a landmark that is held constant (Map::setParameterBlockConstant on a
-    // HomogeneousPointParameterBlock, TestMap.cpp:93): the residual and the pose / extrinsics Jacobians are the usual ones, the
-    // landmark Jacobian is written as zero -- V_l, b_l and the landmark's columns of the Schur complement then vanish exactly and
-    // its step is zero, without a second code path in any kernel downstream
     const double wRaw = obsW[i];
-    const bool lmConstant = wRaw < 0.0;
-    const double w = fabs(wRaw);
     const int lmi = obsLm[i];
     const double4 hp = reinterpret_cast<const double4*>(lm)[lmi];
     double hpw[4] = {hp.x, hp.y, hp.z, hp.w};
     if (df.on) {
-      // the landmark half of the fused step (k_post_solve left it to this kernel): x_cand = x + (cg v_l - cn y_l), the
-      // same arithmetic as retractItem; the lane holding the landmark's first observation stores it and counts the norms
+      // the landmark half of the fused step (k_post_solve left it to this kernel): the lane holding the landmark's first
+      // observation stores it and counts the norms
       double xo[4];
-#pragma unroll
-      for (int k = 0; k < 3; ++k) xo[k] = hpw[k] + (df.cg * df.vL[3 * lmi + k] - df.cn * df.yL[3 * lmi + k]);
-      xo[3] = hpw[3] + 0.0;
+      lmDeferredStep(hpw, df.cg, df.cn, df.vL, df.yL, lmi, xo);
       if (df.lmPtr[lmi] == i) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) { stepSq += (hpw[k] - xo[k]) * (hpw[k] - xo[k]); xSq += hpw[k] * hpw[k]; }
@@ -503,55 +613,7 @@ __device__ __forceinline__ void evalReprojBlock(int block, double* smem, double*
       for (int k = 0; k < 4; ++k) hpw[k] = xo[k];
     }
     double rr[2], jp[12], jl[6], je[12];
-    const bool isPrior = cs == kPriorCam;
-    if (isPrior) {
-      // HomogeneousPointError (HomogeneousPointError.cpp:77-117) as two pseudo-observations of its landmark: e = lm - meas
-      // (first three components), r = S e with S the upper-triangular square-root information; uv = (index into the
-      // prior table, part): part 0 carries rows 0 and 1 of S, part 1 row 2 and a zero row.  No loss function.
-      const double* pr = lmPrior + 12 * (int)uv.x;
-      const bool second = uv.y != 0.0;
-      const double e0 = hpw[0] - pr[0], e1 = hpw[1] - pr[1], e2 = hpw[2] - pr[2];
-      const double* Sa = pr + 3 + (second ? 6 : 0);
-#pragma unroll
-      for (int k = 0; k < 3; ++k) { jl[k] = Sa[k]; jl[3 + k] = second ? 0.0 : pr[6 + k]; }
-      rr[0] = jl[0] * e0 + jl[1] * e1 + jl[2] * e2;
-      rr[1] = jl[3] * e0 + jl[4] * e1 + jl[5] * e2;
-#pragma unroll
-      for (int k = 0; k < 12; ++k) { jp[k] = 0.0; je[k] = 0.0; }
-    } else if (GENERAL && obsS) {
-      reprojEval(sCam[cs], sPose + ps * 7, hpw, sExt + es * 7, uv.x, uv.y, obsS[i], obsS[stride + i], obsS[2 * stride + i], rr, jp, jl, je);
-    } else {
-      reprojEval(sCam[cs], sPose + ps * 7, hpw, sExt + es * 7, uv.x, uv.y, w, rr, jp, jl, je);
-    }
-    const double s = rr[0] * rr[0] + rr[1] * rr[1];
-    if (ROBUST && !isPrior) {
-      // Ceres Corrector: rho'' <= 0 for every loss the window takes -> residual and Jacobian scale by sqrt(rho').  Without a loss
-      // table every observation has CauchyLoss(1); with one, the selector in bits 28-31 of the packed index picks its entry
-      double rho0, rho1, rho2;
-      if (lossTab) {
-        const int sel = (int)(idx >> 28);
-        residualLoss((int)sLoss[2 * sel], sLoss[2 * sel + 1], s, rho0, rho1);
-      } else {
-        cauchyLoss(s, rho0, rho1, rho2);
-      }
-      cost = 0.5 * rho0;
-      const double sc = sqrt(rho1);
-      rr[0] *= sc; rr[1] *= sc;
-#pragma unroll
-      for (int k = 0; k < 12; ++k) jp[k] *= sc;
-#pragma unroll
-      for (int k = 0; k < 6; ++k) jl[k] *= sc;
-      if (WITH_EXT) {
-#pragma unroll
-        for (int k = 0; k < 12; ++k) je[k] *= sc;
-      }
-    } else {
-      cost = 0.5 * s;
-    }
-    if (lmConstant) {
-#pragma unroll
-      for (int k = 0; k < 6; ++k) jl[k] = 0.0;
-    }
+    cost = reprojObservation<ROBUST, WITH_EXT, GENERAL>(idx, uv, wRaw, hpw, (size_t)i, stride, tb, lmPrior, lossTab, obsS, rr, jp, jl, je);
     K1_STORE(&r[i], rr[0]);
     K1_STORE(&r[stride + i], rr[1]);
 #pragma unroll
@@ -1858,10 +1920,10 @@ void launchEvalPrior(const DeviceProblem& p, bool cand, hipStream_t s, bool sumC
 // take tens of microseconds), blocks [F, F + nR) the reprojection residuals with 256 observations each, side by side
 // in one launch, plus one block for the marginalisation prior (hasPrior); the block that finishes last sums the cost
 // (sumCost) and publishes the scalars.
-template <bool WITH_EXT, bool GENERAL>
-__device__ __forceinline__ void k_eval_all_body(const DeviceProblem& p, int cand, int nR, int sumCost, int hasPrior) {
-  __shared__ FactorShared sh;
-  const int F = (int)gridDim.x - nR - hasPrior;
+// (nBlocks: the blocks of the evaluation -- the launch's gridDim.x in k_eval_all; k_eval_build has its chunk blocks behind them)
+template <bool WITH_EXT, bool GENERAL, class NB>
+__device__ __forceinline__ void k_eval_all_body(const DeviceProblem& p, int cand, int nR, int sumCost, int hasPrior, FactorShared& sh, NB nBlocks) {
+  const int F = (int)nBlocks() - nR - hasPrior;
   if ((int)blockIdx.x < F) {
     SVIN_ARGS(SA(p.factors), SA(p.imus), SA(p.linCand), SA(p.linCur), SA(p.poseC), SA(p.pose), SA(p.sbC), SA(p.sb), SA(p.extC), SA(p.ext),
               SA(p.poseOff), SA(p.sbOff), SA(p.extOff), SA(p.partial), SA(p.imuT), SA(p.imuMeas));
@@ -1897,7 +1959,7 @@ __device__ __forceinline__ void k_eval_all_body(const DeviceProblem& p, int cand
   if (sumCost) {
     __shared__ int lastFlag;
     __shared__ double red4[72];
-    if (lastBlockDoneLight(&p.tickets[TK_EVAL], &lastFlag, GridDimX{})) {   // (cost partials and costPrior are cstore()d)
+    if (lastBlockDoneLight(&p.tickets[TK_EVAL], &lastFlag, nBlocks)) {   // (cost partials and costPrior are cstore()d)
       TRACE(19);
       reduceCost(p, nR, F, red4, (cand && p.lmDeferred) ? nR : 0);
       if (threadIdx.x == 0) p.tickets[TK_EVAL] = 0;
@@ -1906,7 +1968,10 @@ __device__ __forceinline__ void k_eval_all_body(const DeviceProblem& p, int cand
   }
 }
 template <bool WITH_EXT, bool GENERAL = false>
-__global__ __launch_bounds__(256) void k_eval_all(DeviceProblem p, int cand, int nR, int sumCost, int hasPrior) { k_eval_all_body<WITH_EXT, GENERAL>(p, cand, nR, sumCost, hasPrior); }
+__global__ __launch_bounds__(256) void k_eval_all(DeviceProblem p, int cand, int nR, int sumCost, int hasPrior) {
+  __shared__ FactorShared sh;
+  k_eval_all_body<WITH_EXT, GENERAL>(p, cand, nR, sumCost, hasPrior, sh, GridDimX{});
+}
 // The slot of this block's window.  The table is written by the host's copy before the launch and by nothing afterwards, so it is
 // read through the CONSTANT address space like the kernel arguments it replaces: every field stays a scalar load the compiler may
 // repeat wherever it likes.  Through a plain global pointer the loads behind the first barrier go through the vector memory path
@@ -2089,9 +2154,9 @@ static int priorAccBlocks(const DeviceProblem& p) { return priorAccBlockCount(p.
 // out of global memory, up to 15 dependent steps per entry.  Same products, same k order, same atomics.
 constexpr int kFactorColRow = 32;                 // ints reserved for colRow (30 used)
 constexpr int kFactorStage = 15 * 30 + 15;        // doubles behind them: J, r
+// (`lin`: the factor's record -- p.linCur[f] for a build of its own, the record the same block has just evaluated in k_eval_build)
 template <bool STAGED>
-__device__ __forceinline__ void factorsAccumulate(const DeviceProblem& p, int f, int* colRow) {
-  const FactorLin& lin = p.linCur[f];
+__device__ __forceinline__ void factorsAccumulateLin(const DeviceProblem& p, const FactorLin& lin, int* colRow) {
   double* Js = reinterpret_cast<double*>(colRow + kFactorColRow);
   double* rs = Js + 15 * 30;
   double jv0 = 0, jv1 = 0, rv = 0;
@@ -2139,6 +2204,9 @@ __device__ __forceinline__ void factorsAccumulate(const DeviceProblem& p, int f,
     }
   }
 }
+
+template <bool STAGED>
+__device__ __forceinline__ void factorsAccumulate(const DeviceProblem& p, int f, int* colRow) { factorsAccumulateLin<STAGED>(p, p.linCur[f], colRow); }
 
 constexpr int kStage = 34;  // doubles staged per observation: Jl 6, Jp 12, Je 12, offP, offE (as double), pad
 
@@ -2411,11 +2479,19 @@ __host__ __device__ constexpr int denseObsBatch(int rows) { return rows <= 128 ?
 // NW: waves per workgroup.  The landmark part always runs on the first 256 threads (16 lanes x 16 landmarks); with NW = 8 the
 // tiles are dealt over twice as many waves (clear, merge, products and slab stores take half as long per wave, and 10 tiles
 // per wave stay in registers where 20 spill).
-template <int MAXT, bool A_MFMA, int NW>
-__device__ __forceinline__ void k_schur_dense_body(const DeviceProblem& p, double mu, int initScale, int nChunkBlocks, int nFacBlocks) {
+// EVAL (the chunk blocks of k_eval_build, fixed extrinsics and A in block copies only): nothing of r / Jp / Jl is loaded -- a lane
+// evaluates the observations of its landmark itself, at the point the launch's evaluation blocks evaluate (`cand`, the deferred
+// landmark step included), with the function they use (reprojObservation); the first observation of a lane is kept in the
+// registers that held the loaded one, those of a longer track are evaluated again in the second pass.  `evalLds` is the LDS the
+// kernel brings (tiles, then the staged tables), `blockBase` the launch's blocks ahead of the chunk blocks.
+template <int MAXT, bool A_MFMA, int NW, bool EVAL = false, bool GENERAL = false>
+__device__ __forceinline__ void k_schur_dense_body(const DeviceProblem& p, double mu, int initScale, int nChunkBlocks, int nFacBlocks,
+                                                   int cand = 0, double* evalLds = nullptr, int blockBase = 0) {
   static_assert(A_MFMA || NW == 4, "the per-wave block copies of A exist for four waves");
-  extern __shared__ double smem[];
-  const int t = threadIdx.x, b = blockIdx.x;
+  static_assert(!EVAL || !A_MFMA, "the evaluating chunk blocks exist for the block-copy form");
+  extern __shared__ double smemDyn[];
+  double* const smem = EVAL ? evalLds : smemDyn;
+  const int t = threadIdx.x, b = EVAL ? (int)blockIdx.x - blockBase : (int)blockIdx.x;
   if (b >= nChunkBlocks) {
     const int e = b - nChunkBlocks;
     TRACE(24);
@@ -2427,6 +2503,9 @@ __device__ __forceinline__ void k_schur_dense_body(const DeviceProblem& p, doubl
   TRACE(24);
   SVIN_ARGS(SA(p.lmPtr), SA(p.poseOff), SA(p.rCur), SA(p.JlCur), SA(p.JpCur), SA(p.obsIdx), SA(p.scaleL), SA(p.Vinv), SA(p.bl), SA(p.hL),
             SA(p.slabs), SA(p.scal), SA(p.L), SA(p.N), SA(p.dC), SA(p.nPose), SA(p.anyExtVariable), SA(p.aBlocks), SA(p.dCPose));
+  if (EVAL)
+    SVIN_ARGS(SA(p.poseC), SA(p.pose), SA(p.extC), SA(p.ext), SA(p.lm), SA(p.lmC), SA(p.cams), SA(p.obsUv), SA(p.obsW), SA(p.vL), SA(p.yL),
+              SA(p.nExt), SA(p.nCam), SA(p.lossTab), SA(p.lmPrior), SA(p.lmDeferred));
   const size_t N = (size_t)p.N;
   const bool WITH_EXT = A_MFMA && p.anyExtVariable != 0;
   const int dC = p.dC, nP = dC / 6;          // reduced 6-blocks (poses, then variable extrinsics)
@@ -2463,6 +2542,10 @@ __device__ __forceinline__ void k_schur_dense_body(const DeviceProblem& p, doubl
   __shared__ int sPoseOff[kDensePoseCap];
   for (int i = t; i < p.nPose && i < kDensePoseCap; i += blockDim.x) sPoseOff[i] = p.poseOff[i];
   const int* poseOffS = sPoseOff;
+  ReprojTables tb = {nullptr, nullptr, nullptr, nullptr};
+  if constexpr (EVAL)   // behind the tiles (an even number of doubles on: the clear below writes pairs)
+    tb = stageReprojTables<true>(smem + ((rows * kDenseLd + (int)extraLds + 1) & ~1), p.nPose, p.nExt, p.nCam, cand ? p.poseC : p.pose,
+                                 cand ? p.extC : p.ext, p.cams, p.lossTab);
   {
     const int nz = rows * kDenseLd + (int)extraLds;   // 16-byte stores: half the LDS instructions of the clear
     for (int i = t; i < (nz >> 1); i += blockDim.x) reinterpret_cast<double2*>(smem)[i] = double2{0.0, 0.0};
@@ -2576,13 +2659,37 @@ __device__ __forceinline__ void k_schur_dense_body(const DeviceProblem& p, doubl
       uint32_t pidx = 0;
 #pragma unroll
       for (int k = 0; k < 12; ++k) pjp[k] = 0;
+      // EVAL: the landmark as the evaluation blocks of this launch see it, and one observation of it evaluated in place
+      double hpw[4] = {0, 0, 0, 0};
+      if constexpr (EVAL) {
+        const bool defer = cand && p.lmDeferred;
+        const double4 hp = reinterpret_cast<const double4*>(defer ? p.lm : (cand ? p.lmC : p.lm))[l];
+        hpw[0] = hp.x; hpw[1] = hp.y; hpw[2] = hp.z; hpw[3] = hp.w;
+        if (defer) {   // (the evaluation block that holds the landmark's first observation stores the same value to lmC)
+          double xo[4];
+          lmDeferredStep(hpw, p.scal->spareA0, p.scal->spareA1, p.vL, p.yL, l, xo);
+#pragma unroll
+          for (int k = 0; k < 4; ++k) hpw[k] = xo[k];
+        }
+      }
+      auto evalObs = [&](size_t o, uint32_t idx, double (&rr)[2], double (&jp)[12], double (&jl)[6]) {
+        if constexpr (EVAL) {
+          double je[12];
+          (void)reprojObservation<true, false, GENERAL>(idx, reinterpret_cast<const double2*>(p.obsUv)[o], p.obsW[o], hpw, o, N, tb, p.lmPrior,
+                                                        p.lossTab, GENERAL ? p.obsS : nullptr, rr, jp, jl, je);
+        }
+      };
       if (has0) {
         pidx = p.obsIdx[o0];
-        pr0[0] = p.rCur[o0]; pr0[1] = p.rCur[N + o0];
+        if constexpr (EVAL) {
+          evalObs(o0, pidx, pr0, pjp, pjl);
+        } else {
+          pr0[0] = p.rCur[o0]; pr0[1] = p.rCur[N + o0];
 #pragma unroll
-        for (int k = 0; k < 6; ++k) pjl[k] = p.JlCur[k * N + o0];
+          for (int k = 0; k < 6; ++k) pjl[k] = p.JlCur[k * N + o0];
 #pragma unroll
-        for (int k = 0; k < 12; ++k) pjp[k] = p.JpCur[k * N + o0];
+          for (int k = 0; k < 12; ++k) pjp[k] = p.JpCur[k * N + o0];
+        }
       }
       TRACE_AFTER(26, pjp[11]);
       // V = sum Jl^T Jl, b = sum Jl^T r over the landmark's observations (16 lanes)
@@ -2590,12 +2697,29 @@ __device__ __forceinline__ void k_schur_dense_body(const DeviceProblem& p, doubl
       for (int i = gl; i < n; i += 16) {
         const size_t o = (size_t)start + i;
         const bool first = i == gl;
-        const double r0 = first ? pr0[0] : p.rCur[o], r1 = first ? pr0[1] : p.rCur[N + o];
-        const double a0 = first ? pjl[0] : p.JlCur[o], a1 = first ? pjl[1] : p.JlCur[N + o], a2 = first ? pjl[2] : p.JlCur[2 * N + o];
-        const double c0 = first ? pjl[3] : p.JlCur[3 * N + o], c1 = first ? pjl[4] : p.JlCur[4 * N + o], c2 = first ? pjl[5] : p.JlCur[5 * N + o];
-        v00 += a0 * a0 + c0 * c0; v01 += a0 * a1 + c0 * c1; v02 += a0 * a2 + c0 * c2;
-        v11 += a1 * a1 + c1 * c1; v12 += a1 * a2 + c1 * c2; v22 += a2 * a2 + c2 * c2;
-        b0 += a0 * r0 + c0 * r1; b1 += a1 * r0 + c1 * r1; b2 += a2 * r0 + c2 * r1;
+        double r0, r1, a0, a1, a2, c0, c1, c2;
+        if constexpr (EVAL) {
+          double er[2] = {pr0[0], pr0[1]}, ejl[6] = {pjl[0], pjl[1], pjl[2], pjl[3], pjl[4], pjl[5]}, ejp[12];
+          if (!first) evalObs(o, p.obsIdx[o], er, ejp, ejl);
+          r0 = er[0]; r1 = er[1];
+          a0 = ejl[0]; a1 = ejl[1]; a2 = ejl[2]; c0 = ejl[3]; c1 = ejl[4]; c2 = ejl[5];
+        } else {
+          r0 = first ? pr0[0] : p.rCur[o]; r1 = first ? pr0[1] : p.rCur[N + o];
+          a0 = first ? pjl[0] : p.JlCur[o]; a1 = first ? pjl[1] : p.JlCur[N + o]; a2 = first ? pjl[2] : p.JlCur[2 * N + o];
+          c0 = first ? pjl[3] : p.JlCur[3 * N + o]; c1 = first ? pjl[4] : p.JlCur[4 * N + o]; c2 = first ? pjl[5] : p.JlCur[5 * N + o];
+        }
+        if constexpr (EVAL) {   // (the sums below as k_schur_dense<9, false, 4> is compiled: dot2Fenced)
+          v00 += dot2Fenced(a0, a0, c0, c0); v01 += dot2Fenced(a0, a1, c0, c1); v02 += dot2Fenced(a0, a2, c0, c2);
+          v11 += dot2Fenced(a1, a1, c1, c1); v12 += dot2Fenced(a1, a2, c1, c2); v22 += dot2Fenced(a2, a2, c2, c2);
+          // (k_schur_dense peels the lane's first observation off its loops, and there the products with r change places)
+          b0 += first ? dot2Fenced(c0, r1, a0, r0) : dot2Fenced(a0, r0, c0, r1);
+          b1 += first ? dot2Fenced(c1, r1, a1, r0) : dot2Fenced(a1, r0, c1, r1);
+          b2 += first ? dot2Fenced(c2, r1, a2, r0) : dot2Fenced(a2, r0, c2, r1);
+        } else {
+          v00 += a0 * a0 + c0 * c0; v01 += a0 * a1 + c0 * c1; v02 += a0 * a2 + c0 * c2;
+          v11 += a1 * a1 + c1 * c1; v12 += a1 * a2 + c1 * c2; v22 += a2 * a2 + c2 * c2;
+          b0 += a0 * r0 + c0 * r1; b1 += a1 * r0 + c1 * r1; b2 += a2 * r0 + c2 * r1;
+        }
       }
       v00 = rowSum16(v00); v01 = rowSum16(v01); v02 = rowSum16(v02); v11 = rowSum16(v11); v12 = rowSum16(v12); v22 = rowSum16(v22);
       b0 = rowSum16(b0); b1 = rowSum16(b1); b2 = rowSum16(b2);
@@ -2645,18 +2769,44 @@ __device__ __forceinline__ void k_schur_dense_body(const DeviceProblem& p, doubl
         const int offP = poseOffS[idx & 0xfff];
         const int offE = WITH_EXT ? p.extOff[(idx >> 12) & 0xfff] : -1;
         if (offP < 0 && offE < 0) continue;
-        const double a0 = first ? pjl[0] : p.JlCur[o], a1 = first ? pjl[1] : p.JlCur[N + o], a2 = first ? pjl[2] : p.JlCur[2 * N + o];
-        const double c0 = first ? pjl[3] : p.JlCur[3 * N + o], c1 = first ? pjl[4] : p.JlCur[4 * N + o], c2 = first ? pjl[5] : p.JlCur[5 * N + o];
+        double a0, a1, a2, c0, c1, c2;
+        double er[2] = {pr0[0], pr0[1]}, ejp[12];   // EVAL: residual and pose Jacobian of this observation
+        if constexpr (EVAL) {
+          double ejl[6] = {pjl[0], pjl[1], pjl[2], pjl[3], pjl[4], pjl[5]};
+#pragma unroll
+          for (int k = 0; k < 12; ++k) ejp[k] = pjp[k];
+          if (!first) evalObs(o, idx, er, ejp, ejl);
+          a0 = ejl[0]; a1 = ejl[1]; a2 = ejl[2]; c0 = ejl[3]; c1 = ejl[4]; c2 = ejl[5];
+        } else {
+          a0 = first ? pjl[0] : p.JlCur[o]; a1 = first ? pjl[1] : p.JlCur[N + o]; a2 = first ? pjl[2] : p.JlCur[2 * N + o];
+          c0 = first ? pjl[3] : p.JlCur[3 * N + o]; c1 = first ? pjl[4] : p.JlCur[4 * N + o]; c2 = first ? pjl[5] : p.JlCur[5 * N + o];
+        }
         // one 6-block of camera-side Jacobian: rows of G (and, with fixed extrinsics, the block of A + Jc^T r)
         auto addBlock = [&](const double* J, int off) {
           double jc[12];
 #pragma unroll
-          for (int k = 0; k < 12; ++k) jc[k] = (first && J == p.JpCur) ? pjp[k] : J[k * N + o];
+          for (int k = 0; k < 12; ++k) {
+            if constexpr (EVAL) jc[k] = ejp[k];
+            else jc[k] = (first && J == p.JpCur) ? pjp[k] : J[k * N + o];
+          }
 #pragma unroll
           for (int a = 0; a < 6; ++a) {
             const double j0 = jc[a], j1 = jc[6 + a];
-            const double e0 = j0 * a0 + j1 * c0, e1 = j0 * a1 + j1 * c1, e2 = j0 * a2 + j1 * c2;
             double* g = Gt + (size_t)(off + a) * kDenseLd + 3 * grp;
+            if constexpr (EVAL) {
+              const double e0 = dot2Fenced(j0, a0, j1, c0), e1 = dot2Fenced(j0, a1, j1, c1), e2 = dot2Fenced(j0, a2, j1, c2);
+              atomicAdd(&g[0], e0 * i00);
+              atomicAdd(&g[1], first ? dot2Fenced(e1, i11, e0, i10) : dot2Fenced(e0, i10, e1, i11));
+              double g2 = __builtin_fma(e2, i22, dot2Fenced(e0, i20, e1, i21));
+              fpFence(g2);
+              atomicAdd(&g[2], g2);
+              double* ap = Amine + (size_t)(off / 6) * kPoseAcc;
+#pragma unroll
+              for (int c = a; c < 6; ++c) atomicAdd(&ap[sym6(a, c)], dot2Fenced(j0, jc[c], j1, jc[6 + c]));
+              atomicAdd(&ap[21 + a], first ? dot2Fenced(j1, er[1], j0, er[0]) : dot2Fenced(j0, er[0], j1, er[1]));
+              continue;
+            }
+            const double e0 = j0 * a0 + j1 * c0, e1 = j0 * a1 + j1 * c1, e2 = j0 * a2 + j1 * c2;
             atomicAdd(&g[0], e0 * i00);
             atomicAdd(&g[1], e0 * i10 + e1 * i11);
             atomicAdd(&g[2], e0 * i20 + e1 * i21 + e2 * i22);
@@ -3907,6 +4057,67 @@ void launchAccumulateNormalEquations(const DeviceProblem& p, double mu, bool ini
     const int n = dC * dC + 3 * dC;
     launch(k_reduce_slabs, dim3((n + 15) / 16), dim3(256), 0, s, q);
   }
+}
+
+// ---------------------------------------------------------------- evaluation + build of the next normal equations in ONE launch
+// The trust-region loop enqueues the build of the next iteration right behind the candidate evaluation (Window::solve); as two
+// launches the chunk blocks of k_schur_dense wait for the whole evaluation -- an IMU factor that re-integrates holds it open five
+// times as long as its reprojection blocks take -- and then start with two dependent round trips for what those blocks wrote a
+// few microseconds earlier.  Here both share a grid and NO block reads what another block of the launch writes:
+//   blocks [0, nEval)   k_eval_all_body as in k_eval_all: same partial slots, same stores of r / Jp / Jl and lmC, the cost ticket
+//                       counts these blocks only.  A factor block then adds its factor to the normal equations
+//                       (factorsAccumulateLin, staged form) from the record it has just written itself.
+//   blocks behind them  the chunk role of k_schur_dense_body<9, false, 4> in its EVAL form: every lane evaluates the observations
+//                       of its landmark with reprojObservation, the function the evaluation blocks store from.
+// The prior's blocks of the build read the gradient and tangent maps the evaluation's prior block writes: they keep a launch of
+// their own (k_prior_accumulate) behind this one.  accFactors = 0 (an entry of S receives three or more unordered terms, see
+// launchEvalBuild): the factor blocks leave their factor to that launch as well (k_factors_only).
+template <bool GENERAL>
+__global__ __launch_bounds__(256) void k_eval_build(DeviceProblem p, int cand, int nR, int hasPrior, int nEval, double mu, int initScale, int nChunkBlocks,
+                                                    int accFactors) {
+  __shared__ FactorShared sh;
+  if ((int)blockIdx.x >= nEval) {
+    k_schur_dense_body<9, false, 4, true, GENERAL>(p, mu, initScale, nChunkBlocks, 0, cand, reinterpret_cast<double*>(&sh), nEval);
+    return;
+  }
+  k_eval_all_body<false, GENERAL>(p, cand, nR, 1, hasPrior, sh, ExtentX{(unsigned int)nEval});
+  if (accFactors && (int)blockIdx.x < nEval - nR - hasPrior) {
+    static_assert(sizeof(sh.fb) >= kFactorColRow * sizeof(int) + kFactorStage * sizeof(double), "a factor's staging area fits the block's LDS");
+    __syncthreads();   // the record (r, J, block table, sc) this block has just stored is read back by all of its threads
+    factorsAccumulateLin<true>(p, (cand ? p.linCand : p.linCur)[blockIdx.x], reinterpret_cast<int*>(sh.fb));
+    TRACE(29);
+  }
+}
+static std::atomic<int> gEvalBuildLaunches{0};
+int evalBuildLaunches() { return gEvalBuildLaunches.load(std::memory_order_relaxed); }
+bool launchEvalBuild(const DeviceProblem& p, bool cand, double mu, bool initScale, bool factorsCommute, int computeUnits, hipStream_t s) {
+  if (!(p.L > 0 && p.N > 0 && p.dC > 0 && p.schurDense) || p.world > 1 || !canFuseEvaluation(p)) return false;
+  const DenseSchurPlan plan = denseSchurPlan(p);
+  const int nR = evalReprojBlockCount(p.N), pri = evalPriorBlockCount(p.priorM), nEval = p.F + nR + pri;
+  const size_t stage = (size_t)(p.nPose + p.nExt) * 7 * 8 + (size_t)p.nCam * sizeof(CameraModel) + kLossTabBytes;
+  // (the dense form never has a chain on the side lane: sbEarlyActive asks for the wide form)
+  if (!evalBuildFits(!plan.aMfma && !p.anyExtVariable, nEval, p.nSlabs, computeUnits, plan.ldsBytes, stage, sizeof(FactorShared))) return false;
+  DeviceProblem pb = p;
+  pb.aBlocks = 0;
+  gLastSchurForm.store(1000 + 10 * 9, std::memory_order_relaxed);
+  gEvalBuildLaunches.fetch_add(1, std::memory_order_relaxed);
+  const dim3 grid(nEval + p.nSlabs);
+  const int acc = factorsCommute ? 1 : 0;
+  if (p.obsS) launch(k_eval_build<true>, grid, dim3(256), 0, s, pb, cand ? 1 : 0, nR, pri, nEval, mu, initScale ? 1 : 0, p.nSlabs, acc);
+  else launch(k_eval_build<false>, grid, dim3(256), 0, s, pb, cand ? 1 : 0, nR, pri, nEval, mu, initScale ? 1 : 0, p.nSlabs, acc);
+  const int nPri = priorAccBlocks(p);
+  if (nPri > 0 || !factorsCommute) {
+    DeviceProblem q = pb;   // the factors' and the prior's linearisation at the evaluated point
+    if (cand) {
+      std::swap(q.linCur, q.linCand);
+      std::swap(q.priorDchi, q.priorDchiC); std::swap(q.priorGrad, q.priorGradC); std::swap(q.priorM3, q.priorM3C);
+    }
+    if (factorsCommute) launch(k_prior_accumulate, dim3(nPri), dim3(256), 0, s, q);
+    else launch(k_factors_only, dim3(p.F + nPri), dim3(256), 0, s, q, p.F);
+  }
+  const int n = p.dC * p.dC + 3 * p.dC;
+  launch(k_reduce_slabs, dim3((n + 15) / 16), dim3(256), 0, s, pb);
+  return true;
 }
 
 // ================================================================ K6: reduced system solve

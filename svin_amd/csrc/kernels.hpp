@@ -255,6 +255,17 @@ int schurDenseABlocks(const DeviceProblem& p);   // DeviceProblem::aBlocks as la
 // block copies, 1: A on MFMA block-wise, 2: A on MFMA tile-wise); 2000 k_blocks_slots + k_schur_rows; 3000 k_schur_panels;
 // 4000 / 4001 pairwise k_schur with LDS slabs / global atomics; 5000 small factors only.
 int lastSchurForm();
+// Evaluation and the build of the normal equations AT THE EVALUATED POINT in one launch (k_eval_build) + k_reduce_slabs: what
+// launchEvalAll(p, cand, true, s) followed by launchAccumulateNormalEquations(view, mu, initScale, s, false) computes, `view` being
+// `p` itself for cand = false and `p` with its current / candidate sets swapped for cand = true.  The accumulators are clean.
+// Returns false, having launched nothing, for a window the launch does not take (pack_plan.hpp evalBuildFits: any form but the
+// narrow dense one with fixed extrinsics, a sharded window, more workgroups than compute units): the caller issues the two launches.
+// factorsCommute: no entry of S receives more than two of the small factors' / the prior's atomic additions (they start from zero,
+// so their order does not matter): the factor blocks of the launch add their factor themselves.  Otherwise the factors and the
+// prior keep a launch of their own (k_factors_only) behind it, where their blocks start together as they do in k_schur_dense --
+// sums of three and more terms then come out the same from run to run as far as they did before.
+bool launchEvalBuild(const DeviceProblem& p, bool cand, double mu, bool initScale, bool factorsCommute, int computeUnits, hipStream_t s);
+int evalBuildLaunches();   // launches of k_eval_build in this process so far (svin_ba_debug_get_option("SVIN_EVAL_BUILD_LAUNCHES"))
 
 // ---- launch wrappers (kernels.hip).  `cand` selects candidate tables/buffers.
 void launchEvalReproj(const DeviceProblem& p, bool cand, bool robust, hipStream_t s);

@@ -39,6 +39,9 @@ enum DebugOption : int {
   kOptSlabChunks,          // SVIN_SLAB_CHUNKS=n: chunks of 16 landmarks per workgroup of k_schur_dense (read by pack())
   kOptNoSbEarly,           // SVIN_NO_SB_EARLY: wide windows factorise the speed / bias chain inside the reduced solve, not beside the build
   kOptNoRowSplit,          // SVIN_NO_ROW_SPLIT: k_schur_rows work list with one accumulator set per block row (read by pack())
+  kOptNoEvalBuild,         // SVIN_NO_EVAL_BUILD: evaluation and the build enqueued behind it as two launches (k_eval_all, k_schur_dense), never k_eval_build
+  kOptLinearizeEvalBuild,  // SVIN_LINEARIZE_EVAL_BUILD: the inspection hooks svin_ba_linearize / svin_ba_debug_reduced_solve take their evaluation and
+                           // build through k_eval_build where solve() would (tests: the launch against the two it replaces, on one handle)
   kOptCount
 };
 
@@ -49,6 +52,7 @@ int debugOptionByName(const char* name, int* value);       // 1 and *value, or 0
 // whose grid differs from window to window, the share (parts per million) that left at once -- beyond their window's own extent, or
 // of a window sitting out the stage (window.cpp, batch_plan.hpp)
 int lastBatchIdlePpm();
+// read-only inspection field "SVIN_EVAL_BUILD_LAUNCHES": how many times this process has launched k_eval_build (kernels.hpp)
 inline bool optOn(DebugOption which) { return debugOption(which) != 0; }
 
 }  // namespace svin

@@ -70,6 +70,19 @@ inline SchurForm chooseSchurForm(int dC, int L, int N, int nPoses, bool anyExtVa
   return f;
 }
 
+// ---- evaluation and build of the next normal equations in ONE launch (k_eval_build: the blocks of the fused evaluation, then the
+// chunk blocks of the narrow dense form, which evaluate their own observations).  Every workgroup of that launch brings the factor
+// blocks' LDS, one workgroup per compute unit: the launch is taken when all of them run at once (a second round of workgroups
+// would cost what the launch boundary it removes costs) and when a chunk block's tiles and staged tables fit that LDS.
+// denseFormPlain: k_schur_dense<9, false, 4> is the window's form (fixed extrinsics, at most 8 tile rows); chunkLdsBytes: the
+// dynamic LDS that form takes; stageBytes: poses, extrinsics, camera models and loss table; ldsBytes: the factor blocks' LDS.
+inline bool evalBuildFits(bool denseFormPlain, int evalBlocks, int chunkBlocks, int computeUnits, size_t chunkLdsBytes, size_t stageBytes,
+                          size_t ldsBytes) {
+  if (!denseFormPlain || evalBlocks <= 0 || chunkBlocks <= 0) return false;
+  if ((long long)evalBlocks + chunkBlocks > computeUnits) return false;
+  return ((chunkLdsBytes + 15) & ~(size_t)15) + stageBytes <= ldsBytes;
+}
+
 // ---- landmark order of wide windows (k_schur_panels): order by VISIBILITY SIGNATURE -- the set of 16-row tiles of the camera
 // matrix a landmark's observations write to (first tile, last tile, then the bit pattern) -- so that the 16 landmarks of a chunk
 // hit the same tile rows and the kernel's step masks drop whole products.  A product step (tile row, tile column, 4 columns of G)

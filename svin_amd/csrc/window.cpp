@@ -65,7 +65,8 @@ struct OptionTable {
         {kOptNoLdsBorder, "SVIN_NO_LDS_BORDER"}, {kOptBlkRounds, "SVIN_BLK_ROUNDS"}, {kOptBatchLanes, "SVIN_BATCH_LANES"},
         {kOptBatchTiming, "SVIN_BATCH_TIMING"}, {kOptNoEvalSplit, "SVIN_NO_EVAL_SPLIT"},
         {kOptSlabChunks, "SVIN_SLAB_CHUNKS"}, {kOptNoSbEarly, "SVIN_NO_SB_EARLY"},
-        {kOptNoRowSplit, "SVIN_NO_ROW_SPLIT"}};
+        {kOptNoRowSplit, "SVIN_NO_ROW_SPLIT"}, {kOptNoEvalBuild, "SVIN_NO_EVAL_BUILD"},
+        {kOptLinearizeEvalBuild, "SVIN_LINEARIZE_EVAL_BUILD"}};
     static_assert(sizeof(kNames) / sizeof(kNames[0]) == kOptCount, "every option has its environment variable");
     for (const auto& n : kNames) {
       name[n.which] = n.env;
@@ -89,6 +90,7 @@ int debugOption(DebugOption which) { return optionTable().v[which].load(std::mem
 int debugOptionByName(const char* name, int* value) {
   if (!name) return 0;
   if (std::strcmp(name, "SVIN_LAST_SCHUR_FORM") == 0) { if (value) *value = lastSchurForm(); return 1; }   // read-only: not in the table
+  if (std::strcmp(name, "SVIN_EVAL_BUILD_LAUNCHES") == 0) { if (value) *value = evalBuildLaunches(); return 1; }   // read-only (kernels.hpp)
   if (std::strcmp(name, "SVIN_LAST_BATCH_IDLE_PPM") == 0) { if (value) *value = lastBatchIdlePpm(); return 1; }   // read-only (options.hpp)
   OptionTable& t = optionTable();
   for (int k = 0; k < kOptCount; ++k)
@@ -1990,6 +1992,18 @@ void Window::packFactors(PackHost& a) {
     hFac.push_back(df);   // (not in factorIds_: the inspection hooks report the graph's factors)
   }
   a.F = (int)hFac.size();
+  // How many terms -- small factors, the prior -- add to the diagonal block of one parameter block, at most.  The factors reach S
+  // with atomic additions onto zero: two of them commute, three do not (k_eval_build, kernels.hpp launchEvalBuild).
+  {
+    std::map<std::pair<int, int>, int> terms;
+    for (const DevFactor& df : hFac)
+      for (int b = 0; b < df.nblk; ++b) ++terms[std::make_pair(df.blkKind[b], df.blkSlot[b])];
+    if (hasPrior_)
+      for (const PriorBlockHost& pb : priorBlocks_)
+        if (pb.mdim > 0) ++terms[std::make_pair((int)pb.kind, slotMapOf(pb.kind).at(pb.id))];
+    maxTermsPerBlock_ = 0;
+    for (const auto& kv : terms) maxTermsPerBlock_ = std::max(maxTermsPerBlock_, kv.second);
+  }
   // prior
   if (hasPrior_) {
     a.priorM = priorM_;
@@ -2298,20 +2312,24 @@ void Window::downloadStates() {
       if (kv.second.kind == F_IMU && !ownsFactor(kv.second)) kv.second.imu.redo = 1;
 }
 
-void Window::evaluateAll(bool cand, hipStream_t s) {
+// buildMu: the caller enqueues the build of the normal equations at the evaluated point (damping *buildMu, clean accumulators)
+// right behind this evaluation -- true is returned when the evaluation's launch has taken that build along (k_eval_build)
+bool Window::evaluateAll(bool cand, hipStream_t s, const double* buildMu, bool buildInitScale) {
   evaluateHostFactors(cand, s);
   prob_.mailbox = distNative_ ? nullptr : mailboxDev_;   // sharded: published after the all-reduce (launchPublishScalars)
   prob_.mailboxSeq = ++mailboxSeq_;
   const int who = costSummedBy(prob_);
   if (canFuseEvaluation(prob_) && !optOn(kOptSplitEval)) {
+    if (buildMu && !optOn(kOptNoEvalBuild) && launchEvalBuild(prob_, cand, *buildMu, buildInitScale, maxTermsPerBlock_ <= 2, deviceComputeUnits(), s)) return true;
     // one launch: the reprojection blocks and the prior run next to the (much longer) IMU factor blocks
     launchEvalAll(prob_, cand, true, s);  // factor, reprojection and prior blocks; the last one sums the cost
-    return;
+    return false;
   }
   launchEvalReproj(prob_, cand, true, s);
   launchEvalFactors(prob_, cand, s, who == 1);
   launchEvalPrior(prob_, cand, s, who == 2);
   if (who == 0) launchCost(prob_, s);
+  return false;
 }
 
 SolverScalars Window::readScalars() {
@@ -2383,14 +2401,19 @@ void Window::solve(size_t numIter, bool verbose) {
   // chain's blocks are complete only after the all-reduce.
   struct SbEarlyGuard { DeviceProblem& q; ~SbEarlyGuard() { q.sideLane = 0; } } sbEarlyGuard{p};
   p.sideLane = (!dist && !optOn(kOptNoSbEarly)) ? 1 : 0;
-  evaluateAll(false, s);
   TrustRegionHost tr;   // every decision of the loop (trust_region.hpp: HIP-free, replayed on the CPU by the tests)
   // The first build depends on no decision (initial damping, metric fixed here): it is enqueued right behind the initial
   // evaluation instead of after the host has seen that evaluation's cost (one mailbox round trip of an idle device per solve).
+  // A build enqueued behind an evaluation rides in the evaluation's launch where k_eval_build takes the window (one GPU,
+  // speculation on: evalBuild; otherwise, and wherever launchEvalBuild declines, the two launches).
+  const bool noSpeculation = optOn(kOptNoSpeculation);
+  const bool evalBuild = !dist && !noSpeculation;
   bool firstBuilt = false;
   const double firstMu = tr.mu;
-  if (!dist && numIter > 0) {
-    launchAccumulateNormalEquations(p, firstMu, true, s, /*zeroFirst=*/false);   // pack() cleared the accumulators
+  const bool firstWanted = !dist && numIter > 0;
+  const bool firstFused = evaluateAll(false, s, (firstWanted && evalBuild) ? &firstMu : nullptr, true);
+  if (firstWanted) {
+    if (!firstFused) launchAccumulateNormalEquations(p, firstMu, true, s, /*zeroFirst=*/false);   // pack() cleared the accumulators
     firstBuilt = true;
   }
   AR(scalD, 4, 0);
@@ -2417,7 +2440,6 @@ void Window::solve(size_t numIter, bool verbose) {
   // launch of the next iteration.  Right behind the candidate evaluation the normal equations of the NEXT iteration
   // are enqueued on the candidate's linearisation (the sets an accepted step swaps in) with the damping an accepted
   // step gets; on acceptance they are simply kept, otherwise the accumulators are re-zeroed before the next build.
-  const bool noSpeculation = optOn(kOptNoSpeculation);
   const bool speculate = !noSpeculation && (!dist || distNative_);
   bool accumulatorsClean = true;   // S / gRed / hC zero (pack() or k_post_solve), nothing speculative in them
   bool specValid = false;          // the accumulators hold the build of the candidate with damping specMu
@@ -2451,15 +2473,19 @@ void Window::solve(size_t numIter, bool verbose) {
       }
       if (tr.reuse || !fuseStep) launchDoglegStep(p, tr.radius, s);
       p.lmDeferred = (deferLm && !tr.reuse) ? 1 : 0;
-      evaluateAll(true, s);
+      const bool specWanted = speculate && accumulatorsClean && tr.iteration < (int)numIter;
+      if (specWanted) specMu = tr.muAfterAccept();
+      const bool specFused = evaluateAll(true, s, (specWanted && evalBuild) ? &specMu : nullptr, false);
       p.lmDeferred = 0;
-      if (speculate && accumulatorsClean && tr.iteration < (int)numIter) {
+      if (specWanted && specFused) {   // (k_eval_build built on the candidate's sets itself: no swapped view)
+        accumulatorsClean = false;
+        specValid = true;
+      } else if (specWanted) {
         DeviceProblem q = p;   // the problem as it looks after an accepted step
         std::swap(q.pose, q.poseC); std::swap(q.ext, q.extC); std::swap(q.sb, q.sbC); std::swap(q.lm, q.lmC);
         std::swap(q.rCur, q.rCand); std::swap(q.JpCur, q.JpCand); std::swap(q.JlCur, q.JlCand); std::swap(q.JeCur, q.JeCand);
         std::swap(q.linCur, q.linCand);
         std::swap(q.priorDchi, q.priorDchiC); std::swap(q.priorGrad, q.priorGradC); std::swap(q.priorM3, q.priorM3C);
-        specMu = tr.muAfterAccept();
         launchAccumulateNormalEquations(q, specMu, false, s, /*zeroFirst=*/false);
         accumulatorsClean = false;
         specValid = true;
@@ -2931,8 +2957,10 @@ int Window::linearize(double mu, double* S, double* g, uint64_t* blockIds, int32
   pack();
   DeviceProblem& p = prob_;
   if (p.d > capD) return -p.d;
-  evaluateAll(false, stream_);
-  launchBuildNormalEquations(p, mu, true, stream_);
+  const bool viaEvalBuild = optOn(kOptLinearizeEvalBuild);
+  if (viaEvalBuild) launchZeroBuild(p, stream_);   // (k_eval_build takes clean accumulators)
+  if (evaluateAll(false, stream_, viaEvalBuild ? &mu : nullptr, true)) launchFinalizeNormalEquations(p, mu, true, stream_);
+  else launchBuildNormalEquations(p, mu, true, stream_);
   SolverScalars sc = readScalars();
   if (cost) *cost = sc.cost;
   if (S) HIP_OK(hipMemcpy2D(S, sizeof(double) * p.d, p.S, sizeof(double) * p.ldS, sizeof(double) * p.d, p.d, hipMemcpyDeviceToHost));
@@ -2961,9 +2989,11 @@ int Window::debugReducedSolve(double mu, double* y, int capD, bool fuseFinalize)
   pack();
   DeviceProblem& p = prob_;
   if (p.d > capD) return -p.d;
-  evaluateAll(false, stream_);
+  const bool viaEvalBuild = fuseFinalize && optOn(kOptLinearizeEvalBuild);
+  if (viaEvalBuild) launchZeroBuild(p, stream_);
+  const bool built = evaluateAll(false, stream_, viaEvalBuild ? &mu : nullptr, true);
   if (fuseFinalize) {   // what solve() enqueues: metric and damping applied inside the solver's load phase
-    launchAccumulateNormalEquations(p, mu, true, stream_, /*zeroFirst=*/true);
+    if (!built) launchAccumulateNormalEquations(p, mu, true, stream_, /*zeroFirst=*/!viaEvalBuild);
     launchSolveReduced(p, stream_, mu, true, /*fuseFinalize=*/true);
   } else {
     launchBuildNormalEquations(p, mu, true, stream_);
@@ -2972,6 +3002,23 @@ int Window::debugReducedSolve(double mu, double* y, int capD, bool fuseFinalize)
   HIP_OK(hipMemcpyAsync(y, p.yC, sizeof(double) * p.d, hipMemcpyDeviceToHost, stream_));
   HIP_OK(hipStreamSynchronize(stream_));
   return p.d;
+}
+int Window::debugBuildArrays(double* gFull, double* hC, int capD, double* Vinv, double* bl, double* hL, double* scaleL, int capL,
+                             int32_t* imuRedo, int capImu, int32_t* sizes3) {
+  const DeviceProblem& p = prob_;
+  HIP_OK(hipStreamSynchronize(stream_));
+  sizes3[0] = p.d; sizes3[1] = p.L; sizes3[2] = p.nImu;
+  auto get = [&](double* dst, const double* src, size_t n) {
+    if (dst && src && n > 0) HIP_OK(hipMemcpy(dst, src, sizeof(double) * n, hipMemcpyDeviceToHost));
+  };
+  if (p.d <= capD) { get(gFull, p.gFull, p.d); get(hC, p.hC, p.d); }
+  if (p.L <= capL) { get(Vinv, p.Vinv, (size_t)6 * p.L); get(bl, p.bl, (size_t)3 * p.L); get(hL, p.hL, (size_t)3 * p.L); get(scaleL, p.scaleL, (size_t)3 * p.L); }
+  if (imuRedo && p.nImu > 0 && p.nImu <= capImu) {
+    std::vector<DevImu> hImu(p.nImu);
+    HIP_OK(hipMemcpy(hImu.data(), p.imus, sizeof(DevImu) * p.nImu, hipMemcpyDeviceToHost));
+    for (int k = 0; k < p.nImu; ++k) imuRedo[k] = hImu[k].redoCounter;
+  }
+  return 1;
 }
 // inspection hook: ONE trust-region iteration on a fresh linearisation, with the launches solve() issues -- build, reduced solve,
 // post-solve pass, dogleg step in the requested form, candidate evaluation -- and everything the step is made of read back, for

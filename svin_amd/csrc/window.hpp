@@ -351,6 +351,9 @@ class Window {
   const long long* pathCounters() const { return pathCounters_; }
   void landmarkHandles(int32_t out[2]) const { out[0] = nextLmHandle_; out[1] = (int32_t)landmarks_.size(); }
   int debugReducedSolve(double mu, double* y, int capD, bool fuseFinalize = false);
+  // read-only inspection (svin_ba_debug_build_arrays): the last build's vectors and per-landmark arrays, the IMU factors' redo counters
+  int debugBuildArrays(double* gFull, double* hC, int capD, double* Vinv, double* bl, double* hL, double* scaleL, int capL,
+                       int32_t* imuRedo, int capImu, int32_t* sizes3);
   int debugPeekSolverScratch(uint64_t off, uint64_t count, double* out);
   // one trust-region iteration with everything the step is made of read back (window.cpp); the arrays may be null
   struct DebugStepOut {
@@ -401,7 +404,8 @@ class Window {
   // device side
   void pack(bool solveFollows = false);   // host graph -> device arrays (sets prob_); solveFollows: called by optimize()
   void downloadStates();       // device tables -> host blocks / landmarks / imu states
-  void evaluateAll(bool cand, hipStream_t s);
+  bool evaluateAll(bool cand, hipStream_t s, const double* buildMu = nullptr, bool buildInitScale = false);
+  int maxTermsPerBlock_ = 0;   // packFactors: small factors + prior that add to one parameter block's diagonal block, at most
   void evaluateHostFactors(bool cand, hipStream_t s);   // F_HOST factors: callbacks at the current / candidate blocks, r and J into their FactorLin records
   void solve(size_t numIter, bool verbose);
   static void solveBatchGroup(const std::vector<Window*>& g, size_t numIter, bool verbose);

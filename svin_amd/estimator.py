@@ -56,7 +56,7 @@ EXPORTS = [
     "svin_ba_set_camera_sensor_states", "svin_ba_set_landmark", "svin_ba_num_frames", "svin_ba_num_landmarks",
     "svin_ba_current_keyframe_id", "svin_ba_current_frame_id", "svin_ba_frame_id_by_age", "svin_ba_is_keyframe",
     "svin_ba_is_in_imu_window", "svin_ba_frame_ids", "svin_ba_landmark_ids", "svin_ba_imu_propagation",
-    "svin_ba_eval_reprojection", "svin_ba_observation_ids", "svin_ba_eval_factors", "svin_ba_linearize", "svin_ba_debug_reduced_solve", "svin_ba_debug_reduced_solve_ex", "svin_ba_debug_trust_region_step", "svin_ba_debug_set_switch", "svin_ba_debug_set_option", "svin_ba_debug_get_option", "svin_ba_debug_sym_eig", "svin_ba_get_path_counters", "svin_ba_debug_landmark_handles", "svin_ba_wait_idle", "svin_ba_debug_peek_solver_scratch",
+    "svin_ba_eval_reprojection", "svin_ba_observation_ids", "svin_ba_eval_factors", "svin_ba_linearize", "svin_ba_debug_reduced_solve", "svin_ba_debug_reduced_solve_ex", "svin_ba_debug_build_arrays", "svin_ba_debug_trust_region_step", "svin_ba_debug_set_switch", "svin_ba_debug_set_option", "svin_ba_debug_get_option", "svin_ba_debug_sym_eig", "svin_ba_get_path_counters", "svin_ba_debug_landmark_handles", "svin_ba_wait_idle", "svin_ba_debug_peek_solver_scratch",
     "svin_ba_get_prior", "svin_ba_describe_block", "svin_ba_bench_jacobian_eval", "svin_ba_bench_jacobian_eval_b2b", "svin_ba_set_pack_mode", "svin_ba_debug_csr", "svin_ba_residual_info",
     "svin_ba_map_add_parameter_block", "svin_ba_set_parameter_block", "svin_ba_map_remove_parameter_block", "svin_ba_map_add_pose_error",
     "svin_ba_map_add_speed_and_bias_error", "svin_ba_map_add_relative_pose_error", "svin_ba_map_add_reprojection_error",
@@ -166,6 +166,7 @@ def load_library():
     sig("svin_ba_linearize", i32, vp, f64, pd, pd, pu64, pi32, pi32, i32, pd)
     sig("svin_ba_debug_reduced_solve", i32, vp, f64, pd, i32)
     sig("svin_ba_debug_reduced_solve_ex", i32, vp, f64, i32, pd, i32)
+    sig("svin_ba_debug_build_arrays", i32, vp, pd, pd, i32, pd, pd, pd, pd, i32, pi32, i32, pi32)
     sig("svin_ba_debug_trust_region_step", i32, vp, f64, f64, i32, i32, pd, pd, pd, i32, pd, pd, pd, pu64, i32, pu64, pi32, pd, i32, pi32)
     sig("svin_ba_debug_set_switch", i32, C.c_char_p, i32)
     sig("svin_ba_debug_set_option", i32, C.c_char_p, i32)
@@ -794,6 +795,17 @@ class Estimator:
         y = np.zeros(cap)
         d = self._check(self.L.svin_ba_debug_reduced_solve_ex(self.h, float(mu), 1 if fused else 0, _d(y), cap), "debug_reduced_solve")
         return y[:d].copy()
+
+    def debug_build_arrays(self):
+        """svin_ba_debug_build_arrays: g_full, h_c, Vinv, b_l, h_l, scale_l of the last build and the IMU factors' redo counters"""
+        sizes = np.zeros(3, np.int32)
+        self._check(self.L.svin_ba_debug_build_arrays(self.h, None, None, 0, None, None, None, None, 0, None, 0, sizes.ctypes.data_as(pi32)), "debug_build_arrays")
+        d, L, n = (int(v) for v in sizes)
+        out = dict(g_full=np.zeros(d), h_c=np.zeros(d), Vinv=np.zeros((L, 6)), b_l=np.zeros((L, 3)), h_l=np.zeros((L, 3)), scale_l=np.zeros((L, 3)),
+                   imu_redo=np.zeros(n, np.int32))
+        self._check(self.L.svin_ba_debug_build_arrays(self.h, _d(out["g_full"]), _d(out["h_c"]), d, _d(out["Vinv"]), _d(out["b_l"]), _d(out["h_l"]),
+                                                      _d(out["scale_l"]), L, out["imu_redo"].ctypes.data_as(pi32), n, sizes.ctypes.data_as(pi32)), "debug_build_arrays")
+        return out
 
     SCALAR_FIELDS = ("cost", "costReproj", "costFactors", "costPrior", "stepNormSq", "xNormSq", "spareA0", "spareA1",
                      "gHatSq", "jgSq", "gnHatSq", "gDotGn", "jySq", "jvDotJy", "jvDotR", "jyDotR")

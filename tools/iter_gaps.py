@@ -1,5 +1,5 @@
 """What the host in the trust-region loop costs: from a `rocprofv3 --kernel-trace` database of the headline
-command, the five kernels of an iteration (k_schur_dense, k_reduce_slabs, k_chol_solve_lds, k_post_solve, k_eval_all) in time
+command, the five kernels of an iteration (k_schur_dense, k_reduce_slabs, k_chol_solve_lds, k_post_solve, k_eval_all; four with k_eval_build) in time
 order -- per iteration (one k_chol_solve_lds start to the next inside a solve): wall time, the sum of its kernels, and the idle
 gaps between them.  usage: python tools/iter_gaps.py <results.db>"""
 import sqlite3
@@ -7,14 +7,15 @@ import sys
 
 import numpy as np
 
-names = ("k_schur_dense", "k_reduce_slabs", "k_chol_solve_lds", "k_post_solve", "k_eval_all")
+names = ("k_schur_dense", "k_reduce_slabs", "k_chol_solve_lds", "k_post_solve", "k_eval_all", "k_eval_build", "k_factors_only", "k_prior_accumulate")
 db = sqlite3.connect(sys.argv[1])
 rows = [(n, s, e) for n, s, e in db.execute("select name, start, end from kernels order by start") if any(k in n for k in names)]
 chol = [i for i, r in enumerate(rows) if "k_chol_solve_lds" in r[0]]
 wall, busy, gaps, ngap = [], [], [], []
 for a, b in zip(chol[:-1], chol[1:]):
     w = (rows[b][1] - rows[a][1]) / 1e3
-    if w > 200.0 or b - a != 5:      # a new solve (upload, reset) or a rejected step in between
+    # five launches, or four where k_eval_build takes evaluation and next build in one (k_chol_solve_lds, k_post_solve, k_eval_build, k_reduce_slabs)
+    if w > 200.0 or b - a != (4 if any("k_eval_build" in r[0] for r in rows[a:b]) else 5):      # a new solve (upload, reset) or a rejected step in between
         continue
     seg = rows[a:b]
     k = sum(e - s for _, s, e in seg) / 1e3
