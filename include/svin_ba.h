@@ -535,6 +535,11 @@ int svin_ba_debug_peek_solver_scratch(svin_ba* h, uint64_t offset, uint64_t coun
  * ROW BY ROW with the reference selects the eigen-solve with svin_ba_debug_set_option("SVIN_MARG_EIG", 1). */
 int svin_ba_get_prior(svin_ba* h, double* H, double* b0, double* J, double* e0, uint64_t* block_ids,
                       int32_t* block_ordering, int32_t* block_mdim, int32_t* n_blocks, int cap_m);
+/* the prior blocks' linearisation points: 9 doubles per block (7 used by a pose / extrinsics block: r, q as x y z w; 9 by a
+ * speed / bias block), in the block order of svin_ba_get_prior -- the values the solver evaluates the prior against (first
+ * estimates: a block keeps the point of the marginalisation that first brought it into the prior).  Read-only.  Returns the
+ * number of blocks, 0 without a prior, -n when lin is NULL or cap_blocks < n. */
+int svin_ba_get_prior_lin(svin_ba* h, double* lin, int cap_blocks);
 /* the linear system of the last svin_ba_apply_marginalization_strategy AFTER MarginalizationError::addResidualBlock (M1,
  * src/MarginalizationError.cpp:126-397) and BEFORE marginalizeOut, kept only when SVIN_MARG_KEEP_PRE is set in the
  * environment (inspection: lets a test arbitrate M1 and M2 / M3 separately): H = [U W; W^T blockdiag(V)], b = [ba; bb] with

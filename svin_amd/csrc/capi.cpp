@@ -625,6 +625,11 @@ int svin_ba_get_prior(svin_ba* h, double* H, double* b0, double* J, double* e0, 
   GUARD_BEGIN return win(h).getPrior(H, b0, J, e0, ids, ord, mdim, nb, cap_m);
   GUARD_END(SVIN_ERR_DEVICE)
 }
+int svin_ba_get_prior_lin(svin_ba* h, double* lin, int cap_blocks) {
+  if (!h) return SVIN_ERR_INVALID_ARG;
+  GUARD_BEGIN return win(h).getPriorLin(lin, cap_blocks);
+  GUARD_END(SVIN_ERR_DEVICE)
+}
 int svin_ba_get_marg_pre(svin_ba* h, int32_t* m, int32_t* n_landmarks, double* U, double* ba, double* W, double* V, double* bb,
                          int32_t* marg_rows, int cap_m, int cap_landmarks) try {
   if (!h) return SVIN_ERR_INVALID_ARG;

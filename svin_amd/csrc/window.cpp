@@ -3140,6 +3140,15 @@ int Window::getPrior(double* H, double* b0, double* J, double* e0, uint64_t* ids
   return m;
 }
 
+// the prior blocks' linearisation points, in getPrior()'s block order: the nine doubles PriorBlock::lin is uploaded with (pack())
+int Window::getPriorLin(double* lin, int capBlocks) const {
+  if (!hasPrior_) return 0;
+  const int n = (int)priorBlocks_.size();
+  if (!lin || n > capBlocks) return -n;
+  for (int i = 0; i < n; ++i) std::memcpy(lin + 9 * (size_t)i, priorBlocks_[i].lin, sizeof(double) * 9);
+  return n;
+}
+
 // ------------------------------------------------------------------------------------------ Map::getLhs (Map.cpp:105-150)
 int Window::lhsDim(uint64_t id) const {
   if (const Block* b = findBlock(id)) return b->kind == B_SB ? 9 : 6;   // a pose on a reduced manifold keeps its six columns

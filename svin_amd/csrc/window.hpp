@@ -366,6 +366,7 @@ class Window {
   int debugTrustRegionStep(double mu, double radius, int form, int commit, const DebugStepOut& out);
   int getPrior(double* H, double* b0, double* J, double* e0, uint64_t* ids, int32_t* ord, int32_t* mdim,
                int32_t* nBlocks, int capM);
+  int getPriorLin(double* lin, int capBlocks) const;   // 9 doubles per prior block (getPrior()'s order); -n when capBlocks < n
   int describeBlock(uint64_t id, uint64_t* frame, int32_t* kind, int32_t* index) const;
   // Map::getLhs (Map.cpp:105-150): sum of J^T J over the residuals of a block, minimal Jacobians at the current values, no loss.
   // Answered from the window's last all-blocks pass (lhs.hip), which is kept until invalidateLhs() -- called by every entry point of

@@ -57,7 +57,7 @@ EXPORTS = [
     "svin_ba_current_keyframe_id", "svin_ba_current_frame_id", "svin_ba_frame_id_by_age", "svin_ba_is_keyframe",
     "svin_ba_is_in_imu_window", "svin_ba_frame_ids", "svin_ba_landmark_ids", "svin_ba_imu_propagation",
     "svin_ba_eval_reprojection", "svin_ba_observation_ids", "svin_ba_eval_factors", "svin_ba_linearize", "svin_ba_debug_reduced_solve", "svin_ba_debug_reduced_solve_ex", "svin_ba_debug_build_arrays", "svin_ba_debug_trust_region_step", "svin_ba_debug_set_switch", "svin_ba_debug_set_option", "svin_ba_debug_get_option", "svin_ba_debug_sym_eig", "svin_ba_get_path_counters", "svin_ba_debug_landmark_handles", "svin_ba_wait_idle", "svin_ba_debug_peek_solver_scratch",
-    "svin_ba_get_prior", "svin_ba_describe_block", "svin_ba_bench_jacobian_eval", "svin_ba_bench_jacobian_eval_b2b", "svin_ba_set_pack_mode", "svin_ba_debug_csr", "svin_ba_residual_info",
+    "svin_ba_get_prior", "svin_ba_get_prior_lin", "svin_ba_describe_block", "svin_ba_bench_jacobian_eval", "svin_ba_bench_jacobian_eval_b2b", "svin_ba_set_pack_mode", "svin_ba_debug_csr", "svin_ba_residual_info",
     "svin_ba_map_add_parameter_block", "svin_ba_set_parameter_block", "svin_ba_map_remove_parameter_block", "svin_ba_map_add_pose_error",
     "svin_ba_map_add_speed_and_bias_error", "svin_ba_map_add_relative_pose_error", "svin_ba_map_add_reprojection_error",
     "svin_ba_map_add_imu_error", "svin_ba_map_add_sonar_error", "svin_ba_map_add_depth_error", "svin_ba_map_add_host_residual",
@@ -177,6 +177,7 @@ def load_library():
     sig("svin_ba_wait_idle", i32, vp)
     sig("svin_ba_debug_peek_solver_scratch", i32, vp, u64, u64, pd)
     sig("svin_ba_get_prior", i32, vp, pd, pd, pd, pd, pu64, pi32, pi32, pi32, i32)
+    sig("svin_ba_get_prior_lin", i32, vp, pd, i32)
     sig("svin_ba_describe_block", i32, vp, u64, pu64, pi32, pi32)
     sig("svin_ba_get_lhs", i32, vp, u64, pd, i32)
     sig("svin_ba_get_lhs_blocks", C.c_int64, vp, i32, pu64, pi32, pd, C.c_int64)
@@ -933,10 +934,12 @@ class Estimator:
         H, b0, J, e0 = np.zeros((n, n)), np.zeros(n), np.zeros((n, n)), np.zeros(n)
         self.L.svin_ba_get_prior(self.h, _d(H), _d(b0), _d(J), _d(e0), ids.ctypes.data_as(pu64), ordr.ctypes.data_as(pi32),
                                  md.ctypes.data_as(pi32), C.byref(nb), n)
+        lin = np.zeros((max(nb.value, 1), 9))
+        assert self.L.svin_ba_get_prior_lin(self.h, _d(lin), nb.value) == nb.value
         blocks = []
         for i in range(nb.value):
             d = self.describe_block(ids[i])
-            blocks.append(dict(id=int(ids[i]), ordering=int(ordr[i]), mdim=int(md[i]), frame=d[0] if d else None,
+            blocks.append(dict(id=int(ids[i]), ordering=int(ordr[i]), mdim=int(md[i]), lin=lin[i].copy(), frame=d[0] if d else None,
                                kind=d[1] if d else None, index=d[2] if d else None))
         return dict(n=n, H=H, b0=b0, J=J, e0=e0, blocks=blocks)
 

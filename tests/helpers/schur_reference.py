@@ -57,8 +57,8 @@ eps = 2^-52 (np.finfo(np.float64).eps).  The same bound with the long-double eps
 its error is at most (eps_ld / eps) tol = 2^-11 tol, which `assemble` asserts to be below tol / 1000.
 
 Not covered by what is compared through this helper or through step_reference.py (the post-solve pass and the dogleg step, which
-build on it): the batched Schur form (k_schur_dense_batch), the sharded path, and a marginalisation prior away from its
-linearisation point (`prior` below is the prior AT that point).
+build on it): the batched Schur form (k_schur_dense_batch) and the sharded path.  (The marginalisation prior away from its
+linearisation point: prior_reference.py, whose result `prior` below takes.)
 """
 import numpy as np
 
@@ -122,8 +122,10 @@ def assemble(records, blocks, mu, dtype=LD, prior=None):
     blocks: [(key, offset, dim)] of the variable camera-side blocks, in the order and at the offsets of the system to compare with.
     prior: None or (H, b0, c0, columns): the marginalisation prior as the quadratic form the device adds at the prior's linearisation
     point -- H into A (and its diagonal into hC), b0 into the gradient, c0 into the cost; columns[i] = the row of the system that
-    row i of the prior belongs to, or -1 (a constant block).  One term per entry, M = |H|, |b0|.  A prior away from its
-    linearisation point (M3 != I, dchi != 0) is not covered.
+    row i of the prior belongs to, or -1 (a constant block).  One term per entry, M = |H|, |b0|.  Or the dict of
+    prior_reference.moved(): the prior at the blocks' current values, away from its linearisation point (M3 != I, dchi != 0) -- M^T H M
+    into A, M^T grad into the gradient, its cost into the cost, each with its number of terms and absolute sum; the first-order effect
+    of the float64 dchi and M (P_S, P_g, the cost's own bound) is added to the tolerances as it stands.
     Returns a dict: S, g, cost (dtype), d, per landmark V / b / kappa (dicts by landmark id), M_S / n_S / M_g / n_g, the
     conditioning sums K_S / K_g, tol_S / tol_g / tol_cost (float64 arrays) and ref_ratio (the reference's own error / tol)."""
     T = dtype
@@ -165,7 +167,23 @@ def assemble(records, blocks, mu, dtype=LD, prior=None):
             ng[idx] += m
         if lm is not None:
             by_lm.setdefault(lm, []).append((idx, Jc, Jl, r))
-    if prior is not None:
+    PS, Pg, tol_prior_cost = np.zeros((d, d), T), np.zeros(d, T), 0.0   # first-order propagation of a moved prior's dchi and M
+    if isinstance(prior, dict):
+        pc = prior["columns"]
+        sel = np.nonzero(pc >= 0)[0]
+        ix, ixp = np.ix_(pc[sel], pc[sel]), np.ix_(sel, sel)
+        A[ix] += np.asarray(prior["S"], T)[ixp]
+        MA[ix] += np.asarray(prior["M_S"], T)[ixp]
+        nS[ix] += prior["n_S"][ixp]
+        PS[ix] += np.asarray(prior["P_S"], T)[ixp]
+        gA[pc[sel]] += np.asarray(prior["g"], T)[sel]
+        Mg[pc[sel]] += np.asarray(prior["M_g"], T)[sel]
+        ng[pc[sel]] += prior["n_g"][sel]
+        Pg[pc[sel]] += np.asarray(prior["P_g"], T)[sel]
+        cost += T(prior["cost"])
+        n_cost += 1
+        tol_prior_cost = prior["tol_cost"]
+    elif prior is not None:
         pc = np.asarray(prior[3])
         sel = np.nonzero(pc >= 0)[0]
         ix = np.ix_(pc[sel], pc[sel])
@@ -244,10 +262,12 @@ def assemble(records, blocks, mu, dtype=LD, prior=None):
     S[np.arange(d), np.arange(d)] += damp
     MS[np.arange(d), np.arange(d)] += np.abs(damp)
     accS[np.arange(d), np.arange(d)] += np.abs(damp)
-    tol_S = EPS64 * np.minimum(np.asarray((nS + C0) * MS + KS, np.float64), np.asarray(RS + (npS + C0) * accS + KS, np.float64))
-    tol_g = EPS64 * np.minimum(np.asarray((ng + C0) * Mg + Kg, np.float64), np.asarray(Rg + (npg + C0) * accg + Kg, np.float64))
+    PS[np.arange(d), np.arange(d)] *= 1 + float(mu)   # (the damping follows hC: d ht / d h <= 1)
+    tol_S = np.asarray(PS, np.float64) + EPS64 * np.minimum(np.asarray((nS + C0) * MS + KS, np.float64), np.asarray(RS + (npS + C0) * accS + KS, np.float64))
+    tol_g = np.asarray(Pg, np.float64) + EPS64 * np.minimum(np.asarray((ng + C0) * Mg + Kg, np.float64), np.asarray(Rg + (npg + C0) * accg + Kg, np.float64))
     # every cost term is non-negative: M = cost; four roundings inside a term (two squares, their sum, the half / the logarithm)
-    tol_cost = EPS64 * (n_cost + 4) * float(cost)
+    # (a moved prior's term carries its own bound, prior_reference.moved: its products are not all positive)
+    tol_cost = EPS64 * (n_cost + 4) * float(cost) + tol_prior_cost
     ref_ratio = np.finfo(T).eps / EPS64
     if T is LD:
         assert ref_ratio < 1e-3, "long double is not wider than double here"

@@ -44,16 +44,17 @@ quaternion -- normalisation (10 operations), exponential (12, with a sine and a 
 stepNormSq and xNormSq (`norms`) are sums of squares in ambient coordinates over the variable blocks and every landmark (the
 landmark's fourth coordinate is part of |x|^2) of the DEVICE's candidate: n non-negative terms, (n + 4) eps times the sum.
 
-The prior is the quadratic form J^T J, J^T e0 of est.marg() at its linearisation point: straight after the FIRST marginalisation of a
-window with nothing optimised in between (tests/test_gpu_lhs.py::test_lhs_with_marginalisation_prior_against_oracle sets that
-up).  A prior away from its linearisation point (M3 != I, dchi != 0) is NOT covered.  Neither are the batched Schur form and
-the sharded path.
+The prior is either the quadratic form J^T J, J^T e0 of est.marg() at its linearisation point -- straight after the FIRST
+marginalisation of a window with nothing optimised in between (tests/test_gpu_lhs.py::test_lhs_with_marginalisation_prior_against_oracle
+sets that up) -- or, away from that point (M3 != I, dchi != 0), the dict of prior_reference.moved(), whose docstring derives the
+bounds of what it adds here.  NOT covered: the batched Schur form and the sharded path.
 
 The same bounds with the long-double eps hold for this reference itself: its error is at most (eps_ld / eps) tol = 2^-11 tol,
 asserted to be below tol / 1000.
 """
 import numpy as np
 
+import prior_reference as pref
 import schur_reference as sr
 
 LD = sr.LD
@@ -138,8 +139,10 @@ def prior_columns(prior, blocks):
 
 
 def stage_a(P, mu, y_C, prior=None):
-    """prior: None or (J, e0, columns) of est.marg() with `columns` from prior_columns().  Returns {name: value}, {name: tol} and the per-record
-    products the second stage needs."""
+    """prior: None, or (J, e0, columns) of est.marg() with `columns` from prior_columns() -- the prior AT its linearisation point --, or
+    the dict of prior_reference.moved(): the prior at the blocks' current values (M^T grad into g, the diagonal of M^T H M into h, the
+    five sums through Mv and My; the first-order effect of the float64 dchi and M is carried into every bound).
+    Returns {name: value}, {name: tol} and the per-record products the second stage needs."""
     T = P.dtype
     mu = T(mu)
     d, L = P.d, P.L
@@ -158,7 +161,19 @@ def stage_a(P, mu, y_C, prior=None):
         np.add.at(Mg, cols, np.abs(J).T @ np.abs(r))
         np.add.at(h, cols, np.einsum("rk,rk->k", J, J))
         np.add.at(ng, cols, len(r))
-    if prior is not None:
+    Pg, Ph = np.zeros(d, T), np.zeros(d, T)   # a moved prior: what the float64 dchi and M do to g and h, to first order
+    moved = prior if isinstance(prior, dict) else None
+    if moved is not None:
+        pcm = moved["columns"]
+        selm = np.nonzero(pcm >= 0)[0]
+        np.add.at(g, pcm[selm], np.asarray(moved["g"], T)[selm])
+        np.add.at(Mg, pcm[selm], np.asarray(moved["M_g"], T)[selm])
+        np.add.at(ng, pcm[selm], moved["n_g"][selm])
+        np.add.at(Pg, pcm[selm], np.asarray(moved["P_g"], T)[selm])
+        # h: the diagonal of M^T H M, at most nine terms that need not be positive: its own bound, relative to the sum h
+        np.add.at(h, pcm[selm], np.diag(np.asarray(moved["S"], T))[selm])
+        np.add.at(Ph, pcm[selm], (np.diag(np.asarray(moved["P_S"], T)) + EPS * (9 + C0) * np.diag(np.asarray(moved["M_S"], T)))[selm])
+    elif prior is not None:
         Jp, e0, pc = np.asarray(prior[0], T), np.asarray(prior[1], T), np.asarray(prior[2])
         sel = pc >= 0
         Js, pcs = Jp[:, sel], pc[sel]
@@ -169,8 +184,9 @@ def stage_a(P, mu, y_C, prior=None):
         np.add.at(ng, pcs, m)
     ht = sr._metric(h)
     v = g / ht
-    dg = EPS * (ng + 1) * Mg
-    tol_vC = EPS * ((ng + 2) * Mg + (ng + 8) * np.abs(g)) / ht
+    dg = EPS * (ng + 1) * Mg + Pg
+    rel_ht = Ph / ht                                  # (d ht / d h <= 1: ht = h between the clamps)
+    tol_vC = EPS * ((ng + 2) * Mg + (ng + 8) * np.abs(g)) / ht + Pg / ht + np.abs(g) / ht * rel_ht
     # landmarks
     V, b, Mb = np.zeros((L, 3, 3), T), np.zeros((L, 3), T), np.zeros((L, 3), T)
     R, nt = np.zeros(L, np.int64), np.zeros(L, np.int64)
@@ -214,7 +230,7 @@ def stage_a(P, mu, y_C, prior=None):
         jv, jy = J @ v[cols], J @ y[cols]
         rows.append((jv, jy, r, EPS * (len(cols) + 2) * (aJ @ np.abs(v[cols])) + aJ @ tol_vC[cols],
                      EPS * (len(cols) + 2) * (aJ @ np.abs(y[cols])), np.abs(jv), np.abs(jy)))
-    if prior is not None:
+    if prior is not None and moved is None:
         # the device forms v^T (J^T J) v with J^T J and J^T e0 computed beforehand: the products of a row are summed over the rows
         # first, so a row's magnitude is |J| |v|, not |J v|, and every term passes through 2 m products
         aJ = np.abs(Js)
@@ -222,7 +238,7 @@ def stage_a(P, mu, y_C, prior=None):
         rows.append((Js @ v[pcs], Js @ y[pcs], e0, EPS * (2 * m + 2) * mv + aJ @ tol_vC[pcs], EPS * (2 * m + 2) * my, mv, my))
     Jv_, Jy_, r_, Ev_, Ey_, aJv, aJy = [np.concatenate(x) for x in zip(*rows)]
     n_rows = len(r_)
-    assert n_rows == P.n_rows + (len(e0) if prior is not None else 0)
+    assert n_rows == P.n_rows + (len(e0) if prior is not None and moved is None else 0)
     val, tol = {}, {}
 
     def put(name, value, prop, M, n):
@@ -232,16 +248,23 @@ def stage_a(P, mu, y_C, prior=None):
                 jvDotJy=(Jv_ @ Jy_, aJv @ Ey_ + aJy @ Ev_, aJv @ aJy), jvDotR=(Jv_ @ r_, Ev_ @ ar_, aJv @ ar_),
                 jyDotR=(Jy_ @ r_, Ey_ @ ar_, aJy @ ar_))
     n_sum = n_rows
+    prior_aux = None if prior is None else (Js, e0, pcs) if moved is None else moved
+    if moved is not None:
+        # the prior's part of a sum is formed by itself (n_p terms of absolute sum M_p) and is then one more term of the sum
+        extra, _ = pref.post_sums(moved, v, y, tol_vC)
+        sums = {name: (value + extra[name][0], prop + extra[name][1] + EPS * (extra[name][3] + C0) * extra[name][2], M + extra[name][2])
+                for name, (value, prop, M) in sums.items()}
+        n_sum += 1
     for name, (value, prop, M) in sums.items():
         put(name, value, prop, M, n_sum)
     # scaled-gradient norms
     n_acc = d + 3 * L
     ag, ab, ay, ayl = np.abs(g), np.abs(b), np.abs(y), np.abs(yl)
     put("gHatSq", (g * g / ht).sum() + (b * b / htL).sum(),
-        (2 * ag * dg / ht + EPS * (ng + 10) * g * g / ht).sum() + (2 * ab * dbl / htL + EPS * (R + 10)[:, None] * b * b / htL).sum(),
+        (2 * ag * dg / ht + (EPS * (ng + 10) + rel_ht) * g * g / ht).sum() + (2 * ab * dbl / htL + EPS * (R + 10)[:, None] * b * b / htL).sum(),
         (g * g / ht).sum() + (b * b / htL).sum(), n_acc)
     put("gnHatSq", (ht * y * y).sum() + (htL * yl * yl).sum(),
-        (EPS * (ng + 10) * ht * y * y).sum() + (2 * htL * ayl * tol_yl + EPS * (R + 10)[:, None] * htL * yl * yl).sum(),
+        ((EPS * (ng + 10) + rel_ht) * ht * y * y).sum() + (2 * htL * ayl * tol_yl + EPS * (R + 10)[:, None] * htL * yl * yl).sum(),
         (ht * y * y).sum() + (htL * yl * yl).sum(), n_acc)
     put("gDotGn", -((g * y).sum() + (b * yl).sum()),
         (ay * dg + EPS * ag * ay).sum() + (ayl * dbl + ab * tol_yl + 3 * EPS * ab * ayl).sum(), (ag * ay).sum() + (ab * ayl).sum(), n_acc)
@@ -253,7 +276,7 @@ def stage_a(P, mu, y_C, prior=None):
     if T is LD:
         assert ref_ratio < 1e-3, "long double is not wider than double here"
     aux = dict(kappa=kappa, ht_C=ht, ht_L=htL, g=g, b=b, X=X, V=V, ref_ratio=ref_ratio, n_rows=n_sum,
-               prior=None if prior is None else (Js, e0, pcs))
+               prior=prior_aux)
     return val, tol, aux
 
 
@@ -332,7 +355,7 @@ def pose_oplus(x, delta):
 def stage_b(P, scal, radius, y_C, v_C, y_L, v_L, x_blocks, lm_x, tol_a, prior=None):
     """scal: the device's group B by field name; y / v: the device's vectors; x_blocks: [(key, values)] of every block of the
     window at the linearisation point (a key that is not in the block table is a constant block); lm_x: L x 4 in P.lm_ids order;
-    tol_a: Stage A's tolerances (for the direct J delta sums); prior: the triple Stage A returned in aux["prior"]."""
+    tol_a: Stage A's tolerances (for the direct J delta sums); prior: what Stage A returned in aux["prior"]."""
     T = P.dtype
     x9 = [float(scal[k]) for k in GROUP_B] + [float(radius)]
     branch = code_branch(x9)
@@ -351,7 +374,11 @@ def stage_b(P, scal, radius, y_C, v_C, y_L, v_L, x_blocks, lm_x, tol_a, prior=No
     parts = [(Jd.reshape(-1), P.r.reshape(-1))] + [(J @ dC[cols], r) for r, cols, J in P.facs]
     Jd_, r_ = [np.concatenate(x) for x in zip(*parts)]
     jd_sq, jd_r = Jd_ @ Jd_, Jd_ @ r_
-    if prior is not None:
+    if isinstance(prior, dict):
+        (sq, _, _, _), (dr, _, _, _) = [pref.post_sums(prior, dC, dC, np.zeros(P.d))[0][k] for k in ("jgSq", "jvDotR")]
+        jd_sq += sq
+        jd_r += dr
+    elif prior is not None:
         Js, e0, pcs = prior
         jd_sq += (Js @ dC[pcs]) @ (Js @ dC[pcs])
         jd_r += (Js @ dC[pcs]) @ e0

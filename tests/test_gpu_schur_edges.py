@@ -10,8 +10,8 @@ them, and every entry of linearize()'s S (both triangles: every form writes both
 rounding bound, the cost inside its own.  The form that ran is read from the library (SVIN_LAST_SCHUR_FORM) and asserted.  The
 printed `error / tol` ratios are a record, not the criterion.
 
-Not covered here: the batched Schur form (k_schur_dense_batch), the sharded path, and a marginalisation prior away from its
-linearisation point.  (The landmark back-substitution and the rest of k_post_solve: tests/test_gpu_step_edges.py.)
+Not covered here: the batched Schur form (k_schur_dense_batch) and the sharded path.  (The landmark back-substitution and the rest
+of k_post_solve: tests/test_gpu_step_edges.py; a marginalisation prior away from its linearisation point: tests/test_gpu_prior_edges.py.)
 """
 import os
 import sys

@@ -16,9 +16,12 @@ for, the hook's y_C must agree with debug_reduced_solve(fused) to the bound of t
 the forms must agree bit for bit wherever they started from the same bits, and all three dogleg branches must have run.  With
 commit the getters return the candidate bit for bit and the hook's candidate cost lies inside the cost bound of
 schur_reference.assemble at the committed state.  The printed `error / tol` ratios are a record, not the criterion.
+test_step_with_moved_prior runs the same on windows whose marginalisation prior lies away from its linearisation point (the last block
+of k_post_solve with M3 != I and grad = b0 + H dchi, tests/helpers/prior_reference.py), and holds a second linearize() at the
+committed state to assemble() there.
 
 The batched kernels are held bit for bit to these forms by tests/test_gpu_batch*.py.  Not covered: the sharded path, the batched
-Schur form, a marginalisation prior away from its linearisation point."""
+Schur form."""
 import os
 import sys
 import time
@@ -153,7 +156,9 @@ def run_case(name, est, design, mus, expect, debug_option, prior_of=None):
         assert dy < (1e-10 if mu >= 1e-4 else 1e-6), dy
         va = cache[first["y_C"].tobytes()][0]
         gn, ag = float(np.sqrt(va["gnHatSq"])), float(va["gHatSq"] * np.sqrt(va["gHatSq"]) / va["jgSq"])
-        assert ag < gn
+        # (a state moved far from a prior of 1e8 and more: the scaled gradient and the Gauss-Newton step are all but parallel and the
+        # Cauchy point may lie beyond the Gauss-Newton step; then no radius interpolates)
+        assert ag < gn or expect.get("prior_dominates")
         radii = [2 * gn, 0.5 * ag] + [float(x) for x in np.linspace(ag, gn, 5)[1:4]] + [float(np.sqrt(np.float64(first["scalars"]["gnHatSq"])))]
         forms = [DEFERRED, SEPARATE] + ([] if expect.get("no_fused_tail") else [FUSED])
         if expect.get("no_fused_tail"):
@@ -183,7 +188,7 @@ def run_case(name, est, design, mus, expect, debug_option, prior_of=None):
                 else:
                     print("%s radius %.6g: forms %d and %d started from different bits (the build's sums are not ordered); candidates %d ulp apart" %
                           (name, radius, forms[0], form, ulps))
-        assert branches == {st.NEWTON, st.CAUCHY, st.INTERP}, branches
+        assert branches == ({st.NEWTON, st.CAUCHY, st.INTERP} if ag < gn else {st.NEWTON, st.CAUCHY}), branches
         record[mu] = worst
         print("%s mu %g: worst error / tol  %s  (max kappa %.3g, %d calls, %d distinct y_C)" %
               (name, mu, "  ".join("%s %.3g" % kv for kv in sorted(worst.items())), float(aux["kappa"].max()), 1 + len(radii) * len(forms), len(cache)))
@@ -198,12 +203,19 @@ def run_case(name, est, design, mus, expect, debug_option, prior_of=None):
     lin = est.linearize(mu)
     kinds = [describe(int(b))[1] for b in lin["block_ids"]]
     blocks = [((KIND[k], int(b)), int(o), DIM[k]) for b, o, k in zip(lin["block_ids"], lin["block_off"], kinds)]
-    # (with a prior the committed state lies away from the prior's linearisation point: its cost term is out of the reference's scope)
-    rf = sr.assemble(recs2, blocks, mu) if prior_of is None else None
+    # (a prior handed over AT its linearisation point: the committed state lies away from that point and is out of that form's scope;
+    # the moved form of prior_reference is evaluated again at the committed state)
+    prior2 = None if prior_of is None else prior_of(blocks)
+    rf = sr.assemble(recs2, blocks, mu, prior=prior2) if prior2 is None or isinstance(prior2, dict) else None
     if rf is not None:
         rc = abs(res["scalars"]["cost"] - float(rf["cost"])) / rf["tol_cost"]
         print("%s: candidate cost against the committed state: error / tol %.3g" % (name, rc))
         assert rc <= 1.0
+    if isinstance(prior2, dict):   # the build at the committed state: it consumes what the candidate evaluation left (dchi, grad, M3)
+        rS, rg = sr.worst_ratio(lin["S"], lin["g"], rf)
+        rc = abs(lin["cost"] - float(rf["cost"])) / rf["tol_cost"]
+        print("%s: linearize() at the committed state: worst error / tol  S %.3g  g %.3g  cost %.3g" % (name, rS, rg, rc))
+        assert rS <= 1.0 and rg <= 1.0 and rc <= 1.0, "the reduced system at the committed state leaves its rounding bound"
     print("%s: %.1f s" % (name, time.time() - t_start))
     return record
 
@@ -251,3 +263,41 @@ def test_step_with_marginalisation_prior(gpu_lib, debug_option):
         run_case("prior_P7", est, None, (1e-4,), dict(), debug_option, prior_of=prior_of)
     syn.feed(est, spec, on_frame=on_frame)
     assert done, "no marginalisation happened"
+
+
+@pytest.mark.parametrize("name,move", [(n, m) for n in ("euroc_P7", "rig_v2_P9") for m in ("optimised", "large")])
+def test_step_with_moved_prior(gpu_lib, debug_option, name, move):
+    """the windows of tests/test_gpu_prior_edges.py with the prior away from its linearisation point -- moved by hand (`large`) or by one
+    more frame and optimize(3) (`optimised`): k_post_solve's last block forms (Mv)^T H (Mv), (Mv)^T grad and their y counterparts with
+    M3 != I, the candidate evaluation writes the prior's dchi / grad / M3 of the candidate, and the build after the commit consumes them"""
+    if not sr.have_long_double():
+        pytest.skip("np.longdouble is not wider than float64 on this machine")
+    import prior_moves as pm
+    import prior_reference as pr
+    import test_gpu_prior_edges as pe
+    from svin_amd.estimator import Estimator
+    est = Estimator(0)
+    ran = []
+
+    def run():
+        prior = pe.device_prior(est)
+
+        def prior_of(blocks):
+            ref = pe.moved_prior(est, prior, blocks)
+            assert (ref["columns"] >= 0).sum() >= 6 and float(np.abs(ref["dchi"]).max()) > 1e-9, "the prior sits at its linearisation point"
+            return ref
+        run_case("%s_%s" % (name, move), est, None, (1e-4,), dict(ext_variable=name.startswith("rig_v2"), prior_dominates=move == "large"), debug_option,
+                 prior_of=prior_of)
+        ran.append(move)
+
+    def at_prior(before):
+        if move == "large":
+            rows = [(pr.KIND_OF[b["kind"]], b["id"]) for b in est.marg()["blocks"] if b["mdim"] > 0]
+            pm.apply("large", rows, est.get_parameter_block, est.set_parameter_block)
+            run()
+            raise pe.Done
+
+    def at_optimised():
+        run()
+    pe.slide(est, name, at_prior, at_optimised)
+    assert ran == [move]
