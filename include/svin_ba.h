@@ -30,6 +30,7 @@ typedef struct svin_ba svin_ba;
 #define SVIN_ERR_NOT_FOUND (-2)
 #define SVIN_ERR_DEVICE (-3)
 #define SVIN_ERR_UNSUPPORTED (-4)
+#define SVIN_ERR_SINGULAR (-5)   /* svin_ba_get_covariance: J^T J is not positive definite (Covariance::Compute returning false) */
 
 /* distortion models (okvis_cv/include/okvis/cameras/ ...Distortion.hpp) */
 #define SVIN_DIST_NONE 0
@@ -278,6 +279,34 @@ int svin_ba_get_lhs(svin_ba* h, uint64_t block_id, double* H, int cap);
 int64_t svin_ba_get_lhs_blocks(svin_ba* h, int n, const uint64_t* block_ids, int32_t* dims, double* H, int64_t cap_doubles);
 /* inspection: the number of all-blocks getLhs passes the handle has run (a look-up does not count) */
 int64_t svin_ba_get_lhs_pass_count(svin_ba* h);
+/* Marginal covariances (Map::computeCovariance, Map.hpp:352-372, which runs ::ceres::Covariance and only prints the result).
+ * Let J be the stacked minimal Jacobian of every residual of the window at the current values, exactly as the trust-region build
+ * sees it: square-root information applied, loss corrector applied (::ceres::Covariance's default apply_loss_function = true),
+ * marginalisation prior, host residuals and HomogeneousPointErrors included, no columns for constant blocks.
+ * Sigma = (J^T J)^-1, in unscaled tangent coordinates (6 for pose and extrinsics blocks, 9 speed / bias, 3 landmarks), without
+ * damping and without the solver's Jacobi metric.  The covariance block of (a, b) is Sigma[a, b], dim(a) x dim(b), row-major; a
+ * constant block has zero covariance with everything (Ceres' convention); Sigma[b, a] equals Sigma[a, b]^T bit for bit, and two
+ * calls return the same bits.  By blocks, with S = A - W V^-1 W^T the reduced system (lower triangle, mirrored) and
+ * Y_l = V_l^-1 W_l^T:  Sigma_cc = S^-1,  Sigma_lc = -Y_l Sigma_cc,  Sigma_ll' = delta_ll' V_l^-1 + Y_l Sigma_cc Y_l'^T.
+ * If J^T J is not positive definite -- a landmark block (a landmark with one observation) or S itself (no gauge prior) -- the
+ * call returns SVIN_ERR_SINGULAR and svin_ba_last_error() names the first offending landmark id or "reduced system"; nothing is
+ * kept and the handle stays usable.  A pivot below 1e-12 of its block's scaled diagonal counts as not positive.
+ * The first call builds the window as svin_ba_linearize(h, 0, ...) does, runs one all-blocks pass on the device and keeps
+ * Sigma_cc and the diagonal block of every landmark; later calls are look-ups (pairs of a landmark with another block: one small
+ * launch on the kept Sigma_cc) until an entry point that can change a value, the graph, a parameterisation or the prior is called.
+ * A covariance call keeps the get_lhs result and a get_lhs call keeps the covariance; both wait for a running marginalisation
+ * job.  The window is left as svin_ba_linearize leaves it: a resident window stays resident, and a following svin_ba_optimize
+ * gives the states of a handle that never asked.
+ * get_covariance: returns rows * cols written; SVIN_ERR_INVALID_ARG if cap is smaller (nothing is written); SVIN_ERR_NOT_FOUND.
+ * get_covariance_blocks: n pairs back to back; cov == NULL only sizes (dims_a / dims_b are filled, either may be NULL); returns
+ * the total number of doubles.
+ * SVIN_ERR_UNSUPPORTED: landmark-sharded mode (world > 1), a window holding a block on a reduced pose manifold, a reduced
+ * system of more than 272 unknowns. */
+int svin_ba_get_covariance(svin_ba* h, uint64_t block_a, uint64_t block_b, double* cov, int cap);
+int64_t svin_ba_get_covariance_blocks(svin_ba* h, int n_pairs, const uint64_t* blocks_a, const uint64_t* blocks_b,
+                                      int32_t* dims_a, int32_t* dims_b, double* cov, int64_t cap_doubles);
+/* inspection: the number of all-blocks covariance passes the handle has run (a look-up does not count) */
+int64_t svin_ba_get_covariance_pass_count(svin_ba* h);
 /* Map::residuals(id) (src/Map.cpp:576-587): ids of every residual touching the block, in insertion order; returns the
  * count (may exceed cap), SVIN_ERR_NOT_FOUND for an unknown block */
 int svin_ba_residuals_of(svin_ba* h, uint64_t block_id, uint64_t* residual_ids, int cap);

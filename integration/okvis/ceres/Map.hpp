@@ -14,7 +14,8 @@
 //     (okvis_ceres/test/TestHomogeneousPointError.cpp:57-99, TestMap.cpp:60-150) builds its graph block by block, checks
 //     Jacobians with isJacobianCorrect, solves and reads the estimates back from its parameter-block objects.
 //   * ::ceres::Problem / Manifold pointers (DO_NOT_TAKE_OWNERSHIP plumbing, Map.cpp:59-64): there is no Ceres.
-//   * computeCovariance (Map.hpp:352-372): debug code of the reference, never called.
+//   * computeCovariance (Map.hpp:352-372) as a member that prints: the reference's own code only logs the result.  What it computes
+//     is here as getCovarianceBlock (svin_ba_get_covariance: the marginal covariance of any pair of blocks, on the device).
 #ifndef INTEGRATION_OKVIS_CERES_MAP_HPP_
 #define INTEGRATION_OKVIS_CERES_MAP_HPP_
 
@@ -373,6 +374,24 @@ class Map {
     H.resize(md, md);
     for (int i = 0; i < md; ++i)
       for (int j = 0; j < md; ++j) H(i, j) = buf[i * md + j];
+  }
+  /// What Map::computeCovariance (Map.hpp:352-372) asks of ::ceres::Covariance, for one pair of blocks: cov = Sigma[a, b] of
+  /// Sigma = (J^T J)^-1 (definition: svin_ba.h, svin_ba_get_covariance), dim(a) x dim(b) in minimal coordinates; zeros for a
+  /// constant block.  Returns false when J^T J is not positive definite (Covariance::Compute returning false; svin_ba_last_error()
+  /// names the block) and throws on every other error.  The first call runs one all-blocks pass on the device, later ones are
+  /// look-ups until something changes; MatrixT as for getLhs.
+  template <class MatrixT>
+  bool getCovarianceBlock(uint64_t parameterBlockIdA, uint64_t parameterBlockIdB, MatrixT& cov) const {
+    need();
+    double buf[81];
+    int32_t da = 0, db = 0;
+    const int64_t n = svin_ba_get_covariance_blocks(h_, 1, &parameterBlockIdA, &parameterBlockIdB, &da, &db, buf, 81);
+    if (n == SVIN_ERR_SINGULAR) return false;
+    if (n <= 0) throw std::runtime_error(std::string("svin_ba_get_covariance: ") + svin_ba_last_error());
+    cov.resize(da, db);
+    for (int i = 0; i < da; ++i)
+      for (int j = 0; j < db; ++j) cov(i, j) = buf[i * db + j];
+    return true;
   }
   /// Map::parameterBlockPtr (Map.hpp:166-170): a snapshot of the block (values, id, fixed, time stamp / initialised flag)
   std::shared_ptr<okvis::ceres::ParameterBlock> parameterBlockPtr(uint64_t id) const {

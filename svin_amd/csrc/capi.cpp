@@ -12,13 +12,14 @@ struct svin_ba {
   explicit svin_ba(int device) : w(device) {}
 };
 
-// The window keeps its last getLhs pass (Window::getLhs) until something changes.  An entry point that calls a NON-const method of
+// The window keeps its last getLhs pass (Window::getLhs) and its last covariance pass (Window::getCovarianceBlocks) until something changes.  An entry point that calls a NON-const method of
 // the window -- every setter, graph edit, parameterisation change, solve, marginalisation, and the inspection hooks that evaluate --
 // reaches it through win(), which drops that result; the look-ups (const methods: getters, graph queries, parameterBlockPtr's
 // svin_ba_get_parameter_block) go through ro(), which cannot call a non-const method, and keep it.  So the reference's landmark loop
 // (Estimator.cpp:902-923: getLhs, then parameterBlockPtr, per landmark) costs one pass.
 static inline Window& win(svin_ba* h) {
   h->w.invalidateLhs();
+  h->w.invalidateCovariance();
   return h->w;
 }
 static inline const Window& ro(const svin_ba* h) { return h->w; }
@@ -781,6 +782,19 @@ int64_t svin_ba_get_lhs_blocks(svin_ba* h, int n, const uint64_t* block_ids, int
   GUARD_END(SVIN_ERR_DEVICE)
 }
 int64_t svin_ba_get_lhs_pass_count(svin_ba* h) try { return h ? ro(h).lhsPassCount() : SVIN_ERR_INVALID_ARG; } CATCH_ALL(SVIN_ERR_DEVICE)
+// (like get_lhs: straight to the window, so that neither query drops what the other keeps)
+int svin_ba_get_covariance(svin_ba* h, uint64_t block_a, uint64_t block_b, double* cov, int cap) {
+  if (!h || !cov || cap < 0) return SVIN_ERR_INVALID_ARG;
+  GUARD_BEGIN return (int)h->w.getCovarianceBlocks(1, &block_a, &block_b, nullptr, nullptr, cov, cap);
+  GUARD_END(SVIN_ERR_DEVICE)
+}
+int64_t svin_ba_get_covariance_blocks(svin_ba* h, int n_pairs, const uint64_t* blocks_a, const uint64_t* blocks_b, int32_t* dims_a,
+                                      int32_t* dims_b, double* cov, int64_t cap_doubles) {
+  if (!h) return SVIN_ERR_INVALID_ARG;
+  GUARD_BEGIN return h->w.getCovarianceBlocks(n_pairs, blocks_a, blocks_b, dims_a, dims_b, cov, cap_doubles);
+  GUARD_END(SVIN_ERR_DEVICE)
+}
+int64_t svin_ba_get_covariance_pass_count(svin_ba* h) try { return h ? ro(h).covariancePassCount() : SVIN_ERR_INVALID_ARG; } CATCH_ALL(SVIN_ERR_DEVICE)
 int svin_ba_set_pack_mode(svin_ba* h, int mode) try {
   if (!h || mode < 0 || mode > 1) return SVIN_ERR_INVALID_ARG;
   win(h).setPackMode(mode);

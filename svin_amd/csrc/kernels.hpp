@@ -22,6 +22,7 @@
 #include "dmath.hpp"
 #include "options.hpp"
 #include "batch_plan.hpp"
+#include "cov_plan.hpp"
 #include "pack_plan.hpp"
 #include "solve_plan.hpp"
 
@@ -346,6 +347,15 @@ struct LhsBlock {
 };
 void launchLhsAll(const DeviceProblem& p, const LhsItem* items, int nItems, const LhsBlock* blocks, int nBlocks, const int2* facs,
                   double* partial, double* out, size_t lmOut, hipStream_t s);
+// ---- marginal covariances (cov.hip; layout of `buf` and launch sizes: cov_plan.hpp planCovariance).  The pass reads what a build
+// with mu = 0 left in `p` (S, the Jacobian arrays of the current point) and fills Sigma_cc, every landmark's diagonal block and the
+// flags (int 0: bit 1 a landmark block / bit 2 the reduced system is not positive definite; int 1: L - the first such landmark).
+// A pair: kind 0 (landmark lm, camera-side or speed / bias block at reduced row `other`, md columns) -> 3 x md; kind 1
+// (landmarks lm, other) -> 3 x 3 WITHOUT the delta term; row-major at out[out ..).
+struct CovPair { int kind, lm, other, md, out, pad; };
+void launchCovariancePass(const DeviceProblem& p, const CovPlan& q, double* buf, hipStream_t s);
+void launchCovariancePairs(const DeviceProblem& p, const CovPlan& q, const double* buf, const CovPair* pairs, int nPairs, double* out,
+                           hipStream_t s);
 // Jacobian-evaluation micro-benchmark entry: B independent copies of the observation set
 void launchEvalReprojBatched(const DeviceProblem& p, int copies, double* rOut, double* JpOut, double* JlOut,
                              double* JeOut, hipStream_t s);

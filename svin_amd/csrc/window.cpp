@@ -14,6 +14,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <dlfcn.h>
+#include <climits>
 #include <limits>
 #include <map>
 #include <mutex>
@@ -3279,6 +3280,177 @@ long long Window::getLhsBlocks(int n, const uint64_t* ids, int32_t* dims, double
     if (it == lhsOff_.end()) std::fill(q, q + md * md, 0.0);
     else std::memcpy(q, lhsHost_.data() + it->second, sizeof(double) * md * md);
     q += md * md;
+  }
+  return total;
+}
+
+// ------------------------------------------------------------------------------------------ marginal covariances (cov.hip)
+// One pass over the whole window: the build of linearize(0, ...) -- the undamped reduced system and the Jacobian arrays of the
+// current point, the window left as that entry point leaves it -- then the factor of the scaled S, its inverse panel by panel
+// and the landmark pass.  Nothing is kept when a block is not positive definite.
+int Window::computeCovariance() {
+  // the refusals first, from the host graph (what pack() will number): no build is spent on a call that is refused
+  {
+    int dHost = 0;
+    bool locked = false;
+    for (const auto& kv : blocks_) {
+      const Block& b = kv.second;
+      if (b.fixed) continue;
+      dHost += b.kind == B_SB ? 9 : 6;
+      locked = locked || (b.kind != B_SB && b.lock != 0);
+    }
+    if (locked) {
+      lastError() = "get_covariance: the window holds a block on a reduced pose manifold";
+      return -4 /* SVIN_ERR_UNSUPPORTED */;
+    }
+    if (dHost > kCovMaxD) {
+      lastError() = "get_covariance: the reduced system has " + std::to_string(dHost) + " unknowns (at most " + std::to_string(kCovMaxD) + ")";
+      return -4 /* SVIN_ERR_UNSUPPORTED */;
+    }
+  }
+  linearize(0.0, nullptr, nullptr, nullptr, nullptr, nullptr, INT_MAX, nullptr);
+  const DeviceProblem& p = prob_;
+  hipStream_t s = stream_;
+  if (p.nLocked > 0) {   // (what the packed problem says is what counts)
+    lastError() = "get_covariance: the window holds a block on a reduced pose manifold";
+    return -4 /* SVIN_ERR_UNSUPPORTED */;
+  }
+  const CovPlan q = planCovariance(p.d, p.dC, p.L);
+  if (!q.supported) {
+    lastError() = "get_covariance: the reduced system has " + std::to_string(p.d) + " unknowns (at most " + std::to_string(kCovMaxD) + ")";
+    return -4 /* SVIN_ERR_UNSUPPORTED */;
+  }
+  dCov_.reserve(std::max<size_t>(q.end, 1));
+  launchCovariancePass(p, q, dCov_.p, s);
+  int flags[kCovFlagInts] = {0, 0, 0, 0};
+  covSigma_.assign(q.sigma.len, 0.0);
+  covLmDiag_.assign(q.lmCov.len, 0.0);
+  HIP_OK(hipMemcpyAsync(flags, dCov_.p + q.flags.off, sizeof(flags), hipMemcpyDeviceToHost, s));
+  if (q.sigma.len > 0) HIP_OK(hipMemcpyAsync(covSigma_.data(), dCov_.p + q.sigma.off, sizeof(double) * q.sigma.len, hipMemcpyDeviceToHost, s));
+  if (q.lmCov.len > 0) HIP_OK(hipMemcpyAsync(covLmDiag_.data(), dCov_.p + q.lmCov.off, sizeof(double) * q.lmCov.len, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipStreamSynchronize(s));
+  // landmarks in CSR order (as observationIds lists them)
+  covLm_.clear();
+  std::vector<uint64_t> lmOrder;
+  if (residentUsed_) {
+    for (const Landmark* lp : lmByHandle_)
+      if (lp && !lp->obs.empty()) lmOrder.push_back(lp->id);
+  } else {
+    lmOrder = lmIds_;
+  }
+  if ((int)lmOrder.size() != p.L) throw std::logic_error("computeCovariance: landmark table and device count disagree");
+  if (flags[0] & 1) {
+    lastError() = "get_covariance: J^T J is not positive definite at landmark " + std::to_string(lmOrder.at((size_t)(p.L - flags[1])));
+    return -5 /* SVIN_ERR_SINGULAR */;
+  }
+  if (flags[0] & 2) {
+    lastError() = "get_covariance: J^T J is not positive definite: reduced system";
+    return -5 /* SVIN_ERR_SINGULAR */;
+  }
+  for (size_t l = 0; l < lmOrder.size(); ++l) covLm_[lmOrder[l]] = (int)l;
+  covOff_.clear();
+  for (size_t k = 0; k < redBlockIds_.size(); ++k) covOff_[redBlockIds_[k]] = redBlockOff_[k];
+  covPlan_ = q;
+  covValid_ = true;
+  ++covPasses_;
+  return 1;
+}
+long long Window::getCovarianceBlocks(int n, const uint64_t* idsA, const uint64_t* idsB, int32_t* dimsA, int32_t* dimsB, double* cov,
+                                      long long capDoubles) {
+  if (world_ > 1 || rcclComm_) {
+    lastError() = "get_covariance: not available in landmark-sharded mode";
+    return -4 /* SVIN_ERR_UNSUPPORTED */;
+  }
+  if (n < 0 || (n > 0 && (!idsA || !idsB))) return -1 /* SVIN_ERR_INVALID_ARG */;
+  quiesce();
+  long long total = 0;
+  for (int i = 0; i < n; ++i) {
+    const int ma = lhsDim(idsA[i]), mb = lhsDim(idsB[i]);
+    if (ma == 0 || mb == 0) return -2 /* SVIN_ERR_NOT_FOUND */;
+    if (dimsA) dimsA[i] = ma;
+    if (dimsB) dimsB[i] = mb;
+    total += (long long)ma * mb;
+  }
+  if (!cov) return total;
+  if (capDoubles < total) return -1 /* SVIN_ERR_INVALID_ARG */;
+  if (!covValid_) {
+    const int rc = computeCovariance();
+    if (rc < 0) return rc;
+  }
+  const DeviceProblem& p = prob_;
+  const int d = p.d;
+  // a block as the pass knows it: a row of the reduced system, a landmark of the device table, or neither (zero covariance)
+  struct Side { int md, off, lm; };
+  auto sideOf = [&](uint64_t id, Side& sd) -> int {
+    sd = Side{lhsDim(id), -1, -1};
+    if (const Block* b = findBlock(id)) {
+      auto it = covOff_.find(id);
+      if (!b->fixed && it != covOff_.end()) sd.off = it->second;
+      return 1;
+    }
+    const Landmark& lm = landmarks_.at(id);
+    if (lm.fixed) return 1;
+    auto it = covLm_.find(id);
+    if (it == covLm_.end()) {   // no residual touches it: its block of J^T J is zero
+      lastError() = "get_covariance: J^T J is not positive definite at landmark " + std::to_string(id);
+      return -5 /* SVIN_ERR_SINGULAR */;
+    }
+    sd.lm = it->second;
+    return 1;
+  };
+  // pairs with a landmark on one side and another block on the other go to the device in one launch
+  struct Todo { double* dst; int rows, cols; bool transposed; int out; };
+  std::vector<CovPair> pairs;
+  std::vector<Todo> todo;
+  int outAt = 0;
+  double* dst = cov;
+  std::vector<Side> sides(2 * (size_t)n);
+  for (int i = 0; i < n; ++i) {   // every block first: an error leaves cov untouched
+    int rc = sideOf(idsA[i], sides[2 * (size_t)i]);
+    if (rc < 0) return rc;
+    rc = sideOf(idsB[i], sides[2 * (size_t)i + 1]);
+    if (rc < 0) return rc;
+  }
+  for (int i = 0; i < n; ++i) {
+    const Side a = sides[2 * (size_t)i], b = sides[2 * (size_t)i + 1];
+    const int sz = a.md * b.md;
+    std::fill(dst, dst + sz, 0.0);
+    if (a.off >= 0 && b.off >= 0) {
+      for (int r = 0; r < a.md; ++r) std::memcpy(dst + (size_t)r * b.md, covSigma_.data() + (size_t)(a.off + r) * d + b.off, sizeof(double) * b.md);
+    } else if (a.lm >= 0 && b.lm >= 0 && a.lm == b.lm) {
+      std::memcpy(dst, covLmDiag_.data() + (size_t)9 * a.lm, sizeof(double) * 9);
+    } else if (a.lm >= 0 && b.lm >= 0) {   // computed for the landmark that comes first on the device; the other order is its transpose
+      const bool swap = a.lm > b.lm;
+      pairs.push_back(CovPair{1, swap ? b.lm : a.lm, swap ? a.lm : b.lm, 3, outAt, 0});
+      todo.push_back(Todo{dst, 3, 3, swap, outAt});
+      outAt += 9;
+    } else if (a.lm >= 0 && b.off >= 0) {
+      pairs.push_back(CovPair{0, a.lm, b.off, b.md, outAt, 0});
+      todo.push_back(Todo{dst, 3, b.md, false, outAt});
+      outAt += 3 * b.md;
+    } else if (a.off >= 0 && b.lm >= 0) {
+      pairs.push_back(CovPair{0, b.lm, a.off, a.md, outAt, 0});
+      todo.push_back(Todo{dst, a.md, 3, true, outAt});
+      outAt += 3 * a.md;
+    }   // (else: a constant block on either side)
+    dst += sz;
+  }
+  if (!pairs.empty()) {
+    hipStream_t s = stream_;
+    dCovPairs_.reserve(pairs.size());
+    dCovPairOut_.reserve((size_t)outAt);
+    std::vector<double> host((size_t)outAt);
+    HIP_OK(hipMemcpyAsync(dCovPairs_.p, pairs.data(), sizeof(CovPair) * pairs.size(), hipMemcpyHostToDevice, s));
+    launchCovariancePairs(p, covPlan_, dCov_.p, dCovPairs_.p, (int)pairs.size(), dCovPairOut_.p, s);
+    HIP_OK(hipMemcpyAsync(host.data(), dCovPairOut_.p, sizeof(double) * host.size(), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    for (const Todo& t : todo) {
+      const double* src = host.data() + t.out;
+      if (!t.transposed) std::memcpy(t.dst, src, sizeof(double) * t.rows * t.cols);
+      else   // src is cols x rows
+        for (int r = 0; r < t.rows; ++r)
+          for (int c = 0; c < t.cols; ++c) t.dst[r * t.cols + c] = src[c * t.rows + r];
+    }
   }
   return total;
 }

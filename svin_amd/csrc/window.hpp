@@ -377,6 +377,20 @@ class Window {
   long long getLhsBlocks(int n, const uint64_t* ids, int32_t* dims, double* H, long long capDoubles);
   void invalidateLhs() { lhsValid_ = false; }
   long long lhsPassCount() const { return lhsPasses_; }   // all-blocks passes run so far (inspection: one per change)
+  // Marginal covariances (cov.hip): Sigma[a, b] of Sigma = (J^T J)^-1, J the minimal Jacobian of every residual as the trust-region
+  // build sees it (square-root information and loss corrector applied, prior / host residuals / HomogeneousPointErrors included,
+  // no columns for constant blocks), unscaled tangent coordinates, undamped; a constant block has zero covariance with everything.
+  // The first call builds the window as linearize(0, ...) does and runs one all-blocks pass, which keeps Sigma_cc and every
+  // landmark's diagonal block (device and host); pairs of a landmark with another block are computed on request from the kept
+  // Sigma_cc.  Kept until invalidateCovariance(), which the C ABI calls wherever it calls invalidateLhs(); neither query drops
+  // the other's result.  getCovarianceBlocks: the pairs back to back, dimsA[i] x dimsB[i] row-major; returns the total
+  // (cov == nullptr: sizes only); SVIN_ERR_INVALID_ARG when capDoubles is too small, SVIN_ERR_NOT_FOUND, SVIN_ERR_UNSUPPORTED
+  // (sharded, a reduced pose manifold, d > kCovMaxD), SVIN_ERR_SINGULAR (lastError() names the first offending block or
+  // "reduced system"; nothing is kept).
+  long long getCovarianceBlocks(int n, const uint64_t* idsA, const uint64_t* idsB, int32_t* dimsA, int32_t* dimsB, double* cov,
+                                long long capDoubles);
+  void invalidateCovariance() { covValid_ = false; }
+  long long covariancePassCount() const { return covPasses_; }   // all-blocks passes run so far (a look-up does not count)
   const MargPre& margPre() const { return margPre_; }
   // Map::parameterBlockPtr / id2parameterBlockMap as values (Map.hpp:166-170, :188): type 0 pose, 1 extrinsics, 2 speed/bias,
   // 3 landmark; returns the ambient dimension (7 / 9 / 4) or SVIN_ERR_NOT_FOUND
@@ -616,6 +630,15 @@ class Window {
   DevBuf<LhsItem> dLhsItems_;
   DevBuf<LhsBlock> dLhsBlocks_;
   DevBuf<int2> dLhsFacs_;
+  int computeCovariance();         // the all-blocks pass: covSigma_ / covLmDiag_ / covOff_ / covLm_; 1 or an error code
+  bool covValid_ = false;
+  long long covPasses_ = 0;
+  CovPlan covPlan_{};
+  std::vector<double> covSigma_, covLmDiag_;       // host copies: Sigma_cc (d x d), the landmarks' diagonal blocks (9 each, CSR order)
+  std::unordered_map<uint64_t, int> covOff_;       // variable pose / extrinsics / speed-bias block -> its first row of the reduced system
+  std::unordered_map<uint64_t, int> covLm_;        // landmark on the device -> its CSR index
+  DevBuf<double> dCov_, dCovPairOut_;              // the window's covariance buffer (cov_plan.hpp), results of the requested pairs
+  DevBuf<CovPair> dCovPairs_;
 };
 
 std::string& lastError();

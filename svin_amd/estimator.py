@@ -77,12 +77,18 @@ EXPORTS = [
     "svin_host_manifold_minus_jacobian", "svin_ba_get_parameter_block", "svin_ba_parameter_block_ids",
     "svin_ba_get_all_landmark_observations", "svin_ba_bench_allreduce", "svin_ba_get_marg_pre", "svin_ba_get_marg_pre_blocks",
     "svin_ba_get_lhs", "svin_ba_get_lhs_blocks", "svin_ba_get_lhs_pass_count",
+    "svin_ba_get_covariance", "svin_ba_get_covariance_blocks", "svin_ba_get_covariance_pass_count",
     "svin_ba_map_set_residual_loss", "svin_ba_map_get_residual_loss",
     "svin_ba_map_set_reprojection_information", "svin_ba_map_get_reprojection_information",
 ]
 
 # residual loss functions (svin_ba_map_set_residual_loss): ceres::TrivialLoss, CauchyLoss(a), HuberLoss(a)
 SVIN_LOSS_NONE, SVIN_LOSS_CAUCHY, SVIN_LOSS_HUBER = 0, 1, 2
+SVIN_ERR_INVALID_ARG, SVIN_ERR_NOT_FOUND, SVIN_ERR_DEVICE, SVIN_ERR_UNSUPPORTED, SVIN_ERR_SINGULAR = -1, -2, -3, -4, -5
+
+
+class SingularError(RuntimeError):
+    """svin_ba_get_covariance: J^T J is not positive definite (SVIN_ERR_SINGULAR); the message names the block"""
 
 ID_PROVIDER_FN = C.CFUNCTYPE(C.c_uint64, C.c_void_p)
 
@@ -182,6 +188,9 @@ def load_library():
     sig("svin_ba_get_lhs", i32, vp, u64, pd, i32)
     sig("svin_ba_get_lhs_blocks", C.c_int64, vp, i32, pu64, pi32, pd, C.c_int64)
     sig("svin_ba_get_lhs_pass_count", C.c_int64, vp)
+    sig("svin_ba_get_covariance", i32, vp, u64, u64, pd, i32)
+    sig("svin_ba_get_covariance_blocks", C.c_int64, vp, i32, pu64, pu64, pi32, pi32, pd, C.c_int64)
+    sig("svin_ba_get_covariance_pass_count", C.c_int64, vp)
     sig("svin_ba_map_set_residual_loss", i32, vp, u64, i32, C.c_double)
     sig("svin_ba_map_get_residual_loss", i32, vp, u64, C.POINTER(C.c_int32), pd)
     sig("svin_ba_map_set_reprojection_information", i32, vp, u64, pd)
@@ -904,6 +913,38 @@ class Estimator:
         H = np.zeros(81)
         md = self._check(self.L.svin_ba_get_lhs(self.h, int(block_id), _d(H), 81), "get_lhs")
         return H[:md * md].reshape(md, md).copy()
+
+    def _check_cov(self, r, what):
+        if r == SVIN_ERR_SINGULAR:
+            raise SingularError("%s failed (%d): %s" % (what, r, self.L.svin_ba_last_error().decode()))
+        return self._check(r, what)
+
+    def get_covariance(self, block_a, block_b):
+        """Sigma[a, b] of Sigma = (J^T J)^-1 (include/svin_ba.h, svin_ba_get_covariance): (dim a, dim b), unscaled tangent
+        coordinates; zeros for a constant block.  Raises SingularError when J^T J is not positive definite.  The first call runs
+        one all-blocks pass; later ones are look-ups until something changes."""
+        return self.get_covariance_blocks([(block_a, block_b)])[0]
+
+    def get_covariance_blocks(self, pairs):
+        """get_covariance of every (a, b) of the list from one call: a list of matrices"""
+        pairs = [(int(a), int(b)) for a, b in pairs]
+        n = len(pairs)
+        ia = np.ascontiguousarray(np.array([a for a, _ in pairs] or [0], dtype=np.uint64))
+        ib = np.ascontiguousarray(np.array([b for _, b in pairs] or [0], dtype=np.uint64))
+        da, db = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+        args = (self.h, n, ia.ctypes.data_as(pu64), ib.ctypes.data_as(pu64), da.ctypes.data_as(pi32), db.ctypes.data_as(pi32))
+        total = self._check_cov(self.L.svin_ba_get_covariance_blocks(*args, None, 0), "get_covariance_blocks")
+        cov = np.zeros(max(total, 1))
+        self._check_cov(self.L.svin_ba_get_covariance_blocks(*args, _d(cov), total), "get_covariance_blocks")
+        out, o = [], 0
+        for r, c in zip(da[:n], db[:n]):
+            out.append(cov[o:o + r * c].reshape(r, c).copy())
+            o += r * c
+        return out
+
+    def covariance_pass_count(self):
+        """all-blocks covariance passes run so far (a look-up does not count)"""
+        return int(self._check(self.L.svin_ba_get_covariance_pass_count(self.h), "covariance_pass_count"))
 
     def lhs_pass_count(self):
         """all-blocks getLhs passes run so far (a cached look-up does not count)"""
