@@ -191,8 +191,7 @@ static SideLane& sideLaneOf(hipStream_t s) {
   }
   return l;
 }
-// partial-sum slots in p.partial (each slot holds up to kMaxPartials doubles)
-constexpr int kMaxPartials = 4096;
+// partial-sum slots in p.partial (each slot holds up to kMaxPartials doubles: build_plan.hpp)
 enum PartialSlot : int {
   PS_COST_REPROJ = 0, PS_COST_FACTORS = 1, PS_JV_SQ = 2, PS_JV_DOT = 3, PS_STEP = 4, PS_XNORM = 5,
   PS_GHAT = 6, PS_GNHAT = 7, PS_GDOTGN = 8, PS_GRADMAX = 9, PS_JY_SQ = 10, PS_JVJY = 11, PS_JY_DOT = 12, PS_COUNT = 13
@@ -660,8 +659,9 @@ static int evalGrid(int N) { return (N + 127) / 128; }
 
 void launchEvalReproj(const DeviceProblem& p, bool cand, bool robust, hipStream_t s) {
   if (p.N == 0) return;
-  const size_t smem = (size_t)(p.nPose * 7 + p.nExt * 7) * 8 + (size_t)p.nCam * sizeof(CameraModel) + kLossTabBytes;
-  const int grid = evalGrid(p.N);
+  const PlannedLaunch alone = evalPlanOf(p).reprojAlone;
+  const size_t smem = alone.ldsBytes;
+  const int grid = alone.grid;
   const double* pose = cand ? p.poseC : p.pose;
   const double* ext = cand ? p.extC : p.ext;
   const double* lm = cand ? p.lmC : p.lm;
@@ -2051,19 +2051,23 @@ __global__ __launch_bounds__(256) void k_eval_rest_split(DeviceProblem p, int ca
   evalRestSplitBody(p, cand, nR, hasPrior, sh, GridDimX{});
 }
 
-constexpr int kEvalSplitBlocks = 512;   // more evaluation blocks than this: reprojection blocks in a launch of their own (launchEvalAll)
-// fused evaluation possible: factors and observations present, camera-owning rank, staging area fits
-bool canFuseEvaluation(const DeviceProblem& p) {
-  const size_t stage = (size_t)(p.nPose + p.nExt) * 7 * 8 + (size_t)p.nCam * sizeof(CameraModel) + kLossTabBytes + 64;
-  return p.F > 0 && p.N > 0 && stage <= sizeof(FactorShared) && (p.N + 255) / 256 + p.F <= kMaxPartials;
+// The plans of build_plan.hpp for a window as it stands: which form, variant, grids and LDS sizes the build takes, how the
+// evaluation and the post-solve pass are issued, how the step is taken.  The options and the two sizes the planner cannot know
+// are read here.
+BuildPlan buildPlanOf(const DeviceProblem& p) { return planBuild(buildDimsOf(p), BuildSwitches{optOn(kOptSchurAMfma)}); }
+EvalPlan evalPlanOf(const DeviceProblem& p) {
+  return planEvaluation(evalDimsOf(p), EvalSwitches{optOn(kOptNoEvalSplit)}, KernelSizes{sizeof(CameraModel), sizeof(FactorShared)});
 }
-static size_t evalSplitStageBytes(const DeviceProblem& p) {
-  return (size_t)48 * 8 + (size_t)(p.nPose + p.nExt) * 7 * 8 + (size_t)p.nCam * sizeof(CameraModel) + kLossTabBytes + 64;
+StepMode stepModeOf(const DeviceProblem& p, bool sharded) {
+  return stepModeOf(StepDims{p.nPose, p.nExt, p.nSb, p.L, p.N, canFuseEvaluation(p)},
+                    StepSwitches{optOn(kOptSplitEval), optOn(kOptNoFuseStep), optOn(kOptNoDeferLm)}, sharded);
 }
+bool canFuseEvaluation(const DeviceProblem& p) { return evalPlanOf(p).fusable; }
 void launchEvalAll(const DeviceProblem& p, bool cand, bool sumCost, hipStream_t s) {
-  const int nR = evalReprojBlockCount(p.N), pri = evalPriorBlockCount(p.priorM);   // (batch_plan.hpp: shared with the batched extents)
-  if (sumCost && p.F + nR + pri > kEvalSplitBlocks && !optOn(kOptNoEvalSplit)) {
-    const size_t stage = evalSplitStageBytes(p);
+  const EvalPlan e = evalPlanOf(p);
+  const int nR = e.nR, pri = e.pri;
+  if (sumCost && e.split) {
+    const size_t stage = e.reprojSplit.ldsBytes;
     // (measured, round 6: the factor blocks on the side stream beside the reprojection blocks, one cost ticket for both launches --
     //  0.665 ms per iteration against 0.65 one after the other: both kernels slow down side by side by more than the overlap gains.
     //  Also measured: the factor blocks FIRST with an event behind them, so that the speculative build's side chain starts beside the
@@ -2071,20 +2075,20 @@ void launchEvalAll(const DeviceProblem& p, bool cand, bool sumCost, hipStream_t 
     //  launch takes 41 us instead of 27 next to it: 0.65 again.  A side stream of the highest priority changes nothing either: the
     //  one workgroup of k_sb_factor / the few of k_sb_forward run 4-5 x slower next to k_schur_rows whatever the queue says.)
     if (p.obsS) {   // a window with general information matrices: the kernels that read obsS
-      if (p.anyExtVariable) launch(k_eval_reproj_split<true, true>, dim3(nR), dim3(256), stage, s, p, cand ? 1 : 0);
-      else launch(k_eval_reproj_split<false, true>, dim3(nR), dim3(256), stage, s, p, cand ? 1 : 0);
-    } else if (p.anyExtVariable) launch(k_eval_reproj_split<true>, dim3(nR), dim3(256), stage, s, p, cand ? 1 : 0);
-    else launch(k_eval_reproj_split<false>, dim3(nR), dim3(256), stage, s, p, cand ? 1 : 0);
-    launch(k_eval_rest_split, dim3(p.F + pri), dim3(256), 0, s, p, cand ? 1 : 0, nR, pri);
+      if (p.anyExtVariable) launch(k_eval_reproj_split<true, true>, dim3(e.reprojSplit.grid), dim3(256), stage, s, p, cand ? 1 : 0);
+      else launch(k_eval_reproj_split<false, true>, dim3(e.reprojSplit.grid), dim3(256), stage, s, p, cand ? 1 : 0);
+    } else if (p.anyExtVariable) launch(k_eval_reproj_split<true>, dim3(e.reprojSplit.grid), dim3(256), stage, s, p, cand ? 1 : 0);
+    else launch(k_eval_reproj_split<false>, dim3(e.reprojSplit.grid), dim3(256), stage, s, p, cand ? 1 : 0);
+    launch(k_eval_rest_split, dim3(e.restSplit.grid), dim3(256), 0, s, p, cand ? 1 : 0, nR, pri);
     return;
   }
   if (p.obsS) {
-    if (p.anyExtVariable) launch(k_eval_all<true, true>, dim3(p.F + nR + pri), dim3(256), 0, s, p, cand ? 1 : 0, nR, sumCost ? 1 : 0, pri);
-    else launch(k_eval_all<false, true>, dim3(p.F + nR + pri), dim3(256), 0, s, p, cand ? 1 : 0, nR, sumCost ? 1 : 0, pri);
+    if (p.anyExtVariable) launch(k_eval_all<true, true>, dim3(e.evalAll.grid), dim3(256), 0, s, p, cand ? 1 : 0, nR, sumCost ? 1 : 0, pri);
+    else launch(k_eval_all<false, true>, dim3(e.evalAll.grid), dim3(256), 0, s, p, cand ? 1 : 0, nR, sumCost ? 1 : 0, pri);
   } else if (p.anyExtVariable)
-    launch(k_eval_all<true>, dim3(p.F + nR + pri), dim3(256), 0, s, p, cand ? 1 : 0, nR, sumCost ? 1 : 0, pri);
+    launch(k_eval_all<true>, dim3(e.evalAll.grid), dim3(256), 0, s, p, cand ? 1 : 0, nR, sumCost ? 1 : 0, pri);
   else
-    launch(k_eval_all<false>, dim3(p.F + nR + pri), dim3(256), 0, s, p, cand ? 1 : 0, nR, sumCost ? 1 : 0, pri);
+    launch(k_eval_all<false>, dim3(e.evalAll.grid), dim3(256), 0, s, p, cand ? 1 : 0, nR, sumCost ? 1 : 0, pri);
 }
 
 // row i of the prior -> (reduced-system row, or -1) with the 3x3 rotation map applied on the fly
@@ -2208,8 +2212,7 @@ __device__ __forceinline__ void factorsAccumulateLin(const DeviceProblem& p, con
 template <bool STAGED>
 __device__ __forceinline__ void factorsAccumulate(const DeviceProblem& p, int f, int* colRow) { factorsAccumulateLin<STAGED>(p, p.linCur[f], colRow); }
 
-constexpr int kStage = 34;  // doubles staged per observation: Jl 6, Jp 12, Je 12, offP, offE (as double), pad
-
+// (kStage, the doubles k_schur stages per observation -- Jl 6, Jp 12, Je 12, offP, offE (as double), pad -- : tile_dims.hpp)
 // Blocks [0, nSchurBlocks) run the landmark Schur complement; the next nFacBlocks accumulate one small factor each
 // (J^T J straight into S with atomics), the rest the marginalisation prior (256 entries of M^T Ht M each), so that the
 // independent parts of the build share one launch.
@@ -2461,10 +2464,8 @@ __global__ __launch_bounds__(256) void k_schur(DeviceProblem p, double mu, int i
 // same 16 landmarks meet in the accumulator back to back, so their cancellation happens at the scale of one
 // chunk (the rounding behaviour of the pairwise kernel).  Tiles stay in registers across chunks; one private slab
 // per block, summed by k_reduce_slabs -- no atomics on S.  Extra blocks of the launch accumulate the small factors.
-constexpr int kDenseLm = 16;              // landmarks per chunk
-constexpr int kDenseK = 3 * kDenseLm;     // columns of G per chunk
-constexpr int kDenseLd = kDenseK + 1;     // odd leading dimension keeps the MFMA operand reads off the same banks
-constexpr int kPoseAcc = 28;              // per pose: 21 (upper 6x6) + 6 (Jp^T r) + pad
+// (kDenseLm landmarks per chunk, kDenseK columns of G, its leading dimension kDenseLd, kPoseAcc doubles per pose block:
+// build_plan.hpp, with the launch sizes made of them)
 
 // index of (a, c), a <= c, in the packed upper triangle of a 6x6 block
 __device__ __forceinline__ int sym6(int a, int c) { return a * 6 - a * (a - 1) / 2 + (c - a); }
@@ -2474,8 +2475,7 @@ __device__ __forceinline__ int sym6(int a, int c) { return a * 6 - a * (a - 1) /
 // A_MFMA: the A part goes through the same MFMA path as G (U = [.. Jc_o^T ..] in batches of obsBatch observations, two
 // columns each, U U^T added to the tiles; the augmented rows carry r) instead of per-wave block copies.  Required with
 // variable extrinsics (their Jacobians add rows to G, and A gets pose-extrinsics cross blocks) and used for the
-// 34-tile variant (the block-copy merge does not fit the register file next to 34 accumulator tiles).
-__host__ __device__ constexpr int denseObsBatch(int rows) { return rows <= 128 ? 32 : (rows <= 192 ? 16 : 8); }
+// 34-tile variant (the block-copy merge does not fit the register file next to 34 accumulator tiles).  (denseObsBatch: build_plan.hpp)
 // NW: waves per workgroup.  The landmark part always runs on the first 256 threads (16 lanes x 16 landmarks); with NW = 8 the
 // tiles are dealt over twice as many waves (clear, merge, products and slab stores take half as long per wave, and 10 tiles
 // per wave stay in registers where 20 spill).
@@ -2520,6 +2520,9 @@ __device__ __forceinline__ void k_schur_dense_body(const DeviceProblem& p, doubl
   const int nPB = p.dCPose / 6, nEB = nP - nPB;
   double* Ash = Aw;
   double* Across = Aw + (size_t)nP * kPoseAcc;
+  // (mirrors denseExtraLdsDoubles of build_plan.hpp, which sized the launch.  Written out here: calling that function changes the
+  //  code of the three A_MFMA instances -- other scalar registers, 99 fewer instructions in <9, true, 4> -- and this kernel's code
+  //  is what every profile of the build was taken on)
   const size_t extraLds = useBlocks ? (size_t)nP * kPoseAcc + (size_t)nEB * nPB * 36
                                     : (A_MFMA ? (size_t)rows * ldU : (size_t)4 * nP * kPoseAcc);
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6), lane = t & 63, grp = t >> 4, gl = t & 15;   // scalar: the tile tests below are SALU
@@ -2994,8 +2997,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? SVIN_BATCH_OCC_SCHUR : 1) void k
 // pairs also add the 6x6 pose blocks of A (per-wave LDS copies) and collect the gradient / column-norm vectors.  One
 // slab (96 x 96 + 3 x 96) per workgroup, summed per pair by k_reduce_panel_slabs.  Fixed extrinsics only (wide
 // windows with variable extrinsics keep the pairwise kernel).
-constexpr int kPanelRows = 96;
-constexpr int kPanelSlab = kPanelRows * kPanelRows + 3 * kPanelRows;
+// (kPanelRows, kPanelSlab: build_plan.hpp)
 static_assert(kPanelChunksPerBlock * 16 <= 256, "one thread per landmark of a workgroup's chunks stages its observation range");
 
 #ifdef SVIN_SCHUR_TIMING
@@ -3357,12 +3359,10 @@ __global__ __launch_bounds__(256, kWavesPerSimd) void k_schur_panels(DeviceProbl
 //    and a register prefetch, 234-275 with pair words: bound by the LDS, whose ds_add_f64 takes 8 cycles per instruction whatever
 //    the number of active lanes and whose queue, kept full by twelve waves, turned every dependent LDS or scalar-memory wait of an
 //    entry's prologue into ~700 cycles.)
-constexpr int kBlkPanelPoses = kPanelRows / 6;   // 16
+// (kBlkPanelPoses, the staged record's stride kBlkStride and the slot pass's kBlkPoseLd: build_plan.hpp)
 constexpr int kBlkRecChunks = kBlkRec / 2;       // 16-byte pieces of a slot record (9)
-constexpr int kBlkStride = 20;                   // doubles per record staged in LDS: 18, then a pair nothing ever writes (zero: the K = 3 padding of every operand)
 constexpr int kBlkStrideChunks = kBlkStride / 2;
-constexpr int kBlkPoseLd = 35;                   // per pose block of the slot pass's accumulators: odd, so that the sixteen slots of a landmark hit different banks
-constexpr int kBlkPart = 34;                     // doubles per pose block of a partial: 21 (A) + 6 (Jp^T r) + 6 (sum E c) + pad
+constexpr int kBlkPart = 34;                    // doubles per pose block of a partial: 21 (A) + 6 (Jp^T r) + 6 (sum E c) + pad
 
 // one THREAD per slot, 1024 slots per workgroup (k_panels_landmarks has left L_l^-1 and c_l in lmFactor): W = sum over the slot's
 // observations of Jp^T Jl (6 x 3), E = W L^-T, E c -> the slot's record; the pose's share of A and Jp^T r -> the workgroup's
@@ -3922,53 +3922,35 @@ void launchZeroBuild(const DeviceProblem& p, hipStream_t s) {
 }
 // zeroFirst = false: the accumulators are already clear (pack() clears them, and k_post_solve clears them again
 // for the next linearisation of the trust-region loop)
-// the dense Gram-matrix form (k_schur_dense): variant, LDS size and DeviceProblem::aBlocks for a window's geometry
-struct DenseSchurPlan { int nTr; bool aMfma, aBlocks; size_t ldsBytes; };
-static DenseSchurPlan denseSchurPlan(const DeviceProblem& p) {
-  const int dC = p.dC;
-  DenseSchurPlan q;
-  q.nTr = (dC + 2 + 15) / 16;
-  const int rows = 16 * q.nTr;
-  q.aMfma = p.anyExtVariable || q.nTr > 8;
-  // A on the MFMA path needs a fill / barrier / clear round per batch of observations; when the blocks of A fit LDS
-  // next to G they are accumulated directly (LDS atomics) and merged into the accumulator tiles once per chunk
-  const int nPB = p.dCPose / 6, nEB = dC / 6 - nPB;
-  const size_t blocksExtra = (size_t)(dC / 6) * kPoseAcc + (size_t)nEB * nPB * 36;
-  const bool forceU = optOn(kOptSchurAMfma);
-  q.aBlocks = q.aMfma && !forceU && ((size_t)rows * kDenseLd + blocksExtra) * 8 <= 150 * 1024;
-  const size_t extra = q.aBlocks ? blocksExtra : (q.aMfma ? (size_t)rows * (2 * denseObsBatch(rows) + 1) : (size_t)4 * (dC / 6) * kPoseAcc);
-  q.ldsBytes = ((size_t)rows * kDenseLd + extra) * 8;
-  return q;
+int schurDenseABlocks(const DeviceProblem& p) {
+  const BuildPlan q = buildPlanOf(p);
+  return (q.form == kBuildDense && q.aBlocks) ? 1 : 0;
 }
-int schurDenseABlocks(const DeviceProblem& p) { return (p.L > 0 && p.N > 0 && p.dC > 0 && p.schurDense && denseSchurPlan(p).aBlocks) ? 1 : 0; }
 static ReducedSolvePlan solvePlanOf(const DeviceProblem& p);                                // (behind the solver kernels, below)
 static bool sbEarlyActive(const DeviceProblem& p, const ReducedSolvePlan& q);
 static void launchSbEarly(const DeviceProblem& p, const ReducedSolvePlan& q, hipStream_t side, double mu, bool initScale);
 static std::atomic<int> gLastSchurForm{0};
 int lastSchurForm() { return gLastSchurForm.load(std::memory_order_relaxed); }
+// the instance of k_schur_dense behind a DenseVariant (build_plan.hpp: the planner alone decides which)
+static auto denseKernelOf(DenseVariant v) -> decltype(&k_schur_dense<9, false, 4>) {
+  switch (v) {
+    case kDense17Mfma8: return k_schur_dense<17, true, 8>;
+    case kDense10Mfma8: return k_schur_dense<10, true, 8>;
+    case kDense9Mfma4: return k_schur_dense<9, true, 4>;
+    case kDense9Copies4: break;
+  }
+  return k_schur_dense<9, false, 4>;
+}
 void launchAccumulateNormalEquations(const DeviceProblem& p, double mu, bool initScale, hipStream_t s, bool zeroFirst) {
-  const int dC = p.dC;
   if (zeroFirst) launchZeroBuild(p, s);
-  const int nFac = p.F;   // this rank's factors
-  const int nPri = priorAccBlocks(p);  // the prior rides along as extra blocks of the same launch
-  if (p.L > 0 && p.N > 0 && dC > 0 && p.schurDense) {
-    const DenseSchurPlan plan = denseSchurPlan(p);
-    const int nTr = plan.nTr;
-    const bool aMfma = plan.aMfma;
-    const size_t ldsBytes = plan.ldsBytes;
-    const dim3 grid(p.nSlabs + nFac + nPri);
+  const BuildPlan q = buildPlanOf(p);
+  const int nFac = q.nFac;   // this rank's factors; the prior rides along as extra blocks of the same launch
+  gLastSchurForm.store(q.formCode, std::memory_order_relaxed);
+  if (q.form == kBuildDense) {
     DeviceProblem pb = p;
-    pb.aBlocks = plan.aBlocks ? 1 : 0;
-    gLastSchurForm.store(1000 + 10 * (nTr > 12 ? 17 : nTr > 8 ? 10 : 9) + (aMfma ? (plan.aBlocks ? 1 : 2) : 0), std::memory_order_relaxed);
-    // <= 16 tile rows: 136 tiles over 8 waves; <= 12 tile rows: 78 tiles
-    if (nTr > 12) launch(k_schur_dense<17, true, 8>, grid, dim3(64 * 8), ldsBytes, s, pb, mu, initScale ? 1 : 0, p.nSlabs, nFac);
-    else if (nTr > 8) launch(k_schur_dense<10, true, 8>, grid, dim3(64 * 8), ldsBytes, s, pb, mu, initScale ? 1 : 0, p.nSlabs, nFac);
-    else if (aMfma) launch(k_schur_dense<9, true, 4>, grid, dim3(64 * 4), ldsBytes, s, pb, mu, initScale ? 1 : 0, p.nSlabs, nFac);
-    else launch(k_schur_dense<9, false, 4>, grid, dim3(64 * 4), ldsBytes, s, pb, mu, initScale ? 1 : 0, p.nSlabs, nFac);
-  } else if (p.L > 0 && p.N > 0 && dC > 0 && p.schurPanels) {
-    // off-diagonal pairs: two G tiles + c; diagonal pairs: one G tile + the per-wave pose blocks + c (smaller)
-    const size_t ldsBytes = ((size_t)2 * kPanelRows * kDenseLd + kDenseK) * 8;
-    static_assert(2 * kPanelRows * kDenseLd >= kPanelRows * kDenseLd + 4 * (kPanelRows / 6) * kPoseAcc, "diagonal pairs fit the same allocation");
+    pb.aBlocks = q.aBlocks ? 1 : 0;
+    launch(denseKernelOf(q.variant), dim3(q.schurDense.grid), dim3(q.denseThreads), q.schurDense.ldsBytes, s, pb, mu, initScale ? 1 : 0, p.nSlabs, nFac);
+  } else if (q.form == kBuildBlockPairs || q.form == kBuildPanels) {
     // Round 4 (config #4, build of the normal equations 1.01 ms -> 0.67 ms, A/B in one gpurun call): two workgroups per CU instead
     // of one (0.79: 86 spilled registers with the next chunk's first observation prefetched, 0.73 without the prefetch and without
     // spills), per-landmark quantities from k_panels_landmarks instead of once per panel pair (0.67).
@@ -3989,73 +3971,49 @@ void launchAccumulateNormalEquations(const DeviceProblem& p, double mu, bool ini
     SideLane* lane = nullptr;
     const ReducedSolvePlan solvePlan = solvePlanOf(p);   // (the plan the solve of this iteration computes as well)
     const bool early = sbEarlyActive(p, solvePlan);
-    gLastSchurForm.store(p.schurBlocks ? 2000 : 3000, std::memory_order_relaxed);
     if (early) {
       lane = &sideLaneOf(s);
       HIP_OK(hipEventRecord(lane->fork, s));
       HIP_OK(hipStreamWaitEvent(lane->side, lane->fork, 0));
-      launch(k_factors_only, dim3(nFac + nPri), dim3(256), 0, lane->side, p, nFac);
+      launch(k_factors_only, dim3(q.factorsOnly.grid), dim3(256), 0, lane->side, p, nFac);
       HIP_OK(hipEventRecord(lane->mid, lane->side));
       launchSbEarly(p, solvePlan, lane->side, mu, initScale);
       HIP_OK(hipEventRecord(lane->join, lane->side));
     }
-    if (p.schurBlocks) {
+    launch(k_panels_landmarks, dim3(q.panelsLandmarks.grid), dim3(256), 0, s, p, mu, initScale ? 1 : 0);
+    if (q.form == kBuildBlockPairs) {
       constexpr int NW = kBlkWaves;
-      const size_t ldsBlk = (size_t)std::max(2 * kBlkBatchRecs * kBlkStride, kBlkPanelPoses * kBlkPanelPoses * 36) * 8;   // (two record buffers / slab image)
-      // the slot pass keeps up to four copies of its per-pose accumulators (one per 16-lane group of a wave: the four landmarks a
-      // wave works on see the same poses, and four lanes adding to one address serialise) -- as many as 64 KB hold
-      int nCopies = 4;
-#ifndef SVIN_SLOT_COPIES_KB
-#define SVIN_SLOT_COPIES_KB 76
-#endif
-      while (nCopies > 1 && (size_t)nCopies * (dC / 6) * kBlkPoseLd * 8 > SVIN_SLOT_COPIES_KB * 1024) nCopies >>= 1;
-      const size_t ldsLm = (size_t)nCopies * (dC / 6) * kBlkPoseLd * 8;
-      const int nSlotBlocks = (p.nSlots + kBlkSlotsPerWorkgroup - 1) / kBlkSlotsPerWorkgroup;
-      launch(k_panels_landmarks, dim3((p.L + 15) / 16), dim3(256), 0, s, p, mu, initScale ? 1 : 0);
-      launch(k_blocks_slots, dim3(nSlotBlocks), dim3(256), ldsLm, s, p, nCopies);
-      launch(k_schur_rows<NW>, dim3(p.nPanelBlocks), dim3(64 * NW), ldsBlk, s, p);
+      launch(k_blocks_slots, dim3(q.blocksSlots.grid), dim3(256), q.blocksSlots.ldsBytes, s, p, q.nCopies);
+      launch(k_schur_rows<NW>, dim3(q.schurRows.grid), dim3(64 * NW), q.schurRows.ldsBytes, s, p);
       if (early) HIP_OK(hipStreamWaitEvent(s, lane->mid, 0));
-      if (nSlotBlocks > 0) launch(k_blocks_pose_reduce, dim3(dC / 6), dim3(1024), 0, s, p, nSlotBlocks);
+      launch(k_blocks_pose_reduce, dim3(q.blocksPoseReduce.grid), dim3(1024), 0, s, p, q.nSlotBlocks);
     } else {
-      launch(k_panels_landmarks, dim3((p.L + 15) / 16), dim3(256), 0, s, p, mu, initScale ? 1 : 0);
-      launch(k_schur_panels<2, false, true>, dim3(p.nPanelBlocks), dim3(256), ldsBytes, s, p, mu, initScale ? 1 : 0, p.nPanelBlocks, nFac);
+      launch(k_schur_panels<2, false, true>, dim3(q.schurPanels.grid), dim3(256), q.schurPanels.ldsBytes, s, p, mu, initScale ? 1 : 0, p.nPanelBlocks, nFac);
     }
-    if (!early) launch(k_factors_only, dim3(nFac + nPri), dim3(256), 0, s, p, nFac);
-    launch(k_reduce_panel_slabs, dim3((kPanelSlab + 15) / 16, p.nPanelPairs), dim3(256), 0, s, p);
+    if (!early) launch(k_factors_only, dim3(q.factorsOnly.grid), dim3(256), 0, s, p, nFac);
+    launch(k_reduce_panel_slabs, dim3(q.reducePanelSlabs.grid, q.reducePanelPairs), dim3(256), 0, s, p);
     // The join comes LAST (the slab sum touches pose rows only, the chain's kernels read speed / bias rows only) but inside this
     // function: once it returns, everything it enqueued is ordered on `s` (a later k_zero_build must not meet a chain still reading S).
     // The chain is what the main stream waits for: k_sb_factor (145 KB of LDS) and k_sb_forward (161 KB per workgroup) need EMPTY CUs
     // and get them only when k_schur_rows (two workgroups of 77 KB per CU, refilled from a queue of ~1 000) runs out -- they end with
     // it however early they are launched, whatever the stream's or the waves' priority (both measured).
     if (early) HIP_OK(hipStreamWaitEvent(s, lane->join, 0));
-    return;
-  } else if (p.L > 0 && p.N > 0 && dC > 0) {
-    const size_t accBytes = ((size_t)dC * dC + 3 * dC) * 8;
-    const size_t stageBytes = (size_t)4 * 64 * kStage * 8;
-    const bool useLds = accBytes + stageBytes <= 150 * 1024;
-    gLastSchurForm.store(useLds ? 4000 : 4001, std::memory_order_relaxed);
-    if (useLds) {
-      const int grid = p.nSlabs;
-      launch(p.anyExtVariable ? k_schur<true, true> : k_schur<true, false>, dim3(grid + nFac + nPri), dim3(256), accBytes + stageBytes,
-             s, p, mu, initScale ? 1 : 0, grid, nFac);
+  } else if (q.form == kBuildPairwise) {
+    if (q.useLds) {
+      launch(p.anyExtVariable ? k_schur<true, true> : k_schur<true, false>, dim3(q.pairwise.grid), dim3(256), q.pairwise.ldsBytes, s, p, mu,
+             initScale ? 1 : 0, q.pairwiseChunkBlocks, nFac);
     } else {
-      (void)hipMemsetAsync(p.slabs, 0, accBytes, s);
-      const int grid = min((p.L + 3) / 4, 2048);
-      DeviceProblem q = p;
-      launch(p.anyExtVariable ? k_schur<false, true> : k_schur<false, false>, dim3(grid + nFac + nPri), dim3(256), stageBytes, s, q,
-             mu, initScale ? 1 : 0, grid, nFac);
+      (void)hipMemsetAsync(p.slabs, 0, q.slabBytes, s);
+      launch(p.anyExtVariable ? k_schur<false, true> : k_schur<false, false>, dim3(q.pairwise.grid), dim3(256), q.pairwise.ldsBytes, s, p, mu,
+             initScale ? 1 : 0, q.pairwiseChunkBlocks, nFac);
     }
   } else {
-    gLastSchurForm.store(5000, std::memory_order_relaxed);
-    launch(k_factors_only, dim3(nFac + nPri), dim3(256), 0, s, p, nFac);
+    launch(k_factors_only, dim3(q.factorsOnly.grid), dim3(256), 0, s, p, nFac);
   }
-  if (p.L > 0 && p.N > 0 && dC > 0) {
-    const size_t accBytes = ((size_t)dC * dC + 3 * dC) * 8;
-    const bool useLds = accBytes + (size_t)4 * 64 * kStage * 8 <= 150 * 1024;
-    DeviceProblem q = p;
-    if (!useLds && !p.schurDense) q.nSlabs = 1;
-    const int n = dC * dC + 3 * dC;
-    launch(k_reduce_slabs, dim3((n + 15) / 16), dim3(256), 0, s, q);
+  if (q.reduceSlabs.grid > 0) {   // the dense and the pairwise form: the slabs the launch above wrote, and no others
+    DeviceProblem ps = p;
+    ps.nSlabs = q.reduceSlabCount;
+    launch(k_reduce_slabs, dim3(q.reduceSlabs.grid), dim3(256), 0, s, ps);
   }
 }
 
@@ -4091,32 +4049,24 @@ __global__ __launch_bounds__(256) void k_eval_build(DeviceProblem p, int cand, i
 static std::atomic<int> gEvalBuildLaunches{0};
 int evalBuildLaunches() { return gEvalBuildLaunches.load(std::memory_order_relaxed); }
 bool launchEvalBuild(const DeviceProblem& p, bool cand, double mu, bool initScale, bool factorsCommute, int computeUnits, hipStream_t s) {
-  if (!(p.L > 0 && p.N > 0 && p.dC > 0 && p.schurDense) || p.world > 1 || !canFuseEvaluation(p)) return false;
-  const DenseSchurPlan plan = denseSchurPlan(p);
-  const int nR = evalReprojBlockCount(p.N), pri = evalPriorBlockCount(p.priorM), nEval = p.F + nR + pri;
-  const size_t stage = (size_t)(p.nPose + p.nExt) * 7 * 8 + (size_t)p.nCam * sizeof(CameraModel) + kLossTabBytes;
-  // (the dense form never has a chain on the side lane: sbEarlyActive asks for the wide form)
-  if (!evalBuildFits(!plan.aMfma && !p.anyExtVariable, nEval, p.nSlabs, computeUnits, plan.ldsBytes, stage, sizeof(FactorShared))) return false;
+  const BuildPlan q = buildPlanOf(p);
+  const EvalPlan e = evalPlanOf(p);
+  if (!evalBuildTaken(buildDimsOf(p), q, e, p.world > 1, computeUnits, sizeof(FactorShared))) return false;
+  const int nR = e.nR, pri = e.pri, nEval = e.evalAll.grid;
   DeviceProblem pb = p;
-  pb.aBlocks = 0;
-  gLastSchurForm.store(1000 + 10 * 9, std::memory_order_relaxed);
+  pb.aBlocks = 0;   // (the form taken is k_schur_dense<9, false, 4>'s: q.variant == kDense9Copies4, q.formCode 1090)
+  gLastSchurForm.store(q.formCode, std::memory_order_relaxed);
   gEvalBuildLaunches.fetch_add(1, std::memory_order_relaxed);
   const dim3 grid(nEval + p.nSlabs);
   const int acc = factorsCommute ? 1 : 0;
   if (p.obsS) launch(k_eval_build<true>, grid, dim3(256), 0, s, pb, cand ? 1 : 0, nR, pri, nEval, mu, initScale ? 1 : 0, p.nSlabs, acc);
   else launch(k_eval_build<false>, grid, dim3(256), 0, s, pb, cand ? 1 : 0, nR, pri, nEval, mu, initScale ? 1 : 0, p.nSlabs, acc);
-  const int nPri = priorAccBlocks(p);
-  if (nPri > 0 || !factorsCommute) {
-    DeviceProblem q = pb;   // the factors' and the prior's linearisation at the evaluated point
-    if (cand) {
-      std::swap(q.linCur, q.linCand);
-      std::swap(q.priorDchi, q.priorDchiC); std::swap(q.priorGrad, q.priorGradC); std::swap(q.priorM3, q.priorM3C);
-    }
-    if (factorsCommute) launch(k_prior_accumulate, dim3(nPri), dim3(256), 0, s, q);
-    else launch(k_factors_only, dim3(p.F + nPri), dim3(256), 0, s, q, p.F);
+  if (q.nPri > 0 || !factorsCommute) {
+    const DeviceProblem view = cand ? withSetsSwapped(pb) : pb;   // the factors' and the prior's linearisation at the evaluated point
+    if (factorsCommute) launch(k_prior_accumulate, dim3(q.nPri), dim3(256), 0, s, view);
+    else launch(k_factors_only, dim3(q.nFac + q.nPri), dim3(256), 0, s, view, q.nFac);
   }
-  const int n = p.dC * p.dC + 3 * p.dC;
-  launch(k_reduce_slabs, dim3((n + 15) / 16), dim3(256), 0, s, pb);
+  launch(k_reduce_slabs, dim3(q.reduceSlabs.grid), dim3(256), 0, s, pb);   // (pb.nSlabs = q.reduceSlabCount: the chunk blocks' slabs)
   return true;
 }
 
@@ -7468,14 +7418,15 @@ __global__ __launch_bounds__(256, SVIN_BATCH_OCC_POST) void k_post_solve_batch(c
 
 
 void launchDoglegPrepare(const DeviceProblem& p, hipStream_t s, double fuseRadius) {
-  const int nLm = postLmBlockCount(p.L, p.N), nFac = postFacBlockCount(p.F);   // (batch_plan.hpp: shared with the batched extents)
-  if (nLm + nFac + 1 > kEvalSplitBlocks && !optOn(kOptNoEvalSplit)) {
-    if (p.anyExtVariable) launch(k_post_solve_wide<true>, dim3(nLm + nFac + 1), dim3(256), 0, s, p, nLm, nFac, fuseRadius);
-    else launch(k_post_solve_wide<false>, dim3(nLm + nFac + 1), dim3(256), 0, s, p, nLm, nFac, fuseRadius);
+  const EvalPlan e = evalPlanOf(p);
+  const int nLm = e.postLm, nFac = e.postFac;
+  if (e.postSplit) {
+    if (p.anyExtVariable) launch(k_post_solve_wide<true>, dim3(e.post.grid), dim3(256), 0, s, p, nLm, nFac, fuseRadius);
+    else launch(k_post_solve_wide<false>, dim3(e.post.grid), dim3(256), 0, s, p, nLm, nFac, fuseRadius);
     return;
   }
-  if (p.anyExtVariable) launch(k_post_solve<true>, dim3(nLm + nFac + 1), dim3(256), 0, s, p, nLm, nFac, fuseRadius);
-  else launch(k_post_solve<false>, dim3(nLm + nFac + 1), dim3(256), 0, s, p, nLm, nFac, fuseRadius);
+  if (p.anyExtVariable) launch(k_post_solve<true>, dim3(e.post.grid), dim3(256), 0, s, p, nLm, nFac, fuseRadius);
+  else launch(k_post_solve<false>, dim3(e.post.grid), dim3(256), 0, s, p, nLm, nFac, fuseRadius);
 }
 
 // final single-block reduction of the cost partials into SolverScalars (used when no later evaluation kernel
@@ -7503,26 +7454,30 @@ void launchDoglegStep(const DeviceProblem& p, double radius, hipStream_t s) {
 // indices and the reduction orders of its own launches: it ends bit for bit where it ends alone.
 bool batchSupported(const DeviceProblem& p) {
   if (!(p.L > 0 && p.N > 0 && p.dC > 0 && p.schurDense && p.d > 0)) return false;
-  if (!canFuseEvaluation(p) || optOn(kOptSplitEval) || optOn(kOptNoFuseStep) || optOn(kOptNoDeferLm)) return false;
-  if ((p.nPose + p.nExt + p.nSb + p.L) > 16384) return false;            // (the fused dogleg step of k_post_solve)
+  if (!batchedStepTakes(stepModeOf(p, /*sharded=*/false))) return false;   // the fused dogleg step of k_post_solve, the landmarks moved by the fused evaluation
   if (!batchedSolverTakes(solvePlanOf(p))) return false;   // the whole system on the LDS-resident solver: no border, no chain elimination
   if (priorAccBlocks(p) > 0 && !p.ownsCamera) return false;
   if (p.nLocked > 0) return false;   // (reduced pose manifolds: k_lock_rows has no batched form)
   if (p.nHostFactors > 0) return false;
   return true;
 }
+static auto denseBatchKernelOf(DenseVariant v) -> decltype(&k_schur_dense_batch<9, false, 4>) {
+  switch (v) {
+    case kDense17Mfma8: return k_schur_dense_batch<17, true, 8>;
+    case kDense10Mfma8: return k_schur_dense_batch<10, true, 8>;
+    case kDense9Mfma4: return k_schur_dense_batch<9, true, 4>;
+    case kDense9Copies4: break;
+  }
+  return k_schur_dense_batch<9, false, 4>;
+}
 void launchBatchRound(const BatchSlot* dSlots, const DeviceProblem& geom, const BatchGrid& grid, int n, int stagesUnion, bool cand, hipStream_t s,
                       bool anyObsS) {
   const DeviceProblem& p = geom;
   if (stagesUnion & kBatchFull) {
-    const DenseSchurPlan plan = denseSchurPlan(p);
-    const dim3 gridB(grid.build, n);
-    if (plan.nTr > 12) launch(k_schur_dense_batch<17, true, 8>, gridB, dim3(64 * 8), plan.ldsBytes, s, dSlots);
-    else if (plan.nTr > 8) launch(k_schur_dense_batch<10, true, 8>, gridB, dim3(64 * 8), plan.ldsBytes, s, dSlots);
-    else if (plan.aMfma) launch(k_schur_dense_batch<9, true, 4>, gridB, dim3(64 * 4), plan.ldsBytes, s, dSlots);
-    else launch(k_schur_dense_batch<9, false, 4>, gridB, dim3(64 * 4), plan.ldsBytes, s, dSlots);
-    const int nRed = p.dC * p.dC + 3 * p.dC;
-    launch(k_reduce_slabs_batch, dim3((nRed + 15) / 16, n), dim3(256), 0, s, dSlots);   // (every window sums its own nSlabs)
+    const BuildPlan plan = buildPlanOf(p);   // (variant, block size, LDS bytes and the slab sum's grid: equal in every window of the batch)
+    if (plan.form != kBuildDense) throw std::logic_error("launchBatchRound: a window batchSupported refuses");
+    launch(denseBatchKernelOf(plan.variant), dim3(grid.build, n), dim3(plan.denseThreads), plan.schurDense.ldsBytes, s, dSlots);
+    launch(k_reduce_slabs_batch, dim3(plan.reduceSlabs.grid, n), dim3(256), 0, s, dSlots);   // (every window sums its own nSlabs)
     const ReducedSolvePlan q = solvePlanOf(p);
     if (!batchedSolverTakes(q)) throw std::logic_error("launchBatchRound: a window batchSupported refuses");
     launch(k_chol_solve_lds_batch<0>, dim3(q.cholLds.grid, n), dim3(kCholLdsThreads), q.cholLds.ldsBytes, s, dSlots, q.dpad, 1, 0, (const double*)nullptr);
@@ -7531,7 +7486,7 @@ void launchBatchRound(const BatchSlot* dSlots, const DeviceProblem& geom, const 
   }
   if (stagesUnion & kBatchReuse) launch(k_step_retract_batch, dim3(grid.step, n), dim3(256), 0, s, dSlots);
   if (stagesUnion & kBatchEval) {
-    const size_t stage = evalSplitStageBytes(p);
+    const size_t stage = evalPlanOf(p).reprojSplit.ldsBytes;
     if (anyObsS) {   // every block reads its own slot's obsS: a window without one takes the scalar arithmetic there as well
       if (p.anyExtVariable) launch(k_eval_reproj_batch<true, true>, dim3(grid.evalR, n), dim3(256), stage, s, dSlots, cand ? 1 : 0);
       else launch(k_eval_reproj_batch<false, true>, dim3(grid.evalR, n), dim3(256), stage, s, dSlots, cand ? 1 : 0);

@@ -25,6 +25,7 @@
 #include "cov_plan.hpp"
 #include "pack_plan.hpp"
 #include "solve_plan.hpp"
+#include "build_plan.hpp"
 
 namespace svin {
 
@@ -39,8 +40,7 @@ inline __host__ __device__ uint32_t packObs(int pose, int ext, int cam, int loss
 }
 // residual loss functions (Ceres' TrivialLoss, CauchyLoss(a), HuberLoss(a)): dmath.hpp residualLoss
 enum LossKind : int { LOSS_NONE = 0, LOSS_CAUCHY = 1, LOSS_HUBER = 2 };
-constexpr int kMaxLosses = 15;   // entries of a window's reprojection loss table (entry 0: CauchyLoss(1))
-constexpr size_t kLossTabBytes = (size_t)2 * kMaxLosses * 8;   // (kind, a) per entry, as doubles: the LDS the evaluation stages
+// (kMaxLosses, kLossTabBytes -- a window's reprojection loss table, entry 0 CauchyLoss(1) -- : build_plan.hpp, with the staging area they size)
 
 struct ImuParams {
   double a_max, g_max, sigma_g_c, sigma_a_c, sigma_bg, sigma_ba, sigma_gw_c, sigma_aw_c, tau, g;
@@ -242,6 +242,26 @@ struct BatchSlot {
   BatchExtents ext;
 };
 inline BatchDims batchDimsOf(const DeviceProblem& p) { return BatchDims{p.L, p.N, p.F, p.nPose, p.nExt, p.nSb, p.priorM, p.ownsCamera, p.nSlabs}; }
+// the integers the planners of build_plan.hpp take
+inline BuildDims buildDimsOf(const DeviceProblem& p) {
+  return BuildDims{p.dC, p.dCPose, p.L, p.N, p.F, p.priorM, p.ownsCamera, p.anyExtVariable, p.schurDense, p.schurPanels, p.schurBlocks, p.nSlabs,
+                   p.nSlots, p.nPanelBlocks, p.nPanelPairs};
+}
+inline EvalDims evalDimsOf(const DeviceProblem& p) { return EvalDims{p.nPose, p.nExt, p.nCam, p.L, p.N, p.F, p.priorM}; }
+// `p` as it looks after an accepted step: the candidate sets (parameter tables, linearisation buffers, the factors' and the
+// prior's linearisation) are the current ones and the other way round
+inline DeviceProblem withSetsSwapped(const DeviceProblem& p) {
+  DeviceProblem q = p;
+  std::swap(q.pose, q.poseC); std::swap(q.ext, q.extC); std::swap(q.sb, q.sbC); std::swap(q.lm, q.lmC);
+  std::swap(q.rCur, q.rCand); std::swap(q.JpCur, q.JpCand); std::swap(q.JlCur, q.JlCand); std::swap(q.JeCur, q.JeCand);
+  std::swap(q.linCur, q.linCand);
+  std::swap(q.priorDchi, q.priorDchiC); std::swap(q.priorGrad, q.priorGradC); std::swap(q.priorM3, q.priorM3C);
+  return q;
+}
+// the plans of a window as it stands (the debug options are read here, once per call)
+BuildPlan buildPlanOf(const DeviceProblem& p);
+EvalPlan evalPlanOf(const DeviceProblem& p);
+StepMode stepModeOf(const DeviceProblem& p, bool sharded);
 void releaseSideLane(hipStream_t s);   // frees the side stream / events kernels.hip keeps for solver stream `s` (before `s` is destroyed)
 bool batchSupported(const DeviceProblem& p);   // the geometry the batched kernels cover (otherwise the window is solved on its own)
 // one round for the `n` windows of dSlots (device copy of the slot table); `geom` = any window of the batch (what the launcher reads
@@ -250,7 +270,7 @@ bool batchSupported(const DeviceProblem& p);   // the geometry the batched kerne
 // `anyObsS`: a window of the batch has DeviceProblem::obsS set (the reprojection blocks then run the kernel that can read it)
 void launchBatchRound(const BatchSlot* dSlots, const DeviceProblem& geom, const BatchGrid& grid, int n, int stagesUnion, bool cand, hipStream_t s,
                       bool anyObsS = false);
-int schurDenseABlocks(const DeviceProblem& p);   // DeviceProblem::aBlocks as launchAccumulateNormalEquations chooses it
+int schurDenseABlocks(const DeviceProblem& p);   // DeviceProblem::aBlocks as launchAccumulateNormalEquations chooses it (BuildPlan::aBlocks)
 // Which landmark-elimination form launchAccumulateNormalEquations launched last in this process (read-only inspection field,
 // svin_ba_debug_get_option("SVIN_LAST_SCHUR_FORM")): 0 none yet; 1000 + 10 MAXT + a for k_schur_dense<MAXT, ...> (a = 0: A in per-wave
 // block copies, 1: A on MFMA block-wise, 2: A on MFMA tile-wise); 2000 k_blocks_slots + k_schur_rows; 3000 k_schur_panels;
@@ -259,7 +279,7 @@ int lastSchurForm();
 // Evaluation and the build of the normal equations AT THE EVALUATED POINT in one launch (k_eval_build) + k_reduce_slabs: what
 // launchEvalAll(p, cand, true, s) followed by launchAccumulateNormalEquations(view, mu, initScale, s, false) computes, `view` being
 // `p` itself for cand = false and `p` with its current / candidate sets swapped for cand = true.  The accumulators are clean.
-// Returns false, having launched nothing, for a window the launch does not take (pack_plan.hpp evalBuildFits: any form but the
+// Returns false, having launched nothing, for a window the launch does not take (build_plan.hpp evalBuildTaken: any form but the
 // narrow dense one with fixed extrinsics, a sharded window, more workgroups than compute units): the caller issues the two launches.
 // factorsCommute: no entry of S receives more than two of the small factors' / the prior's atomic additions (they start from zero,
 // so their order does not matter): the factor blocks of the launch add their factor themselves.  Otherwise the factors and the
@@ -273,7 +293,7 @@ void launchEvalReproj(const DeviceProblem& p, bool cand, bool robust, hipStream_
 void launchEvalFactors(const DeviceProblem& p, bool cand, hipStream_t s, bool sumCost = false);
 void launchEvalPrior(const DeviceProblem& p, bool cand, hipStream_t s, bool sumCost = false, int reprojBlocks = -1);
 // fused evaluation (small factors + reprojection residuals in one launch, 256 observations per block)
-bool canFuseEvaluation(const DeviceProblem& p);
+bool canFuseEvaluation(const DeviceProblem& p);   // EvalPlan::fusable
 void launchEvalAll(const DeviceProblem& p, bool cand, bool sumCost, hipStream_t s);
 int costSummedBy(const DeviceProblem& p);  // 2 = prior evaluation, 1 = factor evaluation, 0 = separate launchCost
 void launchBuildNormalEquations(const DeviceProblem& p, double mu, bool initScale, hipStream_t s);

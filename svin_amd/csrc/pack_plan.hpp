@@ -9,6 +9,7 @@
 #include <cstdint>
 #include <vector>
 #include "batch_plan.hpp"
+#include "tile_dims.hpp"
 
 namespace svin {
 
@@ -47,8 +48,7 @@ struct SchurForm {
 // nPoses: pose slots of the window (a phantom pose not counted); optSlabChunks: SVIN_SLAB_CHUNKS (0: unset)
 inline SchurForm chooseSchurForm(int dC, int L, int N, int nPoses, bool anyExtVar, bool optSchurPairwise, bool optPanelsOld, int optSlabChunks) {
   SchurForm f;
-  const size_t slabSize = (size_t)dC * dC + 3 * dC;
-  f.useLds = slabSize * 8 + (size_t)4 * 64 * 34 * 8 <= 150 * 1024;
+  f.useLds = pairwiseSlabFitsLds(dC);   // (tile_dims.hpp: the launcher's own test)
   f.nSlabs = 1;
   // windows whose camera block fits 16 x 16 MFMA tiles (dC <= 254, e.g. 42 poses or 10 poses with per-frame extrinsics):
   // dense Gram-matrix Schur complement on MFMA
@@ -68,19 +68,6 @@ inline SchurForm chooseSchurForm(int dC, int L, int N, int nPoses, bool anyExtVa
   // A pose block index has to fit 16 bits.
   f.schurBlocks = f.schurPanels && !optPanelsOld && dC / 6 <= kBlkMaxPoseBlocks;
   return f;
-}
-
-// ---- evaluation and build of the next normal equations in ONE launch (k_eval_build: the blocks of the fused evaluation, then the
-// chunk blocks of the narrow dense form, which evaluate their own observations).  Every workgroup of that launch brings the factor
-// blocks' LDS, one workgroup per compute unit: the launch is taken when all of them run at once (a second round of workgroups
-// would cost what the launch boundary it removes costs) and when a chunk block's tiles and staged tables fit that LDS.
-// denseFormPlain: k_schur_dense<9, false, 4> is the window's form (fixed extrinsics, at most 8 tile rows); chunkLdsBytes: the
-// dynamic LDS that form takes; stageBytes: poses, extrinsics, camera models and loss table; ldsBytes: the factor blocks' LDS.
-inline bool evalBuildFits(bool denseFormPlain, int evalBlocks, int chunkBlocks, int computeUnits, size_t chunkLdsBytes, size_t stageBytes,
-                          size_t ldsBytes) {
-  if (!denseFormPlain || evalBlocks <= 0 || chunkBlocks <= 0) return false;
-  if ((long long)evalBlocks + chunkBlocks > computeUnits) return false;
-  return ((chunkLdsBytes + 15) & ~(size_t)15) + stageBytes <= ldsBytes;
 }
 
 // ---- landmark order of wide windows (k_schur_panels): order by VISIBILITY SIGNATURE -- the set of 16-row tiles of the camera

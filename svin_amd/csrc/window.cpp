@@ -2387,13 +2387,12 @@ void Window::solve(size_t numIter, bool verbose) {
   double* scalD = reinterpret_cast<double*>(p.scal);  // [0..7] group A, [8..15] group B, [16..31] the ranks' (gradMax, failMax) pairs
   // the post-solve pass can take the dogleg step itself when no all-reduce sits between them and one workgroup
   // retracts the whole window quickly enough
-  const bool noFuseStep = optOn(kOptNoFuseStep);   // A/B switch for profiling
   // fused step: the landmark half of the retraction rides in the candidate evaluation (k_eval_all), which reads every
   // landmark anyway -- the serial tail of k_post_solve only moves the ~20 parameter blocks.  With the landmarks deferred the
   // fused step has no size limit (round 6: wide windows took a k_step_retract launch per iteration, 9 us, because of theirs)
-  const bool deferPossible = canFuseEvaluation(p) && !optOn(kOptSplitEval) && !optOn(kOptNoDeferLm) && p.L > 0 && p.N > 0;
-  const bool fuseStep = !noFuseStep && !dist && ((p.nPose + p.nExt + p.nSb + p.L) <= 16384 || deferPossible);
-  const bool deferLm = fuseStep && deferPossible;
+  // (build_plan.hpp stepModeOf; SVIN_NO_FUSE_STEP / SVIN_NO_DEFER_LM are A/B switches for profiling)
+  const StepMode stepMode = stepModeOf(p, dist);
+  const bool fuseStep = stepMode.fuseStep, deferLm = stepMode.deferLm;
   // the stop vote (k_set_stop_vote) travels in the slots k_post_solve uses for the fused dogleg coefficients of the deferred
   // landmark step: the two never meet because a sharded solve takes neither the fused nor the deferred step
   if (dist && (fuseStep || deferLm)) throw std::logic_error("sharded solve with a fused step");
@@ -2482,12 +2481,7 @@ void Window::solve(size_t numIter, bool verbose) {
         accumulatorsClean = false;
         specValid = true;
       } else if (specWanted) {
-        DeviceProblem q = p;   // the problem as it looks after an accepted step
-        std::swap(q.pose, q.poseC); std::swap(q.ext, q.extC); std::swap(q.sb, q.sbC); std::swap(q.lm, q.lmC);
-        std::swap(q.rCur, q.rCand); std::swap(q.JpCur, q.JpCand); std::swap(q.JlCur, q.JlCand); std::swap(q.JeCur, q.JeCand);
-        std::swap(q.linCur, q.linCand);
-        std::swap(q.priorDchi, q.priorDchiC); std::swap(q.priorGrad, q.priorGradC); std::swap(q.priorM3, q.priorM3C);
-        launchAccumulateNormalEquations(q, specMu, false, s, /*zeroFirst=*/false);
+        launchAccumulateNormalEquations(withSetsSwapped(p), specMu, false, s, /*zeroFirst=*/false);   // the problem as it looks after an accepted step
         accumulatorsClean = false;
         specValid = true;
       }
@@ -2528,13 +2522,7 @@ void Window::solve(size_t numIter, bool verbose) {
   distNative_ = false;
 }
 
-void Window::swapStateSets() {
-  DeviceProblem& p = prob_;
-  std::swap(p.pose, p.poseC); std::swap(p.ext, p.extC); std::swap(p.sb, p.sbC); std::swap(p.lm, p.lmC);
-  std::swap(p.rCur, p.rCand); std::swap(p.JpCur, p.JpCand); std::swap(p.JlCur, p.JlCand); std::swap(p.JeCur, p.JeCand);
-  std::swap(p.linCur, p.linCand);
-  std::swap(p.priorDchi, p.priorDchiC); std::swap(p.priorGrad, p.priorGradC); std::swap(p.priorM3, p.priorM3C);
-}
+void Window::swapStateSets() { prob_ = withSetsSwapped(prob_); }
 
 // ------------------------------------------------------------------------------------------ batched solve
 // SURVEY 8(e)'s "independent replicas processing different windows" on ONE GPU: a 10-keyframe window keeps 1-3 % of the chip
@@ -3035,10 +3023,9 @@ int Window::debugTrustRegionStep(double mu, double radius, int form, int commit,
   hipStream_t s = stream_;
   const int nBlk = (int)(poseIds_.size() + extIds_.size() + sbIds_.size());
   // the choice of solve()
-  const bool deferPossible = canFuseEvaluation(p) && !optOn(kOptSplitEval) && !optOn(kOptNoDeferLm) && p.L > 0 && p.N > 0;
-  const bool small = (p.nPose + p.nExt + p.nSb + p.L) <= 16384;
-  const bool fuseStep = !optOn(kOptNoFuseStep) && (small || deferPossible);
-  const int chosen = fuseStep ? (deferPossible ? 3 : 1) : 2;
+  const StepMode stepMode = stepModeOf(p, /*sharded=*/false);
+  const bool deferPossible = stepMode.deferPossible, small = stepMode.small;
+  const int chosen = stepMode.chosenForm;
   const int run = form == 0 ? chosen : form;
   o.info[0] = p.d; o.info[1] = p.L; o.info[2] = nBlk; o.info[3] = run;
   o.info[4] = postLmBlockCount(p.L, p.N); o.info[5] = postFacBlockCount(p.F); o.info[6] = stepBlockCount(p.nPose, p.nExt, p.nSb, p.L);

@@ -79,6 +79,42 @@ def device_landmark_order(est, lm_ids):
     return order
 
 
+# (window, debug options, every pose block constant, the code kernels.hpp lists for the form)
+PLANNED = [("narrow_L17", {}, False, 1090), ("narrow_L17", op.PAIR, False, 4000), ("ext_P6_fixed", {}, False, 1091),
+           ("ext_P6_fixed", op.TILE, False, 1092), ("narrow_L1", {}, True, 5000)]
+
+
+@pytest.mark.parametrize("name, opts, fix_poses, code", PLANNED)
+def test_the_form_that_ran_is_the_planned_one(gpu_lib, debug_option, tmp_path, name, opts, fix_poses, code):
+    """SVIN_LAST_SCHUR_FORM after linearize() against planBuild (svin_amd/csrc/build_plan.hpp through the CPU shim of
+    tests/test_build_plan_host.py) on the window's own integers: narrow dense with fixed and with variable extrinsics, pairwise
+    by its switch, and a window whose poses are all constant, which leaves the small factors alone"""
+    import build_plan_lib as bpl
+    from svin_amd.estimator import Estimator
+    lib = bpl.build_shim(tmp_path)
+    design = op.build(name)
+    for k, v in opts.items():
+        debug_option(k, v)
+    est = Estimator(0)
+    fids, _ = syn.feed(est, design.spec)
+    fixed = [design.fixed_frame] if design.fixed_frame is not None else []
+    for b in est.parameter_block_ids():
+        dsc = est.describe_block(b)
+        if dsc is not None and dsc[1] == 0 and (fix_poses or dsc[0] in [fids[f] for f in fixed]):
+            assert est.set_parameter_block_constant(b)
+    ev = est.eval_reprojection()
+    lin = est.linearize(1e-4)
+    ran = Estimator.debug_get_option("SVIN_LAST_SCHUR_FORM")
+    kinds = [est.describe_block(int(b))[1] for b in lin["block_ids"]]
+    switches = (bpl.PAIRWISE if "SVIN_SCHUR_PAIRWISE" in opts else 0) | (bpl.A_MFMA if "SVIN_SCHUR_A_MFMA" in opts else 0)
+    row = bpl.row(6 * (kinds.count(0) + kinds.count(1)), len(set(int(i) for i in ev["lm_id"])), len(ev["r"]), dCPose=6 * kinds.count(0),
+                  any_ext=int(kinds.count(1) > 0), F=len(est.eval_factors()), priorM=0, nPose=design.spec.P, switches=switches)
+    planned = int(bpl.plan(lib, [row], 120, 133584)["formCode"][0])   # (the two sizes do not enter the form)
+    print(name, opts, "dC", row[0], "dCPose", row[1], "L", row[3], "N", row[4], "ran", ran, "planned", planned)
+    assert ran == planned == code
+    del est
+
+
 @pytest.mark.parametrize("name", sorted(op.CASES))
 def test_reduced_system_against_long_double(gpu_lib, debug_option, name):
     if not sr.have_long_double():
