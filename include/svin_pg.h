@@ -58,7 +58,8 @@ int svin_pg_get_drift(const svin_pg* h, double* yaw_drift_deg, double* r_drift, 
  * total seconds (HIP events on the solver's stream) of the last svin_pg_optimize */
 int svin_pg_set_partition(svin_pg* h, int piece_keyframes, int dense_keyframes);
 /* 1 = eliminate the pieces only; 2 (default) = also eliminate the cut keyframes in level-2 pieces (of
- * level2_piece_keyframes cut keyframes, 0 = keep, default 16 / 32) so that the dense root only holds the loop cover */
+ * level2_piece_keyframes cut keyframes, 0 = keep, default 16 / 32, used as max(8, min(., 256 / tangent size)) like the
+ * level-1 length: the level-2 factor kernel's LDS grows with it) so that the dense root only holds the loop cover */
 int svin_pg_set_levels(svin_pg* h, int levels, int level2_piece_keyframes);
 /* out10: ... as above, [6] = unknowns of the dense root solve, [9] = level-2 pieces */
 int svin_pg_get_partition(const svin_pg* h, double* out10);
@@ -66,6 +67,20 @@ int svin_pg_get_partition(const svin_pg* h, double* out10);
 /* ceres::Solver::Summary of the last solve: initial_cost, final_cost, iterations, termination (0 convergence,
  * 1 no convergence, 3 failure), successful steps, solve seconds (device work, inputs resident) */
 int svin_pg_summary(const svin_pg* h, double* out6);
+
+/* ---- debug (tests/test_gpu_posegraph_stages.py): one Levenberg-Marquardt step kept stage by stage */
+
+/* problem construction, symbolic step, evaluation, node pass (with the Jacobi scales), ONE solve of the damped normal
+ * equations at the given trust-region radius, model cost change + candidate, candidate evaluation + final reduction --
+ * the launches of svin_pg_optimize's first iteration, run by the same code; nothing is written back, the drift and the
+ * keyframes stay untouched.  Returns 1, 0 when there is nothing to optimise, <0 on error. */
+int svin_pg_debug_step(svin_pg* h, int earliest_loop_index, int cur_index, double radius);
+/* copies the named array of the last svin_pg_debug_step (as doubles; ints converted) and returns its length, -2 for an
+ * unknown name; out == NULL just returns the length.  Names: local problem ea eb eloop off et eyaw epitch eroll eq esq
+ * yaw pitch roll t q; device res Ja Jb (robustified) g scale colsq nodeBlk (nodes x D x D, lower triangle) y yS
+ * cost costC gradmax model step2 x2 cholFail yawC tC qC; partition rows cols rows2 cols2 (per piece of level 1 / 2)
+ * sepOff nodePiece nodeRow isCover isRoot l2PieceOf (per node) nS nR nPieces nPieces2 BW BW2 */
+long long svin_pg_debug_array(const svin_pg* h, const char* name, double* out, long long cap);
 
 #ifdef __cplusplus
 }

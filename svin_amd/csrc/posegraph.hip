@@ -33,6 +33,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <stdexcept>
 #include <string>
 #include <unordered_map>
@@ -900,6 +901,34 @@ class PoseGraph {
     }
   }
 
+  // debug capture of one LM step (svin_pg_debug_step): optimize() itself runs, tests capture_ on the host where it would
+  // go on iterating or write poses back, and leaves the step's intermediates here instead
+  struct Capture {
+    double radius = 1e4;
+    bool ran = false;
+    std::map<std::string, std::vector<double>> arrays;
+    template <class T>
+    void put(const char* name, const T* v, size_t n) { arrays[name].assign(v, v + n); }
+    template <class T>
+    void put(const char* name, const std::vector<T>& v) { arrays[name].assign(v.begin(), v.end()); }
+    void put1(const char* name, double v) { arrays[name].assign(1, v); }
+  };
+  Capture cap_;
+  Capture* capture_ = nullptr;
+  int debugStep(int earliest, int cur, double radius) {
+    cap_ = Capture();
+    cap_.radius = radius;
+    capture_ = &cap_;
+    try {
+      optimize(earliest, cur);
+    } catch (...) {
+      capture_ = nullptr;
+      throw;
+    }
+    capture_ = nullptr;
+    return cap_.ran ? 1 : 0;
+  }
+
   int optimize(int earliest, int cur) {
     const auto tCall0 = std::chrono::steady_clock::now();
     // ---- local problem (PoseGraph.cpp:262-332 / :436-489)
@@ -963,6 +992,7 @@ class PoseGraph {
       if (!fixed[k]) { off[k] = n; n += D; }
     summary[0] = summary[1] = 0; summary[2] = 0; summary[3] = 0; summary[4] = 0; summary[5] = 0;
     if (n == 0 || ne == 0) {  // nothing to optimise: the poses are still written back and the drift updated
+      if (capture_) return 1;   // (debug step: keyframes untouched)
       writeBack(yaw, pitch, roll, t, q, kfOfLocal, cur);
       return 1;
     }
@@ -1030,6 +1060,7 @@ class PoseGraph {
     // through the piece between them: reach W2 = 2w - 1 cut keyframes); they are eliminated the same way, so the
     // dense root only holds the loop cover and a few level-2 cuts
     const int W2 = 2 * w - 1, BW2 = W2 * D + D - 1;
+    const int l2Len = std::max(8, std::min(l2Len_, 256 / D));   // (the level-2 factor kernel's LDS grows with it)
     std::vector<std::vector<int>> pieceAdjNodes(nPieces);
     for (int e = 0; e < ne; ++e) {
       const int a = ea[e], b = eb[e];
@@ -1047,7 +1078,7 @@ class PoseGraph {
       std::vector<int> cutList;
       for (int k : freeNodes)
         if (isSep[k] && !isCover[k]) cutList.push_back(k);
-      bool useL2 = level2_ && nPieces >= 8 && (int)cutList.size() >= 3 * l2Len_;
+      bool useL2 = level2_ && nPieces >= 8 && (int)cutList.size() >= 3 * l2Len;
       if (useL2) {
         for (const auto& A : pieceAdjNodes)
           for (int x : A)
@@ -1070,7 +1101,7 @@ class PoseGraph {
           ++cnt;
           for (int o : sepAdj[k])
             if (isCover[o] && stamp[o] != nPieces2) { stamp[o] = nPieces2; ++adj; }
-          if ((cnt >= l2Len_ || adj + 12 >= maxAdj2) && i + W2 < C - 1) {
+          if ((cnt >= l2Len || adj + 12 >= maxAdj2) && i + W2 < C - 1) {
             for (int j = 1; j <= W2; ++j) isL2Cut[cutList[i + j]] = 1;
             i += W2;
             ++nPieces2; cnt = 0; adj = 2 * W2;
@@ -1384,7 +1415,7 @@ class PoseGraph {
     // ---- Ceres TrustRegionMinimizer + LevenbergMarquardtStrategy, default options
     const double function_tolerance = 1e-6, gradient_tolerance = 1e-10, parameter_tolerance = 1e-8;
     const double min_relative_decrease = 1e-3, max_radius = 1e16, min_radius = 1e-32;
-    double radius = 1e4, decrease_factor = 2.0;
+    double radius = capture_ ? capture_->radius : 1e4, decrease_factor = 2.0;
     evaluate(false, true, false);
     launch(k_pg_reduce, dim3(1), dim3(256), 0, s_, p, (int)PG_COST, gE, 0);
     readScal();
@@ -1408,6 +1439,44 @@ class PoseGraph {
       else launch(k_pg_model_plus<4>, dim3(gE + gN), dim3(128), 0, s_, p, gE);
       evaluate(true, false, true);   // + the iteration's scalars (and the gradient max of this linearisation)
       readScal();
+      if (capture_) {   // debug step: keep the first iteration's intermediates, no write-back
+        Capture& c = *capture_;
+        auto dev = [&](const char* name, const double* d, size_t cnt) {
+          std::vector<double>& v = c.arrays[name];
+          v.assign(cnt, 0.0);
+          if (cnt) HIP_OK(hipMemcpy(v.data(), d, sizeof(double) * cnt, hipMemcpyDeviceToHost));
+        };
+        c.put("ea", ea); c.put("eb", eb); c.put("eloop", eloop); c.put("off", off);
+        c.put("et", et); c.put("eyaw", eyaw); c.put("epitch", epitch); c.put("eroll", eroll); c.put("eq", eq); c.put("esq", esq);
+        c.put("yaw", yaw); c.put("pitch", pitch); c.put("roll", roll); c.put("t", t); c.put("q", q);
+        dev("res", p.res, (size_t)ne * R); dev("Ja", p.Ja, ne * RD); dev("Jb", p.Jb, ne * RD);
+        dev("g", p.g, n); dev("scale", p.scale, n); dev("colsq", p.colsq, n); dev("y", p.y, n); dev("yS", p.yS, nS);
+        {   // J^T J blocks: nn x D x D, the lower triangle as k_pg_node stores it (stride 36), zero elsewhere
+          std::vector<double> raw((size_t)nn * 36), blk((size_t)nn * D * D, 0.0);
+          HIP_OK(hipMemcpy(raw.data(), p.nodeBlk, sizeof(double) * raw.size(), hipMemcpyDeviceToHost));
+          for (int k = 0; k < nn; ++k)
+            if (off[k] >= 0)
+              for (int c1 = 0; c1 < D; ++c1)
+                for (int c2 = 0; c2 <= c1; ++c2) blk[((size_t)k * D + c1) * D + c2] = raw[(size_t)k * 36 + c1 * D + c2];
+          c.put("nodeBlk", blk);
+        }
+        c.put1("cost", x_cost); c.put1("costC", sc[PG_COST]); c.put1("gradmax", sc[PG_GRADMAX]);
+        c.put1("model", sc[PG_MODEL]); c.put1("step2", sc[PG_STEP2]); c.put1("x2", sc[PG_X2]);
+        c.put1("cholFail", hs.sol.cholFail);
+        dev("tC", p.tC, 3 * (size_t)nn);   // (k_pg_model_plus writes the yaws or the quaternions, not both)
+        if (six_) { dev("qC", p.qC, 4 * (size_t)nn); c.put("yawC", yaw); }
+        else { dev("yawC", p.yawC, nn); c.put("qC", q); }
+        std::vector<int> rows1, cols1, rows2, cols2;
+        for (const PgPiece& pc : L1.pieces) { rows1.push_back(pc.rows); cols1.push_back(pc.cols); }
+        for (const PgPiece& pc : L2.pieces) { rows2.push_back(pc.rows); cols2.push_back(pc.cols); }
+        c.put("rows", rows1); c.put("cols", cols1); c.put("rows2", rows2); c.put("cols2", cols2);
+        c.put("sepOff", sepOff); c.put("nodePiece", nodePiece); c.put("nodeRow", nodeRow);
+        c.put("isCover", isCover); c.put("isRoot", isRoot); c.put("l2PieceOf", l2PieceOf);
+        c.put1("nS", nS); c.put1("nR", nR); c.put1("nPieces", nPieces); c.put1("nPieces2", nPieces2);
+        c.put1("BW", BW); c.put1("BW2", BW2);
+        c.ran = true;
+        return 1;
+      }
       if (freshLinearization && sc[PG_GRADMAX] <= gradient_tolerance) { termination = 0; break; }
       ++iteration;
       const double model_cost_change = -sc[PG_MODEL];
@@ -1609,5 +1678,22 @@ int svin_pg_summary(const svin_pg* h, double* out6) {
   if (!h || !out6) return -1;
   std::memcpy(out6, h->g.summary, sizeof(double) * 6);
   return 1;
+}
+int svin_pg_debug_step(svin_pg* h, int earliest_loop_index, int cur_index, double radius) {
+  if (!h || !(radius > 0.0)) return -1;
+  try {
+    return h->g.debugStep(earliest_loop_index, cur_index, radius);
+  } catch (const std::exception& e) {
+    g_pgError = e.what();
+    return -3;
+  }
+}
+long long svin_pg_debug_array(const svin_pg* h, const char* name, double* out, long long cap) {
+  if (!h || !name) return -1;
+  const auto it = h->g.cap_.arrays.find(name);
+  if (it == h->g.cap_.arrays.end()) return -2;
+  const long long len = (long long)it->second.size();
+  if (out) std::memcpy(out, it->second.data(), sizeof(double) * (size_t)std::min(len, std::max(cap, 0LL)));
+  return len;
 }
 }

@@ -13,8 +13,17 @@ from . import estimator
 PG_EXPORTS = [
     "svin_pg_create", "svin_pg_destroy", "svin_pg_last_error", "svin_pg_add_keyframe", "svin_pg_num_keyframes",
     "svin_pg_optimize", "svin_pg_get_pose", "svin_pg_get_poses", "svin_pg_get_drift", "svin_pg_summary",
-    "svin_pg_set_partition", "svin_pg_get_partition", "svin_pg_set_levels",
+    "svin_pg_set_partition", "svin_pg_get_partition", "svin_pg_set_levels", "svin_pg_debug_step", "svin_pg_debug_array",
 ]
+DEBUG_ARRAYS = [
+    "ea", "eb", "eloop", "off", "et", "eyaw", "epitch", "eroll", "eq", "esq", "yaw", "pitch", "roll", "t", "q",
+    "res", "Ja", "Jb", "g", "scale", "colsq", "nodeBlk", "y", "yS", "cost", "costC", "gradmax", "model", "step2", "x2",
+    "cholFail", "yawC", "tC", "qC", "rows", "cols", "rows2", "cols2", "sepOff", "nodePiece", "nodeRow", "isCover",
+    "isRoot", "l2PieceOf", "nS", "nR", "nPieces", "nPieces2", "BW", "BW2",
+]
+_DEBUG_INTS = {"ea", "eb", "eloop", "off", "cholFail", "rows", "cols", "rows2", "cols2", "sepOff", "nodePiece", "nodeRow",
+               "isCover", "isRoot", "l2PieceOf", "nS", "nR", "nPieces", "nPieces2", "BW", "BW2"}
+_DEBUG_SCALARS = {"cost", "costC", "gradmax", "model", "step2", "x2", "cholFail", "nS", "nR", "nPieces", "nPieces2", "BW", "BW2"}
 
 _BOUND = False
 
@@ -42,6 +51,8 @@ def _lib():
         sig("svin_pg_set_partition", i32, vp, i32, i32)
         sig("svin_pg_get_partition", i32, vp, pd)
         sig("svin_pg_set_levels", i32, vp, i32, i32)
+        sig("svin_pg_debug_step", i32, vp, i32, i32, f64)
+        sig("svin_pg_debug_array", C.c_longlong, vp, C.c_char_p, pd, C.c_longlong)
         _BOUND = True
     return L
 
@@ -116,3 +127,19 @@ class PoseGraph:
 
     def set_levels(self, levels=2, level2_piece_keyframes=0):
         self._check(self.L.svin_pg_set_levels(self.h, levels, level2_piece_keyframes), "set_levels")
+
+    def debug_step(self, earliest_loop_index, cur_index, radius=1e4):
+        """one LM step at `radius`, kept stage by stage (svin_pg_debug_step): dict of the arrays named in include/svin_pg.h,
+        or None when there is nothing to optimise; poses and drift stay untouched"""
+        if self._check(self.L.svin_pg_debug_step(self.h, earliest_loop_index, cur_index, float(radius)), "debug_step") == 0:
+            return None
+        out = {}
+        for name in DEBUG_ARRAYS:
+            n = self._check(self.L.svin_pg_debug_array(self.h, name.encode(), None, 0), "debug_array " + name)
+            a = np.zeros(max(int(n), 1))
+            self._check(self.L.svin_pg_debug_array(self.h, name.encode(), _p(a), int(n)), "debug_array " + name)
+            a = a[:int(n)]
+            if name in _DEBUG_INTS:
+                a = a.astype(np.int64)
+            out[name] = a[0].item() if name in _DEBUG_SCALARS else a
+        return out
