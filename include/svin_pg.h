@@ -68,6 +68,39 @@ int svin_pg_get_partition(const svin_pg* h, double* out10);
  * 1 no convergence, 3 failure), successful steps, solve seconds (device work, inputs resident) */
 int svin_pg_summary(const svin_pg* h, double* out6);
 
+/* ---- marginal covariances of keyframes (ceres::Covariance::GetCovarianceBlockInTangentSpace on the reference's problem)
+ *
+ * For the local problem svin_pg_optimize(h, earliest_loop_index, cur_index) would build now (same keyframes, edges, constant
+ * keyframes, HuberLoss(0.1) corrector), with J the stacked minimal Jacobian (square-root information and loss corrector applied:
+ * apply_loss_function = true) at the poses svin_pg_get_pose returns -- the SVIn poses on a fresh handle, the optimised ones after
+ * an optimisation; the edge measurements stay what optimize() takes them from -- Sigma = (J^T J)^-1, undamped, in the solver's
+ * tangent coordinates: 4-DoF [yaw in degrees, t], 6-DoF [t, dq] with q <- [sin|d| d/|d|, cos|d|] q.  The units are those of the
+ * reference's residual weights (sqrt-information 20 / 100 / 57.3 of the 6-DoF edges, unit weights and the 0.1 loop-yaw weight of
+ * the 4-DoF edges), not metres and radians of a calibrated sensor model.  Covariances are relative to the constant keyframe(s).
+ *
+ * The block of (index_a, index_b) -- the `index` values given to svin_pg_add_keyframe -- is Sigma[a, b], D x D row-major, D = 4
+ * or 6.  A constant keyframe has exactly zero covariance with everything; Sigma[b, a] is Sigma[a, b]^T bit for bit; two calls
+ * return the same bits.  To that end the block of a pair is read off the solve of ONE of its keyframes whoever asks: the one
+ * later in the range is the pair's column keyframe.  Column keyframes are solved in batches of B = 8 (D right-hand sides each)
+ * pushed through the factorisation the solver builds anyway; asking whole columns is cheap for late keyframes and costs a column
+ * keyframe per later row for early ones.
+ *
+ * Returns: -1 for NULL arguments, n_pairs < 0, cur_index < earliest_loop_index or a capacity too small (nothing is written);
+ * -2 for a keyframe outside the range or unknown; -3 for a device error; SVIN_PG_ERR_SINGULAR when J^T J is not positive definite
+ * -- a pivot that is not positive or below 1e-12 of its diagonal entry of the Jacobi-scaled J^T J; svin_pg_last_error() then names
+ * the keyframe index whose block met the pivot, or "root"; nothing is kept and the handle stays usable.  Nothing is written back:
+ * poses, drift, summary and partition record stay as they were.  The factor of the last call is kept and reused until
+ * svin_pg_add_keyframe, svin_pg_optimize, svin_pg_debug_step, svin_pg_set_partition or svin_pg_set_levels is called or another
+ * (earliest_loop_index, cur_index) is given. */
+#define SVIN_PG_ERR_SINGULAR (-5)
+/* n_pairs blocks back to back; cov == NULL only sizes; returns the doubles written (n_pairs * D * D) */
+long long svin_pg_get_covariance_blocks(svin_pg* h, int earliest_loop_index, int cur_index, int n_pairs,
+                                        const int* index_a, const int* index_b, double* cov, long long cap_doubles);
+int svin_pg_get_covariance(svin_pg* h, int earliest_loop_index, int cur_index, int index_a, int index_b,
+                           double* cov, int cap);              /* returns D * D */
+/* inspection: [0] factorisation passes, [1] substitution passes (batches), [2] distinct column keyframes solved, [3] spare */
+int svin_pg_covariance_counters(const svin_pg* h, long long out4[4]);
+
 /* ---- debug (tests/test_gpu_posegraph_stages.py): one Levenberg-Marquardt step kept stage by stage */
 
 /* problem construction, symbolic step, evaluation, node pass (with the Jacobi scales), ONE solve of the damped normal

@@ -6855,6 +6855,18 @@ void launchSolveReduced(const DeviceProblem& p, hipStream_t s, double mu, bool i
   }
   launch(k_sb_back, dim3(q.sbBack.grid), dim3(256), q.sbBack.ldsBytes, s, p, sb);
 }
+// The factorisation alone, on the blocked route whatever the size: L stays in p.cholL (plan regions bigM: the blocks below the
+// diagonal, row-major; diagF: the 64 x 64 diagonal blocks with L_tt^-T in the strict upper triangle of their 16 x 16 diagonal
+// tiles; dinvG: 1 / L_ii) for a caller that substitutes right-hand sides of its own.  The right-hand-side row block rides along.
+ReducedSolvePlan launchFactorBlocked(const DeviceProblem& p, hipStream_t s) {
+  const ReducedSolvePlan q = planWithChainMode(SolveDims{p.d, 0, 0, 0}, SolveSwitches{false, false, false}, 0, /*forceBlocked=*/true);
+  double* dinvG = p.cholL + q.dinvG.off;
+  double* diagF = p.cholL + q.diagF.off;
+  int* ready = reinterpret_cast<int*>(p.cholL + q.ready.off);
+  launch(k_big_load, dim3(q.bigLoad.grid), dim3(256), q.bigLoad.ldsBytes, s, p, q.dp, 0.0, 0, 0, ready, bigReadyInts(q.nb));
+  launch(k_big_chol_chain, dim3(q.bigChain.grid), dim3(256), q.bigChain.ldsBytes, s, p, q.dp, dinvG, diagF, ready);
+  return q;
+}
 
 // ================================================================ post-solve pass and dogleg step
 // traditional dogleg (ceres dogleg_strategy.cc) expressed on the un-scaled vectors:

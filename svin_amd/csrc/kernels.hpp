@@ -312,6 +312,8 @@ void launchGatherStaged(void* block, const GatherArgs& a, hipStream_t s);
 void launchFinalizeNormalEquations(const DeviceProblem& p, double mu, bool initScale, hipStream_t s);
 // Cholesky + GN step of the reduced system; fuseFinalize applies k_finalize_diag (metric + damping) while loading S
 void launchSolveReduced(const DeviceProblem& p, hipStream_t s, double mu = 0.0, bool initScale = false, bool fuseFinalize = false);
+// the blocked route's factorisation alone, at any size; the factor stays in p.cholL at the returned plan's bigM / dinvG / diagF
+ReducedSolvePlan launchFactorBlocked(const DeviceProblem& p, hipStream_t s);
 // grants a kernel `bytes` of dynamic LDS (hipFuncSetAttribute) once per (device, kernel) and only ever upwards: the attribute
 // belongs to the function for the whole process, so the bookkeeping is process-wide and mutex-protected, not per handle
 void ensureDynamicLds(const void* fn, size_t bytes);

@@ -23,16 +23,21 @@
 //           k_pg_piece_back      interior unknowns: x_I = L^-T (y_r - Y_C x_S)
 //           k_pg_model / k_pg_plus / k_pg_reduce   model cost change, candidate = Plus(x, delta), norms
 // Graphs with <= 128 free keyframes skip the pieces (every keyframe is a separator: one dense solve).
+// Marginal covariances of keyframes (svin_pg_get_covariance_blocks): k_pg_cov_* below push unit right-hand sides through the same
+// nested factorisation, undamped, the root on the blocked route whose factor stays in cholL (pg_cov_plan.hpp).
 #include "kernels.hpp"
 #include "dmath.hpp"
+#include "pg_cov_plan.hpp"
 #include "../../include/svin_pg.h"
 
 #include <algorithm>
 #include <chrono>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <map>
 #include <stdexcept>
 #include <string>
@@ -784,6 +789,216 @@ __global__ __launch_bounds__(256) void k_pg_reduce(PgDev p, int slot, int n, int
   if (threadIdx.x == 0) p.scal[slot] = s;
 }
 
+// ---------------------------------------------------------------- marginal covariances (pg_cov_plan.hpp)
+// Right-hand sides of one batch: X = rows x ldx row-major (ldx = kPgCovBatch * D, NC <= ldx columns in use).  Interior rows of
+// level 1 live in Xt (tangent order, the level's rowTan), separator rows in XS (separator order; the level-2 view's rowTan maps
+// its interior rows there), so the piece kernels run on either level's view unchanged.
+struct PgCovDev {
+  double *Xt, *XS;
+  int ldx, NC;
+  const int* slotNode;   // column slot -> node
+  const int* active;     // per level-1 piece: holds a column keyframe of the batch
+};
+
+// the ones of the unit vectors: column slot * D + j has its one in row j of the slot's keyframe
+__global__ __launch_bounds__(kPgCovThreads) void k_pg_cov_units(PgDev p, PgCovDev c) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= c.NC) return;
+  const int node = c.slotNode[t / p.D], j = t % p.D, so = p.sepOff[node];
+  if (so >= 0) c.XS[(size_t)(so + j) * c.ldx + t] = 1.0;
+  else c.Xt[(size_t)(p.off[node] + j) * c.ldx + t] = 1.0;
+}
+
+// w = L^-1 b in place, one workgroup per piece, one column per thread: the band factor in LDS, the last BW values of the
+// thread's column in an LDS ring.  Level 1 (pieceList != nullptr): a column is a unit vector, the substitution starts at its
+// keyframe's row (columns of other pieces are skipped).  Level 2 (pieceList == nullptr): every piece, from row 0.
+__global__ __launch_bounds__(kPgCovThreads) void k_pg_cov_forward(PgDev p, PgCovDev c, double* X, const int* pieceList) {
+  extern __shared__ double sm[];
+  const int piece = pieceList ? pieceList[blockIdx.x] : (int)blockIdx.x;
+  const PgPiece pc = p.pieces[piece];
+  const int n = pc.rows, BW = p.BW, LDB = BW + 1, tid = threadIdx.x;
+  double* Lb = sm;
+  double* ring = Lb + (size_t)p.maxRows * LDB;   // LDB rows of ldx
+  const double* band = p.band + pc.bandOff;
+  for (int i = tid; i < n * LDB; i += kPgCovThreads) Lb[i] = band[i];
+  __syncthreads();
+  if (tid >= c.NC) return;
+  int start = 0;
+  if (pieceList) {
+    const int node = c.slotNode[tid / p.D];
+    start = p.nodePiece[node] == piece ? p.nodeRow[node] : n;
+  }
+  const int* rowOf = p.rowTan + pc.rowPtr;
+  for (int r = start; r < n; ++r) {
+    double* xr = X + (size_t)rowOf[r] * c.ldx + tid;
+    double v = *xr;
+    const double* row = Lb + r * LDB + BW - r;   // L[r][k] = row[k]
+    for (int k = max(r - BW, start); k < r; ++k) v -= row[k] * ring[(k % LDB) * c.ldx + tid];
+    v /= row[r];
+    ring[(r % LDB) * c.ldx + tid] = v;
+    *xr = v;
+  }
+}
+
+// separator right-hand sides -= Y_C^T w: one thread per (separator unknown, column); the pieces that touch the separator in the
+// host's fixed order (rPtr / rSrc), the rows of a piece in ascending order.  A piece that holds no column keyframe of the batch
+// has w = 0 and is skipped (level 1; active == nullptr: every piece).
+__global__ __launch_bounds__(kPgCovThreads) void k_pg_cov_sep(PgDev p, PgCovDev c, const double* X, const int* active) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= p.nS * c.NC) return;
+  const int s = idx / c.NC, col = idx - s * c.NC, sn = s / p.D, comp = s - sn * p.D;
+  const int i0 = p.rPtr[sn], i1 = p.rPtr[sn + 1];
+  if (i0 == i1) return;
+  double acc = 0;
+  for (int i = i0; i < i1; ++i) {
+    const int2 src = p.rSrc[i];
+    if (active && !active[src.x]) continue;
+    const PgPiece pc = p.pieces[src.x];
+    const double* Yc = p.Y + pc.yOff + src.y + comp;
+    const int* rowOf = p.rowTan + pc.rowPtr;
+    double a = 0;
+    for (int r = 0; r < pc.rows; ++r) a += Yc[(size_t)r * pc.ld] * X[(size_t)rowOf[r] * c.ldx + col];
+    acc += a;
+  }
+  c.XS[(size_t)s * c.ldx + col] -= acc;
+}
+
+// Both substitutions against the root's blocked factor, kPgCovRootCols columns per workgroup, 16 rows a step.  L as
+// k_big_chol_chain leaves it: blocks below the diagonal in M (row-major, leading dimension dp), the 64 x 64 diagonal blocks in
+// diagF with the off-diagonal tiles = L and the strict upper triangle of a diagonal tile = L_tt^-T, dinv = 1 / L_ii.
+// Step 1 of a tile: b = x_t - (the rows / columns outside the tile) . x, each sum split over kStripes threads and added in a
+// fixed order; step 2: L_tt^-1 b (forward) or L_tt^-T b (backward) as a 16 x 16 product.
+constexpr int kPgCovRootCols = 4;
+__global__ __launch_bounds__(kPgCovThreads) void k_pg_cov_root(double* XR, int ldx, int NC, int d, int dp, const double* M,
+                                                                const double* dinvG, const double* diagF) {
+  constexpr int kOut = 16 * kPgCovRootCols, kStripes = kPgCovThreads / kOut;
+  static_assert(64 % kStripes == 0 && kOut * kStripes == kPgCovThreads, "a stripe keeps its residue across the 64-blocks");
+  __shared__ double part[kStripes][kOut];
+  __shared__ double b[16][kPgCovRootCols];
+  const int tid = threadIdx.x, o = tid % kOut, stripe = tid / kOut, i = o / kPgCovRootCols, cc = o % kPgCovRootCols;
+  const int col = blockIdx.x * kPgCovRootCols + cc;
+  const bool live = col < NC;
+  const int nT = (d + 15) / 16;
+  for (int pass = 0; pass < 2; ++pass) {
+    for (int tt = 0; tt < nT; ++tt) {
+      const int T = pass == 0 ? tt : nT - 1 - tt, i0 = 16 * T, row = i0 + i;
+      double s = 0;
+      if (live && row < d) {
+        // L[i][k], k < i: in M where the two lie in different 64-blocks, in the diagonal block's lower tiles otherwise
+        const int blk0 = i0 & ~63;
+        const double* x = XR + col;
+        if (pass == 0) {
+          const double* Mrow = M + (size_t)row * dp;
+          const double* Drow = diagF + (size_t)(row >> 6) * 4096 + (row & 63) * 64 - blk0;
+          int k = stripe;
+#pragma unroll 4
+          for (; k < blk0; k += kStripes) s += Mrow[k] * x[(size_t)k * ldx];
+          for (; k < i0; k += kStripes) s += Drow[k] * x[(size_t)k * ldx];
+        } else {
+          const double* Dcol = diagF + (size_t)(row >> 6) * 4096 + (row & 63) - (size_t)blk0 * 64;
+          const double* Mcol = M + row;
+          const int e = min(d, blk0 + 64);
+          int k = i0 + 16 + stripe;
+          for (; k < e; k += kStripes) s += Dcol[(size_t)k * 64] * x[(size_t)k * ldx];
+#pragma unroll 4
+          for (; k < d; k += kStripes) s += Mcol[(size_t)k * dp] * x[(size_t)k * ldx];
+        }
+      }
+      part[stripe][o] = s;
+      __syncthreads();
+      if (stripe == 0) {
+        double v = (live && row < d) ? XR[(size_t)row * ldx + col] : 0.0;
+        for (int q = 0; q < kStripes; ++q) v -= part[q][o];
+        b[i][cc] = v;
+      }
+      __syncthreads();
+      if (stripe == 0 && live && row < d) {
+        // the tile's inverse: (L_tt^-1)[r][c] for r > c sits at tile[c][r]
+        const double* tile = diagF + (size_t)(i0 >> 6) * 4096 + (size_t)(i0 & 63) * 64 + (i0 & 63);
+        double v = dinvG[row] * b[i][cc];
+        if (pass == 0) for (int r = 0; r < i; ++r) v += tile[r * 64 + i] * b[r][cc];
+        else for (int r = i + 1; r < 16 && i0 + r < d; ++r) v += tile[i * 64 + r] * b[r][cc];
+        XR[(size_t)row * ldx + col] = v;
+      }
+      __syncthreads();
+    }
+  }
+}
+
+// x = L^-T (w - Y_C x_S) in place: one workgroup per piece that holds a row keyframe (pieceList; nullptr: every piece).
+// z first, every (row, column) a dot product over the piece's coupling columns in ascending order; then one column per thread
+// from the last row up, the band factor in LDS, the last BW values in an LDS ring.
+__global__ __launch_bounds__(kPgCovThreads) void k_pg_cov_back(PgDev p, PgCovDev c, double* X, const int* pieceList) {
+  extern __shared__ double sm[];
+  const int piece = pieceList ? pieceList[blockIdx.x] : (int)blockIdx.x;
+  const PgPiece pc = p.pieces[piece];
+  const int n = pc.rows, BW = p.BW, LDB = BW + 1, tid = threadIdx.x, nc = pc.cols - 1;
+  double* Lb = sm;
+  double* ring = Lb + (size_t)p.maxRows * LDB;
+  const double* band = p.band + pc.bandOff;
+  const int* rowOf = p.rowTan + pc.rowPtr;
+  const int* colSep = p.colSep + pc.colPtr;
+  for (int i = tid; i < n * LDB; i += kPgCovThreads) Lb[i] = band[i];
+  for (int idx = tid; idx < n * c.NC; idx += kPgCovThreads) {
+    const int r = idx / c.NC, col = idx - r * c.NC;
+    const double* Yr = p.Y + pc.yOff + (size_t)r * pc.ld;
+    double acc = 0;
+    for (int k = 0; k < nc; ++k) acc += Yr[k] * c.XS[(size_t)colSep[k] * c.ldx + col];
+    X[(size_t)rowOf[r] * c.ldx + col] -= acc;
+  }
+  __syncthreads();
+  if (tid >= c.NC) return;
+  for (int r = n - 1; r >= 0; --r) {
+    double* xr = X + (size_t)rowOf[r] * c.ldx + tid;
+    double v = *xr;
+    for (int k = r + 1; k < min(n, r + BW + 1); ++k) v -= Lb[k * LDB + BW - (k - r)] * ring[(k % LDB) * c.ldx + tid];   // L[k][r]
+    v /= Lb[r * LDB + BW];
+    ring[(r % LDB) * c.ldx + tid] = v;
+    *xr = v;
+  }
+}
+
+// the requested blocks: Sigma[a_i, b_j] = s_(a_i) s_(b_j) x[a_i][slot(b) D + j]; a diagonal block takes its upper triangle from
+// its lower one, a block whose index_a is the column keyframe is written transposed.  One thread per entry.
+__global__ __launch_bounds__(kPgCovThreads) void k_pg_cov_write(PgDev p, PgCovDev c, const int4* pairs, int nPairs, double* out) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x, D = p.D, DD = D * D;
+  if (idx >= nPairs * DD) return;
+  const int4 pr = pairs[idx / DD];   // {pair, rowNode, slot, transposed}
+  int i = (idx % DD) / D, j = idx % D;
+  const int colNode = c.slotNode[pr.z];
+  const int oi = i, oj = j;
+  if (pr.y == colNode && i < j) { const int t = i; i = j; j = t; }
+  const int so = p.sepOff[pr.y], col = pr.z * D + j;
+  const double x = so >= 0 ? c.XS[(size_t)(so + i) * c.ldx + col] : c.Xt[(size_t)(p.off[pr.y] + i) * c.ldx + col];
+  const double v = x * (p.scale[p.off[pr.y] + i] * p.scale[p.off[colNode] + j]);
+  out[(size_t)pr.x * DD + (pr.w ? oj * D + oi : oi * D + oj)] = v;
+}
+
+// every pivot of the nested factorisation against the diagonal entry of the scaled normal equations it started from: the first
+// keyframe (lowest node) with a pivot that is not positive or below kPgCovPivotTol of that entry goes to *firstBad
+__global__ __launch_bounds__(kPgCovThreads) void k_pg_cov_pivots(PgDev p, PgDev p2, const int* l2Piece, const int* l2Row, int offR,
+                                                                  const double* dinvG, int* firstBad) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= p.nn || p.off[k] < 0) return;
+  const int D = p.D, o = p.off[k], so = p.sepOff[k];
+  bool bad = false;
+  for (int cI = 0; cI < D; ++cI) {
+    const double s = p.scale[o + cI], aii = p.nodeBlk[(size_t)k * 36 + cI * D + cI] * s * s;
+    double l;
+    if (so < 0) {
+      const PgPiece pc = p.pieces[p.nodePiece[k]];
+      l = p.band[pc.bandOff + (size_t)(p.nodeRow[k] + cI) * (p.BW + 1) + p.BW];
+    } else if (so >= offR) {
+      l = 1.0 / dinvG[so - offR + cI];
+    } else {
+      const PgPiece pc = p2.pieces[l2Piece[k]];
+      l = p2.band[pc.bandOff + (size_t)(l2Row[k] + cI) * (p2.BW + 1) + p2.BW];
+    }
+    bad = bad || !(aii > 0.0) || !(l > 0.0) || !(l * l >= kPgCovPivotTol * aii) || !(l * l <= 4.0 * aii);
+  }
+  if (bad) atomicMin(firstBad, k);
+}
+
 // ---------------------------------------------------------------- host
 struct Keyframe {
   int index = 0, sequence = 0;
@@ -862,6 +1077,11 @@ static void hostR2q(const double* R, double* qo) {  // Eigen::Quaterniond(Matrix
     qo[k] = (R[k * 3 + i] + R[i * 3 + k]) * s;
   }
 }
+
+// J^T J of the covariance pass is not positive definite (svin_pg_get_covariance*: SVIN_PG_ERR_SINGULAR)
+struct PgSingular : std::runtime_error {
+  using std::runtime_error::runtime_error;
+};
 
 class PoseGraph {
  public:
@@ -990,6 +1210,29 @@ class PoseGraph {
     int n = 0;
     for (int k = 0; k < nn; ++k)
       if (!fixed[k]) { off[k] = n; n += D; }
+    cov_.valid = false;   // (every pass through here overwrites the buffers a kept factor lives in)
+    if (covMode_) {
+      // the covariance is taken at the poses svin_pg_get_pose returns; the measurements above stay those of the SVIn poses
+      for (int k = 0; k < nn; ++k) {
+        const Keyframe& kf = kfs[kfOfLocal[k]];
+        bool moved = false;
+        for (int c = 0; c < 3; ++c) moved = moved || kf.P[c] != kf.t[c];
+        for (int c = 0; c < 9; ++c) moved = moved || kf.Rp[c] != kf.Rs[c];
+        if (!moved) continue;
+        yaw[k] = hostYawOfR(kf.Rp);
+        for (int c = 0; c < 3; ++c) t[3 * k + c] = kf.P[c];
+        hostR2q(kf.Rp, &q[4 * k]);
+      }
+      if (n > 0 && ne == 0) {
+        for (int k = 0; k < nn; ++k)
+          if (!fixed[k]) throw PgSingular("svin_pg: J^T J is not positive definite: keyframe " + std::to_string(kfs[kfOfLocal[k]].index) + " has no edge");
+      }
+      if (n == 0) {   // every keyframe of the range is constant: every block is zero
+        cov_ = CovKeep();
+        cov_.valid = true; cov_.earliest = earliest; cov_.cur = cur; cov_.n = 0; cov_.D = D; cov_.off = off;
+        return 1;
+      }
+    }
     summary[0] = summary[1] = 0; summary[2] = 0; summary[3] = 0; summary[4] = 0; summary[5] = 0;
     if (n == 0 || ne == 0) {  // nothing to optimise: the poses are still written back and the drift updated
       if (capture_) return 1;   // (debug step: keyframes untouched)
@@ -1251,8 +1494,9 @@ class PoseGraph {
     LevelHost L2;
     std::vector<int4> xDst;   // {kind | transposed << 4, piece, dstRow, dstCol}: 2 band, 3 coupling, 4 right-hand side
     std::vector<int2> xSrc;   // {row, col} offsets in the separator system
+    std::vector<int> l2Row(nn, -1);
     if (nPieces2 > 0) {
-      std::vector<int> rows(nPieces2, 0), l2Row(nn, -1);
+      std::vector<int> rows(nPieces2, 0);
       for (int k : freeNodes)
         if (l2PieceOf[k] >= 0) { l2Row[k] = rows[l2PieceOf[k]]; rows[l2PieceOf[k]] += D; }
       L2.adj.resize(nPieces2);
@@ -1373,8 +1617,8 @@ class PoseGraph {
       if (six_) launch(k_pg_eval<true>, dim3(gE), dim3(128), 0, s_, p, cand ? 1 : 0, withJac ? 1 : 0, finalReduce ? gN : 0);
       else launch(k_pg_eval<false>, dim3(gE), dim3(128), 0, s_, p, cand ? 1 : 0, withJac ? 1 : 0, finalReduce ? gN : 0);
     };
-    // damped normal equations at the current linearisation -> y (tangent order, scaled space)
-    auto solveNormalEquations = [&](double radius, int& nSolves) {
+    // damped normal equations at the current linearisation, the pieces of both levels eliminated: what is left is the root
+    auto assembleAndEliminate = [&](double radius) {
       HIP_OK(hipMemsetAsync(p.HS, 0, sizeof(double) * ((size_t)nS * nS + (nPieces > 0 ? workTot : 0)), s_));   // H_S | band | Y (| level 2)
       if (six_) launch(k_pg_assemble<6>, dim3(gN + gE), dim3(128), 0, s_, p, radius, gN);
       else launch(k_pg_assemble<4>, dim3(gN + gE), dim3(128), 0, s_, p, radius, gN);
@@ -1394,6 +1638,10 @@ class PoseGraph {
         launch(k_pg_sep_gather, dim3((L2.nDest * D * D + 255) / 256 + (nS + 255) / 256), dim3(256), 0, s_, p2, L2.nDest,
                (L2.nDest * D * D + 255) / 256);
       }
+    };
+    // ... and solved -> y (tangent order, scaled space)
+    auto solveNormalEquations = [&](double radius, int& nSolves) {
+      assembleAndEliminate(radius);
       HIP_OK(hipEventRecord(evA_[nSolves % kPgMaxTimed], s_));
       launchSolveReduced(dp, s_, 0.0, false, false);
       HIP_OK(hipEventRecord(evB_[nSolves % kPgMaxTimed], s_));
@@ -1429,6 +1677,35 @@ class PoseGraph {
         if (six_) launch(k_pg_node<6>, dim3(gN), dim3(128), 0, s_, p, initScale ? 1 : 0);
         else launch(k_pg_node<4>, dim3(gN), dim3(128), 0, s_, p, initScale ? 1 : 0);
         initScale = false;
+      }
+      if (covMode_) {
+        // covariance pass: the UNDAMPED normal equations (1 / radius = 0 exactly: the LM term of pgAssembleNode is x / inf) factorised
+        // down to the root, the root on the blocked route, whose factor stays in cholL; then out of the loop, nothing written back
+        if (!pgCovPieceFits(maxRows, BW, kPgCovBatch * D) || !pgCovPieceFits(L2.maxRows, BW2, kPgCovBatch * D))
+          throw std::runtime_error("svin_pg: a piece's factor does not fit the covariance pass's LDS");
+        assembleAndEliminate(std::numeric_limits<double>::infinity());
+        ReducedSolvePlan rq{};
+        if (nR > 0) rq = launchFactorBlocked(dp, s_);   // (a chain short of a cut has no root)
+        dCovL2_.reserve(2 * (size_t)nn + 2);
+        std::vector<int> l2(2 * (size_t)nn);
+        for (int k = 0; k < nn; ++k) { l2[k] = l2PieceOf[k]; l2[nn + k] = l2Row[k]; }
+        HIP_OK(hipMemcpyAsync(dCovL2_.p, l2.data(), sizeof(int) * l2.size(), hipMemcpyHostToDevice, s_));
+        int* dBad = dCovL2_.p + 2 * (size_t)nn;
+        int firstBad = INT_MAX;
+        HIP_OK(hipMemcpyAsync(dBad, &firstBad, sizeof(int), hipMemcpyHostToDevice, s_));
+        launch(k_pg_cov_pivots, dim3((nn + kPgCovThreads - 1) / kPgCovThreads), dim3(kPgCovThreads), 0, s_, p, p2, (const int*)dCovL2_.p,
+               (const int*)(dCovL2_.p + nn), offR, (const double*)(dChol_.p + rq.dinvG.off), dBad);
+        HIP_OK(hipMemcpyAsync(&firstBad, dBad, sizeof(int), hipMemcpyDeviceToHost, s_));
+        readScal();
+        if (firstBad != INT_MAX)
+          throw PgSingular("svin_pg: J^T J is not positive definite: pivot of keyframe " + std::to_string(kfs[kfOfLocal[firstBad]].index));
+        if (hs.sol.cholFail != 0) throw PgSingular("svin_pg: J^T J is not positive definite: pivot of the root");
+        cov_ = CovKeep();
+        cov_.earliest = earliest; cov_.cur = cur; cov_.nn = nn; cov_.n = n; cov_.D = D; cov_.nS = nS; cov_.offR = offR; cov_.nR = nR;
+        cov_.nPieces = nPieces; cov_.nPieces2 = nPieces2; cov_.p = p; cov_.p2 = p2; cov_.off = off; cov_.nodePiece = nodePiece;
+        cov_.dp = rq.dp; cov_.dinvOff = rq.dinvG.off; cov_.diagOff = rq.diagF.off;
+        cov_.valid = true;
+        return 1;
       }
       if (iteration >= maxIter_) { termination = 1; break; }
       if (radius <= min_radius) { termination = 0; break; }
@@ -1531,6 +1808,126 @@ class PoseGraph {
     return 1;
   }
 
+  // ---- marginal covariances (pg_cov_plan.hpp).  The factor of the last pass stays in the solver's own buffers (band | Y of both
+  // levels, the root's blocked factor in dChol_, the scales) together with the views that index it, until anything overwrites them.
+  struct CovKeep {
+    bool valid = false;
+    int earliest = 0, cur = 0, nn = 0, n = 0, D = 4, nS = 0, offR = 0, nR = 0, nPieces = 0, nPieces2 = 0, dp = 0;
+    size_t dinvOff = 0, diagOff = 0;
+    PgDev p, p2;
+    std::vector<int> off, nodePiece;
+  };
+  CovKeep cov_;
+  bool covMode_ = false;
+  int tangentSize() const { return six_ ? 6 : 4; }
+  long long covCounters[4] = {0, 0, 0, 0};   // factorisation passes, substitution passes, column keyframes solved, spare
+  void invalidateCovariance() { cov_.valid = false; }
+
+  // local index (position in the range) of the keyframes optimize(earliest, cur) would take
+  std::unordered_map<int, int> rangeOf(int earliest, int cur) const {
+    std::unordered_map<int, int> loc;
+    int i = 0;
+    for (const Keyframe& kf : kfs) {
+      if (kf.index < earliest) continue;
+      loc[kf.index] = i++;
+      if (kf.index == cur) break;
+    }
+    return loc;
+  }
+
+  // optimize() in covariance mode: construction, symbolic step, evaluation, node pass, undamped assembly, factorisation.
+  // Summary and partition record are those of the last optimisation again afterwards.
+  void covarianceFactor(int earliest, int cur) {
+    double sumKeep[8];
+    int partKeep[9];
+    std::memcpy(sumKeep, summary, sizeof(sumKeep));
+    std::memcpy(partKeep, partition, sizeof(partKeep));
+    covMode_ = true;
+    try {
+      optimize(earliest, cur);
+    } catch (...) {
+      covMode_ = false;
+      cov_.valid = false;
+      std::memcpy(summary, sumKeep, sizeof(sumKeep));
+      std::memcpy(partition, partKeep, sizeof(partKeep));
+      throw;
+    }
+    covMode_ = false;
+    std::memcpy(summary, sumKeep, sizeof(sumKeep));
+    std::memcpy(partition, partKeep, sizeof(partKeep));
+  }
+
+  // blocks (la[i], lb[i]) in local indices -> out (nPairs x D x D); throws PgSingular
+  void covarianceBlocks(int earliest, int cur, int nPairs, const int* la, const int* lb, double* out) {
+    if (!cov_.valid || cov_.earliest != earliest || cov_.cur != cur) {
+      covarianceFactor(earliest, cur);
+      ++covCounters[0];
+    }
+    const CovKeep& K = cov_;
+    const int D = K.D, DD = D * D;
+    std::vector<double> res((size_t)nPairs * DD, 0.0);
+    if (K.n > 0 && nPairs > 0) {
+      const std::vector<int> noPiece(K.off.size(), -1);
+      const PgCovPlan plan = planPgCovariance(nPairs, la, lb, K.off.data(), K.nPieces > 0 ? K.nodePiece.data() : noPiece.data(), K.nPieces);
+      const int ldx = kPgCovBatch * D;
+      const size_t xtDoubles = (size_t)K.n * ldx, xsDoubles = (size_t)K.nS * ldx;
+      dCovX_.reserve(xtDoubles + xsDoubles);
+      dCovOut_.reserve((size_t)nPairs * DD);
+      HIP_OK(hipMemsetAsync(dCovOut_.p, 0, sizeof(double) * (size_t)nPairs * DD, s_));
+      const PgDev& p = K.p;
+      const PgDev& p2 = K.p2;
+      const size_t lds1 = pgCovPieceLdsBytes(p.maxRows, p.BW, ldx), lds2 = pgCovPieceLdsBytes(p2.maxRows, p2.BW, ldx);
+      for (const PgCovBatch& B : plan.batches) {
+        const int nSlots = (int)B.slotNode.size(), NC = nSlots * D, nFwd = (int)B.fwdPieces.size(), nBack = (int)B.backPieces.size();
+        // one upload: slotNode | active | fwdPieces | backPieces, then the pairs
+        std::vector<int> ints;
+        ints.insert(ints.end(), B.slotNode.begin(), B.slotNode.end());
+        const size_t oActive = ints.size();
+        ints.insert(ints.end(), B.active.begin(), B.active.end());
+        const size_t oFwd = ints.size();
+        ints.insert(ints.end(), B.fwdPieces.begin(), B.fwdPieces.end());
+        const size_t oBack = ints.size();
+        ints.insert(ints.end(), B.backPieces.begin(), B.backPieces.end());
+        dCovInt_.upload(ints, s_);
+        std::vector<int4> prs;
+        for (const PgCovBatchPair& q : B.pairs) prs.push_back(make_int4(q.pair, q.rowNode, q.slot, q.transposed));
+        dCovPairs_.upload(prs, s_);
+        HIP_OK(hipStreamSynchronize(s_));   // (the uploads read host vectors of this iteration)
+        PgCovDev c;
+        c.Xt = dCovX_.p; c.XS = dCovX_.p + xtDoubles; c.ldx = ldx; c.NC = NC;
+        c.slotNode = dCovInt_.p; c.active = dCovInt_.p + oActive;
+        const int* dFwd = dCovInt_.p + oFwd;
+        const int* dBack = dCovInt_.p + oBack;
+        HIP_OK(hipMemsetAsync(dCovX_.p, 0, sizeof(double) * (xtDoubles + xsDoubles), s_));
+        launch(k_pg_cov_units, dim3(1), dim3(kPgCovThreads), 0, s_, p, c);
+        const unsigned gSep = (unsigned)(((size_t)K.nS * NC + kPgCovThreads - 1) / kPgCovThreads);
+        if (K.nPieces > 0 && nFwd > 0) {
+          launch(k_pg_cov_forward, dim3(nFwd), dim3(kPgCovThreads), lds1, s_, p, c, c.Xt, dFwd);
+          launch(k_pg_cov_sep, dim3(gSep), dim3(kPgCovThreads), 0, s_, p, c, (const double*)c.Xt, c.active);
+        }
+        if (K.nPieces2 > 0) {
+          launch(k_pg_cov_forward, dim3(K.nPieces2), dim3(kPgCovThreads), lds2, s_, p2, c, c.XS, (const int*)nullptr);
+          launch(k_pg_cov_sep, dim3(gSep), dim3(kPgCovThreads), 0, s_, p2, c, (const double*)c.XS, (const int*)nullptr);
+        }
+        if (K.nR > 0)
+          launch(k_pg_cov_root, dim3((NC + kPgCovRootCols - 1) / kPgCovRootCols), dim3(kPgCovThreads), 0, s_, c.XS + (size_t)K.offR * ldx, ldx, NC,
+               K.nR, K.dp, (const double*)dChol_.p, (const double*)(dChol_.p + K.dinvOff), (const double*)(dChol_.p + K.diagOff));
+        if (K.nPieces2 > 0) launch(k_pg_cov_back, dim3(K.nPieces2), dim3(kPgCovThreads), lds2, s_, p2, c, c.XS, (const int*)nullptr);
+        if (K.nPieces > 0 && nBack > 0) launch(k_pg_cov_back, dim3(nBack), dim3(kPgCovThreads), lds1, s_, p, c, c.Xt, dBack);
+        if (!prs.empty())
+          launch(k_pg_cov_write, dim3((unsigned)((prs.size() * DD + kPgCovThreads - 1) / kPgCovThreads)), dim3(kPgCovThreads), 0, s_, p, c,
+                 (const int4*)dCovPairs_.p, (int)prs.size(), dCovOut_.p);
+        HIP_OK(hipStreamSynchronize(s_));
+        ++covCounters[1];
+        covCounters[2] += nSlots;
+      }
+      HIP_OK(hipMemcpy(res.data(), dCovOut_.p, sizeof(double) * res.size(), hipMemcpyDeviceToHost));
+      for (const double v : res)
+        if (!std::isfinite(v)) throw std::runtime_error("svin_pg: a covariance block is not finite");
+    }
+    std::memcpy(out, res.data(), sizeof(double) * res.size());
+  }
+
   void writeBack(const std::vector<double>& hy, const std::vector<double>& pitch, const std::vector<double>& roll,
                  const std::vector<double>& ht, const std::vector<double>& hq, const std::vector<int>& kfOfLocal, int cur) {
     const int nn = (int)kfOfLocal.size();
@@ -1576,6 +1973,9 @@ class PoseGraph {
   Buf<int2> dGDst_, dRSrc_, dGDst2_, dRSrc2_, dXSrc_;
   Buf<int> dColSep2_, dRowMap2_, dGPtr2_, dRPtr2_;
   Buf<double> dSp2_;
+  Buf<double> dCovX_, dCovOut_;
+  Buf<int> dCovL2_, dCovInt_;
+  Buf<int4> dCovPairs_;
 };
 
 }  // namespace pg
@@ -1616,6 +2016,7 @@ int svin_pg_add_keyframe(svin_pg* h, int index, int sequence, const double* t, c
   svin::pg::hostQ2R(kf.q, kf.Rs);
   h->g.applyDrift(kf);
   h->g.kfs.push_back(kf);
+  h->g.invalidateCovariance();
   return 1;
 } catch (const std::exception& e) {   // (allocation failure of the keyframe list: nothing crosses the C ABI)
   g_pgError = e.what();
@@ -1656,12 +2057,14 @@ int svin_pg_set_partition(svin_pg* h, int piece_keyframes, int dense_keyframes) 
   if (!h || piece_keyframes < 0 || dense_keyframes < 0) return -1;
   if (piece_keyframes > 0) h->g.pieceLen_ = piece_keyframes;
   h->g.denseNodes_ = dense_keyframes;
+  h->g.invalidateCovariance();
   return 1;
 }
 int svin_pg_set_levels(svin_pg* h, int levels, int level2_piece_keyframes) {
   if (!h || levels < 1 || levels > 2 || level2_piece_keyframes < 0) return -1;
   h->g.level2_ = levels == 2;
   if (level2_piece_keyframes > 0) h->g.l2Len_ = level2_piece_keyframes;
+  h->g.invalidateCovariance();
   return 1;
 }
 int svin_pg_get_partition(const svin_pg* h, double* out10) {
@@ -1687,6 +2090,42 @@ int svin_pg_debug_step(svin_pg* h, int earliest_loop_index, int cur_index, doubl
     g_pgError = e.what();
     return -3;
   }
+}
+long long svin_pg_get_covariance_blocks(svin_pg* h, int earliest_loop_index, int cur_index, int n_pairs, const int* index_a,
+                                        const int* index_b, double* cov, long long cap_doubles) {
+  if (!h || n_pairs < 0 || cur_index < earliest_loop_index || (n_pairs > 0 && (!index_a || !index_b))) return -1;
+  const int D = h->g.tangentSize();
+  const long long need = (long long)n_pairs * D * D;
+  if (cov && cap_doubles < need) return -1;
+  try {
+    const std::unordered_map<int, int> loc = h->g.rangeOf(earliest_loop_index, cur_index);
+    std::vector<int> la(n_pairs), lb(n_pairs);
+    for (int i = 0; i < n_pairs; ++i) {
+      const auto a = loc.find(index_a[i]), b = loc.find(index_b[i]);
+      if (a == loc.end() || b == loc.end()) {
+        g_pgError = "svin_pg: keyframe " + std::to_string(a == loc.end() ? index_a[i] : index_b[i]) + " is not in the range";
+        return -2;
+      }
+      la[i] = a->second; lb[i] = b->second;
+    }
+    if (!cov) return need;
+    h->g.covarianceBlocks(earliest_loop_index, cur_index, n_pairs, la.data(), lb.data(), cov);
+    return need;
+  } catch (const svin::pg::PgSingular& e) {
+    g_pgError = e.what();
+    return SVIN_PG_ERR_SINGULAR;
+  } catch (const std::exception& e) {
+    g_pgError = e.what();
+    return -3;
+  }
+}
+int svin_pg_get_covariance(svin_pg* h, int earliest_loop_index, int cur_index, int index_a, int index_b, double* cov, int cap) {
+  return (int)svin_pg_get_covariance_blocks(h, earliest_loop_index, cur_index, 1, &index_a, &index_b, cov, cap);
+}
+int svin_pg_covariance_counters(const svin_pg* h, long long out4[4]) {
+  if (!h || !out4) return -1;
+  std::memcpy(out4, h->g.covCounters, sizeof(long long) * 4);
+  return 1;
 }
 long long svin_pg_debug_array(const svin_pg* h, const char* name, double* out, long long cap) {
   if (!h || !name) return -1;

@@ -165,12 +165,14 @@ inline int chainModeOf(const SolveDims& m, const SolveSwitches& sw) {
   return denseRoute(m.dC, false, sw) == kRouteBlocked ? 1 : 2;   // (asked without the border rows, which the compact S' would allow)
 }
 
-inline ReducedSolvePlan planWithChainMode(const SolveDims& m, const SolveSwitches& sw, int mode) {
+// forceBlocked: the blocked route whatever the size (chain mode 0 only) -- the one route whose factor stays behind in cholL
+// (bigM, dinvG, diagF), for a caller that substitutes right-hand sides of its own (the pose graph's covariance pass)
+inline ReducedSolvePlan planWithChainMode(const SolveDims& m, const SolveSwitches& sw, int mode, bool forceBlocked = false) {
   ReducedSolvePlan q{};
   q.chainMode = mode;
   q.dSolve = mode ? m.dC : m.d;
   const bool padded = mode == 2 || m.sPadded != 0;   // (the compact S' is padded)
-  q.route = mode == 1 ? kRouteBlocked : denseRoute(q.dSolve, padded, sw);
+  q.route = (mode == 1 || forceBlocked) ? kRouteBlocked : denseRoute(q.dSolve, padded, sw);
   const bool lds = q.route <= kRouteLdsBorderPrepared;
   q.border = lds ? cholBorderRows(q.dSolve, padded, sw) : 0;
   q.dpad = q.border ? 16 * kCholLdsMaxTiles : roundUpTo(q.dSolve, 16);

@@ -14,7 +14,13 @@ PG_EXPORTS = [
     "svin_pg_create", "svin_pg_destroy", "svin_pg_last_error", "svin_pg_add_keyframe", "svin_pg_num_keyframes",
     "svin_pg_optimize", "svin_pg_get_pose", "svin_pg_get_poses", "svin_pg_get_drift", "svin_pg_summary",
     "svin_pg_set_partition", "svin_pg_get_partition", "svin_pg_set_levels", "svin_pg_debug_step", "svin_pg_debug_array",
+    "svin_pg_get_covariance_blocks", "svin_pg_get_covariance", "svin_pg_covariance_counters",
 ]
+ERR_SINGULAR = -5   # SVIN_PG_ERR_SINGULAR
+
+
+class SingularError(RuntimeError):
+    """J^T J of the covariance pass is not positive definite (SVIN_PG_ERR_SINGULAR); mirrors estimator.SingularError"""
 DEBUG_ARRAYS = [
     "ea", "eb", "eloop", "off", "et", "eyaw", "epitch", "eroll", "eq", "esq", "yaw", "pitch", "roll", "t", "q",
     "res", "Ja", "Jb", "g", "scale", "colsq", "nodeBlk", "y", "yS", "cost", "costC", "gradmax", "model", "step2", "x2",
@@ -53,6 +59,10 @@ def _lib():
         sig("svin_pg_set_levels", i32, vp, i32, i32)
         sig("svin_pg_debug_step", i32, vp, i32, i32, f64)
         sig("svin_pg_debug_array", C.c_longlong, vp, C.c_char_p, pd, C.c_longlong)
+        pi = C.POINTER(C.c_int)
+        sig("svin_pg_get_covariance_blocks", C.c_longlong, vp, i32, i32, i32, pi, pi, pd, C.c_longlong)
+        sig("svin_pg_get_covariance", i32, vp, i32, i32, i32, i32, pd, i32)
+        sig("svin_pg_covariance_counters", i32, vp, C.POINTER(C.c_longlong))
         _BOUND = True
     return L
 
@@ -143,3 +153,27 @@ class PoseGraph:
                 a = a.astype(np.int64)
             out[name] = a[0].item() if name in _DEBUG_SCALARS else a
         return out
+
+    def covariance_blocks(self, earliest_loop_index, cur_index, pairs):
+        """Sigma[a, b] for every (a, b) of `pairs` (keyframe indices): n_pairs x D x D, tangent coordinates and units as
+        include/svin_pg.h states them; raises SingularError when J^T J is not positive definite"""
+        pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        ia, ib = np.ascontiguousarray(pairs[:, 0]), np.ascontiguousarray(pairs[:, 1])
+        D = 6 if self.six else 4
+        out = np.zeros((len(pairs), D, D))
+        pi = C.POINTER(C.c_int)
+        rc = self.L.svin_pg_get_covariance_blocks(self.h, earliest_loop_index, cur_index, len(pairs), ia.ctypes.data_as(pi),
+                                                  ib.ctypes.data_as(pi), _p(out), out.size)
+        if rc == ERR_SINGULAR:
+            raise SingularError(self.L.svin_pg_last_error().decode())
+        self._check(rc, "covariance_blocks")
+        return out
+
+    def covariance(self, earliest_loop_index, cur_index, a, b):
+        """the D x D block Sigma[a, b]"""
+        return self.covariance_blocks(earliest_loop_index, cur_index, [(a, b)])[0]
+
+    def covariance_counters(self):
+        c = (C.c_longlong * 4)()
+        self._check(self.L.svin_pg_covariance_counters(self.h, c), "covariance_counters")
+        return dict(factorisations=int(c[0]), passes=int(c[1]), columns=int(c[2]))
