@@ -245,6 +245,41 @@ inline StepMode stepModeOf(const StepDims& m, const StepSwitches& sw, bool shard
   q.chosenForm = q.fuseStep ? (q.deferPossible ? 3 : 1) : 2;
   return q;
 }
+// ---- the step at the head of the evaluation's blocks (k_post_solve without its tail + k_eval_build with a radius).  The serial
+// tail of the post-solve pass -- ticket, partials, reduction, coefficients, retraction of the parameter blocks -- produces only what
+// the blocks of the next launch read first; each of those blocks computes it itself instead, from the partials.  The pair is taken
+// where the narrow pass runs (k_post_solve, not k_post_solve_wide), where the old tail staged everything (its limits below), where the next launch is k_eval_build (a build is wanted behind this
+// evaluation: never on the last iteration of a solve, which k_eval_all follows), and never on a re-used linearisation, whose step
+// k_step_retract takes.  A window with host-evaluated factors keeps the tail: the host reads the candidate blocks before the launch.
+constexpr int kStepHeadMaxD = 1024;       // y_C and v_C staged in LDS (k_post_solve: kStageMax)
+constexpr int kStepHeadMaxItems = 96;     // parameter blocks one pass of a workgroup retracts (k_post_solve: kStageItems)
+constexpr int kStepHeadRedDoubles = 16 * 9 + 8;   // the block sum's rows and group B
+inline size_t stepHeadLdsBytes(int d) { return (size_t)(kStepHeadRedDoubles + 2 * d) * 8; }   // behind a block's staged tables
+// Whether Window::solve enqueues a speculative build behind the candidate evaluation of this iteration: speculation on, clean
+// accumulators (they are, right behind a post-solve pass), and an iteration to use it -- never the last one of the solve.
+inline bool specBuildWanted(bool speculate, bool accumulatorsClean, int iteration, int numIter) {
+  return speculate && accumulatorsClean && iteration < numIter;
+}
+struct StepInEvalIn {
+  int chosenForm;        // StepMode::chosenForm
+  bool sharded;          // more than one GPU (or the forced one-rank communicator)
+  bool buildWanted;      // a speculative build is enqueued behind this iteration's candidate evaluation
+  bool evalBuildTaken;   // evalBuildTaken() of the window
+  bool reuse;            // the iteration re-uses the linearisation (a rejected step before it)
+  bool postSplit;        // EvalPlan::postSplit: the pass is k_post_solve_wide, which keeps its tail
+  bool hostFactors;      // the window has factors the host evaluates
+  bool noStepInEval;     // SVIN_NO_STEP_IN_EVAL
+  int d, items, nPost;   // reduced unknowns, pose + extrinsics + speed/bias blocks, blocks of the post-solve pass
+  size_t evalStageBytes, chunkLdsBytes, stageBytes, factorSharedBytes;   // as evalBuildFits takes them; evalStageBytes: the reprojection blocks' tables behind their reduction scratch
+};
+inline bool stepInEvalTaken(const StepInEvalIn& q) {
+  if (q.noStepInEval || q.chosenForm != 3 || q.sharded || !q.buildWanted || !q.evalBuildTaken || q.reuse || q.postSplit || q.hostFactors) return false;
+  if (q.d <= 0 || q.d > kStepHeadMaxD || q.items <= 0 || q.items > kStepHeadMaxItems || q.nPost <= 0 || q.nPost > kMaxPartials) return false;
+  const size_t head = stepHeadLdsBytes(q.d);
+  if (q.evalStageBytes + head > q.factorSharedBytes) return false;
+  return ((q.chunkLdsBytes + 15) & ~(size_t)15) + q.stageBytes + head <= q.factorSharedBytes;
+}
+
 // the batched round has the fused step with the landmarks deferred and nothing else (k_post_solve_batch, k_eval_reproj_batch)
 inline bool batchedStepTakes(const StepMode& q) { return q.fuseStep && q.deferLm && q.small; }
 

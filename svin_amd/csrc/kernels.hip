@@ -475,14 +475,16 @@ struct ReprojTables { double* sPose; double* sExt; CameraModel* sCam; double* sL
 template <bool ROBUST>
 __device__ __forceinline__ ReprojTables stageReprojTables(double* smem, int nPose, int nExt, int nCam, const double* __restrict__ pose,
                                                           const double* __restrict__ ext, const CameraModel* __restrict__ cams,
-                                                          const double* __restrict__ lossTab) {
+                                                          const double* __restrict__ lossTab, bool blocksStaged = false) {
   ReprojTables tb;
   tb.sPose = smem;                           // nPose*7
   tb.sExt = tb.sPose + nPose * 7;            // nExt*7
   tb.sCam = reinterpret_cast<CameraModel*>(tb.sExt + nExt * 7);  // nCam
   tb.sLoss = reinterpret_cast<double*>(tb.sCam + nCam);          // 2 kMaxLosses (lossTab only: kLossTabBytes)
-  for (int i = threadIdx.x; i < nPose * 7; i += blockDim.x) tb.sPose[i] = pose[i];
-  for (int i = threadIdx.x; i < nExt * 7; i += blockDim.x) tb.sExt[i] = ext[i];
+  if (!blocksStaged) {   // (staged: stepHead has written the candidate poses and extrinsics there itself)
+    for (int i = threadIdx.x; i < nPose * 7; i += blockDim.x) tb.sPose[i] = pose[i];
+    for (int i = threadIdx.x; i < nExt * 7; i += blockDim.x) tb.sExt[i] = ext[i];
+  }
   {
     const double* src = reinterpret_cast<const double*>(cams);
     double* dst = reinterpret_cast<double*>(tb.sCam);
@@ -585,8 +587,8 @@ __device__ __forceinline__ void evalReprojBlock(int block, double* smem, double*
                                                 double* __restrict__ Je, double* __restrict__ costPartial, size_t stride,
                                                 const LmDefer df = LmDefer(), const double* __restrict__ lmPrior = nullptr,
                                                 const double* __restrict__ lossTab = nullptr,
-                                                const double* __restrict__ obsS = nullptr) {
-  const ReprojTables tb = stageReprojTables<ROBUST>(smem, nPose, nExt, nCam, pose, ext, cams, lossTab);
+                                                const double* __restrict__ obsS = nullptr, bool blocksStaged = false) {
+  const ReprojTables tb = stageReprojTables<ROBUST>(smem, nPose, nExt, nCam, pose, ext, cams, lossTab, blocksStaged);
   __syncthreads();
   const int i = block * blockDim.x + threadIdx.x;
   double cost = 0, stepSq = 0, xSq = 0;
@@ -1516,13 +1518,26 @@ __device__ __forceinline__ int blockOff(const DeviceProblem& p, int kind, int sl
 
 // a factor's share of the cost, 0.5 rho(|r|^2) of its loss (LOSS_NONE: 0.5 |r|^2), and sqrt(rho') beside its record (r and J stay
 // as evaluated: Map::getLhs reads them; the solve's consumers scale by lin.sc)
-__device__ __forceinline__ void factorLossStore(const DeviceProblem& p, const DevFactor& fac, FactorLin& lin, int f, double sq) {
+// (returns sqrt(rho'))
+__device__ __forceinline__ double factorLossStore(const DeviceProblem& p, const DevFactor& fac, FactorLin& lin, int f, double sq) {
   double rho0, rho1;
   residualLoss(fac.lossKind, fac.lossScale, sq, rho0, rho1);
-  lin.sc = sqrt(rho1);
+  const double sc = sqrt(rho1);
+  lin.sc = sc;
   cstore(p.partial + (size_t)PS_COST_FACTORS * kMaxPartials + f, 0.5 * rho0);
+  return sc;
 }
-__device__ __forceinline__ void evalFactorBlock(const DeviceProblem& p, int cand, int f, FactorShared& sh) {
+// LDS a factor block's record is staged in for factorsAccumulateLin: colRow (kFactorColRow ints), J and r (kFactorStage doubles), and
+// -- where the block that evaluated the factor hands the record over itself (k_eval_build) -- sc and the block table off[4] | dim[4]
+constexpr int kFactorColRow = 32;                 // ints reserved for colRow (30 used)
+constexpr int kFactorStage = 15 * 30 + 15;        // doubles behind them: J, r
+constexpr int kFactorHandOver = 1 + 4;            // doubles behind those: sc, then eight ints
+// blocksStaged: the factor's parameter blocks are in sh.xs already, one behind the other (stepHead: the candidate this block has
+// retracted itself) -- nothing is read from pose / sb or their candidate copies
+// accStage: the staging area of factorsAccumulateLin behind its colRow ints -- J, r, sc and the block table go there as well as into
+// the record (not for F_HOST factors, whose record the host wrote)
+__device__ __forceinline__ void evalFactorBlock(const DeviceProblem& p, int cand, int f, FactorShared& sh, bool blocksStaged = false,
+                                                double* accStage = nullptr) {
   const int t = threadIdx.x;
   const DevFactor& fac = p.factors[f];
   FactorLin& lin = (cand ? p.linCand : p.linCur)[f];
@@ -1565,10 +1580,12 @@ __device__ __forceinline__ void evalFactorBlock(const DeviceProblem& p, int cand
       if (t < 56) sh.st[t] = (&im.Delta_t)[t];
     };
     stage();
-    if (t >= 64 && t < 71) sh.xs[t - 64] = x0[t - 64];
-    if (t >= 71 && t < 80) sh.xs[7 + t - 71] = s0[t - 71];
-    if (t >= 80 && t < 87) sh.xs[16 + t - 80] = x1[t - 80];
-    if (t >= 87 && t < 96) sh.xs[23 + t - 87] = s1[t - 87];
+    if (!blocksStaged) {
+      if (t >= 64 && t < 71) sh.xs[t - 64] = x0[t - 64];
+      if (t >= 71 && t < 80) sh.xs[7 + t - 71] = s0[t - 71];
+      if (t >= 80 && t < 87) sh.xs[16 + t - 80] = x1[t - 80];
+      if (t >= 87 && t < 96) sh.xs[23 + t - 87] = s1[t - 87];
+    }
     if (t >= 96 && t < 102) sh.st[56 + t - 96] = im.sb_ref[3 + t - 96];
     if (t == 102) sh.st[62] = (double)im.redo;
     if (t == 103) sh.st[63] = dtSecDev(im.t1, im.t0);
@@ -1732,14 +1749,13 @@ __device__ __forceinline__ void evalFactorBlock(const DeviceProblem& p, int cand
     }
   } else {
     for (int k = t; k < m * m; k += blockDim.x) sh.W[k] = fac.sqrtInfo[k];
-    if (t == 0) {
-      const double* x0 = blockPtr(p, cand, fac.blkKind[0], fac.blkSlot[0]);
+    // (instantiated on the staged LDS copies and on the global arrays: one pointer that may hold either is a FLAT access)
+    auto evalSmall = [&](const double* x0, const double* x1) __attribute__((always_inline)) {
       if (fac.kind == F_POSE_PRIOR) {  // PoseError.cpp:87-132
         poseErrorEval(fac.meas, x0, sh.e, sh.F);   // dmath.hpp: the function svin_host_pose_error runs on the CPU
       } else if (fac.kind == F_SB_PRIOR) {  // SpeedAndBiasError.cpp:83-113
         for (int k = 0; k < 9; ++k) { sh.e[k] = fac.meas[k] - x0[k]; sh.F[k * 9 + k] = -1.0; }
       } else if (fac.kind == F_RELPOSE) {  // RelativePoseError.cpp:79-147
-        const double* x1 = blockPtr(p, cand, fac.blkKind[1], fac.blkSlot[1]);
         const TF T0 = makeTF(x0), T1 = makeTF(x1);
         const Quat dq = qnormalized(qmul(T1.q, qnormalized(qinv(T0.q))));
         for (int k = 0; k < 3; ++k) sh.e[k] = T1.r[k] - T0.r[k];
@@ -1772,6 +1788,10 @@ __device__ __forceinline__ void evalFactorBlock(const DeviceProblem& p, int cand
         sh.e[0] = x0[2] - (-1 * fac.meas[0] + fac.meas[1]);
         sh.F[2] = 1.0;
       }
+    };
+    if (t == 0) {
+      if (blocksStaged) evalSmall(sh.xs, sh.xs + 7);   // (two blocks only between two poses: F_RELPOSE)
+      else evalSmall(blockPtr(p, cand, fac.blkKind[0], fac.blkSlot[0]), blockPtr(p, cand, fac.blkKind[1], fac.blkSlot[1]));
     }
   }
   __syncthreads();
@@ -1791,6 +1811,7 @@ __device__ __forceinline__ void evalFactorBlock(const DeviceProblem& p, int cand
           for (int k = 0; k < 15; ++k) sr += w[k] * sh.e[k];
           lin.r[a] = sr;
           sh.rw[a] = sr;
+          if (accStage) accStage[15 * 30 + a] = sr;
         }
         double s0 = 0, s1 = 0;
         const bool second = c0 + 16 < 30;
@@ -1799,6 +1820,10 @@ __device__ __forceinline__ void evalFactorBlock(const DeviceProblem& p, int cand
         for (int k = 0; k < 15; ++k) { s0 += w[k] * Fc[k * 30]; s1 += w[k] * Fc[k * 30 + (second ? 16 : 0)]; }
         lin.J[a * 30 + c0] = s0;
         if (second) lin.J[a * 30 + c0 + 16] = s1;
+        if (accStage) {
+          accStage[a * 30 + c0] = s0;
+          if (second) accStage[a * 30 + c0 + 16] = s1;
+        }
       }
     } else if (a < m) {
       if (c0 == 0) {
@@ -1806,11 +1831,13 @@ __device__ __forceinline__ void evalFactorBlock(const DeviceProblem& p, int cand
         for (int k = 0; k < m; ++k) sr += sh.W[a * m + k] * sh.e[k];
         lin.r[a] = sr;
         sh.rw[a] = sr;
+        if (accStage) accStage[15 * 30 + a] = sr;
       }
       for (int c = c0; c < ncols; c += 16) {
         double sj = 0;
         for (int k = 0; k < m; ++k) sj += sh.W[a * m + k] * sh.F[k * ncols + c];
         lin.J[a * ncols + c] = sj;
+        if (accStage) accStage[a * ncols + c] = sj;
       }
     }
   }
@@ -1819,9 +1846,18 @@ __device__ __forceinline__ void evalFactorBlock(const DeviceProblem& p, int cand
   if (t < 64) {
     const double rv = ((t & 15) < m && t < 16) ? sh.rw[t & 15] : 0.0;
     const double c = rowSum16(rv * rv);
-    if (t == 0) factorLossStore(p, fac, lin, f, c);
+    if (t == 0) {
+      const double sc = factorLossStore(p, fac, lin, f, c);
+      if (accStage) accStage[kFactorStage] = sc;
+    }
   }
-  if (t >= 192 && t < 196) { lin.off[t - 192] = tblOff; lin.dim[t - 192] = tblDim; }
+  if (t >= 192 && t < 196) {
+    lin.off[t - 192] = tblOff; lin.dim[t - 192] = tblDim;
+    if (accStage) {
+      int* tbl = reinterpret_cast<int*>(accStage + kFactorStage + 1);
+      tbl[t - 192] = tblOff; tbl[4 + t - 192] = tblDim;
+    }
+  }
   if (t == 196) { lin.m = m; lin.ncols = ncols; }
   IMU_TICK(qe3);
   IMU_ACC(10, qe0, qe3, t == 0 && fac.kind == F_IMU);
@@ -1859,7 +1895,8 @@ int costSummedBy(const DeviceProblem& p) {
 // cost = 0.5 c0 + bp^T dchi + 0.5 dchi^T Ht dchi ;  grad (lin space) = bp + Ht dchi
 // Ceres multiplies the ambient Jacobian (J_min * lift(x_lin)) by PlusJacobian(x): for a pose block the
 // effective tangent map is M = blockdiag(I3, oplus(q_cur * q_lin^-1)[0:3,0:3]) (MarginalizationError.cpp:798-844).
-__device__ __forceinline__ void priorEvalBlock(const DeviceProblem& p, int cand, double* red) {
+// candBlocks: the candidate blocks in LDS (poses, extrinsics, speed/bias, each kind by slot: stepHead) instead of the candidate arrays
+__device__ __forceinline__ void priorEvalBlock(const DeviceProblem& p, int cand, double* red, const double* candBlocks = nullptr) {
   const int t = threadIdx.x, m = p.priorM;
   double* priorDchi = cand ? p.priorDchiC : p.priorDchi;
   double* priorGrad = cand ? p.priorGradC : p.priorGrad;
@@ -1868,24 +1905,30 @@ __device__ __forceinline__ void priorEvalBlock(const DeviceProblem& p, int cand,
     double* M3 = (cand ? p.priorM3C : p.priorM3) + 9 * b;
     for (int k = 0; k < 9; ++k) M3[k] = (k % 4 == 0) ? 1.0 : 0.0;
     if (pb.mdim == 0) continue;
-    const double* x = blockPtr(p, cand != 0, pb.kind, pb.slot);
-    if (pb.kind == B_SB) {
-      for (int k = 0; k < 9; ++k) priorDchi[pb.ord + k] = x[k] - pb.lin[k];
-    } else {
-      double d[6];
-      poseMinus(x, pb.lin, d);
-      for (int k = 0; k < 6; ++k) priorDchi[pb.ord + k] = d[k];
-      // PlusJacobian normalises q (Transformation ctor); lift uses the raw linearisation quaternion
-      const Quat qc = qnormalized(Quat{x[3], x[4], x[5], x[6]});
-      const Quat ql = Quat{-pb.lin[3], -pb.lin[4], -pb.lin[5], pb.lin[6]};
-      // 2*oplus(q_lin^-1)[0:3,:] * 0.5*oplus(q_cur)[:,0:3]
-      double A[16], B[16], C[16];
-      quatOplusMat4(ql, A);
-      quatOplusMat4(qc, B);
-      mm4(A, B, C);
-      for (int a = 0; a < 3; ++a)
-        for (int c = 0; c < 3; ++c) M3[a * 3 + c] = C[a * 4 + c];
-    }
+    // (instantiated on the LDS copy and on the global arrays: one pointer that may hold either is a FLAT access)
+    auto blockDchi = [&](const double* x) __attribute__((always_inline)) {
+      if (pb.kind == B_SB) {
+        for (int k = 0; k < 9; ++k) priorDchi[pb.ord + k] = x[k] - pb.lin[k];
+      } else {
+        double d[6];
+        poseMinus(x, pb.lin, d);
+        for (int k = 0; k < 6; ++k) priorDchi[pb.ord + k] = d[k];
+        // PlusJacobian normalises q (Transformation ctor); lift uses the raw linearisation quaternion
+        const Quat qc = qnormalized(Quat{x[3], x[4], x[5], x[6]});
+        const Quat ql = Quat{-pb.lin[3], -pb.lin[4], -pb.lin[5], pb.lin[6]};
+        // 2*oplus(q_lin^-1)[0:3,:] * 0.5*oplus(q_cur)[:,0:3]
+        double A[16], B[16], C[16];
+        quatOplusMat4(ql, A);
+        quatOplusMat4(qc, B);
+        mm4(A, B, C);
+        for (int a = 0; a < 3; ++a)
+          for (int c = 0; c < 3; ++c) M3[a * 3 + c] = C[a * 4 + c];
+      }
+    };
+    if (candBlocks)
+      blockDchi(candBlocks + (pb.kind == B_POSE ? pb.slot * 7 : (pb.kind == B_EXT ? (p.nPose + pb.slot) * 7 : (p.nPose + p.nExt) * 7 + pb.slot * 9)));
+    else
+      blockDchi(blockPtr(p, cand != 0, pb.kind, pb.slot));
   }
   __syncthreads();
   // grad = bp + Ht dchi (thread per row), cost
@@ -1916,15 +1959,148 @@ void launchEvalPrior(const DeviceProblem& p, bool cand, hipStream_t s, bool sumC
   launch(k_prior_eval, dim3(1), dim3(256), 0, s, p, cand ? 1 : 0, sumCost ? nA : -1);
 }
 
+// partial slots of the post-solve pass
+constexpr int kPostK = 9;  // A=|Jv|^2 B=|Jy|^2 C=Jv.Jy D=Jv.r E=Jy.r gHat gnHat gDotGn gradMax
+__device__ __constant__ int kPostSlot[kPostK] = {PS_JV_SQ, PS_JY_SQ, PS_JVJY, PS_JV_DOT, PS_JY_DOT, PS_GHAT, PS_GNHAT, PS_GDOTGN, PS_GRADMAX};
+// the same table for compile-time indices (a __constant__ lookup is a memory round trip: nine of them, each followed by its
+// dependent partial load, used to serialise the tail of the post-solve pass)
+__device__ constexpr int postSlotC(int k) {
+  constexpr int tbl[kPostK] = {PS_JV_SQ, PS_JY_SQ, PS_JVJY, PS_JV_DOT, PS_JY_DOT, PS_GHAT, PS_GNHAT, PS_GDOTGN, PS_GRADMAX};
+  return tbl[k];
+}
+__device__ __forceinline__ void retractBlockValues(bool isSb, bool has, bool count, const double* x, const double* v, const double* y,
+                                                   double cg, double cn, double* xo, double* acc);   // (with the post-solve pass, below)
+
+// ---------------------------------------------------------------- the dogleg step at the head of the evaluation's blocks
+// What the tail of k_post_solve computes once, in one workgroup, while the chip waits -- the nine sums over the blocks' partials,
+// the dogleg coefficients, the candidate parameter blocks -- is read first thing by every block of the launch behind it.  With
+// launchDoglegPrepare(noTail) the pass ends at its partials and every evaluation and chunk block of k_eval_build starts here
+// instead: ONE round of loads (the 9 x nPost partials, y_C, v_C, the blocks it needs and their row offsets), the tail's own
+// reduction (the same thread-strided sums per slot, the same blockSumK), doglegCoefficients and retractBlockValues, the candidate
+// into the block's LDS.  Every block holds the same bits; none reads what another block of the launch writes.
+//   kHeadPoses   reprojection and chunk blocks: all poses and extrinsics -> candPose / candExt (the staged tables' places)
+//   kHeadFactor  a factor block: its factor's blocks, one behind the other -> candPose (FactorShared::xs)
+//   kHeadAll     the prior's block: every block -> candPose / candExt / candSb
+//   kHeadRecord  ONE block (the first reprojection block; never a factor block, which ends last when an IMU factor re-integrates):
+//                kHeadPoses, and what only one block may do -- poseC / extC / sbC, the block-only step and state norms, group B,
+//                gradMax, the step's three scalars and the coefficients (k_eval_all and k_step_retract may follow) -- with
+//                cstore(): reduceCost of this launch's last evaluation block reads the record behind the
+//                cost ticket, which this block takes after these stores like every block after its cost partial.
+// The item -> thread map is the tail's, so the recording block's norms are summed in the tail's order.
+// scratch: kStepHeadRedDoubles + 2 p.d doubles of LDS the role uses later (build_plan.hpp stepHeadLdsBytes).
+enum StepHeadRole : int { kHeadPoses = 0, kHeadFactor = 1, kHeadAll = 2, kHeadRecord = 3 };
+struct StepHeadOut { double cg, cn; };
+static_assert(kStepHeadRedDoubles == 16 * kPostK + 8, "the block sum's rows and group B");
+__device__ __forceinline__ StepHeadOut stepHead(const DeviceProblem& p, double radius, int nPost, int role, const DevFactor* fac, double* scratch,
+                                                double* candPose, double* candExt, double* candSb) {
+  const int t = threadIdx.x;
+  double* red = scratch;
+  double* grpB = scratch + 16 * kPostK;
+  double* sYV = grpB + 8;   // y_C, then v_C
+  SVIN_ARGS(SA(p.partial), SA(p.yC), SA(p.vC), SA(p.pose), SA(p.ext), SA(p.sb), SA(p.poseOff), SA(p.extOff), SA(p.sbOff), SA(p.poseC),
+            SA(p.extC), SA(p.sbC), SA(p.scal), SA(p.d), SA(p.nPose), SA(p.nExt), SA(p.nSb));
+  const int d = p.d, nPE = p.nPose + p.nExt, nBlkItems = nPE + p.nSb;
+  TRACE(40);
+  int kind = -1, slot = 0, dst = 0;
+  if (role == kHeadFactor) {
+    if (t < fac->nblk) {
+      kind = fac->blkKind[t]; slot = fac->blkSlot[t];
+      for (int b = 0; b < t; ++b) dst += (fac->blkKind[b] == B_SB) ? 9 : 7;
+      if (dst + (kind == B_SB ? 9 : 7) > 32) kind = -1;   // (FactorShared::xs; no factor kind has more: an IMU factor fills it)
+    }
+  } else {
+    // pose / extrinsics blocks on wave 0, speed-and-bias blocks on wave 1 (k_post_solve's tail)
+    const bool split = nPE <= 64 && p.nSb <= 64;
+    const int item = split ? (t < 64 ? (t < nPE ? t : -1) : (t < 128 && t - 64 < p.nSb ? nPE + t - 64 : -1)) : (t < nBlkItems ? t : -1);
+    if (item >= 0 && !(item >= nPE && (role == kHeadPoses))) {
+      kind = item >= nPE ? B_SB : (item < p.nPose ? B_POSE : B_EXT);
+      slot = kind == B_SB ? item - nPE : (kind == B_POSE ? item : item - p.nPose);
+      dst = slot * (kind == B_SB ? 9 : 7);
+    }
+  }
+  const bool isSb = kind == B_SB;
+  // one round of loads
+  double x[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  int off = -1;
+  if (kind >= 0) {
+    const double* xp = isSb ? p.sb + (size_t)slot * 9 : (kind == B_POSE ? p.pose : p.ext) + (size_t)slot * 7;
+    off = isSb ? p.sbOff[slot] : (kind == B_POSE ? p.poseOff[slot] : p.extOff[slot]);
+#pragma unroll
+    for (int k = 0; k < 9; ++k) x[k] = (k < (isSb ? 9 : 7)) ? xp[k] : 0.0;
+  }
+  double acc[kPostK];
+  {
+    double x0[kPostK];
+#pragma unroll
+    for (int k = 0; k < kPostK; ++k) x0[k] = (t < nPost) ? cload(p.partial + (size_t)postSlotC(k) * kMaxPartials + t) : 0.0;
+    for (int i = t; i < d; i += blockDim.x) { sYV[i] = p.yC[i]; sYV[d + i] = p.vC[i]; }
+    // the tail's reduction over the blocks, fixed order: thread k-strided per slot
+#pragma unroll
+    for (int k = 0; k < kPostK; ++k) {
+      double s = x0[k];
+      const double* src = p.partial + (size_t)postSlotC(k) * kMaxPartials;
+      for (int i = t + blockDim.x; i < nPost; i += blockDim.x) { const double xx = cload(src + i); s = (k == 8) ? fmax(s, xx) : s + xx; }
+      acc[k] = s;
+    }
+  }
+  const double tot = blockSumK<kPostK>(acc, red, 8);
+  TRACE(41);   // sums reduced
+  // slot order A B C D E gHat gnHat gDotGn -> fields 1 4 5 6 7 0 2 3 of group B
+  const int field = (t == 0) ? 1 : (t == 1) ? 4 : (t == 2) ? 5 : (t == 3) ? 6 : (t == 4) ? 7 : (t == 5) ? 0 : (t == 6) ? 2 : 3;
+  if (t < 8) grpB[field] = tot;
+  __syncthreads();   // (group B, and y_C / v_C behind blockSumK's barriers)
+  const DoglegCoeff c = doglegCoefficients(grpB[0], grpB[1], grpB[2], grpB[3], grpB[4], grpB[5], grpB[6], grpB[7], radius);
+  TRACE(42);   // coefficients
+  double a2[2] = {0, 0};
+  if (kind >= 0) {
+    const int nd = isSb ? 9 : 6;
+    double v[9], y[9], xo[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+      v[k] = (off >= 0 && k < nd) ? sYV[d + off + k] : 0.0;
+      y[k] = (off >= 0 && k < nd) ? sYV[off + k] : 0.0;
+    }
+    retractBlockValues(isSb, off >= 0, p.ownsCamera != 0, x, v, y, c.cg, c.cn, xo, a2);
+    double* cd = (role == kHeadFactor) ? candPose : (isSb ? candSb : (kind == B_POSE ? candPose : candExt));
+    if (cd) {
+#pragma unroll
+      for (int k = 0; k < 9; ++k)
+        if (k < (isSb ? 9 : 7)) cd[dst + k] = xo[k];
+    }
+    if (role == kHeadRecord) {
+      double* xc = isSb ? p.sbC + (size_t)slot * 9 : (kind == B_POSE ? p.poseC : p.extC) + (size_t)slot * 7;
+#pragma unroll
+      for (int k = 0; k < 9; ++k)
+        if (k < (isSb ? 9 : 7)) xc[k] = xo[k];
+    }
+  }
+  if (role == kHeadRecord) {
+    const double tt = blockSumK<2>(a2, red, -1);
+    if (t == 0) cstore(&p.scal->stepNormSq, tt);
+    if (t == 1) cstore(&p.scal->xNormSq, tt);
+    if (t < 8) cstore(&p.scal->gHatSq + field, tot);
+    if (t == 8) cstore(&p.scal->gradMax, tot);   // (failMax and the reset of cholFail: the camera block of the pass in front)
+    if (t == 0) { cstore(&p.scal->doglegStepNorm, c.stepNorm); cstore(&p.scal->jdSq, c.jdSq); cstore(&p.scal->jdDotR, c.jdDotR); }
+    if (t == 1) { cstore(&p.scal->spareA0, c.cg); cstore(&p.scal->spareA1, c.cn); }
+  }
+  __syncthreads();   // the candidate is staged; the scratch is the role's again
+  TRACE(43);   // candidate staged
+  return StepHeadOut{c.cg, c.cn};
+}
+
 // Fused evaluation for the trust-region loop: blocks [0, F) evaluate the small factors (IMU re-preintegration can
 // take tens of microseconds), blocks [F, F + nR) the reprojection residuals with 256 observations each, side by side
 // in one launch, plus one block for the marginalisation prior (hasPrior); the block that finishes last sums the cost
 // (sumCost) and publishes the scalars.
 // (nBlocks: the blocks of the evaluation -- the launch's gridDim.x in k_eval_all; k_eval_build has its chunk blocks behind them)
 template <bool WITH_EXT, bool GENERAL, class NB>
-__device__ __forceinline__ void k_eval_all_body(const DeviceProblem& p, int cand, int nR, int sumCost, int hasPrior, FactorShared& sh, NB nBlocks) {
+__device__ __forceinline__ void k_eval_all_body(const DeviceProblem& p, int cand, int nR, int sumCost, int hasPrior, FactorShared& sh, NB nBlocks,
+                                                double headRadius = -1.0, int nPost = 0, int blockBase = 0, bool handOver = false) {
   const int F = (int)nBlocks() - nR - hasPrior;
-  if ((int)blockIdx.x < F) {
+  const int bx = (int)blockIdx.x - blockBase;   // (blockBase: the launch's blocks ahead of the evaluation's -- k_eval_build with its chunk blocks first)
+  const bool head = headRadius > 0.0;   // (k_eval_build behind a post-solve pass without its tail: stepHead)
+  static_assert(sizeof(sh.fb) >= (kStepHeadRedDoubles + 2 * kStepHeadMaxD + 9 * kStepHeadMaxItems) * sizeof(double), "the head's scratch and the prior block's candidate fit FactorShared::fb");
+  if (bx < F) {
     SVIN_ARGS(SA(p.factors), SA(p.imus), SA(p.linCand), SA(p.linCur), SA(p.poseC), SA(p.pose), SA(p.sbC), SA(p.sb), SA(p.extC), SA(p.ext),
               SA(p.poseOff), SA(p.sbOff), SA(p.extOff), SA(p.partial), SA(p.imuT), SA(p.imuMeas));
   } else {
@@ -1933,27 +2109,43 @@ __device__ __forceinline__ void k_eval_all_body(const DeviceProblem& p, int cand
               SA(p.nPose), SA(p.nExt), SA(p.nCam), SA(p.lossTab));
   }
   TRACE(16);
-  if ((int)blockIdx.x < F) {
-    evalFactorBlock(p, cand, blockIdx.x, sh);
+  if (bx < F) {
+    if (head) stepHead(p, headRadius, nPost, kHeadFactor, &p.factors[bx], sh.fb, sh.xs, nullptr, nullptr);
+    // (handOver: k_eval_build's factor blocks add their factor to the build from what they leave in LDS here)
+    evalFactorBlock(p, cand, bx, sh, head, handOver ? reinterpret_cast<double*>(reinterpret_cast<int*>(sh.fb) + kFactorColRow) : nullptr);
     TRACE(17);
-  } else if ((int)blockIdx.x == F + nR) {
-    priorEvalBlock(p, cand, reinterpret_cast<double*>(&sh));
+  } else if (bx == F + nR) {
+    if (head) {
+      double* cb = sh.fb + kStepHeadRedDoubles + 2 * kStepHeadMaxD;
+      stepHead(p, headRadius, nPost, kHeadAll, nullptr, sh.fb, cb, cb + p.nPose * 7, cb + (p.nPose + p.nExt) * 7);
+      priorEvalBlock(p, cand, reinterpret_cast<double*>(&sh), cb);
+    } else {
+      priorEvalBlock(p, cand, reinterpret_cast<double*>(&sh));
+    }
   } else {
     double* smem = reinterpret_cast<double*>(&sh);  // poses / extrinsics / cameras staged in the same LDS
     const bool defer = cand && p.lmDeferred;
     LmDefer df;
     if (defer) {
       df.on = 1;
-      df.cg = p.scal->spareA0; df.cn = p.scal->spareA1;   // the dogleg coefficients of the fused step (k_post_solve)
+      if (head) {
+        // the candidate poses and extrinsics straight into their places in the staged tables, the scratch behind the tables
+        double* tbl = smem + 48;
+        double* scratch = tbl + (p.nPose + p.nExt) * 7 + p.nCam * (int)(sizeof(CameraModel) / 8) + 2 * kMaxLosses;
+        const StepHeadOut h = stepHead(p, headRadius, nPost, bx == F ? kHeadRecord : kHeadPoses, nullptr, scratch, tbl, tbl + p.nPose * 7, nullptr);
+        df.cg = h.cg; df.cn = h.cn;
+      } else {
+        df.cg = p.scal->spareA0; df.cn = p.scal->spareA1;   // the dogleg coefficients of the fused step (k_post_solve)
+      }
       df.vL = p.vL; df.yL = p.yL; df.lmPtr = p.lmPtr; df.lmC = p.lmC;
       df.stepPartial = p.partial + (size_t)PS_STEP * kMaxPartials;
       df.xPartial = p.partial + (size_t)PS_XNORM * kMaxPartials;
     }
-    evalReprojBlock<true, WITH_EXT, GENERAL>(blockIdx.x - F, smem + 48, smem, p.N, p.nPose, p.nExt, p.nCam, cand ? p.poseC : p.pose,
+    evalReprojBlock<true, WITH_EXT, GENERAL>(bx - F, smem + 48, smem, p.N, p.nPose, p.nExt, p.nCam, cand ? p.poseC : p.pose,
                                     cand ? p.extC : p.ext, defer ? p.lm : (cand ? p.lmC : p.lm), p.cams, p.obsUv, p.obsW, p.obsIdx, p.obsLm,
                                     cand ? p.rCand : p.rCur, cand ? p.JpCand : p.JpCur, cand ? p.JlCand : p.JlCur,
                                     cand ? p.JeCand : p.JeCur, p.partial + (size_t)PS_COST_REPROJ * kMaxPartials, (size_t)p.N,
-                                    df, p.lmPrior, p.lossTab, GENERAL ? p.obsS : nullptr);
+                                    df, p.lmPrior, p.lossTab, GENERAL ? p.obsS : nullptr, head && defer);
   }
   TRACE(18);
   if (sumCost) {
@@ -2156,13 +2348,54 @@ static int priorAccBlocks(const DeviceProblem& p) { return priorAccBlockCount(p.
 // STAGED (the factor blocks of k_schur_dense, whose launch brings the LDS): J and r of the factor are copied to LDS with ONE round of
 // loads -- colRow is then followed by kFactorStage doubles -- and the products below read them there; the other callers walk them
 // out of global memory, up to 15 dependent steps per entry.  Same products, same k order, same atomics.
-constexpr int kFactorColRow = 32;                 // ints reserved for colRow (30 used)
-constexpr int kFactorStage = 15 * 30 + 15;        // doubles behind them: J, r
+// (kFactorColRow, kFactorStage, kFactorHandOver: in front of evalFactorBlock)
+// handOver (m, nc): the block has just evaluated the factor itself (evalFactorBlock with accStage) and left J, r, sc and the block
+// table in the staging area -- nothing of the record is read back from global memory.
 // (`lin`: the factor's record -- p.linCur[f] for a build of its own, the record the same block has just evaluated in k_eval_build)
+// the products of one factor, J^T J and J^T r scaled by the loss corrector, added to the normal equations (Jat / rat: where J and r are read)
+template <class JAT, class RAT>
+__device__ __forceinline__ void factorProducts(const DeviceProblem& p, int m, int nc, double sc2, const int* colRow, JAT Jat, RAT rat) {
+  for (int idx = threadIdx.x; idx < nc * nc; idx += blockDim.x) {
+    const int a = idx / nc, b = idx % nc;
+    const int ra = colRow[a], rb = colRow[b];
+    if (ra < 0 || rb < 0) continue;
+    double s = 0;
+    for (int k = 0; k < m; ++k) s += Jat(k * nc + a) * Jat(k * nc + b);
+    s *= sc2;   // the loss corrector (1 without a loss)
+    atomicAdd(&p.S[(size_t)ra * p.ldS + rb], s);
+    if (a == b) {
+      atomicAdd(&p.hC[ra], s);
+      double g = 0;
+      for (int k = 0; k < m; ++k) g += Jat(k * nc + a) * rat(k);
+      g *= sc2;
+      atomicAdd(&p.gRed[ra], g);
+      atomicAdd(&p.gFull[ra], g);
+    }
+  }
+}
 template <bool STAGED>
-__device__ __forceinline__ void factorsAccumulateLin(const DeviceProblem& p, const FactorLin& lin, int* colRow) {
+__device__ __forceinline__ void factorsAccumulateLin(const DeviceProblem& p, const FactorLin& lin, int* colRow, bool handOver = false,
+                                                     int handM = 0, int handNc = 0) {
   double* Js = reinterpret_cast<double*>(colRow + kFactorColRow);
   double* rs = Js + 15 * 30;
+  const int* handTbl = reinterpret_cast<const int*>(Js + kFactorStage + 1);
+  if (STAGED && handOver) {
+    const int m = handM, nc = handNc;
+    const double sc = Js[kFactorStage];
+    const double sc2 = sc * sc;
+    if (threadIdx.x < 30) {
+      int c = threadIdx.x, row = -1, base = 0;
+      for (int b = 0; b < 4; ++b) {
+        const int off = handTbl[b], dim = handTbl[4 + b];
+        if (c >= base && c < base + dim) row = off < 0 ? -1 : off + (c - base);
+        base += dim;
+      }
+      colRow[threadIdx.x] = (c < nc) ? row : -1;
+    }
+    __syncthreads();
+    factorProducts(p, m, nc, sc2, colRow, [&](int i) { return Js[i]; }, [&](int k) { return rs[k]; });
+    return;
+  }
   double jv0 = 0, jv1 = 0, rv = 0;
   const int i0 = threadIdx.x, i1 = threadIdx.x + blockDim.x;
   if (STAGED) {   // addresses that depend on nothing loaded: these requests leave with the scalar loads of m, ncols, dim, off
@@ -2190,23 +2423,7 @@ __device__ __forceinline__ void factorsAccumulateLin(const DeviceProblem& p, con
     colRow[threadIdx.x] = (c < nc) ? row : -1;
   }
   __syncthreads();
-  for (int idx = threadIdx.x; idx < nc * nc; idx += blockDim.x) {
-    const int a = idx / nc, b = idx % nc;
-    const int ra = colRow[a], rb = colRow[b];
-    if (ra < 0 || rb < 0) continue;
-    double s = 0;
-    for (int k = 0; k < m; ++k) s += Jat(k * nc + a) * Jat(k * nc + b);
-    s *= sc2;   // the loss corrector (1 without a loss)
-    atomicAdd(&p.S[(size_t)ra * p.ldS + rb], s);
-    if (a == b) {
-      atomicAdd(&p.hC[ra], s);
-      double g = 0;
-      for (int k = 0; k < m; ++k) g += Jat(k * nc + a) * rat(k);
-      g *= sc2;
-      atomicAdd(&p.gRed[ra], g);
-      atomicAdd(&p.gFull[ra], g);
-    }
-  }
+  factorProducts(p, m, nc, sc2, colRow, Jat, rat);
 }
 
 template <bool STAGED>
@@ -2486,7 +2703,8 @@ __device__ __forceinline__ int sym6(int a, int c) { return a * 6 - a * (a - 1) /
 // kernel brings (tiles, then the staged tables), `blockBase` the launch's blocks ahead of the chunk blocks.
 template <int MAXT, bool A_MFMA, int NW, bool EVAL = false, bool GENERAL = false>
 __device__ __forceinline__ void k_schur_dense_body(const DeviceProblem& p, double mu, int initScale, int nChunkBlocks, int nFacBlocks,
-                                                   int cand = 0, double* evalLds = nullptr, int blockBase = 0) {
+                                                   int cand = 0, double* evalLds = nullptr, int blockBase = 0, double headRadius = -1.0,
+                                                   int nPost = 0) {
   static_assert(A_MFMA || NW == 4, "the per-wave block copies of A exist for four waves");
   static_assert(!EVAL || !A_MFMA, "the evaluating chunk blocks exist for the block-copy form");
   extern __shared__ double smemDyn[];
@@ -2546,9 +2764,22 @@ __device__ __forceinline__ void k_schur_dense_body(const DeviceProblem& p, doubl
   for (int i = t; i < p.nPose && i < kDensePoseCap; i += blockDim.x) sPoseOff[i] = p.poseOff[i];
   const int* poseOffS = sPoseOff;
   ReprojTables tb = {nullptr, nullptr, nullptr, nullptr};
-  if constexpr (EVAL)   // behind the tiles (an even number of doubles on: the clear below writes pairs)
-    tb = stageReprojTables<true>(smem + ((rows * kDenseLd + (int)extraLds + 1) & ~1), p.nPose, p.nExt, p.nCam, cand ? p.poseC : p.pose,
-                                 cand ? p.extC : p.ext, p.cams, p.lossTab);
+  double stepCg = 0.0, stepCn = 0.0;   // EVAL: the coefficients of the deferred landmark step
+  if constexpr (EVAL) {   // behind the tiles (an even number of doubles on: the clear below writes pairs)
+    double* tbl = smem + ((rows * kDenseLd + (int)extraLds + 1) & ~1);
+    const bool head = headRadius > 0.0;
+    if (head) {
+      // the step itself (stepHead): the candidate poses and extrinsics straight into the tables, the scratch behind the tables
+      double* scratch = tbl + (p.nPose + p.nExt) * 7 + p.nCam * (int)(sizeof(CameraModel) / 8) + 2 * kMaxLosses;
+      const StepHeadOut h = stepHead(p, headRadius, nPost, kHeadPoses, nullptr, scratch, tbl, tbl + p.nPose * 7, nullptr);
+      // (the same value in every lane: kept in scalar registers over the chunk loop, whose vector registers are all taken)
+      auto uniform = [](double v) {
+        return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
+      };
+      stepCg = uniform(h.cg); stepCn = uniform(h.cn);
+    }
+    tb = stageReprojTables<true>(tbl, p.nPose, p.nExt, p.nCam, cand ? p.poseC : p.pose, cand ? p.extC : p.ext, p.cams, p.lossTab, head);
+  }
   {
     const int nz = rows * kDenseLd + (int)extraLds;   // 16-byte stores: half the LDS instructions of the clear
     for (int i = t; i < (nz >> 1); i += blockDim.x) reinterpret_cast<double2*>(smem)[i] = double2{0.0, 0.0};
@@ -2670,7 +2901,8 @@ __device__ __forceinline__ void k_schur_dense_body(const DeviceProblem& p, doubl
         hpw[0] = hp.x; hpw[1] = hp.y; hpw[2] = hp.z; hpw[3] = hp.w;
         if (defer) {   // (the evaluation block that holds the landmark's first observation stores the same value to lmC)
           double xo[4];
-          lmDeferredStep(hpw, p.scal->spareA0, p.scal->spareA1, p.vL, p.yL, l, xo);
+          const bool head = headRadius > 0.0;
+          lmDeferredStep(hpw, head ? stepCg : p.scal->spareA0, head ? stepCn : p.scal->spareA1, p.vL, p.yL, l, xo);
 #pragma unroll
           for (int k = 0; k < 4; ++k) hpw[k] = xo[k];
         }
@@ -4031,26 +4263,70 @@ void launchAccumulateNormalEquations(const DeviceProblem& p, double mu, bool ini
 // their own (k_prior_accumulate) behind this one.  accFactors = 0 (an entry of S receives three or more unordered terms, see
 // launchEvalBuild): the factor blocks leave their factor to that launch as well (k_factors_only).
 template <bool GENERAL>
+// stepRadius > 0 (nPost: the blocks of the post-solve pass in front, which ended at its partials): every block takes the dogleg step
+// itself first (stepHead) and evaluates at the candidate in its own LDS.
 __global__ __launch_bounds__(256) void k_eval_build(DeviceProblem p, int cand, int nR, int hasPrior, int nEval, double mu, int initScale, int nChunkBlocks,
-                                                    int accFactors) {
+                                                    int accFactors, double stepRadius, int nPost) {
   __shared__ FactorShared sh;
-  if ((int)blockIdx.x >= nEval) {
-    k_schur_dense_body<9, false, 4, true, GENERAL>(p, mu, initScale, nChunkBlocks, 0, cand, reinterpret_cast<double*>(&sh), nEval);
+  // SVIN_CHUNKS_FIRST (a variant build, tools/build_variant.sh): the chunk blocks, which set the launch's time, take the low block
+  // indices and are dispatched first.  Measured and left off.
+#ifdef SVIN_CHUNKS_FIRST
+  const int evalBase = nChunkBlocks, chunkBase = 0;
+  const bool chunkBlock = (int)blockIdx.x < nChunkBlocks;
+#else
+  const int evalBase = 0, chunkBase = nEval;
+  const bool chunkBlock = (int)blockIdx.x >= nEval;
+#endif
+  if (chunkBlock) {
+    k_schur_dense_body<9, false, 4, true, GENERAL>(p, mu, initScale, nChunkBlocks, 0, cand, reinterpret_cast<double*>(&sh), chunkBase, stepRadius, nPost);
     return;
   }
-  k_eval_all_body<false, GENERAL>(p, cand, nR, 1, hasPrior, sh, ExtentX{(unsigned int)nEval});
-  if (accFactors && (int)blockIdx.x < nEval - nR - hasPrior) {
-    static_assert(sizeof(sh.fb) >= kFactorColRow * sizeof(int) + kFactorStage * sizeof(double), "a factor's staging area fits the block's LDS");
-    __syncthreads();   // the record (r, J, block table, sc) this block has just stored is read back by all of its threads
-    factorsAccumulateLin<true>(p, (cand ? p.linCand : p.linCur)[blockIdx.x], reinterpret_cast<int*>(sh.fb));
+  const int bx = (int)blockIdx.x - evalBase;
+  // SVIN_FACTOR_HAND_OVER (a variant build): the factor blocks add their factor to the build from J, r, sc and the block table they
+  // leave in LDS, not from a re-read of the record they have just stored.  Same bits; measured and left off -- the maximum of
+  // the launch, a re-integrating factor block, did not fall.
+#ifdef SVIN_FACTOR_HAND_OVER
+  const bool handOver = accFactors != 0;
+#else
+  const bool handOver = false;
+#endif
+  k_eval_all_body<false, GENERAL>(p, cand, nR, 1, hasPrior, sh, ExtentX{(unsigned int)nEval}, stepRadius, nPost, evalBase, handOver);
+  if (accFactors && bx < nEval - nR - hasPrior) {
+    static_assert(sizeof(sh.fb) >= kFactorColRow * sizeof(int) + (kFactorStage + kFactorHandOver) * sizeof(double), "a factor's staging area fits the block's LDS");
+    __syncthreads();   // J, r, the block table and sc this block has just left in LDS (a host-evaluated factor: in its record) are read by all of its threads
+    const DevFactor& fac = p.factors[bx];
+    int nc = 0;
+    for (int b = 0; b < fac.nblk; ++b) nc += (fac.blkKind[b] == B_SB) ? 9 : 6;
+    factorsAccumulateLin<true>(p, (cand ? p.linCand : p.linCur)[bx], reinterpret_cast<int*>(sh.fb), handOver && fac.kind != F_HOST, fac.m, nc);
     TRACE(29);
   }
 }
 static std::atomic<int> gEvalBuildLaunches{0};
 int evalBuildLaunches() { return gEvalBuildLaunches.load(std::memory_order_relaxed); }
-bool launchEvalBuild(const DeviceProblem& p, bool cand, double mu, bool initScale, bool factorsCommute, int computeUnits, hipStream_t s) {
+// (build_plan.hpp stepInEvalTaken, with the plans and the sizes this translation unit knows)
+bool stepInEvalTaken(const DeviceProblem& p, bool sharded, bool buildWanted, bool reuse, bool hostFactors, int computeUnits) {
   const BuildPlan q = buildPlanOf(p);
   const EvalPlan e = evalPlanOf(p);
+  StepInEvalIn in{};
+  in.chosenForm = stepModeOf(p, sharded).chosenForm;
+  in.sharded = sharded || p.world > 1;
+  in.buildWanted = buildWanted;
+  in.evalBuildTaken = !optOn(kOptNoEvalBuild) && evalBuildTaken(buildDimsOf(p), q, e, in.sharded, computeUnits, sizeof(FactorShared));
+  in.reuse = reuse;
+  in.postSplit = e.postSplit;
+  in.hostFactors = hostFactors;
+  in.noStepInEval = optOn(kOptNoStepInEval);
+  in.d = p.d; in.items = p.nPose + p.nExt + p.nSb; in.nPost = e.post.grid;
+  in.evalStageBytes = evalStageBytes(evalDimsOf(p), sizeof(CameraModel), true, true);
+  in.chunkLdsBytes = q.schurDense.ldsBytes; in.stageBytes = e.stageBytes; in.factorSharedBytes = sizeof(FactorShared);
+  return stepInEvalTaken(in);
+}
+bool launchEvalBuild(const DeviceProblem& p, bool cand, double mu, bool initScale, bool factorsCommute, int computeUnits, hipStream_t s,
+                     double stepRadius) {
+  const BuildPlan q = buildPlanOf(p);
+  const EvalPlan e = evalPlanOf(p);
+  const bool head = stepRadius > 0.0;
+  if (head && !(cand && p.lmDeferred)) throw std::logic_error("launchEvalBuild: the step rides in the candidate evaluation with deferred landmarks only");
   if (!evalBuildTaken(buildDimsOf(p), q, e, p.world > 1, computeUnits, sizeof(FactorShared))) return false;
   const int nR = e.nR, pri = e.pri, nEval = e.evalAll.grid;
   DeviceProblem pb = p;
@@ -4059,8 +4335,10 @@ bool launchEvalBuild(const DeviceProblem& p, bool cand, double mu, bool initScal
   gEvalBuildLaunches.fetch_add(1, std::memory_order_relaxed);
   const dim3 grid(nEval + p.nSlabs);
   const int acc = factorsCommute ? 1 : 0;
-  if (p.obsS) launch(k_eval_build<true>, grid, dim3(256), 0, s, pb, cand ? 1 : 0, nR, pri, nEval, mu, initScale ? 1 : 0, p.nSlabs, acc);
-  else launch(k_eval_build<false>, grid, dim3(256), 0, s, pb, cand ? 1 : 0, nR, pri, nEval, mu, initScale ? 1 : 0, p.nSlabs, acc);
+  const double radius = head ? stepRadius : -1.0;
+  const int nPost = e.post.grid;
+  if (p.obsS) launch(k_eval_build<true>, grid, dim3(256), 0, s, pb, cand ? 1 : 0, nR, pri, nEval, mu, initScale ? 1 : 0, p.nSlabs, acc, radius, nPost);
+  else launch(k_eval_build<false>, grid, dim3(256), 0, s, pb, cand ? 1 : 0, nR, pri, nEval, mu, initScale ? 1 : 0, p.nSlabs, acc, radius, nPost);
   if (q.nPri > 0 || !factorsCommute) {
     const DeviceProblem view = cand ? withSetsSwapped(pb) : pb;   // the factors' and the prior's linearisation at the evaluated point
     if (factorsCommute) launch(k_prior_accumulate, dim3(q.nPri), dim3(256), 0, s, view);
@@ -6986,15 +7264,7 @@ __global__ __launch_bounds__(256) void k_step_retract_batch(const BatchSlot* __r
 }
 
 
-// partial slots of the post-solve pass
-constexpr int kPostK = 9;  // A=|Jv|^2 B=|Jy|^2 C=Jv.Jy D=Jv.r E=Jy.r gHat gnHat gDotGn gradMax
-__device__ __constant__ int kPostSlot[kPostK] = {PS_JV_SQ, PS_JY_SQ, PS_JVJY, PS_JV_DOT, PS_JY_DOT, PS_GHAT, PS_GNHAT, PS_GDOTGN, PS_GRADMAX};
-// the same table for compile-time indices (a __constant__ lookup is a memory round trip: nine of them, each followed by its
-// dependent partial load, used to serialise the tail of the post-solve pass)
-__device__ constexpr int postSlotC(int k) {
-  constexpr int tbl[kPostK] = {PS_JV_SQ, PS_JY_SQ, PS_JVJY, PS_JV_DOT, PS_JY_DOT, PS_GHAT, PS_GNHAT, PS_GDOTGN, PS_GRADMAX};
-  return tbl[k];
-}
+// (the partial slots of the post-solve pass -- kPostK, kPostSlot, postSlotC -- stand in front of stepHead, which sums them as well)
 
 // One pass over the whole linearisation right after the reduced solve (y_C, and v_C = g/htil from the solver):
 //  landmark blocks (16 lanes per landmark): back-substitution y_l = Vinv (b_l - sum_i Jl_i^T Jc_i y_C), v_l = g_l/htil_l,
@@ -7006,7 +7276,7 @@ __device__ constexpr int postSlotC(int k) {
 //  (nBlocks = nLmBlocks + nFacBlocks + 1: gridDim.x of the window's own launch -- the clears' stride, the ticket and the partial
 //  sums read it from here)
 template <bool WITH_EXT, class NB>
-__device__ __forceinline__ void k_post_solve_body(const DeviceProblem& p, int nLmBlocks, int nFacBlocks, double fuseRadius, NB nBlocks) {
+__device__ __forceinline__ void k_post_solve_body(const DeviceProblem& p, int nLmBlocks, int nFacBlocks, double fuseRadius, NB nBlocks, int noTail = 0) {
   __shared__ double red[16 * kPostK];
   __shared__ int lastFlag;
   const int t = threadIdx.x, b = blockIdx.x;
@@ -7032,8 +7302,9 @@ __device__ __forceinline__ void k_post_solve_body(const DeviceProblem& p, int nL
   const bool staged = p.d <= kStageMax;
   const bool stagedOff = p.nPose <= kStageBlk && p.nExt <= kStageBlk;
   const int nBlkItems = p.nPose + p.nExt + p.nSb;
-  const bool stagedItems = fuseRadius > 0.0 && staged && nBlkItems <= kStageItems;
-  const int cholFailIn = p.scal->cholFail;  // set by earlier kernels only
+  const bool stagedItems = fuseRadius > 0.0 && !noTail && staged && nBlkItems <= kStageItems;
+  // (set by earlier kernels only; read by whichever block may publish it: any block with a tail, the camera block without)
+  const int cholFailIn = (!noTail || b == nLmBlocks + nFacBlocks) ? p.scal->cholFail : 0;
   // Memory round trips of a landmark block: (1) the observation range of the lane group's first landmark, (2) that
   // observation's Jacobians and residual.  The staging loads are issued between the two and land in their shadow.
   struct RawObs { uint32_t idx; double jp[12], je[12], jl[6], rr[2]; };
@@ -7288,6 +7559,18 @@ __device__ __forceinline__ void k_post_solve_body(const DeviceProblem& p, int nL
   const double mine = blockSumK<kPostK>(acc, red, 8);
   TRACE(11);
   if (t < kPostK) cstore(p.partial + (size_t)kPostSlot[t] * kMaxPartials + b, mine);
+  if (noTail) {
+    // The step is taken at the head of the next launch's blocks (k_eval_build, stepHead): no ticket, no tail.  gFull is cleared
+    // HERE all the same -- that launch's factor blocks add to it atomically, a clear over there would race with them -- by its only
+    // reader in this launch, the camera block, each thread the entries it has read itself.
+    // cholFail is handed on and reset HERE as well, where the tail did it -- behind the solver, in front of the build: the chunk
+    // blocks of the next launch raise it for the build they make, and a reset among them would race with that.
+    if (b == nLmBlocks + nFacBlocks) {
+      for (int i = t; i < p.d; i += blockDim.x) p.gFull[i] = 0.0;
+      if (t == 0) { p.scal->failMax = (double)cholFailIn; p.scal->cholFail = 0; }
+    }
+    return;
+  }
   if (!lastBlockDoneLight(&p.tickets[TK_POST], &lastFlag, nBlocks)) return;   // partials, y_l and v_l are cstore()d
   TRACE(2);
   // The tail from here on is the serial end of the iteration: one round trip for the partials of the nine sums, then the
@@ -7415,7 +7698,7 @@ __device__ __forceinline__ void k_post_solve_body(const DeviceProblem& p, int nL
   TRACE(7);
 }
 template <bool WITH_EXT>
-__global__ __launch_bounds__(256) void k_post_solve(DeviceProblem p, int nLmBlocks, int nFacBlocks, double fuseRadius) { k_post_solve_body<WITH_EXT>(p, nLmBlocks, nFacBlocks, fuseRadius, GridDimX{}); }
+__global__ __launch_bounds__(256) void k_post_solve(DeviceProblem p, int nLmBlocks, int nFacBlocks, double fuseRadius, int noTail) { k_post_solve_body<WITH_EXT>(p, nLmBlocks, nFacBlocks, fuseRadius, GridDimX{}, noTail); }
 // (the same body held to 256 registers -- two workgroups per CU -- for grids of more blocks than the chip has CUs: wide windows)
 template <bool WITH_EXT>
 __global__ __launch_bounds__(256, 2) void k_post_solve_wide(DeviceProblem p, int nLmBlocks, int nFacBlocks, double fuseRadius) { k_post_solve_body<WITH_EXT>(p, nLmBlocks, nFacBlocks, fuseRadius, GridDimX{}); }
@@ -7429,16 +7712,20 @@ __global__ __launch_bounds__(256, SVIN_BATCH_OCC_POST) void k_post_solve_batch(c
 }
 
 
-void launchDoglegPrepare(const DeviceProblem& p, hipStream_t s, double fuseRadius) {
+static std::atomic<int> gStepInEvalLaunches{0};
+int stepInEvalLaunches() { return gStepInEvalLaunches.load(std::memory_order_relaxed); }
+void launchDoglegPrepare(const DeviceProblem& p, hipStream_t s, double fuseRadius, bool noTail) {
   const EvalPlan e = evalPlanOf(p);
   const int nLm = e.postLm, nFac = e.postFac;
+  if (noTail && (e.postSplit || !(fuseRadius > 0.0))) throw std::logic_error("launchDoglegPrepare: the pass without a tail is the narrow window's fused step");
   if (e.postSplit) {
     if (p.anyExtVariable) launch(k_post_solve_wide<true>, dim3(e.post.grid), dim3(256), 0, s, p, nLm, nFac, fuseRadius);
     else launch(k_post_solve_wide<false>, dim3(e.post.grid), dim3(256), 0, s, p, nLm, nFac, fuseRadius);
     return;
   }
-  if (p.anyExtVariable) launch(k_post_solve<true>, dim3(e.post.grid), dim3(256), 0, s, p, nLm, nFac, fuseRadius);
-  else launch(k_post_solve<false>, dim3(e.post.grid), dim3(256), 0, s, p, nLm, nFac, fuseRadius);
+  if (noTail) gStepInEvalLaunches.fetch_add(1, std::memory_order_relaxed);
+  if (p.anyExtVariable) launch(k_post_solve<true>, dim3(e.post.grid), dim3(256), 0, s, p, nLm, nFac, fuseRadius, noTail ? 1 : 0);
+  else launch(k_post_solve<false>, dim3(e.post.grid), dim3(256), 0, s, p, nLm, nFac, fuseRadius, noTail ? 1 : 0);
 }
 
 // final single-block reduction of the cost partials into SolverScalars (used when no later evaluation kernel

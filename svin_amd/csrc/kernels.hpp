@@ -285,8 +285,15 @@ int lastSchurForm();
 // so their order does not matter): the factor blocks of the launch add their factor themselves.  Otherwise the factors and the
 // prior keep a launch of their own (k_factors_only) behind it, where their blocks start together as they do in k_schur_dense --
 // sums of three and more terms then come out the same from run to run as far as they did before.
-bool launchEvalBuild(const DeviceProblem& p, bool cand, double mu, bool initScale, bool factorsCommute, int computeUnits, hipStream_t s);
+// stepRadius > 0 (cand only, behind launchDoglegPrepare(..., noTail = true)): every evaluation and chunk block first takes the dogleg
+// step of that radius itself, from the partials of the post-solve pass (stepHead, kernels.hip), and evaluates at the candidate it
+// holds in its own LDS; the first reprojection block stores the candidate blocks and the step's record.
+bool launchEvalBuild(const DeviceProblem& p, bool cand, double mu, bool initScale, bool factorsCommute, int computeUnits, hipStream_t s,
+                     double stepRadius = -1.0);
 int evalBuildLaunches();   // launches of k_eval_build in this process so far (svin_ba_debug_get_option("SVIN_EVAL_BUILD_LAUNCHES"))
+int stepInEvalLaunches();  // post-solve passes launched without their tail so far (svin_ba_debug_get_option("SVIN_STEP_IN_EVAL_LAUNCHES"))
+// Whether the step of this window moves from k_post_solve's tail to the head of k_eval_build's blocks (build_plan.hpp stepInEvalTaken)
+bool stepInEvalTaken(const DeviceProblem& p, bool sharded, bool buildWanted, bool reuse, bool hostFactors, int computeUnits);
 
 // ---- launch wrappers (kernels.hip).  `cand` selects candidate tables/buffers.
 void launchEvalReproj(const DeviceProblem& p, bool cand, bool robust, hipStream_t s);
@@ -344,7 +351,9 @@ void launch(void (*kernel)(P...), dim3 grid, dim3 block, size_t ldsBytes, hipStr
 // (solveReducedScratchDoubles, the doubles DeviceProblem::cholL must hold: solve_plan.hpp)
 // post-solve pass (back-substitution, J*v / J*y sums, norms); fuseRadius > 0: its last block also takes the dogleg
 // step with that radius and retracts (single GPU, narrow windows) -- launchDoglegStep is then not needed
-void launchDoglegPrepare(const DeviceProblem& p, hipStream_t s, double fuseRadius = -1.0);
+// noTail: the blocks store their partials, y_l and v_l and return -- no ticket, no reduction, no step; the launch behind it is
+// launchEvalBuild with the same radius as stepRadius
+void launchDoglegPrepare(const DeviceProblem& p, hipStream_t s, double fuseRadius = -1.0, bool noTail = false);
 void launchDoglegStep(const DeviceProblem& p, double radius, hipStream_t s);  // delta, J*delta pass, candidate, norms
 // sharded mode: the (all-reduced) scalars + sequence number into the pinned-host mailbox, as one wave-wide store
 void launchPublishScalars(const SolverScalars* scal, ScalarMailbox* mailbox, unsigned long long seq, hipStream_t s);

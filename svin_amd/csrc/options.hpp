@@ -42,6 +42,9 @@ enum DebugOption : int {
   kOptNoEvalBuild,         // SVIN_NO_EVAL_BUILD: evaluation and the build enqueued behind it as two launches (k_eval_all, k_schur_dense), never k_eval_build
   kOptLinearizeEvalBuild,  // SVIN_LINEARIZE_EVAL_BUILD: the inspection hooks svin_ba_linearize / svin_ba_debug_reduced_solve take their evaluation and
                            // build through k_eval_build where solve() would (tests: the launch against the two it replaces, on one handle)
+  kOptNoStepInEval,        // SVIN_NO_STEP_IN_EVAL: the dogleg step stays in k_post_solve's tail, never at the head of k_eval_build's blocks
+  kOptStepHookInEval,      // SVIN_STEP_HOOK_IN_EVAL: the inspection hook svin_ba_debug_trust_region_step (form 3) takes its step through
+                           // k_post_solve without the tail + k_eval_build where solve() would (tests: the pair against the tail, on one handle)
   kOptCount
 };
 
@@ -53,6 +56,8 @@ int debugOptionByName(const char* name, int* value);       // 1 and *value, or 0
 // of a window sitting out the stage (window.cpp, batch_plan.hpp)
 int lastBatchIdlePpm();
 // read-only inspection field "SVIN_EVAL_BUILD_LAUNCHES": how many times this process has launched k_eval_build (kernels.hpp)
+// read-only inspection field "SVIN_STEP_IN_EVAL_LAUNCHES": how many post-solve passes this process has launched without their tail,
+// the step left to the blocks of the k_eval_build launch behind them (kernels.hpp)
 inline bool optOn(DebugOption which) { return debugOption(which) != 0; }
 
 }  // namespace svin

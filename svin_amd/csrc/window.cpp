@@ -67,7 +67,8 @@ struct OptionTable {
         {kOptBatchTiming, "SVIN_BATCH_TIMING"}, {kOptNoEvalSplit, "SVIN_NO_EVAL_SPLIT"},
         {kOptSlabChunks, "SVIN_SLAB_CHUNKS"}, {kOptNoSbEarly, "SVIN_NO_SB_EARLY"},
         {kOptNoRowSplit, "SVIN_NO_ROW_SPLIT"}, {kOptNoEvalBuild, "SVIN_NO_EVAL_BUILD"},
-        {kOptLinearizeEvalBuild, "SVIN_LINEARIZE_EVAL_BUILD"}};
+        {kOptLinearizeEvalBuild, "SVIN_LINEARIZE_EVAL_BUILD"}, {kOptNoStepInEval, "SVIN_NO_STEP_IN_EVAL"},
+        {kOptStepHookInEval, "SVIN_STEP_HOOK_IN_EVAL"}};
     static_assert(sizeof(kNames) / sizeof(kNames[0]) == kOptCount, "every option has its environment variable");
     for (const auto& n : kNames) {
       name[n.which] = n.env;
@@ -92,6 +93,7 @@ int debugOptionByName(const char* name, int* value) {
   if (!name) return 0;
   if (std::strcmp(name, "SVIN_LAST_SCHUR_FORM") == 0) { if (value) *value = lastSchurForm(); return 1; }   // read-only: not in the table
   if (std::strcmp(name, "SVIN_EVAL_BUILD_LAUNCHES") == 0) { if (value) *value = evalBuildLaunches(); return 1; }   // read-only (kernels.hpp)
+  if (std::strcmp(name, "SVIN_STEP_IN_EVAL_LAUNCHES") == 0) { if (value) *value = stepInEvalLaunches(); return 1; }   // read-only (kernels.hpp)
   if (std::strcmp(name, "SVIN_LAST_BATCH_IDLE_PPM") == 0) { if (value) *value = lastBatchIdlePpm(); return 1; }   // read-only (options.hpp)
   OptionTable& t = optionTable();
   for (int k = 0; k < kOptCount; ++k)
@@ -2315,17 +2317,24 @@ void Window::downloadStates() {
 
 // buildMu: the caller enqueues the build of the normal equations at the evaluated point (damping *buildMu, clean accumulators)
 // right behind this evaluation -- true is returned when the evaluation's launch has taken that build along (k_eval_build)
-bool Window::evaluateAll(bool cand, hipStream_t s, const double* buildMu, bool buildInitScale) {
+bool Window::evaluateAll(bool cand, hipStream_t s, const double* buildMu, bool buildInitScale, double stepRadius) {
+  const bool stepInEval = stepRadius > 0.0;   // (stepInEvalTaken said so in front of the post-solve pass: the same predicate governs both)
+  if (stepInEval && !hostFactors_.empty()) throw std::logic_error("evaluateAll: the step at the head of the evaluation with host-evaluated factors");
   evaluateHostFactors(cand, s);
   prob_.mailbox = distNative_ ? nullptr : mailboxDev_;   // sharded: published after the all-reduce (launchPublishScalars)
   prob_.mailboxSeq = ++mailboxSeq_;
   const int who = costSummedBy(prob_);
   if (canFuseEvaluation(prob_) && !optOn(kOptSplitEval)) {
-    if (buildMu && !optOn(kOptNoEvalBuild) && launchEvalBuild(prob_, cand, *buildMu, buildInitScale, maxTermsPerBlock_ <= 2, deviceComputeUnits(), s)) return true;
+    if (buildMu && !optOn(kOptNoEvalBuild) &&
+        launchEvalBuild(prob_, cand, *buildMu, buildInitScale, maxTermsPerBlock_ <= 2, deviceComputeUnits(), s, stepInEval ? stepRadius : -1.0))
+      return true;
+    // the post-solve pass without its tail is enqueued already: nothing else takes the step
+    if (stepInEval) throw std::logic_error("evaluateAll: k_eval_build declined a window whose step it was to take");
     // one launch: the reprojection blocks and the prior run next to the (much longer) IMU factor blocks
     launchEvalAll(prob_, cand, true, s);  // factor, reprojection and prior blocks; the last one sums the cost
     return false;
   }
+  if (stepInEval) throw std::logic_error("evaluateAll: the split evaluation cannot take the step");
   launchEvalReproj(prob_, cand, true, s);
   launchEvalFactors(prob_, cand, s, who == 1);
   launchEvalPrior(prob_, cand, s, who == 2);
@@ -2453,6 +2462,7 @@ void Window::solve(size_t numIter, bool verbose) {
     if (!tr.beginIteration(stop)) break;
     const double tIter = nowSec();
     while (true) {
+      bool stepInEval = false;   // this pass of the loop: k_post_solve ends at its partials, k_eval_build takes the step
       if (!tr.reuse) {
         const bool haveFirst = firstBuilt && tr.initScale && tr.mu == firstMu;   // the build enqueued ahead of the loop
         if (firstBuilt && !haveFirst) accumulatorsClean = false;                 // (a retry with more damping: it has to go)
@@ -2467,15 +2477,21 @@ void Window::solve(size_t numIter, bool verbose) {
         }
         launchSolveReduced(p, s, tr.mu, tr.initScale, /*fuseFinalize=*/true);
         p.lmDeferred = deferLm ? 1 : 0;
-        launchDoglegPrepare(p, s, fuseStep ? tr.radius : -1.0);
+        // the step at the head of the candidate evaluation's blocks (build_plan.hpp stepInEvalTaken): where k_eval_build follows --
+        // a speculative build is wanted behind this iteration's evaluation, so never on the last iteration, which k_eval_all ends
+        stepInEval = fuseStep && deferLm && evalBuild &&
+                     stepInEvalTaken(p, dist, specBuildWanted(speculate, /*accumulatorsClean=*/true, tr.iteration, (int)numIter), tr.reuse,
+                                     !hostFactors_.empty(), deviceComputeUnits());
+        launchDoglegPrepare(p, s, fuseStep ? tr.radius : -1.0, stepInEval);
         accumulatorsClean = true;
         AR(scalD + kScalGroupB, 8 + kScalGatherSlots, 0);   // group B and every rank's (gradMax, failMax) pair: one message
       }
       if (tr.reuse || !fuseStep) launchDoglegStep(p, tr.radius, s);
       p.lmDeferred = (deferLm && !tr.reuse) ? 1 : 0;
-      const bool specWanted = speculate && accumulatorsClean && tr.iteration < (int)numIter;
+      const bool specWanted = specBuildWanted(speculate, accumulatorsClean, tr.iteration, (int)numIter);
       if (specWanted) specMu = tr.muAfterAccept();
-      const bool specFused = evaluateAll(true, s, (specWanted && evalBuild) ? &specMu : nullptr, false);
+      if (stepInEval && !(specWanted && evalBuild)) throw std::logic_error("solve: the step was left to a build that is not enqueued");
+      const bool specFused = evaluateAll(true, s, (specWanted && evalBuild) ? &specMu : nullptr, false, stepInEval ? tr.radius : -1.0);
       p.lmDeferred = 0;
       if (specWanted && specFused) {   // (k_eval_build built on the candidate's sets itself: no swapped view)
         accumulatorsClean = false;
@@ -3041,9 +3057,13 @@ int Window::debugTrustRegionStep(double mu, double radius, int form, int commit,
     launchAccumulateNormalEquations(p, mu, true, s, /*zeroFirst=*/true);
     launchSolveReduced(p, s, mu, true, /*fuseFinalize=*/true);
     p.lmDeferred = run == 3 ? 1 : 0;
-    launchDoglegPrepare(p, s, run == 2 ? -1.0 : radius);
+    // SVIN_STEP_HOOK_IN_EVAL: form 3 through the pair solve() takes -- the pass without its tail, the step at the head of k_eval_build's
+    // blocks, whose build (damping mu, on the candidate's sets) lands in the accumulators the pass has just cleared
+    const bool viaHead = run == 3 && optOn(kOptStepHookInEval) && stepInEvalTaken(p, false, true, false, !hostFactors_.empty(), deviceComputeUnits());
+    launchDoglegPrepare(p, s, run == 2 ? -1.0 : radius, viaHead);
     if (run == 2) launchDoglegStep(p, radius, s);
-    evaluateAll(true, s);
+    if (viaHead) evaluateAll(true, s, &mu, false, radius);
+    else evaluateAll(true, s);
     p.lmDeferred = 0;
   }
   const SolverScalars sc = readScalars();

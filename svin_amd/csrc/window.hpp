@@ -419,7 +419,8 @@ class Window {
   // device side
   void pack(bool solveFollows = false);   // host graph -> device arrays (sets prob_); solveFollows: called by optimize()
   void downloadStates();       // device tables -> host blocks / landmarks / imu states
-  bool evaluateAll(bool cand, hipStream_t s, const double* buildMu = nullptr, bool buildInitScale = false);
+  // stepRadius > 0: the post-solve pass in front ended at its partials (launchDoglegPrepare noTail) -- k_eval_build takes the step
+  bool evaluateAll(bool cand, hipStream_t s, const double* buildMu = nullptr, bool buildInitScale = false, double stepRadius = -1.0);
   int maxTermsPerBlock_ = 0;   // packFactors: small factors + prior that add to one parameter block's diagonal block, at most
   void evaluateHostFactors(bool cand, hipStream_t s);   // F_HOST factors: callbacks at the current / candidate blocks, r and J into their FactorLin records
   void solve(size_t numIter, bool verbose);

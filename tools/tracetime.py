@@ -15,7 +15,9 @@ NAMES = {0: "post: block start", 1: "post: work done", 2: "post: last block in",
          16: "eval: block start", 17: "eval: factor block done", 18: "eval: block work done", 19: "eval: last block in", 20: "eval: cost reduced", 21: "eval: sums ready, before mailbox", 22: "eval: after system fence",
          24: "schur: block start", 25: "schur: ranges known", 26: "schur: first batch arrived", 27: "schur: landmark part done",
          28: "schur: chunk block end", 29: "schur: factor block end", 30: "schur: prior block end",   # (k_eval_build: 25 = ranges known, 26 = first observation evaluated)
-         31: "reduce: start", 32: "reduce: loads in", 33: "reduce: end"}
+         31: "reduce: start", 32: "reduce: loads in", 33: "reduce: end",
+         # the step at the head of k_eval_build's blocks (stepHead): same launch and time base as 16-30
+         40: "head: block start", 41: "head: sums reduced", 42: "head: coefficients", 43: "head: candidate staged"}
 spec = syn.make_window()
 est = Estimator(0)
 syn.feed(est, spec)
@@ -31,7 +33,7 @@ for it in (0, 1, 10):
     # k_eval_build (the library counts its launches): evaluation blocks (16-22), chunk blocks (24-28) and the factor blocks'
     # accumulation (29) belong to ONE launch and share a time base; SVIN_NO_EVAL_BUILD=1 gives the two launches' own groups
     fused = Estimator.debug_get_option("SVIN_EVAL_BUILD_LAUNCHES") > n_fused
-    for grp in ((range(0, 13), range(16, 31), range(31, 34)) if fused else (range(0, 13), range(16, 23), range(24, 31), range(31, 34))):
+    for grp in ((range(0, 13), list(range(16, 31)) + list(range(40, 44)), range(31, 34)) if fused else (range(0, 13), range(16, 23), range(24, 31), range(31, 34))):
         t0 = min((int(out[2 * k]) for k in grp if k in NAMES and out[2 * k + 1] != 0), default=None)
         if t0 is None:
             continue
