@@ -540,6 +540,29 @@ int svin_ba_debug_landmark_handles(svin_ba* h, int32_t out[2]);
  * component i of vector j, device_ms (may be NULL) = the fastest of three launches.  Returns 1, 0 if n is out of range,
  * -1 if the result is not finite.  Test hook. */
 int svin_ba_debug_sym_eig(int n, const double* A, double* eigenvalues, double* eigenvectors, double* device_ms);
+/* read-only: the reduced system as it stands on the device after the last svin_ba_linearize / svin_ba_debug_reduced_solve -- S (d x d,
+ * row-major) and g (d); either may be NULL.  The build sums with floating-point atomics, so two builds of the same window differ
+ * in their last bits: this is the one way to see the very system a svin_ba_debug_reduced_solve has just solved (its unfused form
+ * leaves the damped S behind).  Launches nothing.  Returns d, -d if cap_d < d, 0 before the first build.  Test hook. */
+int svin_ba_debug_last_system(svin_ba* h, double* S, double* g, int cap_d);
+/* The reduced solve (S + mu D) y = g on a caller-supplied system, on the current HIP device: the launch sequence the library
+ * runs for a window or a pose-graph root of these dimensions (launchSolveReduced itself, on a minimal problem view), whichever
+ * route the sizes and the switches SVIN_NO_LL / SVIN_NO_SB_ELIM / SVIN_NO_LDS_BORDER select.  Test hook.
+ * d unknowns; sb_chain > 0: the rows dC .. d are sb_chain speed / bias blocks of 9 rows (dC + 9 sb_chain = d) whose part of S is
+ * block-tridiagonal.  S (lower triangle read) starts at s_buffer[s_offset] with leading dimension ld_s (0 = d) inside a buffer of
+ * s_buffer_doubles, all of which is uploaded; s_padded != 0 is the window's form (d rounded up to 16 rows of ld_s >= that many
+ * doubles, zero beyond row / column d), 0 the pose graph's (a principal block of a larger matrix).  fuse_finalize != 0 applies
+ * the metric and damping of h_c inside the solver (init_scale != 0: the scale 1 / (1 + sqrt(h_c)); 0: scale_c); otherwise mu is
+ * not used and the system is solved as it stands.  scratch_fill: the byte the solver's scratch is filled with beforehand.
+ * Outputs: y (d); htil (d, may be NULL); *chol_fail = SolverScalars::cholFail; info10 = chain mode, route (solve_plan.hpp
+ * DenseRoute), unknowns of the dense solve, border rows, grid of k_big_chol_chain, its helper tasks, back-substitution panels,
+ * chain overflow, plan.end (low 31 bits, high bits); s_buffer_after (may be NULL): the whole buffer read back; scratch (may be
+ * NULL): the first plan.end doubles of the solver's scratch, which is sized solveReducedScratchDoubles(d, true).
+ * Returns 1; 0 if cap_scratch < plan.end (info10 is filled); SVIN_ERR_INVALID_ARG for inconsistent sizes. */
+int svin_ba_debug_solve_dense(int d, int dC, int sb_chain, int s_padded, int ld_s, const double* s_buffer, uint64_t s_buffer_doubles,
+                              uint64_t s_offset, const double* g, const double* h_c, const double* scale_c, double mu, int fuse_finalize,
+                              int init_scale, int scratch_fill, double* y, double* htil, int32_t* chol_fail, int32_t* info10,
+                              double* s_buffer_after, double* scratch, uint64_t cap_scratch);
 /* Debug / A-B options of the library (svin_amd/csrc/options.hpp; INTEGRATION.md §5 lists them).  Each option is named after the
  * environment variable that initialises it -- the library looks at the environment ONCE, when the first of them is asked for
  * (svin_ba_create at the latest) -- and only changes through svin_ba_debug_set_option afterwards; a later setenv() of the host

@@ -612,6 +612,22 @@ int svin_ba_debug_sym_eig(int n, const double* A, double* eigenvalues, double* e
   GUARD_BEGIN return svin::debugSymEig(n, A, eigenvalues, eigenvectors, device_ms);
   GUARD_END(SVIN_ERR_DEVICE)
 }
+int svin_ba_debug_last_system(svin_ba* h, double* S, double* g, int cap_d) {
+  if (!h) return SVIN_ERR_INVALID_ARG;
+  GUARD_BEGIN return win(h).debugLastSystem(S, g, cap_d);
+  GUARD_END(SVIN_ERR_DEVICE)
+}
+int svin_ba_debug_solve_dense(int d, int dC, int sb_chain, int s_padded, int ld_s, const double* s_buffer, uint64_t s_buffer_doubles,
+                              uint64_t s_offset, const double* g, const double* h_c, const double* scale_c, double mu, int fuse_finalize,
+                              int init_scale, int scratch_fill, double* y, double* htil, int32_t* chol_fail, int32_t* info10,
+                              double* s_buffer_after, double* scratch, uint64_t cap_scratch) {
+  GUARD_BEGIN
+  const svin::DebugDenseIn in{d, dC, sb_chain, s_padded, ld_s, s_buffer, (size_t)s_buffer_doubles, (size_t)s_offset, g, h_c, scale_c,
+                              mu, fuse_finalize, init_scale, scratch_fill};
+  const svin::DebugDenseOut out{y, htil, chol_fail, info10, s_buffer_after, scratch, (size_t)cap_scratch};
+  return svin::debugSolveDense(in, out);
+  GUARD_END(SVIN_ERR_DEVICE)
+}
 int svin_ba_debug_set_option(const char* name, int value) { return svin::setDebugOption(name, value); }
 int svin_ba_debug_get_option(const char* name, int* value) { return svin::debugOptionByName(name, value); }
 int svin_ba_debug_set_switch(const char* name, int value) { return svin::setDebugOption(name, value ? 1 : 0); }

@@ -3119,6 +3119,15 @@ int Window::debugPeekSolverScratch(uint64_t off, uint64_t count, double* out) {
   HIP_OK(hipMemcpy(out, prob_.cholL + off, sizeof(double) * count, hipMemcpyDeviceToHost));
   return 1;
 }
+int Window::debugLastSystem(double* S, double* g, int capD) {
+  const DeviceProblem& p = prob_;
+  HIP_OK(hipStreamSynchronize(stream_));
+  if (p.d < 1 || !p.S || !p.gRed) return 0;
+  if (p.d > capD) return -p.d;
+  if (S) HIP_OK(hipMemcpy2D(S, sizeof(double) * p.d, p.S, sizeof(double) * p.ldS, sizeof(double) * p.d, p.d, hipMemcpyDeviceToHost));
+  if (g) HIP_OK(hipMemcpy(g, p.gRed, sizeof(double) * p.d, hipMemcpyDeviceToHost));
+  return p.d;
+}
 int Window::getPrior(double* H, double* b0, double* J, double* e0, uint64_t* ids, int32_t* ord, int32_t* mdim,
                      int32_t* nBlocks, int capM) {
   quiesce();
@@ -3682,6 +3691,59 @@ int Window::benchKernelTimes(int iters, double* evalMs, double* buildMs, double*
 #endif
   }
   (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+  return 1;
+}
+
+// inspection hook (svin_ba_debug_solve_dense): launchSolveReduced on a caller-supplied system, through a minimal DeviceProblem view
+// like the one the pose graph's root solve builds.  No window: the current device, the default stream.  The plan is the one
+// launchSolveReduced walks (the same dimensions, the same option table).
+int debugSolveDense(const DebugDenseIn& in, const DebugDenseOut& out) {
+  const int d = in.d, dpad = roundUpTo(d, 16);
+  if (d < 1 || d > 4096 || !in.sBuf || !in.g || !out.y || !out.info) return -1 /* SVIN_ERR_INVALID_ARG */;
+  if (in.sbChain < 0 || in.dC < 0 || in.dC > d || (in.sbChain > 0 && in.dC + 9 * in.sbChain != d)) return -1 /* SVIN_ERR_INVALID_ARG */;
+  // S as the kernels address it: rows x ld doubles from sOff, padded to whole tiles for the window's form
+  const size_t ld = in.ldS ? (size_t)in.ldS : (size_t)d, rows = in.sPadded ? dpad : d, cols = in.sPadded ? dpad : d;
+  if (ld < cols || in.sOff + (rows - 1) * ld + cols > in.sBufDoubles) return -1 /* SVIN_ERR_INVALID_ARG */;
+  if (in.fuseFinalize && (!in.hC || (!in.initScale && !in.scaleC))) return -1 /* SVIN_ERR_INVALID_ARG */;
+  const ReducedSolvePlan q = planReducedSolve(SolveDims{d, in.dC, in.sbChain, in.sPadded ? 1 : 0},
+                                              SolveSwitches{optOn(kOptNoLL), optOn(kOptNoSbElim), optOn(kOptNoLdsBorder)});
+  const size_t scratch = solveReducedScratchDoubles(d, true);
+  out.info[0] = q.chainMode; out.info[1] = (int)q.route; out.info[2] = q.dSolve; out.info[3] = q.border; out.info[4] = q.bigChain.grid;
+  out.info[5] = q.helperTasks; out.info[6] = q.nBackPanels; out.info[7] = q.chainOverflow ? 1 : 0;
+  out.info[8] = (int)(q.end & 0x7fffffff); out.info[9] = (int)(q.end >> 31);
+  if (q.end > scratch) return -3 /* SVIN_ERR_DEVICE */;
+  if (out.scratch && out.capScratch < q.end) return 0;   // sizes only: info says how much
+  const size_t nv = (size_t)dpad + 64;   // every vector: whole tiles and a spare block behind them
+  DevBuf<double> dS, dV, dChol;
+  DevBuf<SolverScalars> dScal;
+  dS.reserve(in.sBufDoubles); dV.reserve(7 * nv); dChol.reserve(scratch); dScal.reserve(1);
+  HIP_OK(hipMemcpy(dS.p, in.sBuf, sizeof(double) * in.sBufDoubles, hipMemcpyHostToDevice));
+  HIP_OK(hipMemset(dV.p, 0, sizeof(double) * 7 * nv));
+  HIP_OK(hipMemset(dChol.p, in.scratchFill & 0xff, sizeof(double) * scratch));
+  HIP_OK(hipMemset(dScal.p, 0, sizeof(SolverScalars)));
+  double *dG = dV.p, *dGFull = dG + nv, *dHc = dGFull + nv, *dHtil = dHc + nv, *dScale = dHtil + nv, *dY = dScale + nv, *dVc = dY + nv;
+  HIP_OK(hipMemcpy(dG, in.g, sizeof(double) * d, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(dGFull, in.g, sizeof(double) * d, hipMemcpyHostToDevice));
+  if (in.hC) HIP_OK(hipMemcpy(dHc, in.hC, sizeof(double) * d, hipMemcpyHostToDevice));
+  if (in.scaleC) HIP_OK(hipMemcpy(dScale, in.scaleC, sizeof(double) * d, hipMemcpyHostToDevice));
+  {   // the metric of an earlier pass, which the unfused form reads: the identity
+    std::vector<double> ones(nv, 1.0);
+    HIP_OK(hipMemcpy(dHtil, ones.data(), sizeof(double) * nv, hipMemcpyHostToDevice));
+  }
+  DeviceProblem dp;
+  std::memset(&dp, 0, sizeof(dp));
+  dp.d = d; dp.dC = in.dC; dp.sbChain = in.sbChain; dp.sPadded = in.sPadded ? 1 : 0; dp.ldS = in.ldS;
+  dp.S = dS.p + in.sOff; dp.gRed = dG; dp.gFull = dGFull; dp.hC = dHc; dp.htilC = dHtil; dp.scaleC = dScale; dp.yC = dY; dp.vC = dVc;
+  dp.cholL = dChol.p; dp.scal = dScal.p;
+  launchSolveReduced(dp, 0, in.mu, in.initScale != 0, in.fuseFinalize != 0);
+  HIP_OK(hipStreamSynchronize(0));
+  SolverScalars sc;
+  HIP_OK(hipMemcpy(&sc, dScal.p, sizeof(sc), hipMemcpyDeviceToHost));
+  if (out.cholFail) *out.cholFail = sc.cholFail;
+  HIP_OK(hipMemcpy(out.y, dY, sizeof(double) * d, hipMemcpyDeviceToHost));
+  if (out.htil) HIP_OK(hipMemcpy(out.htil, dHtil, sizeof(double) * d, hipMemcpyDeviceToHost));
+  if (out.sBufAfter) HIP_OK(hipMemcpy(out.sBufAfter, dS.p, sizeof(double) * in.sBufDoubles, hipMemcpyDeviceToHost));
+  if (out.scratch && q.end > 0) HIP_OK(hipMemcpy(out.scratch, dChol.p, sizeof(double) * q.end, hipMemcpyDeviceToHost));
   return 1;
 }
 

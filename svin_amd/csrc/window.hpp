@@ -355,6 +355,8 @@ class Window {
   int debugBuildArrays(double* gFull, double* hC, int capD, double* Vinv, double* bl, double* hL, double* scaleL, int capL,
                        int32_t* imuRedo, int capImu, int32_t* sizes3);
   int debugPeekSolverScratch(uint64_t off, uint64_t count, double* out);
+  // read-only inspection (svin_ba_debug_last_system): S and g as the last build / reduced solve left them on the device
+  int debugLastSystem(double* S, double* g, int capD);
   // one trust-region iteration with everything the step is made of read back (window.cpp); the arrays may be null
   struct DebugStepOut {
     double* scalars;                               // 38: SolverScalars after the candidate evaluation, cholFail last
@@ -647,4 +649,16 @@ std::string& lastError();
 // inspection hook of the prior's eigen-solver (symeig.hpp; marg.hip): eigenvalues (ascending) and eigenvectors (X[i * n + j] =
 // component i of vector j) of a symmetric n x n matrix, n <= 128, on the current device.  1, 0 (n out of range), -1 (not finite).
 int debugSymEig(int n, const double* A, double* lam, double* X, double* deviceMs);
+// inspection hook of the reduced solve (svin_ba_debug_solve_dense, window.cpp): launchSolveReduced on a caller-supplied system
+struct DebugDenseIn {
+  int d, dC, sbChain, sPadded, ldS;
+  const double* sBuf; size_t sBufDoubles, sOff;   // the buffer S lies in, and where S starts in it
+  const double *g, *hC, *scaleC;
+  double mu; int fuseFinalize, initScale, scratchFill;
+};
+struct DebugDenseOut {
+  double *y, *htil; int* cholFail; int32_t* info;   // info: 10 ints, svin_ba.h
+  double* sBufAfter; double* scratch; size_t capScratch;
+};
+int debugSolveDense(const DebugDenseIn& in, const DebugDenseOut& out);
 }  // namespace svin

@@ -56,7 +56,7 @@ EXPORTS = [
     "svin_ba_set_camera_sensor_states", "svin_ba_set_landmark", "svin_ba_num_frames", "svin_ba_num_landmarks",
     "svin_ba_current_keyframe_id", "svin_ba_current_frame_id", "svin_ba_frame_id_by_age", "svin_ba_is_keyframe",
     "svin_ba_is_in_imu_window", "svin_ba_frame_ids", "svin_ba_landmark_ids", "svin_ba_imu_propagation",
-    "svin_ba_eval_reprojection", "svin_ba_observation_ids", "svin_ba_eval_factors", "svin_ba_linearize", "svin_ba_debug_reduced_solve", "svin_ba_debug_reduced_solve_ex", "svin_ba_debug_build_arrays", "svin_ba_debug_trust_region_step", "svin_ba_debug_set_switch", "svin_ba_debug_set_option", "svin_ba_debug_get_option", "svin_ba_debug_sym_eig", "svin_ba_get_path_counters", "svin_ba_debug_landmark_handles", "svin_ba_wait_idle", "svin_ba_debug_peek_solver_scratch",
+    "svin_ba_eval_reprojection", "svin_ba_observation_ids", "svin_ba_eval_factors", "svin_ba_linearize", "svin_ba_debug_reduced_solve", "svin_ba_debug_reduced_solve_ex", "svin_ba_debug_build_arrays", "svin_ba_debug_trust_region_step", "svin_ba_debug_set_switch", "svin_ba_debug_set_option", "svin_ba_debug_get_option", "svin_ba_debug_sym_eig", "svin_ba_get_path_counters", "svin_ba_debug_landmark_handles", "svin_ba_wait_idle", "svin_ba_debug_peek_solver_scratch", "svin_ba_debug_solve_dense", "svin_ba_debug_last_system",
     "svin_ba_get_prior", "svin_ba_get_prior_lin", "svin_ba_describe_block", "svin_ba_bench_jacobian_eval", "svin_ba_bench_jacobian_eval_b2b", "svin_ba_set_pack_mode", "svin_ba_debug_csr", "svin_ba_residual_info",
     "svin_ba_map_add_parameter_block", "svin_ba_set_parameter_block", "svin_ba_map_remove_parameter_block", "svin_ba_map_add_pose_error",
     "svin_ba_map_add_speed_and_bias_error", "svin_ba_map_add_relative_pose_error", "svin_ba_map_add_reprojection_error",
@@ -182,6 +182,8 @@ def load_library():
     sig("svin_ba_debug_landmark_handles", i32, vp, pi32)
     sig("svin_ba_wait_idle", i32, vp)
     sig("svin_ba_debug_peek_solver_scratch", i32, vp, u64, u64, pd)
+    sig("svin_ba_debug_last_system", i32, vp, pd, pd, i32)
+    sig("svin_ba_debug_solve_dense", i32, i32, i32, i32, i32, i32, pd, u64, u64, pd, pd, pd, f64, i32, i32, i32, pd, pd, pi32, pi32, pd, pd, u64)
     sig("svin_ba_get_prior", i32, vp, pd, pd, pd, pd, pu64, pi32, pi32, pi32, i32)
     sig("svin_ba_get_prior_lin", i32, vp, pd, i32)
     sig("svin_ba_describe_block", i32, vp, u64, pu64, pi32, pi32)
@@ -806,6 +808,13 @@ class Estimator:
         d = self._check(self.L.svin_ba_debug_reduced_solve_ex(self.h, float(mu), 1 if fused else 0, _d(y), cap), "debug_reduced_solve")
         return y[:d].copy()
 
+    def debug_last_system(self, cap=4096):
+        """(S, g) as the last linearize() / debug_reduced_solve() left them on the device; launches nothing"""
+        d = self._check(self.L.svin_ba_debug_last_system(self.h, None, None, cap), "debug_last_system")
+        S, g = np.zeros((d, d)), np.zeros(d)
+        self._check(self.L.svin_ba_debug_last_system(self.h, _d(S), _d(g), d), "debug_last_system")
+        return S, g
+
     def debug_build_arrays(self):
         """svin_ba_debug_build_arrays: g_full, h_c, Vinv, b_l, h_l, scale_l of the last build and the IMU factors' redo counters"""
         sizes = np.zeros(3, np.int32)
@@ -871,6 +880,45 @@ class Estimator:
         if rc != 1:
             raise RuntimeError("svin_ba_debug_sym_eig: %d" % rc)
         return lam, X, float(ms[0])
+
+    @staticmethod
+    def debug_solve_dense(S_buffer, g, d, dC=0, sb_chain=0, padded=True, ldS=0, offset=0, mu=0.0, fused=False, init_scale=True, hC=None,
+                          scaleC=None, want_scratch=False, scratch_fill=0):
+        """the reduced solve on a caller-supplied system (include/svin_ba.h: svin_ba_debug_solve_dense).  S_buffer: the flat buffer
+        S lies in, from `offset` with leading dimension ldS.  -> dict(y, htil, cholFail, S_after (the buffer read back), scratch
+        (the first plan.end doubles of the solver's scratch, or None), and the plan as the library took it: chainMode, route,
+        dSolve, border, bigChainGrid, helperTasks, nBackPanels, chainOverflow, end)"""
+        buf = np.ascontiguousarray(S_buffer, dtype=np.float64).ravel()
+        g = np.ascontiguousarray(g, dtype=np.float64)
+        hC = None if hC is None else np.ascontiguousarray(hC, dtype=np.float64)
+        scaleC = None if scaleC is None else np.ascontiguousarray(scaleC, dtype=np.float64)
+        for v in (g, hC, scaleC):
+            if v is not None and v.shape != (d,):
+                raise ValueError("debug_solve_dense: a vector of %d entries is wanted" % d)
+        L = load_library()
+        y, htil, after = np.zeros(d), np.zeros(d), np.zeros(buf.size)
+        fail, info = np.zeros(1, np.int32), np.zeros(10, np.int32)
+
+        def call(scratch, cap):
+            return L.svin_ba_debug_solve_dense(int(d), int(dC), int(sb_chain), 1 if padded else 0, int(ldS), _d(buf), buf.size, int(offset), _d(g),
+                                               None if hC is None else _d(hC), None if scaleC is None else _d(scaleC), float(mu),
+                                               1 if fused else 0, 1 if init_scale else 0, int(scratch_fill), _d(y), _d(htil),
+                                               fail.ctypes.data_as(pi32), info.ctypes.data_as(pi32), _d(after), scratch, cap)
+        scratch = None
+        if want_scratch:
+            rc = call(_d(np.zeros(1)), 0)   # sizes only
+            if rc < 0:
+                raise RuntimeError("svin_ba_debug_solve_dense: %d (%s)" % (rc, L.svin_ba_last_error().decode()))
+            scratch = np.zeros(max(int(info[8]) + (int(info[9]) << 31), 1))
+            rc = call(_d(scratch), scratch.size)
+        else:
+            rc = call(None, 0)
+        if rc != 1:
+            raise RuntimeError("svin_ba_debug_solve_dense: %d (%s)" % (rc, L.svin_ba_last_error().decode()))
+        names = ("chainMode", "route", "dSolve", "border", "bigChainGrid", "helperTasks", "nBackPanels", "chainOverflow")
+        out = dict(zip(names, (int(v) for v in info[:8])))
+        out.update(y=y, htil=htil, cholFail=int(fail[0]), S_after=after, scratch=scratch, end=int(info[8]) + (int(info[9]) << 31))
+        return out
 
     _MARG_EIG = {"": 0, None: 0, "direct": 1, "cholesky": 2, "jacobi": 3}
 

@@ -138,3 +138,36 @@ def test_chain_elimination_is_used_and_can_be_switched_off(gpu_lib, sb_elim_swit
     assert s0["iterations"] == s1["iterations"] and s0["successful"] == s1["successful"]
     assert abs(s0["final_cost"] - s1["final_cost"]) <= 1e-9 * s1["final_cost"]
     assert np.abs(p0 - p1).max() < 1e-8
+
+
+def test_hook_on_a_window_system_equals_the_window_solve(gpu_lib):
+    """svin_ba_debug_solve_dense (which tests/test_gpu_dense_solve.py feeds systems of its own) on the system of a real window -- the
+    stereo_rig_v2 sliding window in its steady state, d = 198: the LDS-resident solver with 22 border rows -- gives the y of
+    debug_reduced_solve bit for bit: the hook runs the launch sequence the estimator runs.
+    The system is read back behind that very solve (svin_ba_debug_last_system): the build sums with floating-point atomics, two
+    builds of one window differ in their last bits (measured: S of two linearize() calls in a row is not bit-equal, nor is y of two
+    debug_reduced_solve() calls; the hook on linearize()'s S is 2e-15 .. 8e-15 of |y| away), so linearize() -- a build of its own
+    -- is held to the same system to 1e-12 and cannot give the bits."""
+    from svin_amd.estimator import Estimator
+    spec = syn.make_window(P=16, L=60 * 16, n_obs=600 * 16, seed=3, rig="rig_v2", frame_dt=0.25, sonar=True, depth=True)
+    est = Estimator(0)
+    got = {}
+
+    def on_frame(k, fid):
+        est.optimize(3)
+        if not got and est.linearize(1e-4)["d"] == 198:
+            lin = est.linearize(1e-4)
+            y = est.debug_reduced_solve(1e-4)
+            S, g = est.debug_last_system()
+            got.update(lin=lin, y=y, S=S, g=g)
+        est.apply_marginalization(5, 3)
+    syn.feed(est, spec, on_frame=on_frame)
+    assert got, "the window never reached d = 198"
+    d, dpad = 198, 208
+    lin, S, g = got["lin"], got["S"], got["g"]
+    assert S.shape == (d, d) and np.abs(np.tril(S) - np.tril(lin["S"])).max() <= 1e-12 * np.abs(S).max() and np.abs(g - lin["g"]).max() <= 1e-12 * np.abs(g).max()
+    buf = np.zeros((dpad, dpad))
+    buf[:d, :d] = S   # (finalised: the damping is in it, as in the unfused solve of debug_reduced_solve)
+    res = Estimator.debug_solve_dense(buf, g, d, dC=d, padded=True, ldS=dpad)
+    assert (res["route"], res["border"], res["cholFail"]) == (2, 22, 0)   # kRouteLdsBorderPrepared
+    assert np.array_equal(res["y"], got["y"])
