@@ -11,6 +11,7 @@
 // rank-revealing thresholds of the eliminated blocks; it is applied to exactly those blocks here
 // (U - W V^+ W^T with V^+ = D^-1 (D^-1 V D^-1)^+ D^-1), which is the same matrix in exact arithmetic.
 #include "window.hpp"
+#include "marg_plan.hpp"
 #include "symeig.hpp"
 #include "tile16.hpp"
 #include <chrono>
@@ -220,7 +221,7 @@ __device__ void symEig3(const double* A9, double* ev, double* Q) {
 // dot product itself (1e-15 kept the solver chasing that noise for 5+ extra sweeps)
 constexpr double kJacobiOrthTol = 2.0e-14;
 constexpr double kJacobiFinalCos = 3.0e-9;
-constexpr int kJacobiRegLen = 144;   // columns up to this (padded) length are held in registers by their lane group
+// (kJacobiRegLen, the column length the lane groups hold in registers, and jacobiLd, the row length of the LDS images: marg_plan.hpp)
 
 // one 32-bit half at a time through DPP; kCtrl: row_ror:N = 0x120 + N (lane i of a 16-lane row reads lane (i - N) & 15)
 template <int kCtrl>
@@ -262,9 +263,6 @@ __device__ __forceinline__ void jacobiRotation(double al, double be, double ga, 
   c = x * rx;
   s = copysign(0.5 * g2 * rh * rx, d * g2);
 }
-// row length of the LDS images: the column length rounded up to the lane-group size (the tail is kept zero, so the
-// register path needs no predication), odd so that the columns of a round start on different banks
-__host__ __device__ inline int jacobiLd(int n) { return ((n + 15) & ~15) | 1; }
 // Lanes per column pair: 16 (one DPP row).  A tournament round is one dependent chain per wave (LDS read -> inner
 // products -> reduce -> rotation -> LDS write -> barrier) and what it costs is that chain's instruction count, not VALU
 // throughput: 8 lanes per pair (twice the per-lane column length) measured 11 % slower at n = 105.
@@ -427,15 +425,7 @@ __device__ void jacobiEig(double* G, double* Q, int n, int* flag, double* lds) {
   }
   __syncthreads();
 }
-constexpr size_t kJacobiLdsLimit = 158 * 1024 - sizeof(JacobiShared);   // 160 KB per workgroup less the static __shared__ scalars
-static size_t jacobiLdsBytes(int n) {
-  const size_t b = (size_t)2 * n * jacobiLd(n) * sizeof(double);
-  return b <= kJacobiLdsLimit ? b : 0;
-}
-static size_t jacobiLdsBytesGOnly(int n) {
-  const size_t b = (size_t)n * jacobiLd(n) * sizeof(double);
-  return b <= kJacobiLdsLimit && n <= kJacobiRegLen ? b : 0;
-}
+// (the LDS the launches ask for -- jacobiLdsBytes, jacobiLdsBytesGOnly, margCholLdsBytes, symEigLdsBytes: marg_plan.hpp)
 
 // ---------------------------------------------------------------- M2: landmark part (:557-619)
 // per landmark: p_b from diag(V), V' = V/(p_b p_b^T), (V')^+ by 3x3 eigendecomposition with tolerance
@@ -523,10 +513,6 @@ __global__ __launch_bounds__(64) void k_marg_lm_update(MargDev md) {
   }
 }
 
-static size_t margCholLdsBytes(int n) {
-  const size_t nT = ((size_t)n + 15) / 16, NP = 16 * nT;
-  return (NP * (NP + 1) + nT * 16 * kPanelLd + NP) * sizeof(double);
-}
 // ---------------------------------------------------------------- M2 dense part (:622-667) + M3 (:725-758)
 // Single workgroup.  keep/marg index lists select rows of U (m x m).  Outputs the reduced Hk (nk x nk), bk.
 struct DenseArgs {
@@ -1037,8 +1023,6 @@ __global__ __launch_bounds__(1024) void k_marg_final_dc(FinalArgs a, int skipIfD
     }
   }
 }
-constexpr int kSymEigMaxN = symeig::kMaxN;
-static size_t symEigLdsBytes(int n) { return (size_t)n * (n | 1) * sizeof(double); }
 
 // inspection hook (svin_ba_debug_sym_eig): the solver on an arbitrary symmetric matrix
 __global__ __launch_bounds__(1024) void k_sym_eig_debug(int n, const double* A, double* lam, double* Xout, double* scratch, int* okOut) {
@@ -1217,30 +1201,77 @@ __global__ __launch_bounds__(1024) void k_marg_final(FinalArgs a, int useLds, in
   }
 }
 
-// ================================================================ host: policy + job assembly
-namespace {
-template <class T>
-bool contains(const std::vector<T>& v, const T& q) {
-  for (const T& e : v) if (e == q) return true;
-  return false;
-}
-}  // namespace
-
+// ================================================================ host: policy, job tables, reservation, issue, graph update
 static double nowSec() {
   return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
-int Window::applyMarginalizationStrategy(size_t numKeyframes, size_t numImuFrames, std::vector<uint64_t>& removed) {
-  quiesce();
-  const bool timing = optOn(kOptMargTiming);
-  const double tm0 = nowSec();
-  double tm1 = tm0, tm2 = tm0, tm3 = tm0, tm4 = tm0;
-  // ---- policy (Estimator.cpp:495-770), operating on the host graph only
-  auto rit = states_.rbegin();
-  for (size_t k = 0; k < numImuFrames; k++) {
-    rit++;
-    if (rit == states_.rend()) return 1;
+// What the policy (Estimator.cpp:509-770) takes out of the host graph in one call: the residuals to linearise, copied out of the
+// graph as they are removed, and the blocks they connect
+struct Window::MargSelection {
+  struct JobObs { Observation o; uint64_t lmId, extId; double S[3]; bool lmFixed; };   // S: the square-root information of a general observation (o.general)
+  bool hadPrior = false;
+  bool deviceJob = false;       // the observation tables come out of the device-resident CSR (no JobObs, no lmLin)
+  bool reDoFixation = false;    // the pose prior of a leaving frame went with it (:624-629)
+  std::vector<Factor> factors;
+  std::vector<JobObs> obs;
+  int nObs = 0;                 // linearised reprojection residuals (both forms of the job)
+  int m = 0;                    // rows of the dense part
+  std::vector<uint64_t> toMarginalize, margLandmarks;
+  std::vector<PriorBlockHost> dense;   // connected dense blocks in insertion order (after the blocks of the old prior) ...
+  std::vector<uint64_t> lmOrder;       // ... and landmarks
+  std::unordered_map<uint64_t, std::vector<double>> lmLin;   // linearisation points of marginalised landmarks
+  std::vector<unsigned char> poseClass;                      // kMargRemove | kMargLin | kMargNew per pose handle
+  std::vector<PriorBlockHost> kept;    // the blocks of the new prior (filled with the job tables)
+};
+
+// Everything the launches of one job read.  It is assembled on the caller's thread and then only read: by launchMarginalization,
+// which may run on the handle's enqueue thread after applyMarginalizationStrategy has returned, so the closure handed to
+// enqueueAsync holds the job by shared_ptr and nothing else.
+struct Window::MargJob {
+  MargDims dims{};
+  MargPlan plan{};
+  int nSb = 0, nImu = 0;
+  bool deviceJob = false, lossOn = false, generalOn = false, keepPre = false;
+  int margEig = 0;   // SVIN_MARG_EIG, read on the caller's thread
+  hipStream_t stream = nullptr;
+  // host tables at the linearisation points
+  std::vector<double> hPose, hExt, hSb, hLm, hUv, hW, hS, hImuM, lossTab;
+  std::vector<int> oPose, oExt, oSb, hObsLm, hLmPtr, idxLists, jobPoseSlot, jobExtSlot;
+  std::vector<uint32_t> hIdx, hImuT;
+  std::vector<DevFactor> hFac;
+  std::vector<DevImu> hImu;
+  std::vector<unsigned char> poseClass;
+  std::vector<CameraModel> cams;
+  std::vector<StagedCopy> pending;
+  // (H | b0) of the previous prior: bHk is only ever re-allocated when it has to grow, and then the old allocation is kept alive
+  // here until the job has copied out of it
+  const double* oldPrior = nullptr;
+  DevBuf<double> oldPriorKeep;
+  // read by the SVIN_MARG_KEEP_PRE inspection
+  std::vector<uint64_t> lmOrder, toMarginalize;
+  std::vector<PriorBlockHost> dense;
+
+  // Queues the upload of a table.  THE RULE: a pointer handed to flushStaged points into storage this job owns -- `host` is one
+  // of the vectors above, complete when it is staged and never touched again (a vector's storage does not move with the job).
+  template <class B, class V>
+  void stage(B& buf, const V& host) {
+    using T = typename V::value_type;
+    buf.reserve(std::max<size_t>(host.size() + 16 / sizeof(T) + 1, 1));   // room for the 16-byte rounding of the copy
+    if (!host.empty()) pending.push_back({host.data(), sizeof(T) * host.size(), buf.p});
   }
+};
+
+MargFrames Window::margFrames(size_t numKeyframes, size_t numImuFrames) const {
+  std::vector<uint64_t> ids;
+  std::vector<char> isKeyframe;
+  ids.reserve(states_.size()); isKeyframe.reserve(states_.size());
+  for (const auto& kv : states_) { ids.push_back(kv.second.id); isKeyframe.push_back(kv.second.isKeyframe ? 1 : 0); }
+  return selectMargFrames(ids, isKeyframe, numKeyframes, numImuFrames);
+}
+
+// ---- step 1: what the kernels cannot marginalise is refused before anything is modified.  false: lastError() says why
+bool Window::margAccepts(const MargFrames& frames) const {
   // A pose on a reduced manifold (Map::resetParameterization, a Map-level feature okvis::Estimator never uses: Estimator.cpp:801 is
   // commented out): the prior's columns would have to be the 3 / 4 / 2 minimal ones (MarginalizationError.cpp:147-160 takes
   // minimalDimension()).  Not built; refuse before anything is modified.
@@ -1253,32 +1284,31 @@ int Window::applyMarginalizationStrategy(size_t numKeyframes, size_t numImuFrame
   // A constant landmark is marginalised like any other (the policy loop of Estimator.cpp:671-766 never asks): its linearised
   // observations enter the job with the negative weight, so their landmark Jacobian is zero (MarginalizationError.cpp:156 gives a
   // fixed block zero columns, :343 / :367 skip it).  Landmark-sharded handles keep refusing it.
-  const bool refuseFixedLm = numFixedLandmarks_ > 0 && (world_ > 1 || rcclComm_ != nullptr);
-  if (numLandmarkPriors_ > 0 || refuseFixedLm) {
-    // Landmarks that carry a HomogeneousPointError stay out of the marginalisation: the reference's policy loop assumes
-    // every residual of a landmark is a ReprojectionError (Estimator.cpp:689-698) and never meets one, because Estimator
-    // adds none.  Observed from a frame that is about to leave, such a landmark cannot be handled: refuse before anything
-    // is modified.
-    std::vector<uint64_t> leaving;
-    size_t kept = 0;
-    for (auto r2 = rit; r2 != states_.rend(); ++r2) {
-      if (!r2->second.isKeyframe || kept >= numKeyframes) leaving.push_back(r2->second.id);
-      else kept++;
-    }
-    for (const auto& kv : landmarks_) {
-      if (kv.second.priors.empty() && !(refuseFixedLm && kv.second.fixed)) continue;
-      for (const Observation& o : kv.second.obs)
-        if (std::find(leaving.begin(), leaving.end(), o.poseId) != leaving.end()) {
-          lastError() = kv.second.priors.empty()
-                            ? "applyMarginalizationStrategy: a constant landmark of a landmark-sharded handle is observed from a frame that leaves the window"
-                            : "applyMarginalizationStrategy: a landmark with a HomogeneousPointError is observed from a frame that leaves the window";
-          return -1;
-        }
-    }
+  const bool refuseFixedLm = margRefusesFixedLandmarks();
+  if (numLandmarkPriors_ == 0 && !refuseFixedLm) return true;
+  // Landmarks that carry a HomogeneousPointError stay out of the marginalisation: the reference's policy loop assumes
+  // every residual of a landmark is a ReprojectionError (Estimator.cpp:689-698) and never meets one, because Estimator
+  // adds none.  Observed from a frame that is about to leave, such a landmark cannot be handled.
+  const std::vector<uint64_t>& leaving = frames.removeFrames;
+  for (const auto& kv : landmarks_) {
+    if (kv.second.priors.empty() && !(refuseFixedLm && kv.second.fixed)) continue;
+    for (const Observation& o : kv.second.obs)
+      if (std::find(leaving.begin(), leaving.end(), o.poseId) != leaving.end()) {
+        lastError() = kv.second.priors.empty()
+                          ? "applyMarginalizationStrategy: a constant landmark of a landmark-sharded handle is observed from a frame that leaves the window"
+                          : "applyMarginalizationStrategy: a landmark with a HomogeneousPointError is observed from a frame that leaves the window";
+        return false;
+      }
   }
-  // :509-514 the old prior leaves the graph; its content is re-used below
-  const bool hadPrior = hasPrior_;
-  if (hadPrior) {
+  return true;
+}
+
+// ---- step 2: the policy (Estimator.cpp:509-770), operating on the host graph only
+void Window::margApplyPolicy(const MargFrames& frames, MargSelection& sel, std::vector<uint64_t>& removed, bool timing) {
+  const bool refuseFixedLm = margRefusesFixedLandmarks();
+  // :509-514 the old prior leaves the graph; its content is re-used by the job
+  sel.hadPrior = hasPrior_;
+  if (sel.hadPrior) {
     for (const PriorBlockHost& pb : priorBlocks_)
       if (Block* b = findBlock(pb.id)) {
         for (size_t i = 0; i < b->residuals.size(); ++i)
@@ -1286,30 +1316,17 @@ int Window::applyMarginalizationStrategy(size_t numKeyframes, size_t numImuFrame
       }
     priorResId_ = 0;
   }
-  std::vector<uint64_t> removeFrames, removeAllButPose, allLinearizedFrames;
-  size_t countedKeyframes = 0;
-  while (rit != states_.rend()) {
-    if (!rit->second.isKeyframe || countedKeyframes >= numKeyframes) removeFrames.push_back(rit->second.id);
-    else countedKeyframes++;
-    removeAllButPose.push_back(rit->second.id);
-    allLinearizedFrames.push_back(rit->second.id);
-    ++rit;
-  }
-  // the job: residuals to linearise (copied out of the graph as they are removed) and blocks to marginalise
-  struct JobObs { Observation o; uint64_t lmId, extId; double S[3]; bool lmFixed; };   // S: the square-root information of a general observation (o.general)
-  std::vector<Factor> jobFactors;
-  std::vector<JobObs> jobObs;
-  std::vector<uint64_t> toMarginalize;
-  // connected dense blocks in insertion order (after the blocks of the old prior) and landmarks
-  std::vector<PriorBlockHost> dense = priorBlocks_;
-  std::vector<uint64_t> lmOrder;
-  std::unordered_map<uint64_t, std::vector<double>> lmLin;  // linearisation points of marginalised landmarks
+  const std::vector<uint64_t>&removeFrames = frames.removeFrames, &removeAllButPose = frames.removeAllButPose,
+                             &allLinearizedFrames = frames.allLinearizedFrames;
+  std::vector<uint64_t>& toMarginalize = sel.toMarginalize;
+  std::vector<PriorBlockHost>& dense = sel.dense;
+  dense = priorBlocks_;
   // (one flag per block handle: the landmark pass asks "is it connected already" twice per linearised residual)
   std::vector<char> connected[3];
   for (int k = 0; k < 3; ++k) connected[k].assign(std::max(nextBlockH_[k], 1), 0);
   for (const PriorBlockHost& pb : dense)
     if (const Block* b = findBlock(pb.id)) connected[b->kind][b->handle] = 1;
-  auto connectBlock = [&](const Block& b) {
+  auto connect = [&](const Block& b) {
     if (connected[b.kind][b.handle]) return;
     connected[b.kind][b.handle] = 1;
     PriorBlockHost pb;
@@ -1318,21 +1335,11 @@ int Window::applyMarginalizationStrategy(size_t numKeyframes, size_t numImuFrame
     std::memcpy(pb.lin, b.x, sizeof(double) * pb.dim);
     dense.push_back(pb);
   };
-  auto connectDense = [&](uint64_t id) {
-    for (const PriorBlockHost& pb : dense) if (pb.id == id) return;
-    const Block& b = blocks_.at(id);
-    connected[b.kind][b.handle] = 1;
-    PriorBlockHost pb;
-    pb.id = id; pb.kind = b.kind; pb.dim = (b.kind == B_SB) ? 9 : 7;
-    pb.mdim = b.fixed ? 0 : ((b.kind == B_SB) ? 9 : 6);
-    std::memcpy(pb.lin, b.x, sizeof(double) * pb.dim);
-    dense.push_back(pb);
-  };
   auto addFactorToJob = [&](uint64_t rid) {
     auto it = factors_.find(rid);
     if (it == factors_.end()) return;
-    for (int b = 0; b < it->second.nblk; ++b) connectDense(it->second.blocks[b]);
-    jobFactors.push_back(it->second);
+    for (int b = 0; b < it->second.nblk; ++b) connect(blocks_.at(it->second.blocks[b]));
+    sel.factors.push_back(it->second);
     removeFactor(rid);
   };
   auto isReproj = [&](uint64_t rid) { return obsRes2Lm_.count(rid); };
@@ -1355,16 +1362,13 @@ int Window::applyMarginalizationStrategy(size_t numKeyframes, size_t numImuFrame
         if (!isReproj(rid) && !isPrior(rid)) addFactorToJob(rid);
     }
   }
-  bool reDoFixation = false;
   bool landmarksDone = false;
   // The job's observation tables come out of the device-resident CSR when it mirrors the graph as it is now (nothing was
-  // added or removed since the last solve); otherwise they are assembled here from the records the policy removes.
+  // added or removed since the last solve); otherwise they are assembled from the records the policy removes.
   const bool deviceJob = residentValid_ && residentUsed_ && addLog_.empty() && remLog_.empty() && setLog_.empty() && constLog_.empty() && res_.N == (int)numObs_;
+  sel.deviceJob = deviceJob;
   ++pathCounters_[deviceJob ? 2 : 3];
   if (!deviceJob) syncLandmarks();   // the linearisation points of the marginalised landmarks are read from the host graph
-  std::vector<unsigned char> poseClass;
-  std::vector<uint64_t> margLandmarks;
-  int nJobObs = 0;
   for (uint64_t fid : removeFrames) {  // :607-770
     auto it = states_.find(fid);
     it->second.pose.exists = false;
@@ -1375,7 +1379,7 @@ int Window::applyMarginalizationStrategy(size_t numKeyframes, size_t numImuFrame
         auto fit = factors_.find(rid);
         if (fit != factors_.end() && fit->second.kind == F_POSE_PRIOR) {  // :624-629
           removeFactor(rid);
-          reDoFixation = true;
+          sel.reDoFixation = true;
           continue;
         }
         if (!isReproj(rid) && fit != factors_.end()) addFactorToJob(rid);
@@ -1403,7 +1407,7 @@ int Window::applyMarginalizationStrategy(size_t numKeyframes, size_t numImuFrame
       const double tl0 = nowSec();
       const size_t obs0 = numObs_;
       const uint64_t currentKfId = allLinearizedFrames.at(0);
-      std::vector<unsigned char>& cls = poseClass;
+      std::vector<unsigned char>& cls = sel.poseClass;
       cls.assign(std::max(nextBlockH_[B_POSE], 1), 0);
       for (uint64_t f : removeFrames) cls[blocks_.at(f).handle] |= kMargRemove;
       for (uint64_t f : allLinearizedFrames) cls[blocks_.at(f).handle] |= kMargLin;
@@ -1427,7 +1431,7 @@ int Window::applyMarginalizationStrategy(size_t numKeyframes, size_t numImuFrame
       const double tl1 = nowSec();
       for (int h : cand) {
         Landmark& lm = *lmByHandle_[h];
-        if (!lm.priors.empty() || (refuseFixedLm && lm.fixed)) continue;   // see the guard at the top
+        if (!lm.priors.empty() || (refuseFixedLm && lm.fixed)) continue;   // see margAccepts
         if (lm.obs.empty()) {
           removed.push_back(lm.id);
           eraseLandmark(lm);
@@ -1453,19 +1457,19 @@ int Window::applyMarginalizationStrategy(size_t numKeyframes, size_t numImuFrame
           }
           if (action == 2) {
             errorTermAdded = true;
-            connectBlock(*blockByHandle_[B_POSE][ob.poseH]);
-            connectBlock(*blockByHandle_[B_EXT][ob.extH]);
-            if (lmOrder.empty() || lmOrder.back() != lm.id) {
-              lmOrder.push_back(lm.id);
-              if (!deviceJob) lmLin[lm.id].assign(lm.hp, lm.hp + 4);
+            connect(*blockByHandle_[B_POSE][ob.poseH]);
+            connect(*blockByHandle_[B_EXT][ob.extH]);
+            if (sel.lmOrder.empty() || sel.lmOrder.back() != lm.id) {
+              sel.lmOrder.push_back(lm.id);
+              if (!deviceJob) sel.lmLin[lm.id].assign(lm.hp, lm.hp + 4);
             }
             if (!deviceJob) {
-              JobObs jo{ob, lm.id, extIdOf(ob), {0.0, 0.0, 0.0}, lm.fixed};
+              MargSelection::JobObs jo{ob, lm.id, extIdOf(ob), {0.0, 0.0, 0.0}, lm.fixed};
               if (const ObsInformation* gi = generalInformation(ob)) { jo.S[0] = gi->S[0]; jo.S[1] = gi->S[1]; jo.S[2] = gi->S[2]; }   // (detachObsRecord drops the entry)
               else jo.o.general = 0;
-              jobObs.push_back(jo);
+              sel.obs.push_back(jo);
             }
-            ++nJobObs;
+            ++sel.nObs;
           }
           detachObsRecord(lm, ob);
         }
@@ -1478,7 +1482,7 @@ int Window::applyMarginalizationStrategy(size_t numKeyframes, size_t numImuFrame
           eraseLandmark(lm);
         } else if (marginalize && errorTermAdded) {
           toMarginalize.push_back(lm.id);
-          margLandmarks.push_back(lm.id);
+          sel.margLandmarks.push_back(lm.id);
           removed.push_back(lm.id);
           eraseLandmark(lm);
         }
@@ -1489,418 +1493,301 @@ int Window::applyMarginalizationStrategy(size_t numKeyframes, size_t numImuFrame
     }
     states_.erase(it->second.id);
   }
-
-  // ---- device job (M1-M3)
-  tm1 = nowSec();
   std::sort(removed.begin(), removed.end());   // PointMap order (the reference erases while walking its std::map)
-  std::sort(margLandmarks.begin(), margLandmarks.end());
+  std::sort(sel.margLandmarks.begin(), sel.margLandmarks.end());
   obsCachePose_ = 0;
   std::sort(toMarginalize.begin(), toMarginalize.end());
   toMarginalize.erase(std::unique(toMarginalize.begin(), toMarginalize.end()), toMarginalize.end());
-  bool anyWork = !toMarginalize.empty();
   // ordering of the dense part
-  int m = 0;
-  for (PriorBlockHost& pb : dense) { pb.ord = m; m += pb.mdim; }
-  const int Lm = (int)lmOrder.size();
-  std::vector<double> Hk, bk;
-  std::vector<PriorBlockHost> kept;
-  if (m > 0 || Lm > 0) {
-    hipStream_t s = stream_;
-    // sub-problem tables at the linearisation points
-    std::vector<uint64_t> jPose, jExt, jSb;
-    std::unordered_map<uint64_t, int> sPose, sExt, sSb, sLm;
-    std::vector<double> hPose, hExt, hSb, hLm;
-    std::vector<int> oPose, oExt, oSb;
-    for (const PriorBlockHost& pb : dense) {
-      const int off = pb.mdim > 0 ? pb.ord : -1;
-      if (pb.kind == B_POSE) { sPose[pb.id] = (int)jPose.size(); jPose.push_back(pb.id); hPose.insert(hPose.end(), pb.lin, pb.lin + 7); oPose.push_back(off); }
-      else if (pb.kind == B_EXT) { sExt[pb.id] = (int)jExt.size(); jExt.push_back(pb.id); hExt.insert(hExt.end(), pb.lin, pb.lin + 7); oExt.push_back(off); }
-      else { sSb[pb.id] = (int)jSb.size(); jSb.push_back(pb.id); hSb.insert(hSb.end(), pb.lin, pb.lin + 9); oSb.push_back(off); }
-    }
-    if (hExt.empty()) { hExt.assign(7, 0.0); hExt[6] = 1.0; oExt.push_back(-1); }
-    if (hPose.empty()) { hPose.assign(7, 0.0); hPose[6] = 1.0; oPose.push_back(-1); }
-    if (!deviceJob)
-      for (int l = 0; l < Lm; ++l) {
-        sLm[lmOrder[l]] = l;
-        const std::vector<double>& hp = lmLin.at(lmOrder[l]);
-        hLm.insert(hLm.end(), hp.begin(), hp.end());
-      }
-    // observations sorted landmark-major (the policy hands them over landmark by landmark already)
-    if (!deviceJob)
-      std::stable_sort(jobObs.begin(), jobObs.end(), [&](const JobObs& a, const JobObs& b) { return sLm.at(a.lmId) < sLm.at(b.lmId); });
-    const int N = nJobObs;
-    std::vector<double> hUv, hW;
-    std::vector<uint32_t> hIdx;
-    std::vector<int> hObsLm, hLmPtr(deviceJob ? 0 : Lm + 1, 0);
-    bool anyExtVar = false;
-    // device job: the tables below are written by k_window_marg_gather from the resident CSR; it needs to know the class of
-    // every pose handle and where a block sits in the job's tables
-    std::vector<int> jobPoseSlot, jobExtSlot;
-    if (deviceJob) {
-      jobPoseSlot.assign(std::max(nextBlockH_[B_POSE], 1), -1); jobExtSlot.assign(std::max(nextBlockH_[B_EXT], 1), -1);
-      for (const auto& kv : sPose) jobPoseSlot[blocks_.at(kv.first).handle] = kv.second;
-      for (const auto& kv : sExt) jobExtSlot[blocks_.at(kv.first).handle] = kv.second;
-    }
-    // DeviceProblem::obsS of the job (3 N, component-major): only when one of its observations has a general information matrix
-    bool generalOn = false;
-    for (const JobObs& jo : jobObs) generalOn = generalOn || jo.o.general;
-    std::vector<double> hS(generalOn ? 3 * jobObs.size() : 0);
-    for (const JobObs& jo : jobObs) {
-      hUv.push_back(jo.o.uv[0]); hUv.push_back(jo.o.uv[1]);
-      const double w = obsWeight(jo.o.size);
-      hW.push_back(jo.lmFixed ? -w : w);   // (the sign Window::pack() and the resident CSR give a constant landmark's observations)
-      if (generalOn) {
-        const size_t o = hW.size() - 1, n = jobObs.size();
-        hS[o] = jo.o.general ? jo.S[0] : w; hS[n + o] = jo.o.general ? jo.S[1] : 0.0; hS[2 * n + o] = jo.o.general ? jo.S[2] : w;
-      }
-      const int es = sExt.count(jo.extId) ? sExt.at(jo.extId) : 0;
-      hIdx.push_back(packObs(sPose.at(jo.o.poseId), es, jo.o.cam, jo.o.loss));
-      hObsLm.push_back(sLm.at(jo.lmId));
-      hLmPtr[sLm.at(jo.lmId) + 1]++;
-    }
-    if (!deviceJob) for (int l = 0; l < Lm; ++l) hLmPtr[l + 1] += hLmPtr[l];
-    for (int o : oExt) if (o >= 0) anyExtVar = true;
-    // factors
-    std::vector<DevFactor> hFac;
-    std::vector<DevImu> hImu;
-    std::vector<uint32_t> hImuT;
-    std::vector<double> hImuM;
-    for (Factor& f : jobFactors) {
-      DevFactor df;
-      std::memset(&df, 0, sizeof(df));
-      df.kind = f.kind; df.nblk = f.nblk; df.m = f.m; df.imuIndex = -1;
-      for (int b = 0; b < f.nblk; ++b) {
-        const uint64_t id = f.blocks[b];
-        if (sPose.count(id)) { df.blkKind[b] = B_POSE; df.blkSlot[b] = sPose.at(id); }
-        else if (sExt.count(id)) { df.blkKind[b] = B_EXT; df.blkSlot[b] = sExt.at(id); }
-        else { df.blkKind[b] = B_SB; df.blkSlot[b] = sSb.at(id); }
-      }
-      df.lossKind = f.lossKind; df.lossScale = f.lossScale;
-      std::memcpy(df.meas, f.meas, sizeof(df.meas));
-      std::memcpy(df.aux, f.aux, sizeof(df.aux));
-      std::memcpy(df.sqrtInfo, f.sqrtInfo, sizeof(df.sqrtInfo));
-      if (f.kind == F_IMU) {
-        df.imuIndex = (int)hImu.size();
-        f.imu.sampleStart = (int)(hImuT.size() / 2);
-        f.imu.sampleCount = (int)(f.imuT.size() / 2);
-        hImu.push_back(f.imu);
-        hImuT.insert(hImuT.end(), f.imuT.begin(), f.imuT.end());
-        hImuM.insert(hImuM.end(), f.imuMeas.begin(), f.imuMeas.end());
-      }
-      hFac.push_back(df);
-    }
-    const int F = (int)hFac.size();
-    const bool lossOn = nLoss_ > 1;   // observations with a loss other than CauchyLoss(1): the job evaluates them through the loss table
-    // The job is asynchronous (nothing below waits for the device): every table travels in the one pinned block of
-    // flushStaged, which waits for the previous block's DMA itself.
-    tm2 = nowSec();
-    double* dbgScal = nullptr;
-    // persistent job buffers (grow-only): hipMalloc / hipFree per call used to cost more than the algebra
-    MargBuffers& mb = margBuf_;
-    auto &bPose = mb.bPose, &bExt = mb.bExt, &bSb = mb.bSb, &bLm = mb.bLm, &bUv = mb.bUv, &bW = mb.bW, &bLin = mb.bLin,
-         &bU = mb.bU, &bW2 = mb.bW2, &bV = mb.bV, &bVec = mb.bVec, &bScratch = mb.bScratch;
-    auto &bOP = mb.bOP, &bOE = mb.bOE, &bOS = mb.bOS, &bLmPtr = mb.bLmPtr, &bObsLm = mb.bObsLm, &bIdxList = mb.bIdxList,
-         &bFlag = mb.bFlag;
-    auto &bIdx = mb.bIdx, &bImuT = mb.bImuT;
-    auto& bFac = mb.bFac;
-    auto& bFacLin = mb.bFacLin;
-    auto& bImu = mb.bImu;
-    auto &bImuM = mb.bImuM, &bPartial = mb.bPartial;
-    auto& bScal = mb.bScal;
-    // M2 dense part: which rows stay (the new prior) and which are marginalised
-    std::vector<int> keepIdx, margIdx;
-    for (const PriorBlockHost& pb : dense) {
-      const bool marg = std::binary_search(toMarginalize.begin(), toMarginalize.end(), pb.id);
-      for (int k = 0; k < pb.mdim; ++k) (marg ? margIdx : keepIdx).push_back(pb.ord + k);
-      if (!marg) kept.push_back(pb);
-    }
-    const int nk = (int)keepIdx.size(), nm = (int)margIdx.size();
-    std::vector<int> idxLists(keepIdx);
-    idxLists.insert(idxLists.end(), margIdx.begin(), margIdx.end());
-    const size_t mm = std::max(m, 1), L3 = std::max(3 * Lm, 1);
-    bU.reserve(mm * mm + 2); bW2.reserve(mm * L3 + 2); bV.reserve((size_t)9 * std::max(Lm, 1) + 2); bVec.reserve(mm + 2 * L3 + 16);
-    auto pendingPtr = std::make_shared<std::vector<StagedCopy>>();
-    std::vector<StagedCopy>& pending = *pendingPtr;
-    {   // the job's tables: one pinned block, one DMA, one scatter kernel (17 pageable copies cost ~100 us of enqueueing)
-      // U, W, V and the vectors start from zero: clears riding in the same launch
-      pending.push_back({nullptr, sizeof(double) * mm * mm, bU.p});
-      pending.push_back({nullptr, sizeof(double) * mm * L3, bW2.p});
-      pending.push_back({nullptr, sizeof(double) * 9 * (size_t)std::max(Lm, 1), bV.p});
-      pending.push_back({nullptr, sizeof(double) * (mm + 2 * L3 + 14), bVec.p});
-      auto stage = [&](auto& buf, const auto& host) {
-        using T = typename std::decay_t<decltype(host)>::value_type;
-        buf.reserve(std::max<size_t>(host.size() + 16 / sizeof(T) + 1, 1));   // room for the 16-byte rounding of the copy
-        if (!host.empty()) pending.push_back({host.data(), sizeof(T) * host.size(), buf.p});
-      };
-      stage(bPose, hPose); stage(bExt, hExt); stage(bSb, hSb); stage(bLm, hLm); stage(bUv, hUv); stage(bW, hW);
-      if (generalOn) stage(mb.bS, hS);
-      stage(bOP, oPose); stage(bOE, oExt); stage(bOS, oSb); stage(bLmPtr, hLmPtr); stage(bObsLm, hObsLm); stage(bIdx, hIdx);
-      stage(bFac, hFac); stage(bImu, hImu); stage(bImuT, hImuT); stage(bImuM, hImuM);
-      stage(dCams_, cameras_);
-      if (lossOn) stage(dLossTab_, lossTab_);   // (a fixed-size member: appended to, never reallocated or rewritten)
-      stage(bIdxList, idxLists);
-      if (deviceJob) {
-        stage(res_.poseClass, poseClass); stage(res_.poseSlotOfH, jobPoseSlot); stage(res_.extSlotOfH, jobExtSlot);
-        bLm.reserve(std::max<size_t>((size_t)4 * Lm, 1)); bUv.reserve(std::max<size_t>((size_t)2 * N, 1)); bW.reserve(std::max<size_t>(N, 1));
-        bLmPtr.reserve((size_t)Lm + 1); bObsLm.reserve(std::max<size_t>(N, 1)); bIdx.reserve(std::max<size_t>(N, 1));
-        res_.margScratch.reserve(std::max<size_t>((size_t)2 * res_.L, 1));
-      }
-    }
-    // ---- everything the launches below need is fixed from here on; no allocation and no host table is touched after this point,
-    // so the launches themselves (a DMA, the scatter and 6-13 kernels: 25-50 us of API calls) can be issued by the handle's
-    // enqueue thread while this call goes on with the graph update and returns (Window::quiesce joins it before the stream, the
-    // job buffers or the prior are touched again)
-    bLin.reserve(std::max<size_t>((size_t)32 * N, 1));
-    bFacLin.reserve(std::max(F, 1));
-    bPartial.reserve((size_t)16 * 4096);
-    bScal.reserve(1);
-    bFlag.reserve(8);
-    int ordk = 0;
-    for (PriorBlockHost& pb : kept) { pb.ord = ordk; ordk += pb.mdim; }
-    Hk.assign((size_t)nk * nk, 0.0);
-    bk.assign(nk, 0.0);
-    auto &bHk = mb.bHk, &bOut = mb.bOut;
-    const int oldPriorM = (hadPrior && priorM_ > 0) ? priorM_ : 0;
-    const double* oldPrior = mb.bHk.p;   // (H | b0) of the previous prior: bHk is only ever re-allocated below when it has to grow ...
-    DevBuf<double> oldPriorKeep;         // ... and then the old allocation is kept alive until the job has copied out of it
-    if (std::max<size_t>((size_t)nk * nk + nk, 1) > bHk.cap && oldPriorM > 0) { std::swap(oldPriorKeep.p, bHk.p); std::swap(oldPriorKeep.cap, bHk.cap); }
-    bHk.reserve(std::max<size_t>((size_t)nk * nk + nk, 1));
-    if (nk > 0 && nm > 0) bScratch.reserve((size_t)2 * nm * nm + (size_t)nk * nm + 2 * nm + 16);
-    const size_t n2k = (size_t)nk * nk;
-    if (nk > 0) bOut.reserve(5 * n2k + 4 * nk + 16);
-    if (nk > 0) priorHostValid_ = false;  // results stay on the device (solver reads Ht / bp / c0 in place); getPrior() fetches
-    const int nPoseJ = (int)(hPose.size() / 7), nExtJ = (int)(hExt.size() / 7), nSbJ = (int)jSb.size(), nImuJ = (int)hImu.size();
-    const int nCamJ = (int)cameras_.size();
-    const bool keepPre = optOn(kOptMargKeepPre);
-    const int margEig = debugOption(kOptMargEig);   // read HERE, on the caller's thread: the job may be issued by the enqueue thread
-    // the host tables the staged block is filled from must outlive this call when the job is issued by the enqueue thread
-    struct JobTables {
-      std::vector<double> hPose, hExt, hSb, hLm, hUv, hW, hS, hImuM;
-      std::vector<int> oPose, oExt, oSb, hObsLm, hLmPtr, idxLists, jobPoseSlot, jobExtSlot;
-      std::vector<uint32_t> hIdx, hImuT;
-      std::vector<DevFactor> hFac;
-      std::vector<DevImu> hImu;
-      std::vector<unsigned char> poseClass;
-      std::vector<CameraModel> cams;
-      DevBuf<double> oldPriorKeep;
-    };
-    auto tables = std::make_shared<JobTables>();
-    const bool syncJob = optOn(kOptMargSyncEnqueue);   // A/B switch: issue the launches from this thread
-    const bool runInline = timing || keepPre || syncJob;
-    double** dbgScalPtr = runInline ? &dbgScal : nullptr;
-    // (explicit captures: the job buffers are reached through `this` -- a by-value capture of the DevBuf aliases above would copy,
-    // and later free, the buffers themselves; lmOrder / dense / toMarginalize are only read by the inline inspection path)
-    auto launchJob = [this, tables, pendingPtr, lossOn, generalOn, N, Lm, m, F, nk, nm, mm, L3, n2k, oldPriorM, oldPrior, anyExtVar, deviceJob, nPoseJ, nExtJ,
-                      nSbJ, nImuJ, nCamJ, keepPre, margEig, dbgScalPtr, s, &lmOrder, &dense, &toMarginalize]() {
-      MargBuffers& mb = margBuf_;
-      auto &bPose = mb.bPose, &bExt = mb.bExt, &bSb = mb.bSb, &bLm = mb.bLm, &bUv = mb.bUv, &bW = mb.bW, &bLin = mb.bLin,
-           &bU = mb.bU, &bW2 = mb.bW2, &bV = mb.bV, &bVec = mb.bVec, &bScratch = mb.bScratch;
-      auto &bOP = mb.bOP, &bOE = mb.bOE, &bOS = mb.bOS, &bLmPtr = mb.bLmPtr, &bObsLm = mb.bObsLm, &bIdxList = mb.bIdxList, &bFlag = mb.bFlag;
-      auto &bIdx = mb.bIdx, &bImuT = mb.bImuT;
-      auto& bFac = mb.bFac;
-      auto& bFacLin = mb.bFacLin;
-      auto& bImu = mb.bImu;
-      auto &bImuM = mb.bImuM, &bPartial = mb.bPartial;
-      auto& bScal = mb.bScal;
-      auto &bHk = mb.bHk, &bOut = mb.bOut;
-      flushStaged(*pendingPtr, s);
-      if (deviceJob && (N > 0 || Lm > 0)) {
-        MargGatherArgs ga;
-        std::memset(&ga, 0, sizeof(ga));
-        ga.L = res_.L; ga.H = res_.H; ga.expectN = N; ga.expectLm = Lm;
-        ga.lmPtr = res_.lmPtr[res_.cur].p; ga.handleOfSlot = res_.handleOfSlot[res_.cur].p;
-        ga.uv = res_.uv[res_.cur].p; ga.w = res_.w[res_.cur].p; ga.hnd = res_.hnd[res_.cur].p;
-        ga.lmHp = res_.lmHp.p;
-        ga.poseClass = res_.poseClass.p; ga.jobPoseSlot = res_.poseSlotOfH.p; ga.jobExtSlot = res_.extSlotOfH.p;
-        ga.jLmPtr = bLmPtr.p; ga.jObsLm = bObsLm.p; ga.jIdx = bIdx.p; ga.jUv = bUv.p; ga.jW = bW.p; ga.jLm = bLm.p;
-        ga.scratch = res_.margScratch.p;
-        ga.status = resStatusDev_;
-        launchWindowMargGather(ga, s);
-      }
-    {   // (the four clears rode in the scatter launch of the staged block) the two copies of the old prior land inside the cleared U / ba
-      // old prior content (H_, b0_) occupies the leading block: it is still on the device, exactly where k_marg_dense left it
-      if (oldPriorM > 0) {
-        FillJobs copies;
-        copies.n = 0;
-        addFill(copies, bU.p, oldPrior, (size_t)oldPriorM * oldPriorM, oldPriorM, m, oldPriorM);
-        addFill(copies, bVec.p, oldPrior + (size_t)oldPriorM * oldPriorM, oldPriorM);
-        launchFillJobs(copies, s);
-      }
-    }
-    DeviceProblem q;
-    std::memset(&q, 0, sizeof(q));
-    q.nPose = nPoseJ; q.nExt = nExtJ; q.nSb = nSbJ;
-    q.L = Lm; q.N = N; q.F = F; q.nImu = nImuJ; q.d = m; q.dC = 0; q.nCam = nCamJ;
-    q.anyExtVariable = anyExtVar ? 1 : 0;
-    q.ownsCamera = 1;
-    q.pose = bPose.p; q.ext = bExt.p; q.sb = bSb.p; q.lm = bLm.p;
-    q.poseC = bPose.p; q.extC = bExt.p; q.sbC = bSb.p; q.lmC = bLm.p;
-    q.poseOff = bOP.p; q.extOff = bOE.p; q.sbOff = bOS.p;
-    q.cams = dCams_.p;
-    q.lossTab = lossOn ? dLossTab_.p : nullptr;
-    q.obsS = generalOn ? mb.bS.p : nullptr;
-    q.lmPtr = bLmPtr.p; q.obsUv = bUv.p; q.obsW = bW.p; q.obsIdx = bIdx.p; q.obsLm = bObsLm.p;
-    q.rCur = bLin.p; q.JpCur = bLin.p + (size_t)2 * N; q.JlCur = bLin.p + (size_t)14 * N; q.JeCur = bLin.p + (size_t)20 * N;
-    q.factors = bFac.p; q.linCur = bFacLin.p; q.linCand = bFacLin.p;
-    q.imus = bImu.p; q.imuT = bImuT.p; q.imuMeas = bImuM.p;
-    q.scal = bScal.p; q.partial = bPartial.p;
-    MargDev md;
-    md.m = m; md.Lm = Lm; md.N = N; md.F = F;
-    md.U = bU.p; md.ba = bVec.p; md.W = bW2.p; md.V = bV.p; md.bb = bVec.p + mm;
-    double* vb = bVec.p + mm + L3;
-    // M1: evaluate at the linearisation points (each residual's loss corrector as in :283-330) and accumulate
-    if (N > 0) {
-      launchEvalReproj(q, false, true, s);
-      const dim3 camGrid(q.nPose + q.nExt, anyExtVar ? 1 + q.nCam : 1);
-      if (anyExtVar) {
-        launch(k_marg_accum_lm<true>, dim3((Lm + 63) / 64), dim3(64), 0, s, q, md);
-        launch(k_marg_accum_cam<true>, camGrid, dim3(64), 0, s, q, md);
-      } else {
-        launch(k_marg_accum_lm<false>, dim3((Lm + 63) / 64), dim3(64), 0, s, q, md);
-        launch(k_marg_accum_cam<false>, camGrid, dim3(64), 0, s, q, md);
-      }
-    }
-    if (F > 0) {
-      launchEvalFactors(q, false, s);
-      launch(k_marg_accum_factors, dim3(1), dim3(256), 0, s, q, md);
-    }
-    if (keepPre) {   // inspection: the system after M1 (svin_ba_get_marg_pre), before anything is eliminated
-      HIP_OK(hipStreamSynchronize(s));
-      margPre_.m = m; margPre_.Lm = Lm;
-      margPre_.U.assign((size_t)m * m, 0.0); margPre_.ba.assign(std::max(m, 1), 0.0);
-      margPre_.W.assign((size_t)m * 3 * Lm, 0.0); margPre_.V.assign((size_t)9 * Lm, 0.0); margPre_.bb.assign((size_t)3 * Lm, 0.0);
-      if (m > 0) {
-        HIP_OK(hipMemcpy(margPre_.U.data(), bU.p, sizeof(double) * m * m, hipMemcpyDeviceToHost));
-        HIP_OK(hipMemcpy(margPre_.ba.data(), bVec.p, sizeof(double) * m, hipMemcpyDeviceToHost));
-      }
-      if (Lm > 0) {
-        if (m > 0) HIP_OK(hipMemcpy(margPre_.W.data(), bW2.p, sizeof(double) * m * 3 * Lm, hipMemcpyDeviceToHost));
-        HIP_OK(hipMemcpy(margPre_.V.data(), bV.p, sizeof(double) * 9 * Lm, hipMemcpyDeviceToHost));
-        HIP_OK(hipMemcpy(margPre_.bb.data(), md.bb, sizeof(double) * 3 * Lm, hipMemcpyDeviceToHost));
-      }
-      margPre_.margRows.clear();
-      margPre_.denseIds.clear(); margPre_.denseOrd.clear(); margPre_.denseMdim.clear();
-      margPre_.lmIds.assign(lmOrder.begin(), lmOrder.end());
-      for (const PriorBlockHost& pb : dense) { margPre_.denseIds.push_back(pb.id); margPre_.denseOrd.push_back(pb.ord); margPre_.denseMdim.push_back(pb.mdim); }
-      for (const PriorBlockHost& pb : dense) {
-        const bool mg = std::binary_search(toMarginalize.begin(), toMarginalize.end(), pb.id);
-        for (int k = 0; k < pb.mdim; ++k) margPre_.margRows.push_back(mg ? 1 : 0);
-      }
-    }
-    // M2 landmark part
-    if (Lm > 0 && m > 0) {
-      launch(k_marg_lm_prepare, dim3((Lm + 127) / 128), dim3(128), 0, s, md, vb);
-      launch(k_marg_lm_apply, dim3(m), dim3(256), 0, s, md, (const double*)vb);
-      launch(k_marg_lm_update, dim3(((m + 15) / 16) * ((m + 15) / 16)), dim3(64), 0, s, md);
-    }
-    // M2 dense part
-    if (nk > 0) {
-      if (nm > 0) {
-        DenseArgs da;
-        da.m = m; da.nk = nk; da.nm = nm;
-        da.keep = bIdxList.p; da.marg = bIdxList.p + nk;
-        da.U = bU.p; da.ba = bVec.p;
-        da.Hk = bHk.p; da.bk = bHk.p + (size_t)nk * nk;
-        da.Vm = bScratch.p; da.Qm = bScratch.p + (size_t)nm * nm; da.tmp = bScratch.p + (size_t)2 * nm * nm;
-        da.flag = bFlag.p;
-        {
-          const size_t ldsEig = jacobiLdsBytes(nm);
-          const size_t ldsProd = sizeof(double) * ((size_t)2 * nk * nm + (size_t)nm * nm);   // W, Mu, N^T of the products
-          const bool prodLds = ldsProd <= kJacobiLdsLimit;
-          const size_t ldsTile = margCholLdsBytes(nm);   // the certified Cholesky route of the pseudo-inverse, on tiles
-          const bool tileChol = ldsTile <= kJacobiLdsLimit;
-          const size_t lds = std::max(std::max(ldsEig, prodLds ? ldsProd : (size_t)0), tileChol ? ldsTile : (size_t)0);
-          launch(k_marg_dense, dim3(1), dim3(1024), lds, s, da, ldsEig ? 1 : 0, prodLds ? 1 : 0, tileChol ? 1 : 0);
-        }
-      } else {
-        HIP_OK(hipMemcpyAsync(bHk.p, bU.p, sizeof(double) * (size_t)m * m, hipMemcpyDeviceToDevice, s));
-        HIP_OK(hipMemcpyAsync(bHk.p + (size_t)m * m, bVec.p, sizeof(double) * m, hipMemcpyDeviceToDevice, s));
-      }
-      // M3
-      const size_t n2 = n2k;
-      FinalArgs fa;
-      fa.n = nk; fa.H = bHk.p; fa.b0 = bHk.p + n2;
-      fa.G = bOut.p; fa.Q = bOut.p + n2; fa.J = bOut.p + 2 * n2; fa.Ht = bOut.p + 3 * n2;
-      fa.e0 = bOut.p + 4 * n2; fa.bp = bOut.p + 4 * n2 + nk; fa.scal = bOut.p + 4 * n2 + 2 * nk;
-      fa.tmp = bOut.p + 4 * n2 + 2 * nk + 8;
-      fa.flag = bFlag.p;
-      if (dbgScalPtr) *dbgScalPtr = fa.scal;
-      {
-        // Eigen-solver of the prior (k_marg_final's `useLds`):
-        //   4  A + delta I = R^T R, one-sided Jacobi on the rows of R, image in LDS (default: n <= 136)
-        //   6  the same with the image in global memory (larger priors)
-        //   1 / 0  the ONE fall-back: one-sided Jacobi on A itself with G and Q in LDS (n <= 96) / in global memory; taken
-        //          inside the kernel when a pivot of the factorisation is not positive, or with SVIN_MARG_EIG=jacobi
-        //          (the test that keeps the fall-back honest)
-        const bool want = margEig != 0;   // SVIN_MARG_EIG: 1 "direct", 2 "cholesky", 3 "jacobi" (options.hpp)
-        const bool forceFallback = margEig == 3;
-        const size_t ldsBoth = jacobiLdsBytes(nk), ldsOne = jacobiLdsBytesGOnly(nk);
-        const int mode = forceFallback ? (ldsBoth ? 1 : 0) : (ldsOne ? 4 : 6);
-        const size_t lds = (mode == 4) ? std::max(ldsOne, ldsBoth) : (mode == 1 ? ldsBoth : 0);
-        // default since round 5: the direct solve (tridiagonalisation + divide and conquer) for priors up to 128 unknowns, the
-        // Jacobi kernel behind it as the fall-back for a non-finite result (it returns at once when flag[4] says "done");
-        // SVIN_MARG_EIG=cholesky / jacobi select the round-2 solvers alone
-        // ... and ahead of both, for a prior of full numerical rank (every steady-state prior of the sliding windows), the Cholesky
-        // factor with its certificate that the rank rule drops nothing (k_marg_final_chol); SVIN_MARG_EIG=direct skips it
-        const bool wantDirect = margEig == 1;
-        const bool direct = (!want || wantDirect) && nk <= kSymEigMaxN;
-        const bool chol = !want && nk <= kSymEigMaxN;
-        if (chol) {
-          const size_t ldsC = margCholLdsBytes(nk);
-          launch(k_marg_final_chol, dim3(1), dim3(1024), ldsC, s, fa);
-        }
-        if (direct) {
-          const size_t ldsDc = symEigLdsBytes(nk);
-          launch(k_marg_final_dc, dim3(1), dim3(1024), ldsDc, s, fa, chol ? 1 : 0);
-        }
-        launch(k_marg_final, dim3(1), dim3(1024), lds, s, fa, mode, (mode == 4 && ldsBoth) ? 1 : 0, direct ? 1 : 0);
-      }
-    }
-    };
-    // move the host tables behind the staged pointers into the job (a vector's storage does not move with it)
-    tables->hPose = std::move(hPose); tables->hExt = std::move(hExt); tables->hSb = std::move(hSb); tables->hLm = std::move(hLm);
-    tables->hUv = std::move(hUv); tables->hW = std::move(hW); tables->hS = std::move(hS); tables->hImuM = std::move(hImuM);
-    tables->oPose = std::move(oPose); tables->oExt = std::move(oExt); tables->oSb = std::move(oSb); tables->hObsLm = std::move(hObsLm);
-    tables->hLmPtr = std::move(hLmPtr); tables->idxLists = std::move(idxLists); tables->jobPoseSlot = std::move(jobPoseSlot);
-    tables->jobExtSlot = std::move(jobExtSlot); tables->hIdx = std::move(hIdx); tables->hImuT = std::move(hImuT);
-    tables->hFac = std::move(hFac); tables->hImu = std::move(hImu); tables->poseClass = std::move(poseClass);
-    std::swap(tables->oldPriorKeep.p, oldPriorKeep.p); std::swap(tables->oldPriorKeep.cap, oldPriorKeep.cap);
-    if (runInline) launchJob();
-    else enqueueAsync(std::move(launchJob));
-    tm3 = nowSec();
-    if (timing) {
-      HIP_OK(hipStreamSynchronize(s));
-      int fl[4] = {0, 0, 0, 0};
-      HIP_OK(hipMemcpy(fl, bFlag.p, sizeof(fl), hipMemcpyDeviceToHost));
-      double sc3[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-      if (mb.bOut.p) HIP_OK(hipMemcpy(sc3, dbgScal, sizeof(sc3), hipMemcpyDeviceToHost));
-      std::printf("[marg] m %d Lm %d; Jacobi sweeps of the last eigen-solve: %d; eigenvalues <= tol: %d (min %.3e max %.3e)\n", m, Lm,
-                  fl[1], fl[2], sc3[1], sc3[2]);
-      if (mb.bOut.p && sc3[7] > 0 && fl[3] != -8) {   // the eigenvalues sit behind p[] in the kernel's scratch (flag[3] == -8: the certified
-                                                        // Cholesky route produced the prior -- tmp + n holds b0 / p there, no eigenvalues exist)
-        const int nn = (int)sc3[7];
-        std::vector<double> evh(nn);
-        HIP_OK(hipMemcpy(evh.data(), dbgScal + 8 + nn, sizeof(double) * nn, hipMemcpyDeviceToHost));
-        std::sort(evh.begin(), evh.end());
-        std::printf("[marg] smallest eigenvalues:");
-        for (int i = 0; i < std::min(nn, 8); ++i) std::printf(" %.3e", evh[i]);
-        std::printf("  (tol %.3e)\n", 2.220446049250313e-16 * nn * sc3[2]);
-      }
-      std::printf("[marg] k_marg_final: n %d, prepare %.0f us, eigen-solve %.0f us (two-phase: phase 1 %d us; %.0f shader clocks per us), "
-                  "J / e0 / J^T J %.0f us\n", (int)sc3[7], sc3[3] / 100.0, sc3[4] / 100.0, fl[3], sc3[6] / std::max(1.0, sc3[4] / 100.0),
-                  sc3[5] / 100.0);
-    }
-    (void)anyWork;
+  for (PriorBlockHost& pb : dense) { pb.ord = sel.m; sel.m += pb.mdim; }
+}
+
+// ---- step 3: the job's tables at the linearisation points, the host-assembled form (observations from sel.obs) or the
+// device-gathered one (k_window_marg_gather writes them from the resident CSR), its dimensions and its plan
+void Window::margBuildTables(MargSelection& sel, MargJob& job) {
+  const bool deviceJob = sel.deviceJob;
+  const int Lm = (int)sel.lmOrder.size();
+  std::unordered_map<uint64_t, int> sPose, sExt, sSb, sLm;
+  for (const PriorBlockHost& pb : sel.dense) {
+    const int off = pb.mdim > 0 ? pb.ord : -1;
+    if (pb.kind == B_POSE) { sPose[pb.id] = (int)job.oPose.size(); job.hPose.insert(job.hPose.end(), pb.lin, pb.lin + 7); job.oPose.push_back(off); }
+    else if (pb.kind == B_EXT) { sExt[pb.id] = (int)job.oExt.size(); job.hExt.insert(job.hExt.end(), pb.lin, pb.lin + 7); job.oExt.push_back(off); }
+    else { sSb[pb.id] = (int)job.oSb.size(); job.hSb.insert(job.hSb.end(), pb.lin, pb.lin + 9); job.oSb.push_back(off); }
   }
-  tm4 = nowSec();
-  // ---- graph update (:710-716, :788-811)
-  for (uint64_t id : toMarginalize)
-    if (!std::binary_search(margLandmarks.begin(), margLandmarks.end(), id)) removeBlock(id);
+  job.nSb = (int)job.oSb.size();
+  if (job.hExt.empty()) { job.hExt.assign(7, 0.0); job.hExt[6] = 1.0; job.oExt.push_back(-1); }
+  if (job.hPose.empty()) { job.hPose.assign(7, 0.0); job.hPose[6] = 1.0; job.oPose.push_back(-1); }
+  if (!deviceJob) {
+    for (int l = 0; l < Lm; ++l) {
+      sLm[sel.lmOrder[l]] = l;
+      const std::vector<double>& hp = sel.lmLin.at(sel.lmOrder[l]);
+      job.hLm.insert(job.hLm.end(), hp.begin(), hp.end());
+    }
+    // observations sorted landmark-major (the policy hands them over landmark by landmark already)
+    std::stable_sort(sel.obs.begin(), sel.obs.end(),
+                     [&](const MargSelection::JobObs& a, const MargSelection::JobObs& b) { return sLm.at(a.lmId) < sLm.at(b.lmId); });
+    job.hLmPtr.assign(Lm + 1, 0);
+  } else {
+    // device job: k_window_marg_gather needs to know the class of every pose handle and where a block sits in the job's tables
+    job.poseClass = std::move(sel.poseClass);
+    job.jobPoseSlot.assign(std::max(nextBlockH_[B_POSE], 1), -1); job.jobExtSlot.assign(std::max(nextBlockH_[B_EXT], 1), -1);
+    for (const auto& kv : sPose) job.jobPoseSlot[blocks_.at(kv.first).handle] = kv.second;
+    for (const auto& kv : sExt) job.jobExtSlot[blocks_.at(kv.first).handle] = kv.second;
+  }
+  // DeviceProblem::obsS of the job (3 N, component-major): only when one of its observations has a general information matrix
+  for (const MargSelection::JobObs& jo : sel.obs) job.generalOn = job.generalOn || jo.o.general;
+  job.hS.assign(job.generalOn ? 3 * sel.obs.size() : 0, 0.0);
+  for (const MargSelection::JobObs& jo : sel.obs) {
+    job.hUv.push_back(jo.o.uv[0]); job.hUv.push_back(jo.o.uv[1]);
+    const double w = obsWeight(jo.o.size);
+    job.hW.push_back(jo.lmFixed ? -w : w);   // (the sign Window::pack() and the resident CSR give a constant landmark's observations)
+    if (job.generalOn) {
+      const size_t o = job.hW.size() - 1, n = sel.obs.size();
+      job.hS[o] = jo.o.general ? jo.S[0] : w; job.hS[n + o] = jo.o.general ? jo.S[1] : 0.0; job.hS[2 * n + o] = jo.o.general ? jo.S[2] : w;
+    }
+    const int es = sExt.count(jo.extId) ? sExt.at(jo.extId) : 0;
+    job.hIdx.push_back(packObs(sPose.at(jo.o.poseId), es, jo.o.cam, jo.o.loss));
+    job.hObsLm.push_back(sLm.at(jo.lmId));
+    job.hLmPtr[sLm.at(jo.lmId) + 1]++;
+  }
+  if (!deviceJob) for (int l = 0; l < Lm; ++l) job.hLmPtr[l + 1] += job.hLmPtr[l];
+  bool anyExtVar = false;
+  for (int o : job.oExt) if (o >= 0) anyExtVar = true;
+  for (Factor& f : sel.factors)
+    packFactorInto(f, [&](uint64_t id, int& kind, int& slot) {
+      if (sPose.count(id)) { kind = B_POSE; slot = sPose.at(id); }
+      else if (sExt.count(id)) { kind = B_EXT; slot = sExt.at(id); }
+      else { kind = B_SB; slot = sSb.at(id); }
+    }, job.hFac, job.hImu, job.hImuT, job.hImuM);
+  job.nImu = (int)job.hImu.size();
+  // M2 dense part: which rows stay (the new prior) and which are marginalised
+  std::vector<int> margIdx;
+  for (const PriorBlockHost& pb : sel.dense) {
+    const bool marg = std::binary_search(sel.toMarginalize.begin(), sel.toMarginalize.end(), pb.id);
+    for (int k = 0; k < pb.mdim; ++k) (marg ? margIdx : job.idxLists).push_back(pb.ord + k);
+    if (!marg) sel.kept.push_back(pb);
+  }
+  const int nk = (int)job.idxLists.size(), nm = (int)margIdx.size();
+  job.idxLists.insert(job.idxLists.end(), margIdx.begin(), margIdx.end());
+  int ordk = 0;
+  for (PriorBlockHost& pb : sel.kept) { pb.ord = ordk; ordk += pb.mdim; }
+  job.cams = cameras_;
+  job.deviceJob = deviceJob;
+  job.lossOn = nLoss_ > 1;   // observations with a loss other than CauchyLoss(1): the job evaluates them through the loss table
+  if (job.lossOn) job.lossTab = lossTab_;
+  job.keepPre = optOn(kOptMargKeepPre);
+  job.margEig = debugOption(kOptMargEig);   // read HERE, on the caller's thread: the job may be issued by the enqueue thread
+  job.stream = stream_;
+  job.dims = MargDims{sel.m, Lm, sel.nObs, (int)job.hFac.size(), nk, nm, (int)(job.hPose.size() / 7), (int)(job.hExt.size() / 7),
+                      (int)cameras_.size(), anyExtVar ? 1 : 0, (sel.hadPrior && priorM_ > 0) ? priorM_ : 0};
+  job.plan = planMargJob(job.dims, MargSwitches{job.margEig}, MargKernelSizes{sizeof(JacobiShared)});
+  job.lmOrder = std::move(sel.lmOrder);
+  job.dense = std::move(sel.dense);
+  job.toMarginalize = sel.toMarginalize;
+}
+
+// ---- step 4: the persistent job buffers (grow-only: hipMalloc / hipFree per call used to cost more than the algebra) sized from
+// the plan, and the job's tables queued for the one pinned block of flushStaged (one DMA, one scatter kernel: 17 pageable copies
+// cost ~100 us of enqueueing).  The job is asynchronous: nothing here waits for the device.
+void Window::margReserveAndStage(MargJob& job) {
+  MargBuffers& mb = margBuf_;
+  const MargPlan& q = job.plan;
+  mb.bU.reserve(q.bU); mb.bW2.reserve(q.bW2); mb.bV.reserve(q.bV); mb.bVec.reserve(q.bVec);
+  // U, W, V and the vectors start from zero: clears riding in the same launch
+  job.pending.push_back({nullptr, sizeof(double) * q.clearU, mb.bU.p});
+  job.pending.push_back({nullptr, sizeof(double) * q.clearW2, mb.bW2.p});
+  job.pending.push_back({nullptr, sizeof(double) * q.clearV, mb.bV.p});
+  job.pending.push_back({nullptr, sizeof(double) * q.clearVec, mb.bVec.p});
+  job.stage(mb.bPose, job.hPose); job.stage(mb.bExt, job.hExt); job.stage(mb.bSb, job.hSb); job.stage(mb.bLm, job.hLm);
+  job.stage(mb.bUv, job.hUv); job.stage(mb.bW, job.hW);
+  if (job.generalOn) job.stage(mb.bS, job.hS);
+  job.stage(mb.bOP, job.oPose); job.stage(mb.bOE, job.oExt); job.stage(mb.bOS, job.oSb); job.stage(mb.bLmPtr, job.hLmPtr);
+  job.stage(mb.bObsLm, job.hObsLm); job.stage(mb.bIdx, job.hIdx);
+  job.stage(mb.bFac, job.hFac); job.stage(mb.bImu, job.hImu); job.stage(mb.bImuT, job.hImuT); job.stage(mb.bImuM, job.hImuM);
+  job.stage(dCams_, job.cams);
+  if (job.lossOn) job.stage(dLossTab_, job.lossTab);
+  job.stage(mb.bIdxList, job.idxLists);
+  if (job.deviceJob) {
+    job.stage(res_.poseClass, job.poseClass); job.stage(res_.poseSlotOfH, job.jobPoseSlot); job.stage(res_.extSlotOfH, job.jobExtSlot);
+    mb.bLm.reserve(q.gLm); mb.bUv.reserve(q.gUv); mb.bW.reserve(q.gW);
+    mb.bLmPtr.reserve(q.gLmPtr); mb.bObsLm.reserve(q.gObsLm); mb.bIdx.reserve(q.gIdx);
+    res_.margScratch.reserve(margGatherScratchInts(res_.L));
+  }
+  mb.bLin.reserve(q.bLin);
+  mb.bFacLin.reserve(q.bFacLin);
+  mb.bPartial.reserve(q.bPartial);
+  mb.bScal.reserve(q.bScal);
+  mb.bFlag.reserve(q.bFlag);
+  job.oldPrior = mb.bHk.p;
+  if (q.bHk > mb.bHk.cap && job.dims.oldPriorM > 0) { std::swap(job.oldPriorKeep.p, mb.bHk.p); std::swap(job.oldPriorKeep.cap, mb.bHk.cap); }
+  mb.bHk.reserve(q.bHk);
+  mb.bScratch.reserve(q.bScratch);
+  mb.bOut.reserve(q.bOut);
+  if (job.dims.nk > 0) priorHostValid_ = false;  // results stay on the device (solver reads Ht / bp / c0 in place); getPrior() fetches
+}
+
+// ---- step 5: M1-M3, next to their kernels.  Everything the launches need was fixed by steps 3 and 4: no allocation and no host
+// table is touched here, so the launches themselves (a DMA, the scatter and 6-13 kernels: 25-50 us of API calls) can be issued by
+// the handle's enqueue thread while the call goes on with the graph update and returns (Window::quiesce joins it before the stream,
+// the job buffers or the prior are touched again).  It walks the plan: no size or offset is formed here.
+void Window::launchMarginalization(const MargJob& job) {
+  MargBuffers& mb = margBuf_;
+  const MargPlan& pl = job.plan;
+  const MargDims& d = job.dims;
+  hipStream_t s = job.stream;
+  flushStaged(job.pending, s);
+  if (job.deviceJob && (d.N > 0 || d.Lm > 0)) {
+    MargGatherArgs ga;
+    std::memset(&ga, 0, sizeof(ga));
+    ga.L = res_.L; ga.H = res_.H; ga.expectN = d.N; ga.expectLm = d.Lm;
+    ga.lmPtr = res_.lmPtr[res_.cur].p; ga.handleOfSlot = res_.handleOfSlot[res_.cur].p;
+    ga.uv = res_.uv[res_.cur].p; ga.w = res_.w[res_.cur].p; ga.hnd = res_.hnd[res_.cur].p;
+    ga.lmHp = res_.lmHp.p;
+    ga.poseClass = res_.poseClass.p; ga.jobPoseSlot = res_.poseSlotOfH.p; ga.jobExtSlot = res_.extSlotOfH.p;
+    ga.jLmPtr = mb.bLmPtr.p; ga.jObsLm = mb.bObsLm.p; ga.jIdx = mb.bIdx.p; ga.jUv = mb.bUv.p; ga.jW = mb.bW.p; ga.jLm = mb.bLm.p;
+    ga.scratch = res_.margScratch.p;
+    ga.status = resStatusDev_;
+    launchWindowMargGather(ga, s);
+  }
+  // (the four clears rode in the scatter launch of the staged block) the two copies of the old prior land inside the cleared U / ba:
+  // its content (H_, b0_) occupies the leading block and is still on the device, exactly where k_marg_dense left it
+  if (d.oldPriorM > 0) {
+    FillJobs copies;
+    copies.n = 0;
+    addFill(copies, mb.bU.p, job.oldPrior + pl.oldH.off, pl.oldH.len, d.oldPriorM, d.m, d.oldPriorM);
+    addFill(copies, mb.bVec.p + pl.ba.off, job.oldPrior + pl.oldB0.off, pl.oldB0.len);
+    launchFillJobs(copies, s);
+  }
+  DeviceProblem q;
+  std::memset(&q, 0, sizeof(q));
+  q.nPose = d.nPose; q.nExt = d.nExt; q.nSb = job.nSb;
+  q.L = d.Lm; q.N = d.N; q.F = d.F; q.nImu = job.nImu; q.d = d.m; q.dC = 0; q.nCam = d.nCam;
+  q.anyExtVariable = d.anyExtVar;
+  q.ownsCamera = 1;
+  q.pose = mb.bPose.p; q.ext = mb.bExt.p; q.sb = mb.bSb.p; q.lm = mb.bLm.p;
+  q.poseC = mb.bPose.p; q.extC = mb.bExt.p; q.sbC = mb.bSb.p; q.lmC = mb.bLm.p;
+  q.poseOff = mb.bOP.p; q.extOff = mb.bOE.p; q.sbOff = mb.bOS.p;
+  q.cams = dCams_.p;
+  q.lossTab = job.lossOn ? dLossTab_.p : nullptr;
+  q.obsS = job.generalOn ? mb.bS.p : nullptr;
+  q.lmPtr = mb.bLmPtr.p; q.obsUv = mb.bUv.p; q.obsW = mb.bW.p; q.obsIdx = mb.bIdx.p; q.obsLm = mb.bObsLm.p;
+  q.rCur = mb.bLin.p + pl.linR.off; q.JpCur = mb.bLin.p + pl.linJp.off; q.JlCur = mb.bLin.p + pl.linJl.off; q.JeCur = mb.bLin.p + pl.linJe.off;
+  q.factors = mb.bFac.p; q.linCur = mb.bFacLin.p; q.linCand = mb.bFacLin.p;
+  q.imus = mb.bImu.p; q.imuT = mb.bImuT.p; q.imuMeas = mb.bImuM.p;
+  q.scal = mb.bScal.p; q.partial = mb.bPartial.p;
+  MargDev md;
+  md.m = d.m; md.Lm = d.Lm; md.N = d.N; md.F = d.F;
+  md.U = mb.bU.p; md.ba = mb.bVec.p + pl.ba.off; md.W = mb.bW2.p; md.V = mb.bV.p; md.bb = mb.bVec.p + pl.bb.off;
+  double* vb = mb.bVec.p + pl.vb.off;
+  // M1: evaluate at the linearisation points (each residual's loss corrector as in :283-330) and accumulate
+  if (pl.reproj) {
+    launchEvalReproj(q, false, true, s);
+    const dim3 camGrid(pl.accumCamX, pl.accumCamY);
+    if (d.anyExtVar) {
+      launch(k_marg_accum_lm<true>, dim3(pl.accumLm.grid), dim3(64), pl.accumLm.ldsBytes, s, q, md);
+      launch(k_marg_accum_cam<true>, camGrid, dim3(64), 0, s, q, md);
+    } else {
+      launch(k_marg_accum_lm<false>, dim3(pl.accumLm.grid), dim3(64), pl.accumLm.ldsBytes, s, q, md);
+      launch(k_marg_accum_cam<false>, camGrid, dim3(64), 0, s, q, md);
+    }
+  }
+  if (pl.factors) {
+    launchEvalFactors(q, false, s);
+    launch(k_marg_accum_factors, dim3(pl.accumFactors.grid), dim3(256), pl.accumFactors.ldsBytes, s, q, md);
+  }
+  if (job.keepPre) {   // inspection: the system after M1 (svin_ba_get_marg_pre), before anything is eliminated
+    const int m = d.m, Lm = d.Lm;
+    HIP_OK(hipStreamSynchronize(s));
+    margPre_.m = m; margPre_.Lm = Lm;
+    margPre_.U.assign((size_t)m * m, 0.0); margPre_.ba.assign(std::max(m, 1), 0.0);
+    margPre_.W.assign((size_t)m * 3 * Lm, 0.0); margPre_.V.assign((size_t)9 * Lm, 0.0); margPre_.bb.assign((size_t)3 * Lm, 0.0);
+    if (m > 0) {
+      HIP_OK(hipMemcpy(margPre_.U.data(), md.U, sizeof(double) * m * m, hipMemcpyDeviceToHost));
+      HIP_OK(hipMemcpy(margPre_.ba.data(), md.ba, sizeof(double) * m, hipMemcpyDeviceToHost));
+    }
+    if (Lm > 0) {
+      if (m > 0) HIP_OK(hipMemcpy(margPre_.W.data(), md.W, sizeof(double) * m * 3 * Lm, hipMemcpyDeviceToHost));
+      HIP_OK(hipMemcpy(margPre_.V.data(), md.V, sizeof(double) * 9 * Lm, hipMemcpyDeviceToHost));
+      HIP_OK(hipMemcpy(margPre_.bb.data(), md.bb, sizeof(double) * 3 * Lm, hipMemcpyDeviceToHost));
+    }
+    margPre_.margRows.clear();
+    margPre_.denseIds.clear(); margPre_.denseOrd.clear(); margPre_.denseMdim.clear();
+    margPre_.lmIds.assign(job.lmOrder.begin(), job.lmOrder.end());
+    for (const PriorBlockHost& pb : job.dense) { margPre_.denseIds.push_back(pb.id); margPre_.denseOrd.push_back(pb.ord); margPre_.denseMdim.push_back(pb.mdim); }
+    for (const PriorBlockHost& pb : job.dense) {
+      const bool mg = std::binary_search(job.toMarginalize.begin(), job.toMarginalize.end(), pb.id);
+      for (int k = 0; k < pb.mdim; ++k) margPre_.margRows.push_back(mg ? 1 : 0);
+    }
+  }
+  // M2 landmark part
+  if (pl.lmPrepare.grid) {
+    launch(k_marg_lm_prepare, dim3(pl.lmPrepare.grid), dim3(128), pl.lmPrepare.ldsBytes, s, md, vb);
+    launch(k_marg_lm_apply, dim3(pl.lmApply.grid), dim3(256), pl.lmApply.ldsBytes, s, md, (const double*)vb);
+    launch(k_marg_lm_update, dim3(pl.lmUpdate.grid), dim3(64), pl.lmUpdate.ldsBytes, s, md);
+  }
+  // M2 dense part
+  if (pl.dense.grid) {
+    DenseArgs da;
+    da.m = d.m; da.nk = d.nk; da.nm = d.nm;
+    da.keep = mb.bIdxList.p; da.marg = mb.bIdxList.p + d.nk;
+    da.U = mb.bU.p; da.ba = mb.bVec.p + pl.ba.off;
+    da.Hk = mb.bHk.p + pl.Hk.off; da.bk = mb.bHk.p + pl.bk.off;
+    da.Vm = mb.bScratch.p + pl.Vm.off; da.Qm = mb.bScratch.p + pl.Qm.off; da.tmp = mb.bScratch.p + pl.denseTmp.off;
+    da.flag = mb.bFlag.p;
+    launch(k_marg_dense, dim3(pl.dense.grid), dim3(1024), pl.dense.ldsBytes, s, da, pl.denseUseLds, pl.denseProdLds, pl.denseTileChol);
+  } else if (pl.copyPair) {
+    HIP_OK(hipMemcpyAsync(mb.bHk.p + pl.Hk.off, mb.bU.p, sizeof(double) * pl.Hk.len, hipMemcpyDeviceToDevice, s));
+    HIP_OK(hipMemcpyAsync(mb.bHk.p + pl.bk.off, mb.bVec.p + pl.ba.off, sizeof(double) * pl.bk.len, hipMemcpyDeviceToDevice, s));
+  }
+  // M3 (which eigen-solvers run, and k_marg_final's mode: planMargJob)
+  if (pl.final.grid) {
+    FinalArgs fa;
+    fa.n = d.nk; fa.H = mb.bHk.p + pl.Hk.off; fa.b0 = mb.bHk.p + pl.bk.off;
+    fa.G = mb.bOut.p + pl.G.off; fa.Q = mb.bOut.p + pl.Q.off; fa.J = mb.bOut.p + pl.J.off; fa.Ht = mb.bOut.p + pl.Ht.off;
+    fa.e0 = mb.bOut.p + pl.e0.off; fa.bp = mb.bOut.p + pl.bp.off; fa.scal = mb.bOut.p + pl.scal.off;
+    fa.tmp = mb.bOut.p + pl.finalTmp.off;
+    fa.flag = mb.bFlag.p;
+    if (pl.finalChol.grid) launch(k_marg_final_chol, dim3(pl.finalChol.grid), dim3(1024), pl.finalChol.ldsBytes, s, fa);
+    if (pl.finalDc.grid) launch(k_marg_final_dc, dim3(pl.finalDc.grid), dim3(1024), pl.finalDc.ldsBytes, s, fa, pl.finalDcAfterChol);
+    launch(k_marg_final, dim3(pl.final.grid), dim3(1024), pl.final.ldsBytes, s, fa, pl.finalMode, pl.finalFallbackLds, pl.finalSkipIfDone);
+  }
+}
+
+// SVIN_MARG_TIMING: what the device reports of the job it has just run (the launches were issued inline)
+void Window::margPrintDeviceTiming(const MargJob& job) {
+  const MargBuffers& mb = margBuf_;
+  HIP_OK(hipStreamSynchronize(job.stream));
+  int fl[4] = {0, 0, 0, 0};
+  HIP_OK(hipMemcpy(fl, mb.bFlag.p, sizeof(fl), hipMemcpyDeviceToHost));
+  double sc3[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  const double* dbgScal = job.plan.final.grid ? mb.bOut.p + job.plan.scal.off : nullptr;   // FinalArgs::scal
+  if (dbgScal) HIP_OK(hipMemcpy(sc3, dbgScal, sizeof(sc3), hipMemcpyDeviceToHost));
+  std::printf("[marg] m %d Lm %d; Jacobi sweeps of the last eigen-solve: %d; eigenvalues <= tol: %d (min %.3e max %.3e)\n", job.dims.m, job.dims.Lm,
+              fl[1], fl[2], sc3[1], sc3[2]);
+  if (dbgScal && sc3[7] > 0 && fl[3] != -8) {   // the eigenvalues sit behind p[] in the kernel's scratch (flag[3] == -8: the certified
+                                                // Cholesky route produced the prior -- tmp + n holds b0 / p there, no eigenvalues exist)
+    const int nn = (int)sc3[7];
+    std::vector<double> evh(nn);
+    HIP_OK(hipMemcpy(evh.data(), dbgScal + 8 + nn, sizeof(double) * nn, hipMemcpyDeviceToHost));
+    std::sort(evh.begin(), evh.end());
+    std::printf("[marg] smallest eigenvalues:");
+    for (int i = 0; i < std::min(nn, 8); ++i) std::printf(" %.3e", evh[i]);
+    std::printf("  (tol %.3e)\n", 2.220446049250313e-16 * nn * sc3[2]);
+  }
+  std::printf("[marg] k_marg_final: n %d, prepare %.0f us, eigen-solve %.0f us (two-phase: phase 1 %d us; %.0f shader clocks per us), "
+              "J / e0 / J^T J %.0f us\n", (int)sc3[7], sc3[3] / 100.0, sc3[4] / 100.0, fl[3], sc3[6] / std::max(1.0, sc3[4] / 100.0),
+              sc3[5] / 100.0);
+}
+
+// ---- step 6: graph update (:710-716, :788-811) -- the marginalised blocks leave, the prior's bookkeeping, the re-done fixation
+void Window::margUpdateGraph(const MargSelection& sel) {
+  for (uint64_t id : sel.toMarginalize)
+    if (!std::binary_search(sel.margLandmarks.begin(), sel.margLandmarks.end(), id)) removeBlock(id);
   int nk = 0;
-  for (const PriorBlockHost& pb : kept) nk += pb.mdim;
+  for (const PriorBlockHost& pb : sel.kept) nk += pb.mdim;
   if (nk > 0) {
     hasPrior_ = true;
-    priorBlocks_ = kept;
+    priorBlocks_ = sel.kept;
     priorM_ = nk;
     priorResId_ = nextResId_++;
     for (const PriorBlockHost& pb : priorBlocks_) blocks_.at(pb.id).residuals.push_back(priorResId_);
@@ -1909,19 +1796,44 @@ int Window::applyMarginalizationStrategy(size_t numKeyframes, size_t numImuFrame
     priorBlocks_.clear();
     priorM_ = 0;
   }
-  if (reDoFixation && !states_.empty()) {
+  if (sel.reDoFixation && !states_.empty()) {
     const uint64_t firstId = states_.begin()->first;
-    double information[36] = {0};
-    information[35] = 1.0e14; information[0] = 1.0e14; information[7] = 1.0e14; information[14] = 1.0e14;
     Factor f;
     f.kind = F_POSE_PRIOR; f.nblk = 1; f.blocks[0] = firstId; f.m = 6;
     std::memcpy(f.meas, blocks_.at(firstId).x, 7 * sizeof(double));
-    // Eigen LLT early-exit semantics
+    // information 1e14 on the position and the yaw; Eigen LLT early-exit semantics
     for (int i = 0; i < 36; ++i) f.sqrtInfo[i] = 0;
     f.sqrtInfo[0] = f.sqrtInfo[7] = f.sqrtInfo[14] = std::sqrt(1.0e14);
     f.sqrtInfo[35] = 1.0e14;
     addFactor(std::move(f));
   }
+}
+
+int Window::applyMarginalizationStrategy(size_t numKeyframes, size_t numImuFrames, std::vector<uint64_t>& removed) {
+  quiesce();
+  const bool timing = optOn(kOptMargTiming);
+  const double tm0 = nowSec();
+  double tm1 = tm0, tm2 = tm0, tm3 = tm0, tm4 = tm0;
+  const MargFrames frames = margFrames(numKeyframes, numImuFrames);
+  if (!frames.enough) return 1;
+  if (!margAccepts(frames)) return -1;
+  MargSelection sel;
+  margApplyPolicy(frames, sel, removed, timing);
+  tm1 = nowSec();
+  if (sel.m > 0 || !sel.lmOrder.empty()) {   // the device job (M1-M3)
+    auto job = std::make_shared<MargJob>();
+    margBuildTables(sel, *job);
+    tm2 = nowSec();
+    margReserveAndStage(*job);
+    // SVIN_MARG_SYNC_ENQUEUE is the A/B switch that issues the launches from this thread; the timing and inspection paths read
+    // what the job leaves
+    if (timing || job->keepPre || optOn(kOptMargSyncEnqueue)) launchMarginalization(*job);
+    else enqueueAsync([this, job]() { launchMarginalization(*job); });
+    tm3 = nowSec();
+    if (timing) margPrintDeviceTiming(*job);
+  }
+  tm4 = nowSec();
+  margUpdateGraph(sel);
   if (timing)
     std::printf("[marg] policy %.0f us, job assembly %.0f us, upload+enqueue %.0f us, device wait %.0f us, graph update %.0f us\n",
                 1e6 * (tm1 - tm0), 1e6 * (tm2 - tm1), 1e6 * (tm3 - tm2), 1e6 * (tm4 - tm3), 1e6 * (nowSec() - tm4));

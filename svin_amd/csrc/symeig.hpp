@@ -15,6 +15,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <type_traits>
+#include "tile_dims.hpp"   // kSymEigMaxN
 
 namespace svin {
 namespace symeig {
@@ -22,7 +23,7 @@ namespace symeig {
 using lds_double = __attribute__((address_space(3))) double;
 typedef double d4 __attribute__((ext_vector_type(4)));
 
-constexpr int kMaxN = 128;
+constexpr int kMaxN = kSymEigMaxN;
 constexpr int kThreads = 1024;
 constexpr double kEps = 2.220446049250313e-16;
 

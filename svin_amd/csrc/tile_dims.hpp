@@ -7,6 +7,7 @@
 namespace svin {
 
 constexpr int kPanelLd = 17;  // leading dimension of the 16x16 LDS tiles of the dense solvers
+constexpr int kSymEigMaxN = 128;  // largest matrix of the prior's direct eigen-solver (symeig.hpp; planned in marg_plan.hpp)
 
 // pairwise form of the landmark elimination (k_schur): four waves stage 64 observations each, and a workgroup keeps a private
 // slab (the dC x dC block + gRed | gFull | hC) in LDS when it fits next to that.  ONE function: pack() sizes the slab buffer and

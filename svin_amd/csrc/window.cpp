@@ -1958,31 +1958,15 @@ void Window::packFactors(PackHost& a) {
   for (auto& kv : factors_) {
     Factor& f = kv.second;
     if (!ownsFactor(f)) continue;
-    DevFactor df;
-    std::memset(&df, 0, sizeof(df));
-    df.kind = f.kind; df.nblk = f.nblk; df.m = f.m; df.imuIndex = -1;
-    df.lossKind = f.lossKind; df.lossScale = f.lossScale;
-    for (int b = 0; b < f.nblk; ++b) {
-      df.blkKind[b] = blocks_.at(f.blocks[b]).kind;
-      df.blkSlot[b] = slotMapOf(df.blkKind[b]).at(f.blocks[b]);
-    }
-    std::memcpy(df.meas, f.meas, sizeof(df.meas));
-    std::memcpy(df.aux, f.aux, sizeof(df.aux));
-    std::memcpy(df.sqrtInfo, f.sqrtInfo, sizeof(df.sqrtInfo));
-    if (f.kind == F_IMU) {
-      df.imuIndex = (int)hImu.size();
-      f.imu.sampleStart = (int)(hImuT.size() / 2);
-      f.imu.sampleCount = (int)(f.imuT.size() / 2);
-      hImu.push_back(f.imu);
-      hImuT.insert(hImuT.end(), f.imuT.begin(), f.imuT.end());
-      hImuM.insert(hImuM.end(), f.imuMeas.begin(), f.imuMeas.end());
-    }
     if (f.kind == F_HOST) {
       if (world_ > 1 || rcclComm_) throw std::runtime_error("svin_ba: host cost functions are not available in sharded mode");
       hostFactors_.push_back(std::make_pair((int)hFac.size(), f.id));
     }
     factorIds_.push_back(f.id);
-    hFac.push_back(df);
+    packFactorInto(f, [&](uint64_t id, int& kind, int& slot) {
+      kind = blocks_.at(id).kind;
+      slot = slotMapOf(kind).at(id);
+    }, hFac, hImu, hImuT, hImuM);
   }
   hPoseOffKeep_ = a.hPoseOff; hExtOffKeep_ = a.hExtOff; hSbOffKeep_ = a.hSbOff;
   if (a.phantom) {

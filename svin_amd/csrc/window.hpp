@@ -116,6 +116,31 @@ struct Factor {
   double lossScale = 1.0;
 };
 
+// Appends a factor to the device tables of a problem: its DevFactor record and, for an IMU factor, its pre-integration state and
+// samples.  slotOf(blockId, kind, slot) says where each of its blocks sits in that problem's state tables (pack(): the window's
+// slot maps; the marginalisation job: the job's own tables).
+template <class SlotOf>
+inline void packFactorInto(Factor& f, SlotOf&& slotOf, std::vector<DevFactor>& hFac, std::vector<DevImu>& hImu,
+                           std::vector<uint32_t>& hImuT, std::vector<double>& hImuM) {
+  DevFactor df;
+  std::memset(&df, 0, sizeof(df));
+  df.kind = f.kind; df.nblk = f.nblk; df.m = f.m; df.imuIndex = -1;
+  df.lossKind = f.lossKind; df.lossScale = f.lossScale;
+  for (int b = 0; b < f.nblk; ++b) slotOf(f.blocks[b], df.blkKind[b], df.blkSlot[b]);
+  std::memcpy(df.meas, f.meas, sizeof(df.meas));
+  std::memcpy(df.aux, f.aux, sizeof(df.aux));
+  std::memcpy(df.sqrtInfo, f.sqrtInfo, sizeof(df.sqrtInfo));
+  if (f.kind == F_IMU) {
+    df.imuIndex = (int)hImu.size();
+    f.imu.sampleStart = (int)(hImuT.size() / 2);
+    f.imu.sampleCount = (int)(f.imuT.size() / 2);
+    hImu.push_back(f.imu);
+    hImuT.insert(hImuT.end(), f.imuT.begin(), f.imuT.end());
+    hImuM.insert(hImuM.end(), f.imuMeas.begin(), f.imuMeas.end());
+  }
+  hFac.push_back(df);
+}
+
 struct StateInfo { uint64_t id = 0; bool exists = false; };
 struct State {
   uint64_t id = 0;
@@ -168,7 +193,10 @@ struct DevBuf {
   }
 };
 
-// device buffers of the marginalisation job (marg.hip), kept across calls
+// device buffers of the marginalisation job (marg.hip), kept across calls and grow-only.  What each must hold for a job, and where
+// the launches keep U | ba | bb | vb, Vm | Qm | tmp, Hk | bk and G | Q | J | Ht | e0 | bp | scal | tmp in bVec, bScratch, bHk and bOut,
+// is planned by marg_plan.hpp (planMargJob): Window::margReserveAndStage reserves from the plan, launchMarginalization reads it.
+struct MargFrames;   // marg_plan.hpp
 struct MargBuffers {
   DevBuf<double> bPose, bExt, bSb, bLm, bUv, bW, bS, bLin, bU, bW2, bV, bVec, bScratch, bImuM, bPartial, bHk, bOut;
   DevBuf<int> bOP, bOE, bOS, bLmPtr, bObsLm, bIdxList, bFlag;
@@ -432,8 +460,19 @@ class Window {
   // the record of the last evaluation has reached the mailbox (no mailbox: true -- readScalars() synchronises)
   bool scalarsReady() const { return !mailbox_ || *reinterpret_cast<const volatile unsigned long long*>(&mailbox_->seq) == mailboxSeq_; }
 
-  // marginalisation (device algebra in marg.hip)
-  friend class Marginalizer;
+  // marginalisation (marg.hip): the steps of applyMarginalizationStrategy(), in order.  The sizes, offsets and launch shapes between
+  // margBuildTables and launchMarginalization are marg_plan.hpp's (planMargJob), which frames leave is selectMargFrames.
+  struct MargSelection;   // what the policy takes out of the host graph
+  struct MargJob;         // everything the launches read: host tables, staged copies, dimensions, plan (held by shared_ptr)
+  MargFrames margFrames(size_t numKeyframes, size_t numImuFrames) const;
+  bool margRefusesFixedLandmarks() const { return numFixedLandmarks_ > 0 && (world_ > 1 || rcclComm_ != nullptr); }
+  bool margAccepts(const MargFrames& frames) const;     // 1. refusals; nothing is modified before they pass
+  void margApplyPolicy(const MargFrames& frames, MargSelection& sel, std::vector<uint64_t>& removed, bool timing);   // 2. Estimator.cpp:509-770, host graph only
+  void margBuildTables(MargSelection& sel, MargJob& job);   // 3. job tables (host-assembled or device-gathered form), dimensions, plan
+  void margReserveAndStage(MargJob& job);                   // 4. device buffers from the plan; every upload queued in the job
+  void launchMarginalization(const MargJob& job);           // 5. M1-M3; on this thread or on the enqueue thread
+  void margUpdateGraph(const MargSelection& sel);           // 6. prior bookkeeping, the re-done fixation
+  void margPrintDeviceTiming(const MargJob& job);           // SVIN_MARG_TIMING
 
   int device_ = 0;
   int rank_ = 0, world_ = 1;
