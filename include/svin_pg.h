@@ -37,6 +37,44 @@ int svin_pg_add_keyframe(svin_pg* h, int index, int sequence, const double* t, c
                          const double* loop_rel_t, const double* loop_rel_q, double loop_rel_yaw_deg);
 int svin_pg_num_keyframes(const svin_pg* h);
 
+/* ---- caller-given edges (no reference counterpart: pose_graph only knows the edges it builds from the keyframe list)
+ *
+ * A constraint between any two keyframes of the list: a second loop closure on a keyframe, an edge between two sessions or
+ * vehicles, a relocalisation, an edge weighted by a measured covariance.  The measurement is the pose of keyframe b in the frame
+ * of keyframe a, exactly as loop_rel_* of svin_pg_add_keyframe: rel_t = R_a^T (t_b - t_a); 6-DoF: rel_q = q_a^-1 q_b and
+ * rel_yaw_deg is ignored; 4-DoF: rel_yaw_deg = yaw_b - yaw_a, rel_q may be NULL, pitch and roll are those of a's SVIn pose.
+ * index_a / index_b are `index` values of keyframes already in the list (the last keyframe with that index, as for a loop edge);
+ * a may come after b in the list and the sequences may differ.
+ *
+ * Residual.  u is the unit-weight residual of the built-in error terms: 4-DoF [R^T d - rel_t (3, metres), wrap(yaw_b - yaw_a -
+ * rel_yaw) (degrees)], 6-DoF [R_a^T d - rel_t, 2 vec(rel_q conj(q_a^-1 q_b))].  r = S u with S = L^T, information = L L^T (the
+ * convention of svin_ba_map_add_reprojection_error); information is D x D row-major in the order of u, D = 4 or 6; NULL = the
+ * loop-edge weights of that DoF (4-DoF diag(1, 1, 1, 0.1)^2, 6-DoF diag(20, 20, 20, 100, 100, 100)^2).  The loss -- loss_kind one
+ * of the numeric values of svin_ba.h's SVIN_LOSS_NONE (0) / SVIN_LOSS_CAUCHY (1) / SVIN_LOSS_HUBER (2), loss_scale = a -- acts on
+ * s = |r|^2 with Ceres' corrector; the edge's cost is rho(s) / 2.  NULL information with Huber(0.1) is the built-in loop edge.
+ * rel_q is used as given, like loop_rel_q: rel_q and -rel_q are the same rotation but flip the sign of the rotation rows of u.
+ * That is without effect under an information that does not couple rotation with translation (the built-in weights); with one
+ * that does, hand over the rel_q of the hemisphere of q_a^-1 q_b (their dot product positive).
+ *
+ * An edge takes part in svin_pg_optimize(earliest, cur), svin_pg_debug_step and svin_pg_get_covariance_blocks when both its
+ * keyframes are in the range.  It stands in the edge list at the turn of its later keyframe (list order), after that keyframe's
+ * sequential and loop edges, in the order of the add_edge calls.  With one constant end it contributes to the other end's block
+ * and to the cost, with two to the cost only.  Pairs of keyframes that carry three or more edges have their block of the normal
+ * equations summed in the order of the edge list: results are the same bits from run to run.
+ *
+ * svin_pg_add_edge returns the edge id (>= 1, never reused within a handle); -1 for a NULL handle, NULL rel_t, NULL rel_q in
+ * 6-DoF, index_a == index_b, numbers that are not finite, an unknown loss kind, a loss_scale that is not finite and > 0 (ignored
+ * for NONE), an information that is not symmetric (I[i][j] != I[j][i]), not finite or not positive definite (a Cholesky pivot not
+ * above D eps of its diagonal entry); -2 for an unknown keyframe index or edge id; svin_pg_last_error() has the text.  A refused
+ * call changes nothing.  add_edge and remove_edge drop the kept covariance factor like svin_pg_add_keyframe.  svin_pg_get_edge
+ * fills whichever outputs are not NULL; information is the matrix in force (the default weights squared where NULL was given). */
+int svin_pg_add_edge(svin_pg* h, int index_a, int index_b, const double* rel_t, const double* rel_q, double rel_yaw_deg,
+                     const double* information, int loss_kind, double loss_scale);
+int svin_pg_remove_edge(svin_pg* h, int edge_id);
+int svin_pg_num_edges(const svin_pg* h);
+int svin_pg_get_edge(const svin_pg* h, int edge_id, int* index_a, int* index_b, double* rel_t, double* rel_q,
+                     double* rel_yaw_deg, double* information, int* loss_kind, double* loss_scale);
+
 /* one pass of the optimisation thread's loop body for cur_index (PoseGraph.cpp:236-351 / :397-516): keyframes with
  * index >= earliest_loop_index up to cur_index are optimised, their poses updated in place */
 int svin_pg_optimize(svin_pg* h, int earliest_loop_index, int cur_index);
@@ -76,7 +114,8 @@ int svin_pg_summary(const svin_pg* h, double* out6);
  * an optimisation; the edge measurements stay what optimize() takes them from -- Sigma = (J^T J)^-1, undamped, in the solver's
  * tangent coordinates: 4-DoF [yaw in degrees, t], 6-DoF [t, dq] with q <- [sin|d| d/|d|, cos|d|] q.  The units are those of the
  * reference's residual weights (sqrt-information 20 / 100 / 57.3 of the 6-DoF edges, unit weights and the 0.1 loop-yaw weight of
- * the 4-DoF edges), not metres and radians of a calibrated sensor model.  Covariances are relative to the constant keyframe(s).
+ * the 4-DoF edges), not metres and radians of a calibrated sensor model; an edge given with a measured information matrix
+ * (svin_pg_add_edge) enters in the units of that matrix.  Covariances are relative to the constant keyframe(s).
  *
  * The block of (index_a, index_b) -- the `index` values given to svin_pg_add_keyframe -- is Sigma[a, b], D x D row-major, D = 4
  * or 6.  A constant keyframe has exactly zero covariance with everything; Sigma[b, a] is Sigma[a, b]^T bit for bit; two calls
@@ -90,7 +129,7 @@ int svin_pg_summary(const svin_pg* h, double* out6);
  * -- a pivot that is not positive or below 1e-12 of its diagonal entry of the Jacobi-scaled J^T J; svin_pg_last_error() then names
  * the keyframe index whose block met the pivot, or "root"; nothing is kept and the handle stays usable.  Nothing is written back:
  * poses, drift, summary and partition record stay as they were.  The factor of the last call is kept and reused until
- * svin_pg_add_keyframe, svin_pg_optimize, svin_pg_debug_step, svin_pg_set_partition or svin_pg_set_levels is called or another
+ * svin_pg_add_keyframe, svin_pg_add_edge, svin_pg_remove_edge, svin_pg_optimize, svin_pg_debug_step, svin_pg_set_partition or svin_pg_set_levels is called or another
  * (earliest_loop_index, cur_index) is given. */
 #define SVIN_PG_ERR_SINGULAR (-5)
 /* n_pairs blocks back to back; cov == NULL only sizes; returns the doubles written (n_pairs * D * D) */
@@ -109,8 +148,9 @@ int svin_pg_covariance_counters(const svin_pg* h, long long out4[4]);
  * keyframes stay untouched.  Returns 1, 0 when there is nothing to optimise, <0 on error. */
 int svin_pg_debug_step(svin_pg* h, int earliest_loop_index, int cur_index, double radius);
 /* copies the named array of the last svin_pg_debug_step (as doubles; ints converted) and returns its length, -2 for an
- * unknown name; out == NULL just returns the length.  Names: local problem ea eb eloop off et eyaw epitch eroll eq esq
- * yaw pitch roll t q; device res Ja Jb (robustified) g scale colsq nodeBlk (nodes x D x D, lower triangle) y yS
+ * unknown name; out == NULL just returns the length.  Names: local problem ea eb eloop (0 sequential, 1 loop, 2 caller-given) off
+ * et eyaw epitch eroll eq esq (ones on caller-given edges) yaw pitch roll t q; ekind (0 sequential, 1 loop, 2 caller) einfo
+ * (ne x D x D, the factor S applied, diagonal for the built-in edges) eloss (ne x 2: kind, scale) eid (edge id, 0 = built-in); device res Ja Jb (robustified) g scale colsq nodeBlk (nodes x D x D, lower triangle) y yS
  * cost costC gradmax model step2 x2 cholFail yawC tC qC; partition rows cols rows2 cols2 (per piece of level 1 / 2)
  * sepOff nodePiece nodeRow isCover isRoot l2PieceOf (per node) nS nR nPieces nPieces2 BW BW2 */
 long long svin_pg_debug_array(const svin_pg* h, const char* name, double* out, long long cap);

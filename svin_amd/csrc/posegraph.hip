@@ -23,11 +23,15 @@
 //           k_pg_piece_back      interior unknowns: x_I = L^-T (y_r - Y_C x_S)
 //           k_pg_model / k_pg_plus / k_pg_reduce   model cost change, candidate = Plus(x, delta), norms
 // Graphs with <= 128 free keyframes skip the pieces (every keyframe is a separator: one dense solve).
+// Caller-given edges (svin_pg_add_edge; pg_edges.hpp) stand in the same edge list: k_pg_eval_edges evaluates
+// a list that holds any (unit-weight residual, the edge's upper-triangular factor, its own loss), k_pg_assemble_shared sums the
+// blocks of keyframe pairs that carry three or more edges in a fixed order; everything downstream reads res / Ja / Jb as before.
 // Marginal covariances of keyframes (svin_pg_get_covariance_blocks): k_pg_cov_* below push unit right-hand sides through the same
 // nested factorisation, undamped, the root on the blocked route whose factor stays in cholL (pg_cov_plan.hpp).
 #include "kernels.hpp"
 #include "dmath.hpp"
 #include "pg_cov_plan.hpp"
+#include "pg_edges.hpp"
 #include "../../include/svin_pg.h"
 
 #include <algorithm>
@@ -135,7 +139,8 @@ __device__ __forceinline__ double pgBlockMax(double v, double* red) {
 }
 
 // residual and minimal Jacobians of one edge (tangent order 4-DoF: [yaw, t]; 6-DoF: [t, dq], q <- [sin|d| d/|d|, cos|d|] q)
-template <bool SIX>
+// UNIT: the unit-weight residual u of a caller-given edge (no yaw weight, no sqrt-information); its factor comes after
+template <bool SIX, bool UNIT = false>
 __device__ __forceinline__ void pgEdge(const PgDev& p, int e, bool cand, double* r, double* Ja, double* Jb) {
   const int a = p.ea[e], b = p.eb[e];
   const double* T = cand ? p.tC : p.t;
@@ -144,7 +149,7 @@ __device__ __forceinline__ void pgEdge(const PgDev& p, int e, bool cand, double*
     const double* Y = cand ? p.yawC : p.yaw;
     double R[9], dR[9];
     pgYpr2R(Y[a], p.epitch[e], p.eroll[e], R, dR);
-    const bool loop = p.eloop[e] != 0;
+    const bool loop = !UNIT && p.eloop[e] != 0;
     const double wt = 1.0, wy = loop ? 0.1 : 1.0;  // FourDOFWeightError: weight 1, yaw / 10 (PoseGraph.h:182, :206)
     for (int k = 0; k < 3; ++k) {
       const double ti = R[k] * d[0] + R[3 + k] * d[1] + R[6 + k] * d[2];    // (R^T d)[k]
@@ -161,7 +166,8 @@ __device__ __forceinline__ void pgEdge(const PgDev& p, int e, bool cand, double*
     const double* Qn = cand ? p.qC : p.q;
     const Quat qa{Qn[4 * a], Qn[4 * a + 1], Qn[4 * a + 2], Qn[4 * a + 3]}, qb{Qn[4 * b], Qn[4 * b + 1], Qn[4 * b + 2], Qn[4 * b + 3]};
     const Quat qm{p.eq[4 * e], p.eq[4 * e + 1], p.eq[4 * e + 2], p.eq[4 * e + 3]};
-    const double* si = p.esq + 6 * e;
+    const double one[6] = {1.0, 1.0, 1.0, 1.0, 1.0, 1.0};
+    const double* si = UNIT ? one : p.esq + 6 * e;
     const Mat3 Ra = quatToR(qa);
     double pab[3];
     for (int k = 0; k < 3; ++k) pab[k] = Ra.m[k] * d[0] + Ra.m[3 + k] * d[1] + Ra.m[6 + k] * d[2];
@@ -232,6 +238,103 @@ __global__ __launch_bounds__(128) void k_pg_eval(PgDev p, int cand, int withJac,
       } else {
         cost = 0.5 * s;
       }
+    } else {
+      cost = 0.5 * s;
+    }
+    if (withJac) {
+#pragma unroll
+      for (int k = 0; k < R; ++k) p.res[(size_t)e * R + k] = sc * r[k];
+#pragma unroll
+      for (int k = 0; k < RD; ++k) { p.Ja[(size_t)e * RD + k] = sc * Ja[k]; p.Jb[(size_t)e * RD + k] = sc * Jb[k]; }
+    }
+  }
+  const double bs = pgBlockSum(cost, red);
+  if (threadIdx.x == 0) p.partial[PG_COST * kPgMaxPartials + blockIdx.x] = bs;
+  if (finalReduceNodeBlocks <= 0) return;
+  // candidate evaluation = last kernel of an iteration: whichever block finishes last reduces every scalar of the
+  // iteration (one launch less per iteration)
+  __shared__ int isLast;
+  __threadfence();
+  __syncthreads();
+  if (threadIdx.x == 0) isLast = atomicAdd(p.ticket, 1) == (int)gridDim.x - 1;
+  __syncthreads();
+  if (!isLast) return;
+  __threadfence();
+  pgFinalReduce(p, gridDim.x, finalReduceNodeBlocks, red);
+  if (threadIdx.x == 0) *p.ticket = 0;
+}
+
+// Caller-given edges (svin_pg_add_edge, pg_edges.hpp): per edge of the list its slot among them (-1: a built-in edge), per
+// slot the packed upper-triangular factor S (NS = R (R + 1) / 2 doubles, row k = S[k][k .. R - 1]) and the loss (kind, scale).
+struct PgEdgeDev {
+  const int* slot;
+  const double* S;
+  const double* loss;
+};
+// r = S u, J = S Ju in place, ascending over the rows: row k only needs rows >= k.  Every index is a compile-time constant.
+template <int R, int D>
+__device__ __forceinline__ void pgApplyFactor(const double* Sg, double* r, double* Ja, double* Jb) {
+  constexpr int NS = R * (R + 1) / 2;
+  double S[NS];
+#pragma unroll
+  for (int i = 0; i < NS; ++i) S[i] = Sg[i];
+#pragma unroll
+  for (int k = 0; k < R; ++k) {
+    const int base = k * R - k * (k - 1) / 2;   // pgEdgeFactorAt(R, k, k)
+    double rk = S[base] * r[k];
+#pragma unroll
+    for (int j = k + 1; j < R; ++j) rk += S[base + j - k] * r[j];
+    r[k] = rk;
+#pragma unroll
+    for (int c = 0; c < D; ++c) {
+      double a = S[base] * Ja[k * D + c], b = S[base] * Jb[k * D + c];
+#pragma unroll
+      for (int j = k + 1; j < R; ++j) { a += S[base + j - k] * Ja[j * D + c]; b += S[base + j - k] * Jb[j * D + c]; }
+      Ja[k * D + c] = a;
+      Jb[k * D + c] = b;
+    }
+  }
+}
+// k_pg_eval for an edge list that holds caller-given edges: a built-in edge takes k_pg_eval's expressions, a caller-given one
+// u, Ju by the same pgEdge at unit weights, then its factor and its own loss (dmath.hpp residualLoss on s = |r|^2).  The end of
+// the launch is k_pg_eval's, restated: k_pg_eval itself stays as it was, instruction for instruction.
+template <bool SIX>
+__global__ __launch_bounds__(128) void k_pg_eval_edges(PgDev p, PgEdgeDev ce, int cand, int withJac, int finalReduceNodeBlocks) {
+  constexpr int D = SIX ? 6 : 4, R = D, RD = R * D, NS = R * (R + 1) / 2;
+  __shared__ double red[2];
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  double cost = 0;
+  if (e < p.ne) {
+    double r[R], Ja[RD], Jb[RD];
+    const int slot = ce.slot[e];
+    int kind = p.eloop[e] ? (int)LOSS_HUBER : (int)LOSS_NONE;
+    double a = 0.1;
+    if (slot < 0) {
+      pgEdge<SIX>(p, e, cand != 0, r, Ja, Jb);
+    } else {
+      pgEdge<SIX, true>(p, e, cand != 0, r, Ja, Jb);
+      pgApplyFactor<R, D>(ce.S + (size_t)slot * NS, r, Ja, Jb);
+      kind = (int)ce.loss[2 * slot];
+      a = ce.loss[2 * slot + 1];
+    }
+    double s = 0;
+#pragma unroll
+    for (int k = 0; k < R; ++k) s += r[k] * r[k];
+    double sc = 1.0;
+    if (kind == LOSS_HUBER) {   // k_pg_eval's expressions with the edge's own scale
+      const double b = a * a;
+      if (s > b) {
+        const double rt = sqrt(s);
+        cost = 0.5 * (2.0 * a * rt - b);
+        sc = sqrt(fmax(2.2250738585072014e-308, a / rt));
+      } else {
+        cost = 0.5 * s;
+      }
+    } else if (kind == LOSS_CAUCHY) {
+      double rho0, rho1;
+      residualLoss(LOSS_CAUCHY, a, s, rho0, rho1);
+      cost = 0.5 * rho0;
+      sc = sqrt(rho1);
     } else {
       cost = 0.5 * s;
     }
@@ -336,8 +439,8 @@ __device__ __forceinline__ void pgAssembleNode(const PgDev& p, double radius, in
 }
 
 // one thread per edge between two free nodes: the off-diagonal block J_b^T J_a (rows of b, columns of a), scaled,
-// added to its destination.  At most two edges share a destination block (a sequential and a loop edge between the
-// same pair), so the atomic adds commute exactly.
+// added to its destination.  At most two of these edges share a destination block (a pair with three or more goes to
+// k_pg_assemble_shared and has kind 0 here), so the atomic adds commute exactly.
 template <int D>
 __device__ __forceinline__ void pgAssembleEdge(const PgDev& p, int vb) {
   constexpr int R = D;
@@ -378,6 +481,42 @@ __global__ __launch_bounds__(128) void k_pg_assemble(PgDev p, double radius, int
   if (blockIdx.x == 0 && threadIdx.x == 0) *p.fail = 0;   // (read back after the solve; set by the piece / dense factorisations)
   if ((int)blockIdx.x < nNodeBlocks) pgAssembleNode(p, radius, blockIdx.x);
   else pgAssembleEdge<D>(p, blockIdx.x - nNodeBlocks);
+}
+
+// where an edge's off-diagonal block goes (pgAssembleEdge's addresses): entry (r, c) of the block sits at base[r * ld + c]
+__device__ __forceinline__ double* pgEdgeDstBase(const PgDev& p, const int4& dst, int kind, size_t& ld) {
+  if (kind == 1) { ld = p.nS; return p.HS + (size_t)dst.z * p.nS + dst.w; }
+  const PgPiece pc = p.pieces[dst.y];
+  if (kind == 2) { ld = p.BW; return p.band + pc.bandOff + (size_t)dst.z * (p.BW + 1) + (dst.w - dst.z + p.BW); }  // (r, c) -> r * LDB + c - r + BW
+  ld = pc.ld;
+  return p.Y + pc.yOff + (size_t)dst.z * pc.ld + dst.w;
+}
+// The blocks of pairs that carry three or more edges (pg_edges.hpp pgSharedDestinations): one thread per entry of the
+// block adds the edges' terms in the order of the edge list and stores the sum -- nothing else writes these blocks.  The
+// edges of such a pair keep their destination in edgeDst with the kind moved to bits 8-11, which pgAssembleEdge skips.
+template <int D>
+__global__ __launch_bounds__(128) void k_pg_assemble_shared(PgDev p, const int* sPtr, const int* sEdge, int nGroups) {
+  constexpr int R = D, DD = D * D;
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= nGroups * DD) return;
+  const int g = idx / DD, r = (idx - g * DD) / D, c = idx - g * DD - r * D;
+  double acc = 0;
+  for (int i = sPtr[g]; i < sPtr[g + 1]; ++i) {
+    const int e = sEdge[i];
+    const int rowIsB = (p.edgeDst[e].x >> 4) & 1;
+    const int c1 = rowIsB ? r : c, c2 = rowIsB ? c : r;   // J_b's column, J_a's column
+    const double* Ja = p.Ja + (size_t)e * R * D;
+    const double* Jb = p.Jb + (size_t)e * R * D;
+    double s = 0;
+#pragma unroll
+    for (int q = 0; q < R; ++q) s += Jb[q * D + c1] * Ja[q * D + c2];
+    s *= p.scale[p.off[p.eb[e]] + c1] * p.scale[p.off[p.ea[e]] + c2];
+    acc += s;
+  }
+  const int4 dst = p.edgeDst[sEdge[sPtr[g]]];
+  size_t ld;
+  double* base = pgEdgeDstBase(p, dst, (dst.x >> 8) & 15, ld);
+  base[(size_t)r * ld + c] = acc;
 }
 
 // ---------------------------------------------------------------- pieces
@@ -1010,6 +1149,16 @@ struct Keyframe {
   double loopT[3] = {0, 0, 0}, loopQ[4] = {0, 0, 0, 1}, loopYaw = 0;
 };
 
+// a caller-given edge (svin_pg_add_edge): the pose of keyframe b in the frame of keyframe a, its factor S (pg_edges.hpp) and loss
+struct CallerEdge {
+  int id = 0, indexA = 0, indexB = 0;
+  double t[3] = {0, 0, 0}, q[4] = {0, 0, 0, 1}, yaw = 0;
+  double S[21] = {0};
+  double info[36] = {0};   // as given, or S^T S of the default weights
+  int lossKind = 0;
+  double lossScale = 1.0;
+};
+
 template <class T>
 struct Buf {
   T* p = nullptr;
@@ -1104,6 +1253,8 @@ class PoseGraph {
   }
 
   std::vector<Keyframe> kfs;
+  std::vector<CallerEdge> edges;   // svin_pg_add_edge, in the order of the calls
+  int nextEdgeId = 1;              // ids are not reused within a handle
   double summary[8] = {0, 0, 0, 1, 0, 0, 0, 0};   // [6] = seconds of the symbolic step (host)
   int partition[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}; // [7] level-2 pieces, [8] root unknowns; [5] = unknowns of the dense solve       // free keyframes, separator keyframes, pieces, max piece rows, Schur tiles,
                                                   // separator unknowns, timed dense solves ([7] of summary = their seconds)
@@ -1159,6 +1310,17 @@ class PoseGraph {
     std::unordered_map<int, size_t> posOfIndex;
     posOfIndex.reserve(kfs.size() * 2);
     for (size_t k = 0; k < kfs.size(); ++k) posOfIndex[kfs[k].index] = k;
+    // caller-given edges: each at the turn of its later keyframe (list order), in the order of the add_edge calls
+    std::vector<int> ekind, eid, eslot;                 // per edge: 0 sequential, 1 loop, 2 caller; edge id; slot among the caller edges
+    std::vector<double> cS, cLoss;                      // per slot: packed factor, (kind, scale)
+    std::vector<std::pair<size_t, int>> callerAt;       // (position of the later keyframe, entry of `edges`)
+    for (size_t c = 0; c < edges.size(); ++c) {
+      const auto pa = posOfIndex.find(edges[c].indexA), pb = posOfIndex.find(edges[c].indexB);
+      if (pa != posOfIndex.end() && pb != posOfIndex.end()) callerAt.push_back({std::max(pa->second, pb->second), (int)c});
+    }
+    std::stable_sort(callerAt.begin(), callerAt.end(), [](const std::pair<size_t, int>& x, const std::pair<size_t, int>& y) { return x.first < y.first; });
+    size_t callerNext = 0;
+    const int NS = pgEdgeFactorSize(six_ ? 6 : 4);
     int i = 0;
     for (size_t k = 0; k < kfs.size(); ++k) {
       const Keyframe& kf = kfs[k];
@@ -1179,6 +1341,7 @@ class PoseGraph {
           const double d[3] = {t[3 * i] - t[3 * (i - j)], t[3 * i + 1] - t[3 * (i - j) + 1], t[3 * i + 2] - t[3 * (i - j) + 2]};
           for (int c = 0; c < 3; ++c) et.push_back(Ra[c] * d[0] + Ra[3 + c] * d[1] + Ra[6 + c] * d[2]);
           ea.push_back(i - j); eb.push_back(i); eloop.push_back(0);
+          ekind.push_back(0); eid.push_back(0); eslot.push_back(-1);
           eyaw.push_back(yaw[i] - yaw[i - j]); epitch.push_back(pitch[i - j]); eroll.push_back(roll[i - j]);
           const double n2 = qa[0] * qa[0] + qa[1] * qa[1] + qa[2] * qa[2] + qa[3] * qa[3];
           const double qai[4] = {-qa[0] / n2, -qa[1] / n2, -qa[2] / n2, qa[3] / n2};
@@ -1195,12 +1358,27 @@ class PoseGraph {
         if (lit != posOfIndex.end()) ci = localOf[lit->second];
         if (ci >= 0) {
           ea.push_back(ci); eb.push_back(i); eloop.push_back(1);
+          ekind.push_back(1); eid.push_back(0); eslot.push_back(-1);
           et.insert(et.end(), kf.loopT, kf.loopT + 3);
           eyaw.push_back(kf.loopYaw); epitch.push_back(pitch[ci]); eroll.push_back(roll[ci]);
           eq.insert(eq.end(), kf.loopQ, kf.loopQ + 4);
           const double si[6] = {20, 20, 20, 100, 100, 100};
           esq.insert(esq.end(), si, si + 6);
         }
+      }
+      while (callerNext < callerAt.size() && callerAt[callerNext].first < k) ++callerNext;   // (their later keyframe is out of the range)
+      for (; callerNext < callerAt.size() && callerAt[callerNext].first == k; ++callerNext) {
+        const CallerEdge& ce = edges[callerAt[callerNext].second];
+        const int la = localOf[posOfIndex[ce.indexA]], lb = localOf[posOfIndex[ce.indexB]];
+        if (la < 0 || lb < 0) continue;   // reaches outside [earliest, cur]: left out
+        ea.push_back(la); eb.push_back(lb); eloop.push_back(2);
+        ekind.push_back(2); eid.push_back(ce.id); eslot.push_back((int)(cLoss.size() / 2));
+        et.insert(et.end(), ce.t, ce.t + 3);
+        eyaw.push_back(ce.yaw); epitch.push_back(pitch[la]); eroll.push_back(roll[la]);
+        eq.insert(eq.end(), ce.q, ce.q + 4);
+        esq.insert(esq.end(), 6, 1.0);   // (unit weights: the factor S comes after)
+        cS.insert(cS.end(), ce.S, ce.S + NS);
+        cLoss.push_back((double)ce.lossKind); cLoss.push_back(ce.lossScale);
       }
       if (kf.index == cur) { ++i; break; }
       ++i;
@@ -1490,6 +1668,10 @@ class PoseGraph {
       }
       edgeDst[e] = d4;
     }
+    // pairs with three or more edges: their blocks are summed in the order of the edge list by k_pg_assemble_shared
+    const PgSharedDst shared = pgSharedDestinations(ne, ea.data(), eb.data(), off.data());
+    for (int e : shared.edge) edgeDst[e].x = ((edgeDst[e].x & 15) << 8) | (edgeDst[e].x & 16);
+    const int nShared = shared.groups(), nCaller = (int)(cLoss.size() / 2);
     // level 2: pieces of cut keyframes; their blocks are copied out of the level-1 separator system
     LevelHost L2;
     std::vector<int4> xDst;   // {kind | transposed << 4, piece, dstRow, dstCol}: 2 band, 3 coupling, 4 right-hand side
@@ -1537,6 +1719,8 @@ class PoseGraph {
     dEt_.upload(et, s_); dEyaw_.upload(eyaw, s_); dEpitch_.upload(epitch, s_); dEroll_.upload(eroll, s_);
     dEq_.upload(eq, s_); dEsq_.upload(esq, s_);
     dNodePtr_.upload(nodePtr, s_); dNodeEdge_.upload(nodeEdge, s_);
+    if (nCaller > 0) { dESlot_.upload(eslot, s_); dES_.upload(cS, s_); dELoss_.upload(cLoss, s_); }
+    if (nShared > 0) { dSPtr_.upload(shared.ptr, s_); dSEdge_.upload(shared.edge, s_); }
     dSepOff_.upload(sepOff, s_); dNodePiece_.upload(nodePiece, s_); dNodeRow_.upload(nodeRow, s_);
     dPieces_.upload(L1.pieces, s_); dEdgeDst_.upload(edgeDst, s_); dColSep_.upload(L1.colSep, s_); dRowTan_.upload(L1.rowMap, s_);
     dTileWork_.upload(L1.tileWork, s_); dGPtr_.upload(L1.gPtr, s_); dGDst_.upload(L1.gDst, s_); dGSrc_.upload(L1.gSrc, s_);
@@ -1613,7 +1797,13 @@ class PoseGraph {
       HIP_OK(hipStreamSynchronize(s_));
     };
     // residuals (+ Jacobians) at the current point or the candidate; finalReduce: the launch also sums the iteration's scalars
+    const PgEdgeDev ce{dESlot_.p, dES_.p, dELoss_.p};
     auto evaluate = [&](bool cand, bool withJac, bool finalReduce) {
+      if (nCaller > 0) {   // (a list of built-in edges runs k_pg_eval as it always did)
+        if (six_) launch(k_pg_eval_edges<true>, dim3(gE), dim3(128), 0, s_, p, ce, cand ? 1 : 0, withJac ? 1 : 0, finalReduce ? gN : 0);
+        else launch(k_pg_eval_edges<false>, dim3(gE), dim3(128), 0, s_, p, ce, cand ? 1 : 0, withJac ? 1 : 0, finalReduce ? gN : 0);
+        return;
+      }
       if (six_) launch(k_pg_eval<true>, dim3(gE), dim3(128), 0, s_, p, cand ? 1 : 0, withJac ? 1 : 0, finalReduce ? gN : 0);
       else launch(k_pg_eval<false>, dim3(gE), dim3(128), 0, s_, p, cand ? 1 : 0, withJac ? 1 : 0, finalReduce ? gN : 0);
     };
@@ -1622,6 +1812,11 @@ class PoseGraph {
       HIP_OK(hipMemsetAsync(p.HS, 0, sizeof(double) * ((size_t)nS * nS + (nPieces > 0 ? workTot : 0)), s_));   // H_S | band | Y (| level 2)
       if (six_) launch(k_pg_assemble<6>, dim3(gN + gE), dim3(128), 0, s_, p, radius, gN);
       else launch(k_pg_assemble<4>, dim3(gN + gE), dim3(128), 0, s_, p, radius, gN);
+      if (nShared > 0) {
+        const unsigned gS = (unsigned)((nShared * D * D + 127) / 128);
+        if (six_) launch(k_pg_assemble_shared<6>, dim3(gS), dim3(128), 0, s_, p, (const int*)dSPtr_.p, (const int*)dSEdge_.p, nShared);
+        else launch(k_pg_assemble_shared<4>, dim3(gS), dim3(128), 0, s_, p, (const int*)dSPtr_.p, (const int*)dSEdge_.p, nShared);
+      }
       if (nPieces > 0) {
         if (six_) launch(k_pg_piece_factor<6, 4>, dim3(nPieces), dim3(kPgPieceThreads), ldsFactor, s_, p);
         else launch(k_pg_piece_factor<4, 2>, dim3(nPieces), dim3(kPgPieceThreads), ldsFactor, s_, p);
@@ -1724,6 +1919,21 @@ class PoseGraph {
           if (cnt) HIP_OK(hipMemcpy(v.data(), d, sizeof(double) * cnt, hipMemcpyDeviceToHost));
         };
         c.put("ea", ea); c.put("eb", eb); c.put("eloop", eloop); c.put("off", off);
+        c.put("ekind", ekind); c.put("eid", eid);
+        {   // the factor and loss in force per edge: diagonal weights and Huber(0.1) on loops for the built-in edges
+          std::vector<double> einfo((size_t)ne * R * R, 0.0), eloss(2 * (size_t)ne, 0.0);
+          for (int e = 0; e < ne; ++e) {
+            double* F = &einfo[(size_t)e * R * R];
+            if (eslot[e] >= 0) {
+              pgEdgeFactorFull(&cS[(size_t)eslot[e] * NS], R, F);
+              eloss[2 * e] = cLoss[2 * eslot[e]]; eloss[2 * e + 1] = cLoss[2 * eslot[e] + 1];
+            } else {
+              for (int k = 0; k < R; ++k) F[k * R + k] = six_ ? esq[6 * (size_t)e + k] : (k == 3 && eloop[e] ? 0.1 : 1.0);
+              eloss[2 * e] = eloop[e] ? (double)LOSS_HUBER : (double)LOSS_NONE; eloss[2 * e + 1] = eloop[e] ? 0.1 : 0.0;
+            }
+          }
+          c.put("einfo", einfo); c.put("eloss", eloss);
+        }
         c.put("et", et); c.put("eyaw", eyaw); c.put("epitch", epitch); c.put("eroll", eroll); c.put("eq", eq); c.put("esq", esq);
         c.put("yaw", yaw); c.put("pitch", pitch); c.put("roll", roll); c.put("t", t); c.put("q", q);
         dev("res", p.res, (size_t)ne * R); dev("Ja", p.Ja, ne * RD); dev("Jb", p.Jb, ne * RD);
@@ -1974,6 +2184,8 @@ class PoseGraph {
   Buf<int> dColSep2_, dRowMap2_, dGPtr2_, dRPtr2_;
   Buf<double> dSp2_;
   Buf<double> dCovX_, dCovOut_;
+  Buf<int> dESlot_, dSPtr_, dSEdge_;   // caller-given edges: slot per edge; shared destination blocks
+  Buf<double> dES_, dELoss_;
   Buf<int> dCovL2_, dCovInt_;
   Buf<int4> dCovPairs_;
 };
@@ -2023,6 +2235,80 @@ int svin_pg_add_keyframe(svin_pg* h, int index, int sequence, const double* t, c
   return -3;
 }
 int svin_pg_num_keyframes(const svin_pg* h) { return h ? (int)h->g.kfs.size() : -1; }
+int svin_pg_add_edge(svin_pg* h, int index_a, int index_b, const double* rel_t, const double* rel_q, double rel_yaw_deg,
+                     const double* information, int loss_kind, double loss_scale) try {
+  if (!h) { g_pgError = "svin_pg_add_edge: NULL handle"; return -1; }
+  const bool six = h->g.tangentSize() == 6;
+  const int D = h->g.tangentSize();
+  auto refuse = [](const std::string& why) { g_pgError = "svin_pg_add_edge: " + why; return -1; };
+  if (!rel_t || (six && !rel_q)) return refuse("NULL measurement");
+  if (index_a == index_b) return refuse("an edge needs two keyframes");
+  svin::pg::CallerEdge ce;
+  ce.indexA = index_a; ce.indexB = index_b;
+  std::memcpy(ce.t, rel_t, sizeof(ce.t));
+  if (rel_q) std::memcpy(ce.q, rel_q, sizeof(ce.q));
+  ce.yaw = six ? 0.0 : rel_yaw_deg;
+  bool finite = std::isfinite(ce.yaw);
+  for (int c = 0; c < 3; ++c) finite = finite && std::isfinite(ce.t[c]);
+  for (int c = 0; c < 4; ++c) finite = finite && std::isfinite(ce.q[c]);
+  if (!finite) return refuse("the measurement is not finite");
+  if (!svin::pgEdgeLossValid(loss_kind, loss_scale)) return refuse("unknown loss kind, or a loss scale that is not finite and > 0");
+  ce.lossKind = loss_kind;
+  ce.lossScale = loss_kind == 0 ? 1.0 : loss_scale;
+  if (information) {
+    const int st = svin::pgEdgeFactor(information, D, ce.S);
+    if (st != svin::PG_INFO_OK) return refuse(svin::pgInfoStatusText(st));
+    std::memcpy(ce.info, information, sizeof(double) * D * D);
+  } else {
+    svin::pgEdgeDefaultFactor(six, ce.S);
+    svin::pgEdgeFactorGram(ce.S, D, ce.info);
+  }
+  bool haveA = false, haveB = false;
+  for (const svin::pg::Keyframe& kf : h->g.kfs) { haveA = haveA || kf.index == index_a; haveB = haveB || kf.index == index_b; }
+  if (!haveA || !haveB) {
+    g_pgError = "svin_pg_add_edge: keyframe " + std::to_string(haveA ? index_b : index_a) + " is not in the list";
+    return -2;
+  }
+  ce.id = h->g.nextEdgeId;
+  h->g.edges.push_back(ce);
+  ++h->g.nextEdgeId;
+  h->g.invalidateCovariance();
+  return ce.id;
+} catch (const std::exception& e) {
+  g_pgError = e.what();
+  return -3;
+}
+int svin_pg_remove_edge(svin_pg* h, int edge_id) {
+  if (!h) return -1;
+  for (size_t i = 0; i < h->g.edges.size(); ++i)
+    if (h->g.edges[i].id == edge_id) {
+      h->g.edges.erase(h->g.edges.begin() + (std::ptrdiff_t)i);
+      h->g.invalidateCovariance();
+      return 1;
+    }
+  g_pgError = "svin_pg_remove_edge: no edge " + std::to_string(edge_id);
+  return -2;
+}
+int svin_pg_num_edges(const svin_pg* h) { return h ? (int)h->g.edges.size() : -1; }
+int svin_pg_get_edge(const svin_pg* h, int edge_id, int* index_a, int* index_b, double* rel_t, double* rel_q, double* rel_yaw_deg,
+                     double* information, int* loss_kind, double* loss_scale) {
+  if (!h) return -1;
+  for (const svin::pg::CallerEdge& ce : h->g.edges) {
+    if (ce.id != edge_id) continue;
+    const int D = h->g.tangentSize();
+    if (index_a) *index_a = ce.indexA;
+    if (index_b) *index_b = ce.indexB;
+    if (rel_t) std::memcpy(rel_t, ce.t, sizeof(ce.t));
+    if (rel_q) std::memcpy(rel_q, ce.q, sizeof(ce.q));
+    if (rel_yaw_deg) *rel_yaw_deg = ce.yaw;
+    if (information) std::memcpy(information, ce.info, sizeof(double) * D * D);
+    if (loss_kind) *loss_kind = ce.lossKind;
+    if (loss_scale) *loss_scale = ce.lossScale;
+    return 1;
+  }
+  g_pgError = "svin_pg_get_edge: no edge " + std::to_string(edge_id);
+  return -2;
+}
 int svin_pg_optimize(svin_pg* h, int earliest_loop_index, int cur_index) {
   if (!h) return -1;
   try {

@@ -15,7 +15,9 @@ PG_EXPORTS = [
     "svin_pg_optimize", "svin_pg_get_pose", "svin_pg_get_poses", "svin_pg_get_drift", "svin_pg_summary",
     "svin_pg_set_partition", "svin_pg_get_partition", "svin_pg_set_levels", "svin_pg_debug_step", "svin_pg_debug_array",
     "svin_pg_get_covariance_blocks", "svin_pg_get_covariance", "svin_pg_covariance_counters",
+    "svin_pg_add_edge", "svin_pg_remove_edge", "svin_pg_num_edges", "svin_pg_get_edge",
 ]
+LOSS_NONE, LOSS_CAUCHY, LOSS_HUBER = 0, 1, 2   # svin_ba.h SVIN_LOSS_*
 ERR_SINGULAR = -5   # SVIN_PG_ERR_SINGULAR
 
 
@@ -25,9 +27,9 @@ DEBUG_ARRAYS = [
     "ea", "eb", "eloop", "off", "et", "eyaw", "epitch", "eroll", "eq", "esq", "yaw", "pitch", "roll", "t", "q",
     "res", "Ja", "Jb", "g", "scale", "colsq", "nodeBlk", "y", "yS", "cost", "costC", "gradmax", "model", "step2", "x2",
     "cholFail", "yawC", "tC", "qC", "rows", "cols", "rows2", "cols2", "sepOff", "nodePiece", "nodeRow", "isCover",
-    "isRoot", "l2PieceOf", "nS", "nR", "nPieces", "nPieces2", "BW", "BW2",
+    "isRoot", "l2PieceOf", "nS", "nR", "nPieces", "nPieces2", "BW", "BW2", "ekind", "einfo", "eloss", "eid",
 ]
-_DEBUG_INTS = {"ea", "eb", "eloop", "off", "cholFail", "rows", "cols", "rows2", "cols2", "sepOff", "nodePiece", "nodeRow",
+_DEBUG_INTS = {"ea", "eb", "eloop", "ekind", "eid", "off", "cholFail", "rows", "cols", "rows2", "cols2", "sepOff", "nodePiece", "nodeRow",
                "isCover", "isRoot", "l2PieceOf", "nS", "nR", "nPieces", "nPieces2", "BW", "BW2"}
 _DEBUG_SCALARS = {"cost", "costC", "gradmax", "model", "step2", "x2", "cholFail", "nS", "nR", "nPieces", "nPieces2", "BW", "BW2"}
 
@@ -63,6 +65,10 @@ def _lib():
         sig("svin_pg_get_covariance_blocks", C.c_longlong, vp, i32, i32, i32, pi, pi, pd, C.c_longlong)
         sig("svin_pg_get_covariance", i32, vp, i32, i32, i32, i32, pd, i32)
         sig("svin_pg_covariance_counters", i32, vp, C.POINTER(C.c_longlong))
+        sig("svin_pg_add_edge", i32, vp, i32, i32, pd, pd, f64, pd, i32, f64)
+        sig("svin_pg_remove_edge", i32, vp, i32)
+        sig("svin_pg_num_edges", i32, vp)
+        sig("svin_pg_get_edge", i32, vp, i32, pi, pi, pd, pd, pd, pd, pi, pd)
         _BOUND = True
     return L
 
@@ -103,6 +109,32 @@ class PoseGraph:
             rq = np.ascontiguousarray(rq, np.float64)
             self._check(self.L.svin_pg_add_keyframe(self.h, index, sequence, _p(t), _p(q), int(li), _p(rt), _p(rq), float(ry)),
                         "add_keyframe")
+
+    def add_edge(self, index_a, index_b, rel_t, rel_q=None, rel_yaw_deg=0.0, information=None, loss=LOSS_NONE, loss_scale=1.0):
+        """a caller-given edge: the pose of keyframe b in the frame of keyframe a (rel_t, rel_q xyzw in 6-DoF, rel_yaw_deg in
+        4-DoF), information D x D or None for the loop-edge weights, loss one of LOSS_NONE / LOSS_CAUCHY / LOSS_HUBER on
+        |S u|^2; returns the edge id"""
+        rt = np.ascontiguousarray(rel_t, np.float64)
+        rq = None if rel_q is None else np.ascontiguousarray(rel_q, np.float64)
+        info = None if information is None else np.ascontiguousarray(information, np.float64)
+        return self._check(self.L.svin_pg_add_edge(self.h, int(index_a), int(index_b), _p(rt), None if rq is None else _p(rq),
+                                                   float(rel_yaw_deg), None if info is None else _p(info), int(loss),
+                                                   float(loss_scale)), "add_edge")
+
+    def remove_edge(self, edge_id):
+        self._check(self.L.svin_pg_remove_edge(self.h, int(edge_id)), "remove_edge")
+
+    def num_edges(self):
+        return self.L.svin_pg_num_edges(self.h)
+
+    def get_edge(self, edge_id):
+        D = 6 if self.six else 4
+        ia, ib, lk = C.c_int(0), C.c_int(0), C.c_int(0)
+        t, q, yaw, info, ls = np.zeros(3), np.zeros(4), np.zeros(1), np.zeros((D, D)), np.zeros(1)
+        self._check(self.L.svin_pg_get_edge(self.h, int(edge_id), C.byref(ia), C.byref(ib), _p(t), _p(q), _p(yaw), _p(info),
+                                            C.byref(lk), _p(ls)), "get_edge")
+        return dict(index_a=ia.value, index_b=ib.value, rel_t=t, rel_q=q, rel_yaw_deg=float(yaw[0]), information=info,
+                    loss=lk.value, loss_scale=float(ls[0]))
 
     def optimize(self, earliest_loop_index, cur_index):
         self._check(self.L.svin_pg_optimize(self.h, earliest_loop_index, cur_index), "optimize")
