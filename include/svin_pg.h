@@ -75,6 +75,54 @@ int svin_pg_num_edges(const svin_pg* h);
 int svin_pg_get_edge(const svin_pg* h, int edge_id, int* index_a, int* index_b, double* rel_t, double* rel_q,
                      double* rel_yaw_deg, double* information, int* loss_kind, double* loss_scale);
 
+/* ---- absolute keyframe measurements and the gauge (no reference counterpart: pose_graph only knows relative constraints)
+ *
+ * A prior says where ONE keyframe is: a depth from the pressure sensor, a GPS / USBL fix, a surveyed marker, a full pose.  The
+ * measurement is in the frame of the variables the optimisation moves -- the frame svin_pg_get_pose answers in.  kind:
+ * SVIN_PG_PRIOR_POSE (m = D rows: t, and q in 6-DoF or yaw_deg in 4-DoF), SVIN_PG_PRIOR_POSITION (m = 3 rows: t),
+ * SVIN_PG_PRIOR_DEPTH (m = 1 row: t[2]; t[0], t[1], q and yaw_deg are not read).  q and yaw_deg are only read by POSE (q may be
+ * NULL otherwise, and always in 4-DoF); q is a unit quaternion [x y z w], its conjugate is taken for its inverse.
+ *
+ * Residual.  u follows the order of the edges' u: 4-DoF [t_k - t (metres), wrap(yaw_k - yaw_deg) (degrees)], 6-DoF [t_k - t,
+ * 2 vec(q_k q^-1)]; POSITION keeps rows 0..2, DEPTH row 2.  r = S u_sel with S = L^T, information = L L^T: m x m row-major in the
+ * order of the kept rows, NULL = identity.  The loss (kinds and scale as for svin_pg_add_edge) acts on s = |r|^2, the prior's cost
+ * is rho(s) / 2.  Jacobians in the solver's tangent (4-DoF [yaw, t], 6-DoF [t, dq] with q <- [sin|d| d/|d|, cos|d|] q): identity
+ * on t, 1 on yaw, 2 (e_w I - [e_v]x) on dq with e = q_k q^-1.  q is used with the sign given: q and -q are the same rotation but
+ * flip the sign of the rotation rows of u.  That is without effect under an information that does not couple rotation with
+ * translation; with one that does, hand over the q of the hemisphere of q_k (their dot product positive).
+ *
+ * `index` resolves to the last keyframe of the list with that index when a problem is built.  A prior joins
+ * svin_pg_optimize(earliest, cur), svin_pg_debug_step and svin_pg_get_covariance_blocks when its keyframe is in the range; it
+ * stands in the list at its keyframe's turn, after that keyframe's sequential, loop and caller-given edges, in the order of the
+ * add_prior calls.  A prior on a constant keyframe adds to the cost only.  A keyframe may be held by priors alone.
+ *
+ * The gauge.  gauge = 0 (default) keeps the reference's constant keyframes: the first of the range, and in 6-DoF every keyframe of
+ * sequence 0.  gauge = 1 holds none constant; the priors then have to tie the graph to the world.  Enough for a connected graph:
+ * 6-DoF position on three keyframes that are not collinear, or one POSE; 4-DoF (pitch and roll are not variables) position on two
+ * keyframes that differ horizontally, or one POSE.  DEPTH priors alone never are.  With too few, svin_pg_optimize still runs (the
+ * Levenberg-Marquardt diagonal makes every system solvable) and svin_pg_get_covariance_blocks answers SVIN_PG_ERR_SINGULAR
+ * through its pivot test.  Covariances are relative to whatever ties the graph: the constant keyframes at gauge 0, the priors at
+ * gauge 1, where no block is zero.
+ *
+ * svin_pg_add_prior returns the prior id (>= 1, a space of its own, never reused within a handle); -1 for a NULL handle, an unknown
+ * kind, NULL t, NULL q for a 6-DoF POSE, numbers that are not finite, an unknown loss kind, a loss_scale that is not finite and > 0
+ * (ignored for NONE), an information that is not symmetric entry by entry, not finite or not positive definite (the pivot rule of
+ * svin_pg_add_edge on the m x m matrix); -2 for an unknown keyframe index or prior id; svin_pg_set_gauge -1 for a gauge other than
+ * 0 / 1.  A refused call changes nothing.  add_prior, remove_prior and set_gauge drop the kept covariance factor.
+ * svin_pg_get_prior fills whichever outputs are not NULL: t (3; zeros where not read), q (4; identity where not read), information
+ * m x m (the identity where NULL was given). */
+#define SVIN_PG_PRIOR_POSE     0
+#define SVIN_PG_PRIOR_POSITION 1
+#define SVIN_PG_PRIOR_DEPTH    2
+int svin_pg_add_prior(svin_pg* h, int index, int kind, const double* t, const double* q, double yaw_deg,
+                      const double* information, int loss_kind, double loss_scale);
+int svin_pg_remove_prior(svin_pg* h, int prior_id);
+int svin_pg_num_priors(const svin_pg* h);
+int svin_pg_get_prior(const svin_pg* h, int prior_id, int* index, int* kind, double* t, double* q, double* yaw_deg,
+                      double* information, int* loss_kind, double* loss_scale);
+int svin_pg_set_gauge(svin_pg* h, int gauge);   /* 0 = the reference's constant keyframes (default), 1 = free */
+int svin_pg_get_gauge(const svin_pg* h);
+
 /* one pass of the optimisation thread's loop body for cur_index (PoseGraph.cpp:236-351 / :397-516): keyframes with
  * index >= earliest_loop_index up to cur_index are optimised, their poses updated in place */
 int svin_pg_optimize(svin_pg* h, int earliest_loop_index, int cur_index);
@@ -115,7 +163,7 @@ int svin_pg_summary(const svin_pg* h, double* out6);
  * tangent coordinates: 4-DoF [yaw in degrees, t], 6-DoF [t, dq] with q <- [sin|d| d/|d|, cos|d|] q.  The units are those of the
  * reference's residual weights (sqrt-information 20 / 100 / 57.3 of the 6-DoF edges, unit weights and the 0.1 loop-yaw weight of
  * the 4-DoF edges), not metres and radians of a calibrated sensor model; an edge given with a measured information matrix
- * (svin_pg_add_edge) enters in the units of that matrix.  Covariances are relative to the constant keyframe(s).
+ * (svin_pg_add_edge) enters in the units of that matrix.  Covariances are relative to the constant keyframe(s), or at gauge 1 to the priors (svin_pg_set_gauge).
  *
  * The block of (index_a, index_b) -- the `index` values given to svin_pg_add_keyframe -- is Sigma[a, b], D x D row-major, D = 4
  * or 6.  A constant keyframe has exactly zero covariance with everything; Sigma[b, a] is Sigma[a, b]^T bit for bit; two calls
@@ -129,7 +177,7 @@ int svin_pg_summary(const svin_pg* h, double* out6);
  * -- a pivot that is not positive or below 1e-12 of its diagonal entry of the Jacobi-scaled J^T J; svin_pg_last_error() then names
  * the keyframe index whose block met the pivot, or "root"; nothing is kept and the handle stays usable.  Nothing is written back:
  * poses, drift, summary and partition record stay as they were.  The factor of the last call is kept and reused until
- * svin_pg_add_keyframe, svin_pg_add_edge, svin_pg_remove_edge, svin_pg_optimize, svin_pg_debug_step, svin_pg_set_partition or svin_pg_set_levels is called or another
+ * svin_pg_add_keyframe, svin_pg_add_edge, svin_pg_remove_edge, svin_pg_add_prior, svin_pg_remove_prior, svin_pg_set_gauge, svin_pg_optimize, svin_pg_debug_step, svin_pg_set_partition or svin_pg_set_levels is called or another
  * (earliest_loop_index, cur_index) is given. */
 #define SVIN_PG_ERR_SINGULAR (-5)
 /* n_pairs blocks back to back; cov == NULL only sizes; returns the doubles written (n_pairs * D * D) */
@@ -148,9 +196,9 @@ int svin_pg_covariance_counters(const svin_pg* h, long long out4[4]);
  * keyframes stay untouched.  Returns 1, 0 when there is nothing to optimise, <0 on error. */
 int svin_pg_debug_step(svin_pg* h, int earliest_loop_index, int cur_index, double radius);
 /* copies the named array of the last svin_pg_debug_step (as doubles; ints converted) and returns its length, -2 for an
- * unknown name; out == NULL just returns the length.  Names: local problem ea eb eloop (0 sequential, 1 loop, 2 caller-given) off
- * et eyaw epitch eroll eq esq (ones on caller-given edges) yaw pitch roll t q; ekind (0 sequential, 1 loop, 2 caller) einfo
- * (ne x D x D, the factor S applied, diagonal for the built-in edges) eloss (ne x 2: kind, scale) eid (edge id, 0 = built-in); device res Ja Jb (robustified) g scale colsq nodeBlk (nodes x D x D, lower triangle) y yS
+ * unknown name; out == NULL just returns the length.  Names: local problem ea eb (eb = ea on a prior) eloop (0 sequential, 1 loop, 2 caller-given, 3 prior) off
+ * et eyaw epitch eroll eq esq (ones on caller-given edges) yaw pitch roll t q; ekind (0 sequential, 1 loop, 2 caller, 3 prior) einfo
+ * (ne x D x D, the factor S applied, diagonal for the built-in edges, a prior's embedded in the rows it keeps) eloss (ne x 2: kind, scale) eid (edge or prior id, 0 = built-in) eprior (prior kind, -1 on other entries); device res Ja Jb (robustified) g scale colsq nodeBlk (nodes x D x D, lower triangle) y yS
  * cost costC gradmax model step2 x2 cholFail yawC tC qC; partition rows cols rows2 cols2 (per piece of level 1 / 2)
  * sepOff nodePiece nodeRow isCover isRoot l2PieceOf (per node) nS nR nPieces nPieces2 BW BW2 */
 long long svin_pg_debug_array(const svin_pg* h, const char* name, double* out, long long cap);

@@ -26,12 +26,15 @@
 // Caller-given edges (svin_pg_add_edge; pg_edges.hpp) stand in the same edge list: k_pg_eval_edges evaluates
 // a list that holds any (unit-weight residual, the edge's upper-triangular factor, its own loss), k_pg_assemble_shared sums the
 // blocks of keyframe pairs that carry three or more edges in a fixed order; everything downstream reads res / Ja / Jb as before.
+// Absolute keyframe measurements (svin_pg_add_prior; pg_priors.hpp) are one-ended entries of that list:
+// k_pg_eval_terms evaluates a list that holds any; svin_pg_set_gauge chooses whether the reference's keyframes stay constant.
 // Marginal covariances of keyframes (svin_pg_get_covariance_blocks): k_pg_cov_* below push unit right-hand sides through the same
 // nested factorisation, undamped, the root on the blocked route whose factor stays in cholL (pg_cov_plan.hpp).
 #include "kernels.hpp"
 #include "dmath.hpp"
 #include "pg_cov_plan.hpp"
 #include "pg_edges.hpp"
+#include "pg_priors.hpp"
 #include "../../include/svin_pg.h"
 
 #include <algorithm>
@@ -322,6 +325,109 @@ __global__ __launch_bounds__(128) void k_pg_eval_edges(PgDev p, PgEdgeDev ce, in
     for (int k = 0; k < R; ++k) s += r[k] * r[k];
     double sc = 1.0;
     if (kind == LOSS_HUBER) {   // k_pg_eval's expressions with the edge's own scale
+      const double b = a * a;
+      if (s > b) {
+        const double rt = sqrt(s);
+        cost = 0.5 * (2.0 * a * rt - b);
+        sc = sqrt(fmax(2.2250738585072014e-308, a / rt));
+      } else {
+        cost = 0.5 * s;
+      }
+    } else if (kind == LOSS_CAUCHY) {
+      double rho0, rho1;
+      residualLoss(LOSS_CAUCHY, a, s, rho0, rho1);
+      cost = 0.5 * rho0;
+      sc = sqrt(rho1);
+    } else {
+      cost = 0.5 * s;
+    }
+    if (withJac) {
+#pragma unroll
+      for (int k = 0; k < R; ++k) p.res[(size_t)e * R + k] = sc * r[k];
+#pragma unroll
+      for (int k = 0; k < RD; ++k) { p.Ja[(size_t)e * RD + k] = sc * Ja[k]; p.Jb[(size_t)e * RD + k] = sc * Jb[k]; }
+    }
+  }
+  const double bs = pgBlockSum(cost, red);
+  if (threadIdx.x == 0) p.partial[PG_COST * kPgMaxPartials + blockIdx.x] = bs;
+  if (finalReduceNodeBlocks <= 0) return;
+  // candidate evaluation = last kernel of an iteration: whichever block finishes last reduces every scalar of the
+  // iteration (one launch less per iteration)
+  __shared__ int isLast;
+  __threadfence();
+  __syncthreads();
+  if (threadIdx.x == 0) isLast = atomicAdd(p.ticket, 1) == (int)gridDim.x - 1;
+  __syncthreads();
+  if (!isLast) return;
+  __threadfence();
+  pgFinalReduce(p, gridDim.x, finalReduceNodeBlocks, red);
+  if (threadIdx.x == 0) *p.ticket = 0;
+}
+
+// Absolute keyframe measurements (svin_pg_add_prior, pg_priors.hpp): a one-ended entry of the list, ea = eb
+// = its keyframe, eloop = 3, the measurement in et / eyaw / eq.  u and Ju = du / d(tangent of the keyframe) at unit weight, in the
+// order of the edges' u: 4-DoF [t_k - t_m, wrap(yaw_k - yaw_m)], tangent [yaw, t]; 6-DoF [t_k - t_m, 2 vec(e)], e = q_k q_m^-1
+// (q_m a unit quaternion, its conjugate for its inverse), tangent [t, dq]: q_k <- [d, 1] q_k to first order moves e by [d, 0] e,
+// whose vector part is e_w d + d x e_v, so d(2 vec e) / dd = 2 (e_w I - [e_v]x).
+template <bool SIX>
+__device__ __forceinline__ void pgPrior(const PgDev& p, int e, bool cand, double* u, double* Ju) {
+  constexpr int D = SIX ? 6 : 4;
+  const int k = p.ea[e];
+  const double* T = cand ? p.tC : p.t;
+#pragma unroll
+  for (int i = 0; i < D * D; ++i) Ju[i] = 0.0;
+  if constexpr (!SIX) {
+    const double* Y = cand ? p.yawC : p.yaw;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { u[c] = T[3 * k + c] - p.et[3 * e + c]; Ju[c * 4 + 1 + c] = 1.0; }
+    u[3] = pgNormalizeAngle(Y[k] - p.eyaw[e]);
+    Ju[12] = 1.0;
+  } else {
+    const double* Qn = cand ? p.qC : p.q;
+    const Quat qk{Qn[4 * k], Qn[4 * k + 1], Qn[4 * k + 2], Qn[4 * k + 3]};
+    const Quat qe = qmul(qk, Quat{-p.eq[4 * e], -p.eq[4 * e + 1], -p.eq[4 * e + 2], p.eq[4 * e + 3]});
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { u[c] = T[3 * k + c] - p.et[3 * e + c]; Ju[c * 6 + c] = 1.0; }
+    u[3] = 2.0 * qe.x; u[4] = 2.0 * qe.y; u[5] = 2.0 * qe.z;
+    Ju[3 * 6 + 3] = 2.0 * qe.w;  Ju[3 * 6 + 4] = 2.0 * qe.z;  Ju[3 * 6 + 5] = -2.0 * qe.y;
+    Ju[4 * 6 + 3] = -2.0 * qe.z; Ju[4 * 6 + 4] = 2.0 * qe.w;  Ju[4 * 6 + 5] = 2.0 * qe.x;
+    Ju[5 * 6 + 3] = 2.0 * qe.y;  Ju[5 * 6 + 4] = -2.0 * qe.x; Ju[5 * 6 + 5] = 2.0 * qe.w;
+  }
+}
+// k_pg_eval_edges for a list that holds priors: sequential, loop and caller-given entries take its expressions, a prior u, Ju by
+// pgPrior, then its embedded factor (the rows it does not keep come out zero) and its own loss; its Jb is stored as zeros, so
+// that everything downstream reads the entry like any other.  The end of the launch is k_pg_eval's, restated once more, for the
+// reason section 9b gives: k_pg_eval and k_pg_eval_edges stay as they were, instruction for instruction.
+template <bool SIX>
+__global__ __launch_bounds__(128) void k_pg_eval_terms(PgDev p, PgEdgeDev ce, int cand, int withJac, int finalReduceNodeBlocks) {
+  constexpr int D = SIX ? 6 : 4, R = D, RD = R * D, NS = R * (R + 1) / 2;
+  __shared__ double red[2];
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  double cost = 0;
+  if (e < p.ne) {
+    double r[R], Ja[RD], Jb[RD];
+    const int slot = ce.slot[e];
+    int kind = p.eloop[e] ? (int)LOSS_HUBER : (int)LOSS_NONE;
+    double a = 0.1;
+    if (slot < 0) {
+      pgEdge<SIX>(p, e, cand != 0, r, Ja, Jb);
+    } else {
+      if (p.eloop[e] == 3) {
+        pgPrior<SIX>(p, e, cand != 0, r, Ja);
+#pragma unroll
+        for (int k = 0; k < RD; ++k) Jb[k] = 0.0;
+      } else {
+        pgEdge<SIX, true>(p, e, cand != 0, r, Ja, Jb);
+      }
+      pgApplyFactor<R, D>(ce.S + (size_t)slot * NS, r, Ja, Jb);
+      kind = (int)ce.loss[2 * slot];
+      a = ce.loss[2 * slot + 1];
+    }
+    double s = 0;
+#pragma unroll
+    for (int k = 0; k < R; ++k) s += r[k] * r[k];
+    double sc = 1.0;
+    if (kind == LOSS_HUBER) {   // k_pg_eval's expressions with the entry's own scale
       const double b = a * a;
       if (s > b) {
         const double rt = sqrt(s);
@@ -1159,6 +1265,17 @@ struct CallerEdge {
   double lossScale = 1.0;
 };
 
+// an absolute measurement of one keyframe (svin_pg_add_prior): kind, the measurement in the frame of the optimised variables, its
+// embedded factor S (pg_priors.hpp) and loss
+struct PriorTerm {
+  int id = 0, index = 0, kind = 0;
+  double t[3] = {0, 0, 0}, q[4] = {0, 0, 0, 1}, yaw = 0;
+  double S[21] = {0};
+  double info[36] = {0};   // m x m as given, or the identity
+  int lossKind = 0;
+  double lossScale = 1.0;
+};
+
 template <class T>
 struct Buf {
   T* p = nullptr;
@@ -1255,6 +1372,9 @@ class PoseGraph {
   std::vector<Keyframe> kfs;
   std::vector<CallerEdge> edges;   // svin_pg_add_edge, in the order of the calls
   int nextEdgeId = 1;              // ids are not reused within a handle
+  std::vector<PriorTerm> priors;   // svin_pg_add_prior, in the order of the calls; ids of their own, not reused either
+  int nextPriorId = 1;
+  int gauge = 0;                   // svin_pg_set_gauge: 0 the reference's constant keyframes, 1 none
   double summary[8] = {0, 0, 0, 1, 0, 0, 0, 0};   // [6] = seconds of the symbolic step (host)
   int partition[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}; // [7] level-2 pieces, [8] root unknowns; [5] = unknowns of the dense solve       // free keyframes, separator keyframes, pieces, max piece rows, Schur tiles,
                                                   // separator unknowns, timed dense solves ([7] of summary = their seconds)
@@ -1311,7 +1431,8 @@ class PoseGraph {
     posOfIndex.reserve(kfs.size() * 2);
     for (size_t k = 0; k < kfs.size(); ++k) posOfIndex[kfs[k].index] = k;
     // caller-given edges: each at the turn of its later keyframe (list order), in the order of the add_edge calls
-    std::vector<int> ekind, eid, eslot;                 // per edge: 0 sequential, 1 loop, 2 caller; edge id; slot among the caller edges
+    std::vector<int> ekind, eid, eslot, eprior;         // per entry: 0 sequential, 1 loop, 2 caller, 3 prior; edge / prior id; slot among
+                                                        // the entries with a factor of their own; prior kind or -1
     std::vector<double> cS, cLoss;                      // per slot: packed factor, (kind, scale)
     std::vector<std::pair<size_t, int>> callerAt;       // (position of the later keyframe, entry of `edges`)
     for (size_t c = 0; c < edges.size(); ++c) {
@@ -1320,8 +1441,16 @@ class PoseGraph {
     }
     std::stable_sort(callerAt.begin(), callerAt.end(), [](const std::pair<size_t, int>& x, const std::pair<size_t, int>& y) { return x.first < y.first; });
     size_t callerNext = 0;
+    // priors: each at the turn of its keyframe (the last of the list with that index), after the keyframe's edges, in call order
+    std::vector<std::pair<size_t, int>> priorAt;        // (position of the keyframe, entry of `priors`)
+    for (size_t c = 0; c < priors.size(); ++c) {
+      const auto pk = posOfIndex.find(priors[c].index);
+      if (pk != posOfIndex.end()) priorAt.push_back({pk->second, (int)c});
+    }
+    std::stable_sort(priorAt.begin(), priorAt.end(), [](const std::pair<size_t, int>& x, const std::pair<size_t, int>& y) { return x.first < y.first; });
+    size_t priorNext = 0;
     const int NS = pgEdgeFactorSize(six_ ? 6 : 4);
-    int i = 0;
+    int i = 0, nPrior = 0;
     for (size_t k = 0; k < kfs.size(); ++k) {
       const Keyframe& kf = kfs[k];
       if (kf.index < earliest) continue;
@@ -1332,7 +1461,7 @@ class PoseGraph {
       t.insert(t.end(), kf.t, kf.t + 3);
       q.insert(q.end(), kf.q, kf.q + 4);
       seq.push_back(kf.sequence);
-      fixed.push_back(six_ ? (kf.index == earliest || kf.sequence == 0) : (kf.index <= earliest));
+      fixed.push_back(gauge == 1 ? false : (six_ ? (kf.index == earliest || kf.sequence == 0) : (kf.index <= earliest)));
       const int nSeq = six_ ? 4 : 2;
       for (int j = 1; j <= nSeq; ++j) {
         if (i - j >= 0 && seq[i] == seq[i - j]) {
@@ -1341,7 +1470,7 @@ class PoseGraph {
           const double d[3] = {t[3 * i] - t[3 * (i - j)], t[3 * i + 1] - t[3 * (i - j) + 1], t[3 * i + 2] - t[3 * (i - j) + 2]};
           for (int c = 0; c < 3; ++c) et.push_back(Ra[c] * d[0] + Ra[3 + c] * d[1] + Ra[6 + c] * d[2]);
           ea.push_back(i - j); eb.push_back(i); eloop.push_back(0);
-          ekind.push_back(0); eid.push_back(0); eslot.push_back(-1);
+          ekind.push_back(0); eid.push_back(0); eslot.push_back(-1); eprior.push_back(-1);
           eyaw.push_back(yaw[i] - yaw[i - j]); epitch.push_back(pitch[i - j]); eroll.push_back(roll[i - j]);
           const double n2 = qa[0] * qa[0] + qa[1] * qa[1] + qa[2] * qa[2] + qa[3] * qa[3];
           const double qai[4] = {-qa[0] / n2, -qa[1] / n2, -qa[2] / n2, qa[3] / n2};
@@ -1358,7 +1487,7 @@ class PoseGraph {
         if (lit != posOfIndex.end()) ci = localOf[lit->second];
         if (ci >= 0) {
           ea.push_back(ci); eb.push_back(i); eloop.push_back(1);
-          ekind.push_back(1); eid.push_back(0); eslot.push_back(-1);
+          ekind.push_back(1); eid.push_back(0); eslot.push_back(-1); eprior.push_back(-1);
           et.insert(et.end(), kf.loopT, kf.loopT + 3);
           eyaw.push_back(kf.loopYaw); epitch.push_back(pitch[ci]); eroll.push_back(roll[ci]);
           eq.insert(eq.end(), kf.loopQ, kf.loopQ + 4);
@@ -1372,13 +1501,26 @@ class PoseGraph {
         const int la = localOf[posOfIndex[ce.indexA]], lb = localOf[posOfIndex[ce.indexB]];
         if (la < 0 || lb < 0) continue;   // reaches outside [earliest, cur]: left out
         ea.push_back(la); eb.push_back(lb); eloop.push_back(2);
-        ekind.push_back(2); eid.push_back(ce.id); eslot.push_back((int)(cLoss.size() / 2));
+        ekind.push_back(2); eid.push_back(ce.id); eslot.push_back((int)(cLoss.size() / 2)); eprior.push_back(-1);
         et.insert(et.end(), ce.t, ce.t + 3);
         eyaw.push_back(ce.yaw); epitch.push_back(pitch[la]); eroll.push_back(roll[la]);
         eq.insert(eq.end(), ce.q, ce.q + 4);
         esq.insert(esq.end(), 6, 1.0);   // (unit weights: the factor S comes after)
         cS.insert(cS.end(), ce.S, ce.S + NS);
         cLoss.push_back((double)ce.lossKind); cLoss.push_back(ce.lossScale);
+      }
+      while (priorNext < priorAt.size() && priorAt[priorNext].first < k) ++priorNext;   // (their keyframe is before the range)
+      for (; priorNext < priorAt.size() && priorAt[priorNext].first == k; ++priorNext) {
+        const PriorTerm& pt = priors[priorAt[priorNext].second];
+        ea.push_back(i); eb.push_back(i); eloop.push_back(3);   // one-ended: eb = ea, Jb stored as zeros
+        ekind.push_back(3); eid.push_back(pt.id); eslot.push_back((int)(cLoss.size() / 2)); eprior.push_back(pt.kind);
+        et.insert(et.end(), pt.t, pt.t + 3);
+        eyaw.push_back(pt.yaw); epitch.push_back(0.0); eroll.push_back(0.0);
+        eq.insert(eq.end(), pt.q, pt.q + 4);
+        esq.insert(esq.end(), 6, 1.0);
+        cS.insert(cS.end(), pt.S, pt.S + NS);
+        cLoss.push_back((double)pt.lossKind); cLoss.push_back(pt.lossScale);
+        ++nPrior;
       }
       if (kf.index == cur) { ++i; break; }
       ++i;
@@ -1418,12 +1560,13 @@ class PoseGraph {
       return 1;
     }
     // incident edges per node (edge order = insertion order: deterministic accumulation)
-    std::vector<int> nodePtr(nn + 1, 0), nodeEdge(2 * (size_t)ne);
-    for (int e = 0; e < ne; ++e) { nodePtr[ea[e] + 1]++; nodePtr[eb[e] + 1]++; }
+    // (a prior is one-ended: ONE incidence, on side a -- a second one would count its block twice)
+    std::vector<int> nodePtr(nn + 1, 0), nodeEdge(2 * (size_t)ne - nPrior);
+    for (int e = 0; e < ne; ++e) { nodePtr[ea[e] + 1]++; if (ekind[e] != 3) nodePtr[eb[e] + 1]++; }
     for (int k = 0; k < nn; ++k) nodePtr[k + 1] += nodePtr[k];
     {
       std::vector<int> curp(nodePtr.begin(), nodePtr.end() - 1);
-      for (int e = 0; e < ne; ++e) { nodeEdge[curp[ea[e]]++] = 2 * e; nodeEdge[curp[eb[e]]++] = 2 * e + 1; }
+      for (int e = 0; e < ne; ++e) { nodeEdge[curp[ea[e]]++] = 2 * e; if (ekind[e] != 3) nodeEdge[curp[eb[e]]++] = 2 * e + 1; }
     }
     const auto tSym0 = std::chrono::steady_clock::now();
     // ---- symbolic step: separators (cuts of w keyframes + a vertex cover of the long edges) and pieces
@@ -1485,7 +1628,7 @@ class PoseGraph {
     std::vector<std::vector<int>> pieceAdjNodes(nPieces);
     for (int e = 0; e < ne; ++e) {
       const int a = ea[e], b = eb[e];
-      if (pos[a] < 0 || pos[b] < 0) continue;
+      if (pos[a] < 0 || pos[b] < 0 || a == b) continue;   // (a == b: a prior, it couples nothing)
       if (!isSep[a] && !isSep[b] && pieceOf[a] != pieceOf[b]) throw std::runtime_error("svin_pg: partition left an edge between two pieces");
       if (!isSep[a] && isSep[b]) pieceAdjNodes[pieceOf[a]].push_back(b);
       if (!isSep[b] && isSep[a]) pieceAdjNodes[pieceOf[b]].push_back(a);
@@ -1507,7 +1650,7 @@ class PoseGraph {
               if (x != y) sepAdj[x].push_back(y);
         for (int e = 0; e < ne; ++e) {
           const int a = ea[e], b = eb[e];
-          if (pos[a] >= 0 && pos[b] >= 0 && isSep[a] && isSep[b]) { sepAdj[a].push_back(b); sepAdj[b].push_back(a); }
+          if (a != b && pos[a] >= 0 && pos[b] >= 0 && isSep[a] && isSep[b]) { sepAdj[a].push_back(b); sepAdj[b].push_back(a); }
         }
         for (int k : freeNodes)
           if (isSep[k]) { auto& A = sepAdj[k]; std::sort(A.begin(), A.end()); A.erase(std::unique(A.begin(), A.end()), A.end()); }
@@ -1653,7 +1796,7 @@ class PoseGraph {
     for (int e = 0; e < ne; ++e) {
       const int a = ea[e], b = eb[e];
       int4 d4 = make_int4(0, 0, 0, 0);
-      if (pos[a] >= 0 && pos[b] >= 0) {
+      if (a != b && pos[a] >= 0 && pos[b] >= 0) {   // (a prior has no off-diagonal block: kind 0)
         if (isSep[a] && isSep[b]) {
           const bool rowB = sepOff[b] > sepOff[a];
           d4 = make_int4(1 | (rowB ? 16 : 0), 0, rowB ? sepOff[b] : sepOff[a], rowB ? sepOff[a] : sepOff[b]);
@@ -1799,6 +1942,11 @@ class PoseGraph {
     // residuals (+ Jacobians) at the current point or the candidate; finalReduce: the launch also sums the iteration's scalars
     const PgEdgeDev ce{dESlot_.p, dES_.p, dELoss_.p};
     auto evaluate = [&](bool cand, bool withJac, bool finalReduce) {
+      if (nPrior > 0) {    // (a list without priors launches what it always did)
+        if (six_) launch(k_pg_eval_terms<true>, dim3(gE), dim3(128), 0, s_, p, ce, cand ? 1 : 0, withJac ? 1 : 0, finalReduce ? gN : 0);
+        else launch(k_pg_eval_terms<false>, dim3(gE), dim3(128), 0, s_, p, ce, cand ? 1 : 0, withJac ? 1 : 0, finalReduce ? gN : 0);
+        return;
+      }
       if (nCaller > 0) {   // (a list of built-in edges runs k_pg_eval as it always did)
         if (six_) launch(k_pg_eval_edges<true>, dim3(gE), dim3(128), 0, s_, p, ce, cand ? 1 : 0, withJac ? 1 : 0, finalReduce ? gN : 0);
         else launch(k_pg_eval_edges<false>, dim3(gE), dim3(128), 0, s_, p, ce, cand ? 1 : 0, withJac ? 1 : 0, finalReduce ? gN : 0);
@@ -1919,7 +2067,7 @@ class PoseGraph {
           if (cnt) HIP_OK(hipMemcpy(v.data(), d, sizeof(double) * cnt, hipMemcpyDeviceToHost));
         };
         c.put("ea", ea); c.put("eb", eb); c.put("eloop", eloop); c.put("off", off);
-        c.put("ekind", ekind); c.put("eid", eid);
+        c.put("ekind", ekind); c.put("eid", eid); c.put("eprior", eprior);
         {   // the factor and loss in force per edge: diagonal weights and Huber(0.1) on loops for the built-in edges
           std::vector<double> einfo((size_t)ne * R * R, 0.0), eloss(2 * (size_t)ne, 0.0);
           for (int e = 0; e < ne; ++e) {
@@ -2309,6 +2457,84 @@ int svin_pg_get_edge(const svin_pg* h, int edge_id, int* index_a, int* index_b, 
   g_pgError = "svin_pg_get_edge: no edge " + std::to_string(edge_id);
   return -2;
 }
+int svin_pg_add_prior(svin_pg* h, int index, int kind, const double* t, const double* q, double yaw_deg, const double* information,
+                      int loss_kind, double loss_scale) try {
+  if (!h) { g_pgError = "svin_pg_add_prior: NULL handle"; return -1; }
+  const bool six = h->g.tangentSize() == 6;
+  const int D = h->g.tangentSize();
+  auto refuse = [](const std::string& why) { g_pgError = "svin_pg_add_prior: " + why; return -1; };
+  if (!svin::pgPriorKindValid(kind)) return refuse("unknown kind");
+  if (!t || (six && kind == svin::PG_PRIOR_POSE && !q)) return refuse("NULL measurement");
+  if (!svin::pgPriorMeasurementFinite(kind, six, t, q, yaw_deg)) return refuse("the measurement is not finite");
+  svin::pg::PriorTerm pt;
+  pt.index = index; pt.kind = kind;
+  if (kind == svin::PG_PRIOR_DEPTH) pt.t[2] = t[2];   // (t[0], t[1], q and yaw_deg are not read)
+  else std::memcpy(pt.t, t, sizeof(pt.t));
+  if (kind == svin::PG_PRIOR_POSE) {
+    if (six) std::memcpy(pt.q, q, sizeof(pt.q));
+    else pt.yaw = yaw_deg;
+  }
+  if (!svin::pgEdgeLossValid(loss_kind, loss_scale)) return refuse("unknown loss kind, or a loss scale that is not finite and > 0");
+  pt.lossKind = loss_kind;
+  pt.lossScale = loss_kind == 0 ? 1.0 : loss_scale;
+  const int m = svin::pgPriorRows(kind, D);
+  const int st = svin::pgPriorFactor(kind, D, information, pt.S);
+  if (st != svin::PG_INFO_OK) return refuse(svin::pgInfoStatusText(st));
+  if (information) std::memcpy(pt.info, information, sizeof(double) * m * m);
+  else for (int k = 0; k < m; ++k) pt.info[k * m + k] = 1.0;
+  bool have = false;
+  for (const svin::pg::Keyframe& kf : h->g.kfs) have = have || kf.index == index;
+  if (!have) {
+    g_pgError = "svin_pg_add_prior: keyframe " + std::to_string(index) + " is not in the list";
+    return -2;
+  }
+  pt.id = h->g.nextPriorId;
+  h->g.priors.push_back(pt);
+  ++h->g.nextPriorId;
+  h->g.invalidateCovariance();
+  return pt.id;
+} catch (const std::exception& e) {
+  g_pgError = e.what();
+  return -3;
+}
+int svin_pg_remove_prior(svin_pg* h, int prior_id) {
+  if (!h) return -1;
+  for (size_t i = 0; i < h->g.priors.size(); ++i)
+    if (h->g.priors[i].id == prior_id) {
+      h->g.priors.erase(h->g.priors.begin() + (std::ptrdiff_t)i);
+      h->g.invalidateCovariance();
+      return 1;
+    }
+  g_pgError = "svin_pg_remove_prior: no prior " + std::to_string(prior_id);
+  return -2;
+}
+int svin_pg_num_priors(const svin_pg* h) { return h ? (int)h->g.priors.size() : -1; }
+int svin_pg_get_prior(const svin_pg* h, int prior_id, int* index, int* kind, double* t, double* q, double* yaw_deg, double* information,
+                      int* loss_kind, double* loss_scale) {
+  if (!h) return -1;
+  for (const svin::pg::PriorTerm& pt : h->g.priors) {
+    if (pt.id != prior_id) continue;
+    const int m = svin::pgPriorRows(pt.kind, h->g.tangentSize());
+    if (index) *index = pt.index;
+    if (kind) *kind = pt.kind;
+    if (t) std::memcpy(t, pt.t, sizeof(pt.t));
+    if (q) std::memcpy(q, pt.q, sizeof(pt.q));
+    if (yaw_deg) *yaw_deg = pt.yaw;
+    if (information) std::memcpy(information, pt.info, sizeof(double) * m * m);
+    if (loss_kind) *loss_kind = pt.lossKind;
+    if (loss_scale) *loss_scale = pt.lossScale;
+    return 1;
+  }
+  g_pgError = "svin_pg_get_prior: no prior " + std::to_string(prior_id);
+  return -2;
+}
+int svin_pg_set_gauge(svin_pg* h, int gauge) {
+  if (!h || (gauge != 0 && gauge != 1)) return -1;
+  h->g.gauge = gauge;
+  h->g.invalidateCovariance();
+  return 1;
+}
+int svin_pg_get_gauge(const svin_pg* h) { return h ? h->g.gauge : -1; }
 int svin_pg_optimize(svin_pg* h, int earliest_loop_index, int cur_index) {
   if (!h) return -1;
   try {

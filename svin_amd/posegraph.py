@@ -16,7 +16,10 @@ PG_EXPORTS = [
     "svin_pg_set_partition", "svin_pg_get_partition", "svin_pg_set_levels", "svin_pg_debug_step", "svin_pg_debug_array",
     "svin_pg_get_covariance_blocks", "svin_pg_get_covariance", "svin_pg_covariance_counters",
     "svin_pg_add_edge", "svin_pg_remove_edge", "svin_pg_num_edges", "svin_pg_get_edge",
+    "svin_pg_add_prior", "svin_pg_remove_prior", "svin_pg_num_priors", "svin_pg_get_prior", "svin_pg_set_gauge", "svin_pg_get_gauge",
 ]
+PRIOR_POSE, PRIOR_POSITION, PRIOR_DEPTH = 0, 1, 2   # svin_pg.h SVIN_PG_PRIOR_*
+GAUGE_REFERENCE, GAUGE_FREE = 0, 1
 LOSS_NONE, LOSS_CAUCHY, LOSS_HUBER = 0, 1, 2   # svin_ba.h SVIN_LOSS_*
 ERR_SINGULAR = -5   # SVIN_PG_ERR_SINGULAR
 
@@ -27,9 +30,9 @@ DEBUG_ARRAYS = [
     "ea", "eb", "eloop", "off", "et", "eyaw", "epitch", "eroll", "eq", "esq", "yaw", "pitch", "roll", "t", "q",
     "res", "Ja", "Jb", "g", "scale", "colsq", "nodeBlk", "y", "yS", "cost", "costC", "gradmax", "model", "step2", "x2",
     "cholFail", "yawC", "tC", "qC", "rows", "cols", "rows2", "cols2", "sepOff", "nodePiece", "nodeRow", "isCover",
-    "isRoot", "l2PieceOf", "nS", "nR", "nPieces", "nPieces2", "BW", "BW2", "ekind", "einfo", "eloss", "eid",
+    "isRoot", "l2PieceOf", "nS", "nR", "nPieces", "nPieces2", "BW", "BW2", "ekind", "einfo", "eloss", "eid", "eprior",
 ]
-_DEBUG_INTS = {"ea", "eb", "eloop", "ekind", "eid", "off", "cholFail", "rows", "cols", "rows2", "cols2", "sepOff", "nodePiece", "nodeRow",
+_DEBUG_INTS = {"ea", "eb", "eloop", "ekind", "eid", "eprior", "off", "cholFail", "rows", "cols", "rows2", "cols2", "sepOff", "nodePiece", "nodeRow",
                "isCover", "isRoot", "l2PieceOf", "nS", "nR", "nPieces", "nPieces2", "BW", "BW2"}
 _DEBUG_SCALARS = {"cost", "costC", "gradmax", "model", "step2", "x2", "cholFail", "nS", "nR", "nPieces", "nPieces2", "BW", "BW2"}
 
@@ -69,6 +72,12 @@ def _lib():
         sig("svin_pg_remove_edge", i32, vp, i32)
         sig("svin_pg_num_edges", i32, vp)
         sig("svin_pg_get_edge", i32, vp, i32, pi, pi, pd, pd, pd, pd, pi, pd)
+        sig("svin_pg_add_prior", i32, vp, i32, i32, pd, pd, f64, pd, i32, f64)
+        sig("svin_pg_remove_prior", i32, vp, i32)
+        sig("svin_pg_num_priors", i32, vp)
+        sig("svin_pg_get_prior", i32, vp, i32, pi, pi, pd, pd, pd, pd, pi, pd)
+        sig("svin_pg_set_gauge", i32, vp, i32)
+        sig("svin_pg_get_gauge", i32, vp)
         _BOUND = True
     return L
 
@@ -135,6 +144,41 @@ class PoseGraph:
                                             C.byref(lk), _p(ls)), "get_edge")
         return dict(index_a=ia.value, index_b=ib.value, rel_t=t, rel_q=q, rel_yaw_deg=float(yaw[0]), information=info,
                     loss=lk.value, loss_scale=float(ls[0]))
+
+    def prior_rows(self, kind):
+        return {PRIOR_POSE: 6 if self.six else 4, PRIOR_POSITION: 3, PRIOR_DEPTH: 1}[int(kind)]
+
+    def add_prior(self, index, kind, t, q=None, yaw_deg=0.0, information=None, loss=LOSS_NONE, loss_scale=1.0):
+        """an absolute measurement of keyframe `index` in the frame poses() answers in: kind PRIOR_POSE (t, and q xyzw in 6-DoF
+        or yaw_deg in 4-DoF), PRIOR_POSITION (t) or PRIOR_DEPTH (t[2]); information m x m (m = prior_rows(kind)) or None for the
+        identity; loss as for add_edge; returns the prior id"""
+        t = np.ascontiguousarray(t, np.float64)
+        q = None if q is None else np.ascontiguousarray(q, np.float64)
+        info = None if information is None else np.ascontiguousarray(information, np.float64)
+        return self._check(self.L.svin_pg_add_prior(self.h, int(index), int(kind), _p(t), None if q is None else _p(q), float(yaw_deg),
+                                                    None if info is None else _p(info), int(loss), float(loss_scale)), "add_prior")
+
+    def remove_prior(self, prior_id):
+        self._check(self.L.svin_pg_remove_prior(self.h, int(prior_id)), "remove_prior")
+
+    def num_priors(self):
+        return self.L.svin_pg_num_priors(self.h)
+
+    def get_prior(self, prior_id):
+        idx, kind, lk = C.c_int(0), C.c_int(0), C.c_int(0)
+        t, q, yaw, info, ls = np.zeros(3), np.zeros(4), np.zeros(1), np.zeros(36), np.zeros(1)
+        self._check(self.L.svin_pg_get_prior(self.h, int(prior_id), C.byref(idx), C.byref(kind), _p(t), _p(q), _p(yaw), _p(info),
+                                             C.byref(lk), _p(ls)), "get_prior")
+        m = self.prior_rows(kind.value)
+        return dict(index=idx.value, kind=kind.value, t=t, q=q, yaw_deg=float(yaw[0]), information=info[:m * m].reshape(m, m).copy(),
+                    loss=lk.value, loss_scale=float(ls[0]))
+
+    def set_gauge(self, gauge):
+        """GAUGE_REFERENCE: the reference's constant keyframes (default); GAUGE_FREE: none, the priors tie the graph"""
+        self._check(self.L.svin_pg_set_gauge(self.h, int(gauge)), "set_gauge")
+
+    def gauge(self):
+        return self.L.svin_pg_get_gauge(self.h)
 
     def optimize(self, earliest_loop_index, cur_index):
         self._check(self.L.svin_pg_optimize(self.h, earliest_loop_index, cur_index), "optimize")
