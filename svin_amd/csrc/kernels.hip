@@ -829,14 +829,17 @@ struct FactorShared {
   double rw[15];      // weighted residual
   // re-preintegration (imuIntegrate): per-step inputs (P0), the two serial chains (P1), the blocks of F_delta
   // per step (P2/P3, double buffered for the covariance wave) and the published integrals
-  double pre[64 * 33];
+  double pre[128 * 33];  // 128 steps x kPreLd (a round of 64 uses the first 64 rows); P4's 4 x 512 publish area
   double fb[128 * 93];   // 128 steps x kFbLd
-  double seq[65 * 13];
+  double seq[130 * 13];  // 65 rows x kSeqLd per half of a round of 128 (a round of 64 uses the first 65)
   double tot[64];
   double tile[16 * kPanelLd];  // 15x15 covariance / information padded to the 16x16 wave-level factorisation
   double dinv[16];
   int flag, used;
 };
+// (k_imu_propagation, k_eval_factors, k_eval_all, k_eval_rest_split / k_eval_rest_batch and k_eval_build hold one each, next
+// to the shared variables of their own: 1 608 bytes in k_eval_build, less in the others)
+static_assert(sizeof(FactorShared) + 2048 <= 160 * 1024, "FactorShared and its kernels' own shared variables fit the 160 KiB of LDS of a gfx950 CU");
 
 // normalised pose -> Transformation(r, q) semantics (q normalised, C from normalised q)
 struct TF { double r[3]; Quat q; Mat3 C; };
@@ -859,8 +862,11 @@ struct ImuState {
   double Ci[9], Cdi[9], ai[3], adi[3], dal[9], dv[9], dp[9], Delta_t;
   int used;
 };
-constexpr int kImuSuper = 64;  // integration steps per round of the per-step phases P0..P3
 constexpr int kImuBlock = 128;  // integration steps per block of the covariance stage (sh.fb)
+// integration steps per round of the per-step phases P0..P3 (imuIntegrate's ROUND): a whole block, or -- SVIN_IMU_ROUND64 --
+// the 64 of one wave, two rounds per block
+constexpr int kImuRoundBlock = kImuBlock, kImuRoundWave = 64;
+constexpr int kSeqHalfRows = 65;   // sh.seq: the states before each of a half's 64 steps and the one after its last
 constexpr int kPreLd = 33;     // odd row strides keep the one-thread-per-step phases off the same LDS banks
 constexpr int kFbLd = 93;   // 87 entries of the step + the five process-noise values of P4 (87..91); sh.fb is sized for it
 constexpr int kSeqLd = 13;
@@ -873,6 +879,21 @@ __device__ __forceinline__ void negCrossDesc(int i, int j, int& comp, double& si
   sign = ((j - i + 3) % 3 == 1) ? 1.0 : -1.0;
 }
 
+// imuIntegrate, P1: the carried state applied to a half's prefixes, with the contraction written out (see there).
+// qmul(a, b) (dmath.hpp) as fma(.., fma(.., fma(first product, second product))) per component
+__device__ __forceinline__ Quat imuCarryQmul(const Quat& a, const Quat& b) {
+  Quat o;
+  o.w = __builtin_fma(-a.z, b.z, __builtin_fma(-a.y, b.y, __builtin_fma(a.w, b.w, -(a.x * b.x))));
+  o.x = __builtin_fma(-a.z, b.y, __builtin_fma(a.y, b.z, __builtin_fma(a.w, b.x, a.x * b.w)));
+  o.y = __builtin_fma(-a.x, b.z, __builtin_fma(a.z, b.x, __builtin_fma(a.w, b.y, a.y * b.w)));
+  o.z = __builtin_fma(-a.y, b.x, __builtin_fma(a.x, b.y, __builtin_fma(a.w, b.z, a.z * b.w)));
+  return o;
+}
+// row[0] x[0] + row[1] x[3] + row[2] x[6]: a row of a 3x3 matrix times a column of another (x: the column's first entry)
+__device__ __forceinline__ double imuCarryRow(const double* row, const double* x) {
+  return __builtin_fma(row[2], x[6], __builtin_fma(row[0], x[0], row[1] * x[3]));
+}
+
 #ifdef SVIN_IMU_TIMING
 __device__ double g_imuDbg[16];
 #define IMU_TICK(var) long long var = __builtin_readcyclecounter()
@@ -883,11 +904,15 @@ __device__ double g_imuDbg[16];
 #endif
 
 // Re-preintegration (ImuError.cpp:118-243 redo / :309-452 propagation) restructured so that only the two
-// genuinely serial chains stay serial, every round handling kImuSuper integration steps:
+// genuinely serial chains stay serial, every round handling ROUND integration steps:
 //   P0  one thread per step : time bookkeeping, interpolation at the interval ends, saturation test,
 //                             omega/acc minus bias, dq, R(dq^-1), rightJacobian*dt                -> sh.pre
 //   P1  wave 0 / wave 1     : Delta_q_{k+1} = Delta_q_k (x) dq_k  /  cross_{k+1} = R(dq^-1) cross_k + rJ dt
 //                             (the only recurrences that are not plain sums)                       -> sh.seq
+//                             ROUND = 128: waves 2 / 3 scan steps 64.. of the round beside them, take the state after step 63
+//                             from the row waves 0 / 1 have left in sh.seq and apply it the way a second round of 64 does
+//                             (sh.seq keeps 65 rows per half: "after step 63" and "before step 64" are formed by different
+//                             expressions and may differ in the sign of a zero)
 //   P2  one thread per step : C, C_1, the per-step increments of every integral and the blocks of F_delta
 //                             that do not involve running sums                                      -> sh.fb
 //   P3  wave 0, one lane per scalar component: the running sums C_integral, acc_integral, dv_db_g (in step
@@ -895,17 +920,18 @@ __device__ double g_imuDbg[16];
 //   P4  all four waves      : P <- F P F^T + Q as v_mfma_f64_16x16x4_f64 products with P held in the MFMA accumulator
 //                             layout; the steps of a block are split into four segments (one per SIMD), each wave
 //                             carries its segment's covariance and transition product, wave 0 chains the segments
-template <bool REDO>
+template <bool REDO, int ROUND>
 __device__ void imuIntegrate(const DevImu& im, const uint32_t* __restrict__ T, const double* __restrict__ M,
                              const double* sb, FactorShared& sh, ImuState& st) {
+  static_assert(ROUND == kImuRoundWave || ROUND == kImuRoundBlock, "a round is one wave's 64 steps or a covariance block");
   const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
   const int n = im.sampleCount;
   const uint32_t t0[2] = {im.t0[0], im.t0[1]}, end[2] = {im.t1[0], im.t1[1]};
   const double sgw2 = im.par.sigma_gw_c * im.par.sigma_gw_c, saw2 = im.par.sigma_aw_c * im.par.sigma_aw_c;
   IMU_TICK(qStart);
 
-  Quat Dq = {0, 0, 0, 1};  // wave 0
-  double cross[9] = {0};   // wave 1
+  Quat Dq = {0, 0, 0, 1};  // wave 0 (wave 2 of a round of 128: the state after step 63 of the round)
+  double cross[9] = {0};   // wave 1 (wave 3 likewise)
   // wave 0, P3: lane c owns one scalar component: run1 (first sum) and run2 (second sum)
   //   c 0..8 C_integral/C_doubleintegral, 9..11 acc_integral/acc_doubleintegral, 12..20 dv_db_g/dp_db_g,
   //   21..29 dalpha_db_g, 30 Delta_t, 31 number of executed steps
@@ -975,8 +1001,8 @@ __device__ void imuIntegrate(const DevImu& im, const uint32_t* __restrict__ T, c
 
   for (int blk0 = 0; blk0 < n; blk0 += kImuBlock) {
    const int nb = min(kImuBlock, n - blk0);
-   for (int s0 = blk0; s0 < blk0 + nb; s0 += kImuSuper) {
-    const int ns = min(kImuSuper, blk0 + nb - s0);
+   for (int s0 = blk0; s0 < blk0 + nb; s0 += ROUND) {
+    const int ns = min(ROUND, blk0 + nb - s0);
     double* fbw = sh.fb + (size_t)(s0 - blk0) * kFbLd;
     // ---------------- P0
     IMU_TICK(qp0);
@@ -1034,13 +1060,22 @@ __device__ void imuIntegrate(const DevImu& im, const uint32_t* __restrict__ T, c
     IMU_ACC(0, qp0, qp1, t == 0);
     __syncthreads();
     IMU_TICK(qp2);
-    // ---------------- P1: the two serial chains, side by side
-    if (wave == 0 && ns > 0) {
+    // ---------------- P1: the two serial chains, side by side -- and, in a round of 128, the two halves of each chain side by
+    // side: every wave scans the 64 steps of its half, then the halves are chained (h) through the state after step 63
+    constexpr bool kHalves = ROUND > 64;
+    const int half = kHalves ? (wave >> 1) : 0;
+    const int nsH = kHalves ? (half ? ns - 64 : min(ns, 64)) : ns;   // steps of this wave's half (<= 0: none)
+    const bool scans = (kHalves || wave < 2) && nsH > 0;
+    const double* preH = sh.pre + half * 64 * kPreLd;
+    double* seqH = sh.seq + half * kSeqHalfRows * kSeqLd;
+    Quat q = {0, 0, 0, 1}, e = {0, 0, 0, 1};
+    double R[9], B[9], Re[9], Be[9];
+    if ((wave & 1) == 0 && scans) {
       // Delta_q chain as a wave-wide inclusive scan (quaternion products are associative): lane i carries dq_i
       // (identity for a step that is not executed), six combine levels instead of ns serial products
-      const double* pr = sh.pre + min(lane, ns - 1) * kPreLd;
-      const bool act = lane < ns && pr[28] != 0.0;
-      Quat q = act ? Quat{pr[4], pr[5], pr[6], pr[7]} : Quat{0, 0, 0, 1};
+      const double* pr = preH + min(lane, nsH - 1) * kPreLd;
+      const bool act = lane < nsH && pr[28] != 0.0;
+      q = act ? Quat{pr[4], pr[5], pr[6], pr[7]} : Quat{0, 0, 0, 1};
       // inclusive scan without LDS (__shfl_up is ds_bpermute: 8 LDS round trips per level here): four levels inside the
       // 16-lane rows (row_shr), then the row totals travel down the wave (row_bcast:15, row_bcast:31)
 #define SVIN_QSCAN(CTRL, MASK, COND)                                                                                 \
@@ -1057,20 +1092,14 @@ __device__ void imuIntegrate(const DevImu& im, const uint32_t* __restrict__ T, c
       SVIN_QSCAN(0x142, 0xa, (lane >> 4) & 1)
       SVIN_QSCAN(0x143, 0xc, lane >= 32)
 #undef SVIN_QSCAN
-      Quat e = {dppScanMov<0x138, 0xf>(q.x), dppScanMov<0x138, 0xf>(q.y), dppScanMov<0x138, 0xf>(q.z), dppScanMov<0x138, 0xf>(q.w)};
+      e = Quat{dppScanMov<0x138, 0xf>(q.x), dppScanMov<0x138, 0xf>(q.y), dppScanMov<0x138, 0xf>(q.z), dppScanMov<0x138, 0xf>(q.w)};
       if (lane == 0) e = Quat{0, 0, 0, 1};
-      const Quat before = qmul(Dq, e);     // Delta_q before step `lane`
-      if (lane < ns) { double* sq = sh.seq + lane * kSeqLd; sq[0] = before.x; sq[1] = before.y; sq[2] = before.z; sq[3] = before.w; }
-      const Quat tot = {readlaneD(q.x, ns - 1), readlaneD(q.y, ns - 1), readlaneD(q.z, ns - 1), readlaneD(q.w, ns - 1)};
-      Dq = qmul(Dq, tot);
-      if (lane == 0) { double* sq = sh.seq + ns * kSeqLd; sq[0] = Dq.x; sq[1] = Dq.y; sq[2] = Dq.z; sq[3] = Dq.w; }
     }
-    if (wave == 1 && ns > 0) {
+    if ((wave & 1) == 1 && scans) {
       // cross chain M <- R_i M + B_i (3x3, B_i = rightJacobian dt): affine maps compose associatively,
       // (R_l, B_l) after (R_e, B_e) = (R_l R_e, R_l B_e + B_l); same scan, lane i carries step i's map
-      const double* pr = sh.pre + min(lane, ns - 1) * kPreLd;
-      const bool act = lane < ns && pr[28] != 0.0;
-      double R[9], B[9];
+      const double* pr = preH + min(lane, nsH - 1) * kPreLd;
+      const bool act = lane < nsH && pr[28] != 0.0;
 #pragma unroll
       for (int k = 0; k < 9; ++k) { R[k] = act ? pr[8 + k] : ((k % 4 == 0) ? 1.0 : 0.0); B[k] = act ? pr[17 + k] : 0.0; }
 #define SVIN_ASCAN(CTRL, MASK, COND)                                                                                 \
@@ -1093,38 +1122,70 @@ __device__ void imuIntegrate(const DevImu& im, const uint32_t* __restrict__ T, c
       SVIN_ASCAN(0x142, 0xa, (lane >> 4) & 1)
       SVIN_ASCAN(0x143, 0xc, lane >= 32)
 #undef SVIN_ASCAN
-      // exclusive prefix applied to the state at the start of the round; the inclusive one of the last step ends it
-      double Re[9], Be[9];
+      // exclusive prefix (applied to the state at the start of the half below; the inclusive one of the last step ends it)
 #pragma unroll
       for (int k = 0; k < 9; ++k) { Re[k] = dppScanMov<0x138, 0xf>(R[k]); Be[k] = dppScanMov<0x138, 0xf>(B[k]); }
       if (lane == 0) {
 #pragma unroll
         for (int k = 0; k < 9; ++k) { Re[k] = (k % 4 == 0) ? 1.0 : 0.0; Be[k] = 0.0; }
       }
-      double after[9];
+    }
+    const int nHalves = (kHalves && ns > 64) ? 2 : 1;
+    for (int h = 0; h < nHalves; ++h) {
+      if (h == 1) {   // the low half's waves have left the state after step 63 in their last row
+        __syncthreads();
+        const double* carry = sh.seq + 64 * kSeqLd;
+        if (wave == 2) Dq = Quat{carry[0], carry[1], carry[2], carry[3]};
+        if (wave == 3) {
 #pragma unroll
-      for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          const double bef = (Re[3 * r] * cross[c] + Re[3 * r + 1] * cross[3 + c] + Re[3 * r + 2] * cross[6 + c]) + Be[3 * r + c];
-          after[3 * r + c] = (R[3 * r] * cross[c] + R[3 * r + 1] * cross[3 + c] + R[3 * r + 2] * cross[6 + c]) + B[3 * r + c];
-          if (lane < ns) sh.seq[lane * kSeqLd + 4 + 3 * r + c] = bef;
+          for (int k = 0; k < 9; ++k) cross[k] = carry[4 + k];
         }
+      }
+      // The products with the carried state spell their fused multiply-adds out (imuCarryQmul, imuCarryRow): left to
+      // -ffp-contract, a*b + c*d becomes fma(a, b, c*d) in one instance of this template and fma(c, d, a*b) in the other, and
+      // the two round lengths differ in the last bit wherever the carried state is not the identity.  The forms are the ones
+      // the rounds of 64 had as the only instance.
+      if (half == h && (wave & 1) == 0 && scans) {
+        const Quat before = imuCarryQmul(Dq, e);     // Delta_q before step `lane` of the half
+        if (lane < nsH) { double* sq = seqH + lane * kSeqLd; sq[0] = before.x; sq[1] = before.y; sq[2] = before.z; sq[3] = before.w; }
+        const Quat tot = {readlaneD(q.x, nsH - 1), readlaneD(q.y, nsH - 1), readlaneD(q.z, nsH - 1), readlaneD(q.w, nsH - 1)};
+        Dq = imuCarryQmul(Dq, tot);
+        if (lane == 0) { double* sq = seqH + nsH * kSeqLd; sq[0] = Dq.x; sq[1] = Dq.y; sq[2] = Dq.z; sq[3] = Dq.w; }
+      }
+      if (half == h && (wave & 1) == 1 && scans) {
+        double after[9];
 #pragma unroll
-      for (int k = 0; k < 9; ++k) cross[k] = readlaneD(after[k], ns - 1);
+        for (int r = 0; r < 3; ++r)
 #pragma unroll
-      for (int k = 0; k < 9; ++k)
-        if (lane == k) sh.seq[ns * kSeqLd + 4 + k] = cross[k];
+          for (int c = 0; c < 3; ++c) {
+            const double bef = imuCarryRow(Re + 3 * r, cross + c) + Be[3 * r + c];
+            after[3 * r + c] = imuCarryRow(R + 3 * r, cross + c) + B[3 * r + c];
+            if (lane < nsH) seqH[lane * kSeqLd + 4 + 3 * r + c] = bef;
+          }
+#pragma unroll
+        for (int k = 0; k < 9; ++k) cross[k] = readlaneD(after[k], nsH - 1);
+#pragma unroll
+        for (int k = 0; k < 9; ++k)
+          if (lane == k) seqH[nsH * kSeqLd + 4 + k] = cross[k];
+      }
     }
     IMU_TICK(qp3);
     IMU_ACC(1, qp2, qp3, t == 0);
     IMU_ACC(6, qp2, qp3, t == 64);
     __syncthreads();
     IMU_TICK(qp4);
+    if (nHalves == 2) {   // the state at the end of the round, back to the waves that carry it from block to block
+      const double* endRow = sh.seq + (kSeqHalfRows + ns - 64) * kSeqLd;
+      if (wave == 0) Dq = Quat{endRow[0], endRow[1], endRow[2], endRow[3]};
+      if (wave == 1) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) cross[k] = endRow[4 + k];
+      }
+    }
     // ---------------- P2
     if (t < ns) {
       const double* pr = sh.pre + t * kPreLd;
-      const double* sq = sh.seq + t * kSeqLd;
+      const double* sq = sh.seq + (t + (t >> 6)) * kSeqLd;   // (a half's 65 rows: step t, and the state after it one row on)
       double* fb = fbw + t * kFbLd;
       if (pr[28] == 0.0) {
         for (int k = 0; k < kFbLd; ++k) fb[k] = 0.0;
@@ -1353,11 +1414,13 @@ __device__ void imuIntegrate(const DevImu& im, const uint32_t* __restrict__ T, c
   IMU_ACC(3, qStart, qEnd, t == 0);
 }
 
+// (round64: SVIN_IMU_ROUND64, uniform across the launch -- the per-step phases in rounds of 64 steps instead of a block's 128)
 __device__ void imuRedoPreintegration(DevImu& im, const uint32_t* __restrict__ imuT, const double* __restrict__ imuM,
-                                      const double* sb, FactorShared& sh) {
+                                      const double* sb, FactorShared& sh, int round64) {
   const int t = threadIdx.x;
   ImuState st;
-  imuIntegrate<true>(im, imuT + 2 * (size_t)im.sampleStart, imuM + 6 * (size_t)im.sampleStart, sb, sh, st);
+  if (round64) imuIntegrate<true, kImuRoundWave>(im, imuT + 2 * (size_t)im.sampleStart, imuM + 6 * (size_t)im.sampleStart, sb, sh, st);
+  else imuIntegrate<true, kImuRoundBlock>(im, imuT + 2 * (size_t)im.sampleStart, imuM + 6 * (size_t)im.sampleStart, sb, sh, st);
   // symmetrise P, information = P^-1 (via Cholesky), symmetrise, sqrtInfo = chol(information)^T  (:246-258).
   // Both factorisations run on the register-resident 16x16 routine of the reduced solver (one wave, identity
   // padding): it returns L and L^-1 together, so information = L^-T L^-1 needs no triangular solves.
@@ -1433,7 +1496,7 @@ void debugImuTiming(double* out, bool reset) {
 // out[0] = number of integration steps (or -1), optional 15x15 jacobian / covariance.
 __global__ __launch_bounds__(256) void k_imu_propagation(const DevImu* imPtr, const uint32_t* __restrict__ T,
                                                          const double* __restrict__ M, double* io, double* jac,
-                                                         double* cov, int* used) {
+                                                         double* cov, int* used, int round64) {
   __shared__ FactorShared sh;
   const int t = threadIdx.x;
   const DevImu& im = *imPtr;
@@ -1445,7 +1508,8 @@ __global__ __launch_bounds__(256) void k_imu_propagation(const DevImu* imPtr, co
   double sb[9];
   for (int k = 0; k < 9; ++k) sb[k] = io[7 + k];
   ImuState st;
-  imuIntegrate<false>(im, T, M, sb, sh, st);
+  if (round64) imuIntegrate<false, kImuRoundWave>(im, T, M, sb, sh, st);
+  else imuIntegrate<false, kImuRoundBlock>(im, T, M, sb, sh, st);
   const TF T0 = makeTF(io);
   const double gz = im.par.g * (6371009.0 / sqrt(6371009.0 * 6371009.0));
   const double gW[3] = {im.par.g * 0.0, im.par.g * 0.0, gz};
@@ -1536,8 +1600,9 @@ constexpr int kFactorHandOver = 1 + 4;            // doubles behind those: sc, t
 // retracted itself) -- nothing is read from pose / sb or their candidate copies
 // accStage: the staging area of factorsAccumulateLin behind its colRow ints -- J, r, sc and the block table go there as well as into
 // the record (not for F_HOST factors, whose record the host wrote)
-__device__ __forceinline__ void evalFactorBlock(const DeviceProblem& p, int cand, int f, FactorShared& sh, bool blocksStaged = false,
-                                                double* accStage = nullptr) {
+// imuRound64: SVIN_IMU_ROUND64 as the launch was given it (imuRedoPreintegration)
+__device__ __forceinline__ void evalFactorBlock(const DeviceProblem& p, int cand, int f, FactorShared& sh, int imuRound64,
+                                                bool blocksStaged = false, double* accStage = nullptr) {
   const int t = threadIdx.x;
   const DevFactor& fac = p.factors[f];
   FactorLin& lin = (cand ? p.linCand : p.linCur)[f];
@@ -1601,7 +1666,7 @@ __device__ __forceinline__ void evalFactorBlock(const DeviceProblem& p, int cand
       double sbl[9];
       for (int k = 0; k < 9; ++k) sbl[k] = sh.xs[7 + k];
       __syncthreads();
-      imuRedoPreintegration(im, p.imuT, p.imuMeas, sbl, sh);
+      imuRedoPreintegration(im, p.imuT, p.imuMeas, sbl, sh, imuRound64);
       if (t == 0) { im.redo = 0; im.redoCounter++; }
 #pragma unroll
       for (int k = 0; k < 6; ++k) Db[k] = 0;
@@ -1863,9 +1928,9 @@ __device__ __forceinline__ void evalFactorBlock(const DeviceProblem& p, int cand
   IMU_ACC(10, qe0, qe3, t == 0 && fac.kind == F_IMU);
 }
 
-__global__ __launch_bounds__(256) void k_eval_factors(DeviceProblem p, int cand, int costBlocksA) {
+__global__ __launch_bounds__(256) void k_eval_factors(DeviceProblem p, int cand, int costBlocksA, int imuRound64) {
   __shared__ FactorShared sh;
-  evalFactorBlock(p, cand, blockIdx.x, sh);
+  evalFactorBlock(p, cand, blockIdx.x, sh, imuRound64);
   // the factor block that finishes last also sums the cost (reprojection partials were written by the previous
   // kernel of the stream) -- saves the separate reduction launch
   if (costBlocksA >= 0) {
@@ -1877,13 +1942,16 @@ __global__ __launch_bounds__(256) void k_eval_factors(DeviceProblem p, int cand,
   }
 }
 
+// SVIN_IMU_ROUND64, read once per launch (the last argument of every kernel that holds a FactorShared)
+static int imuRound64Arg() { return optOn(kOptImuRound64) ? 1 : 0; }
+
 void launchImuPropagation(const DevImu* im, const uint32_t* T, const double* M, double* io, double* jac, double* cov,
                           int* used, hipStream_t s) {
-  launch(k_imu_propagation, dim3(1), dim3(256), 0, s, im, T, M, io, jac, cov, used);
+  launch(k_imu_propagation, dim3(1), dim3(256), 0, s, im, T, M, io, jac, cov, used, imuRound64Arg());
 }
 
 void launchEvalFactors(const DeviceProblem& p, bool cand, hipStream_t s, bool sumCost) {
-  launch(k_eval_factors, dim3(p.F), dim3(256), 0, s, p, cand ? 1 : 0, sumCost ? (p.N > 0 ? evalGrid(p.N) : 0) : -1);
+  launch(k_eval_factors, dim3(p.F), dim3(256), 0, s, p, cand ? 1 : 0, sumCost ? (p.N > 0 ? evalGrid(p.N) : 0) : -1, imuRound64Arg());
 }
 // which kernel of evaluateAll sums the cost: 2 = prior evaluation, 1 = factor evaluation, 0 = separate launch
 int costSummedBy(const DeviceProblem& p) {
@@ -2095,7 +2163,7 @@ __device__ __forceinline__ StepHeadOut stepHead(const DeviceProblem& p, double r
 // (nBlocks: the blocks of the evaluation -- the launch's gridDim.x in k_eval_all; k_eval_build has its chunk blocks behind them)
 template <bool WITH_EXT, bool GENERAL, class NB>
 __device__ __forceinline__ void k_eval_all_body(const DeviceProblem& p, int cand, int nR, int sumCost, int hasPrior, FactorShared& sh, NB nBlocks,
-                                                double headRadius = -1.0, int nPost = 0, int blockBase = 0, bool handOver = false) {
+                                                int imuRound64, double headRadius = -1.0, int nPost = 0, int blockBase = 0, bool handOver = false) {
   const int F = (int)nBlocks() - nR - hasPrior;
   const int bx = (int)blockIdx.x - blockBase;   // (blockBase: the launch's blocks ahead of the evaluation's -- k_eval_build with its chunk blocks first)
   const bool head = headRadius > 0.0;   // (k_eval_build behind a post-solve pass without its tail: stepHead)
@@ -2112,7 +2180,7 @@ __device__ __forceinline__ void k_eval_all_body(const DeviceProblem& p, int cand
   if (bx < F) {
     if (head) stepHead(p, headRadius, nPost, kHeadFactor, &p.factors[bx], sh.fb, sh.xs, nullptr, nullptr);
     // (handOver: k_eval_build's factor blocks add their factor to the build from what they leave in LDS here)
-    evalFactorBlock(p, cand, bx, sh, head, handOver ? reinterpret_cast<double*>(reinterpret_cast<int*>(sh.fb) + kFactorColRow) : nullptr);
+    evalFactorBlock(p, cand, bx, sh, imuRound64, head, handOver ? reinterpret_cast<double*>(reinterpret_cast<int*>(sh.fb) + kFactorColRow) : nullptr);
     TRACE(17);
   } else if (bx == F + nR) {
     if (head) {
@@ -2160,9 +2228,9 @@ __device__ __forceinline__ void k_eval_all_body(const DeviceProblem& p, int cand
   }
 }
 template <bool WITH_EXT, bool GENERAL = false>
-__global__ __launch_bounds__(256) void k_eval_all(DeviceProblem p, int cand, int nR, int sumCost, int hasPrior) {
+__global__ __launch_bounds__(256) void k_eval_all(DeviceProblem p, int cand, int nR, int sumCost, int hasPrior, int imuRound64) {
   __shared__ FactorShared sh;
-  k_eval_all_body<WITH_EXT, GENERAL>(p, cand, nR, sumCost, hasPrior, sh, GridDimX{});
+  k_eval_all_body<WITH_EXT, GENERAL>(p, cand, nR, sumCost, hasPrior, sh, GridDimX{}, imuRound64);
 }
 // The slot of this block's window.  The table is written by the host's copy before the launch and by nothing afterwards, so it is
 // read through the CONSTANT address space like the kernel arguments it replaces: every field stays a scalar load the compiler may
@@ -2201,12 +2269,12 @@ __device__ __forceinline__ void evalReprojSplitBody(const DeviceProblem& p, int 
 // (nBlocks = F + hasPrior: the launch's gridDim.x for one window, the window's own extent in a batch; nR: the reprojection
 // partials of the launch before)
 template <class NB>
-__device__ __forceinline__ void evalRestSplitBody(const DeviceProblem& p, int cand, int nR, int hasPrior, FactorShared& sh, NB nBlocks) {
+__device__ __forceinline__ void evalRestSplitBody(const DeviceProblem& p, int cand, int nR, int hasPrior, FactorShared& sh, NB nBlocks, int imuRound64) {
   const int F = (int)nBlocks() - hasPrior;
   if ((int)blockIdx.x < F) {
     SVIN_ARGS(SA(p.factors), SA(p.imus), SA(p.linCand), SA(p.linCur), SA(p.poseC), SA(p.pose), SA(p.sbC), SA(p.sb), SA(p.extC), SA(p.ext),
               SA(p.poseOff), SA(p.sbOff), SA(p.extOff), SA(p.partial), SA(p.imuT), SA(p.imuMeas));
-    evalFactorBlock(p, cand, blockIdx.x, sh);
+    evalFactorBlock(p, cand, blockIdx.x, sh, imuRound64);
   } else {
     priorEvalBlock(p, cand, reinterpret_cast<double*>(&sh));
   }
@@ -2224,12 +2292,12 @@ __global__ __launch_bounds__(256) void k_eval_reproj_batch(const BatchSlot* __re
   if (!(sl.stages & kBatchEval) || (int)blockIdx.x >= sl.ext.evalR) return;   // (beyond the window's own blocks: no partial, no store)
   evalReprojSplitBody<WITH_EXT, GENERAL>(sl.p, cand, smem);
 }
-__global__ __launch_bounds__(256) void k_eval_rest_batch(const BatchSlot* __restrict__ slots, int cand) {
+__global__ __launch_bounds__(256) void k_eval_rest_batch(const BatchSlot* __restrict__ slots, int cand, int imuRound64) {
   __shared__ FactorShared sh;
   const BatchSlot& sl = batchSlot(slots);
   const int nBlocks = sl.ext.evalF + sl.ext.evalPri;
   if (!(sl.stages & kBatchEval) || (int)blockIdx.x >= nBlocks) return;
-  evalRestSplitBody(sl.p, cand, sl.ext.evalR, sl.ext.evalPri, sh, ExtentX{(unsigned int)nBlocks});
+  evalRestSplitBody(sl.p, cand, sl.ext.evalR, sl.ext.evalPri, sh, ExtentX{(unsigned int)nBlocks}, imuRound64);
 }
 // The same two launches for ONE window whose evaluation has more blocks than the chip has CUs (wide windows: 1 954 reprojection
 // blocks at 500 000 observations): in k_eval_all every block carries the factor blocks' LDS, one workgroup per CU.
@@ -2238,9 +2306,9 @@ __global__ __launch_bounds__(256) void k_eval_reproj_split(DeviceProblem p, int 
   extern __shared__ double smem[];
   evalReprojSplitBody<WITH_EXT, GENERAL>(p, cand, smem);
 }
-__global__ __launch_bounds__(256) void k_eval_rest_split(DeviceProblem p, int cand, int nR, int hasPrior) {
+__global__ __launch_bounds__(256) void k_eval_rest_split(DeviceProblem p, int cand, int nR, int hasPrior, int imuRound64) {
   __shared__ FactorShared sh;
-  evalRestSplitBody(p, cand, nR, hasPrior, sh, GridDimX{});
+  evalRestSplitBody(p, cand, nR, hasPrior, sh, GridDimX{}, imuRound64);
 }
 
 // The plans of build_plan.hpp for a window as it stands: which form, variant, grids and LDS sizes the build takes, how the
@@ -2271,16 +2339,16 @@ void launchEvalAll(const DeviceProblem& p, bool cand, bool sumCost, hipStream_t 
       else launch(k_eval_reproj_split<false, true>, dim3(e.reprojSplit.grid), dim3(256), stage, s, p, cand ? 1 : 0);
     } else if (p.anyExtVariable) launch(k_eval_reproj_split<true>, dim3(e.reprojSplit.grid), dim3(256), stage, s, p, cand ? 1 : 0);
     else launch(k_eval_reproj_split<false>, dim3(e.reprojSplit.grid), dim3(256), stage, s, p, cand ? 1 : 0);
-    launch(k_eval_rest_split, dim3(e.restSplit.grid), dim3(256), 0, s, p, cand ? 1 : 0, nR, pri);
+    launch(k_eval_rest_split, dim3(e.restSplit.grid), dim3(256), 0, s, p, cand ? 1 : 0, nR, pri, imuRound64Arg());
     return;
   }
   if (p.obsS) {
-    if (p.anyExtVariable) launch(k_eval_all<true, true>, dim3(e.evalAll.grid), dim3(256), 0, s, p, cand ? 1 : 0, nR, sumCost ? 1 : 0, pri);
-    else launch(k_eval_all<false, true>, dim3(e.evalAll.grid), dim3(256), 0, s, p, cand ? 1 : 0, nR, sumCost ? 1 : 0, pri);
+    if (p.anyExtVariable) launch(k_eval_all<true, true>, dim3(e.evalAll.grid), dim3(256), 0, s, p, cand ? 1 : 0, nR, sumCost ? 1 : 0, pri, imuRound64Arg());
+    else launch(k_eval_all<false, true>, dim3(e.evalAll.grid), dim3(256), 0, s, p, cand ? 1 : 0, nR, sumCost ? 1 : 0, pri, imuRound64Arg());
   } else if (p.anyExtVariable)
-    launch(k_eval_all<true>, dim3(e.evalAll.grid), dim3(256), 0, s, p, cand ? 1 : 0, nR, sumCost ? 1 : 0, pri);
+    launch(k_eval_all<true>, dim3(e.evalAll.grid), dim3(256), 0, s, p, cand ? 1 : 0, nR, sumCost ? 1 : 0, pri, imuRound64Arg());
   else
-    launch(k_eval_all<false>, dim3(e.evalAll.grid), dim3(256), 0, s, p, cand ? 1 : 0, nR, sumCost ? 1 : 0, pri);
+    launch(k_eval_all<false>, dim3(e.evalAll.grid), dim3(256), 0, s, p, cand ? 1 : 0, nR, sumCost ? 1 : 0, pri, imuRound64Arg());
 }
 
 // row i of the prior -> (reduced-system row, or -1) with the 3x3 rotation map applied on the fly
@@ -4266,7 +4334,7 @@ template <bool GENERAL>
 // stepRadius > 0 (nPost: the blocks of the post-solve pass in front, which ended at its partials): every block takes the dogleg step
 // itself first (stepHead) and evaluates at the candidate in its own LDS.
 __global__ __launch_bounds__(256) void k_eval_build(DeviceProblem p, int cand, int nR, int hasPrior, int nEval, double mu, int initScale, int nChunkBlocks,
-                                                    int accFactors, double stepRadius, int nPost) {
+                                                    int accFactors, double stepRadius, int nPost, int imuRound64) {
   __shared__ FactorShared sh;
   // SVIN_CHUNKS_FIRST (a variant build, tools/build_variant.sh): the chunk blocks, which set the launch's time, take the low block
   // indices and are dispatched first.  Measured and left off.
@@ -4290,7 +4358,7 @@ __global__ __launch_bounds__(256) void k_eval_build(DeviceProblem p, int cand, i
 #else
   const bool handOver = false;
 #endif
-  k_eval_all_body<false, GENERAL>(p, cand, nR, 1, hasPrior, sh, ExtentX{(unsigned int)nEval}, stepRadius, nPost, evalBase, handOver);
+  k_eval_all_body<false, GENERAL>(p, cand, nR, 1, hasPrior, sh, ExtentX{(unsigned int)nEval}, imuRound64, stepRadius, nPost, evalBase, handOver);
   if (accFactors && bx < nEval - nR - hasPrior) {
     static_assert(sizeof(sh.fb) >= kFactorColRow * sizeof(int) + (kFactorStage + kFactorHandOver) * sizeof(double), "a factor's staging area fits the block's LDS");
     __syncthreads();   // J, r, the block table and sc this block has just left in LDS (a host-evaluated factor: in its record) are read by all of its threads
@@ -4337,8 +4405,8 @@ bool launchEvalBuild(const DeviceProblem& p, bool cand, double mu, bool initScal
   const int acc = factorsCommute ? 1 : 0;
   const double radius = head ? stepRadius : -1.0;
   const int nPost = e.post.grid;
-  if (p.obsS) launch(k_eval_build<true>, grid, dim3(256), 0, s, pb, cand ? 1 : 0, nR, pri, nEval, mu, initScale ? 1 : 0, p.nSlabs, acc, radius, nPost);
-  else launch(k_eval_build<false>, grid, dim3(256), 0, s, pb, cand ? 1 : 0, nR, pri, nEval, mu, initScale ? 1 : 0, p.nSlabs, acc, radius, nPost);
+  if (p.obsS) launch(k_eval_build<true>, grid, dim3(256), 0, s, pb, cand ? 1 : 0, nR, pri, nEval, mu, initScale ? 1 : 0, p.nSlabs, acc, radius, nPost, imuRound64Arg());
+  else launch(k_eval_build<false>, grid, dim3(256), 0, s, pb, cand ? 1 : 0, nR, pri, nEval, mu, initScale ? 1 : 0, p.nSlabs, acc, radius, nPost, imuRound64Arg());
   if (q.nPri > 0 || !factorsCommute) {
     const DeviceProblem view = cand ? withSetsSwapped(pb) : pb;   // the factors' and the prior's linearisation at the evaluated point
     if (factorsCommute) launch(k_prior_accumulate, dim3(q.nPri), dim3(256), 0, s, view);
@@ -7791,7 +7859,7 @@ void launchBatchRound(const BatchSlot* dSlots, const DeviceProblem& geom, const 
       else launch(k_eval_reproj_batch<false, true>, dim3(grid.evalR, n), dim3(256), stage, s, dSlots, cand ? 1 : 0);
     } else if (p.anyExtVariable) launch(k_eval_reproj_batch<true>, dim3(grid.evalR, n), dim3(256), stage, s, dSlots, cand ? 1 : 0);
     else launch(k_eval_reproj_batch<false>, dim3(grid.evalR, n), dim3(256), stage, s, dSlots, cand ? 1 : 0);
-    launch(k_eval_rest_batch, dim3(grid.evalRest, n), dim3(256), 0, s, dSlots, cand ? 1 : 0);
+    launch(k_eval_rest_batch, dim3(grid.evalRest, n), dim3(256), 0, s, dSlots, cand ? 1 : 0, imuRound64Arg());
   }
 }
 

@@ -45,6 +45,8 @@ enum DebugOption : int {
   kOptNoStepInEval,        // SVIN_NO_STEP_IN_EVAL: the dogleg step stays in k_post_solve's tail, never at the head of k_eval_build's blocks
   kOptStepHookInEval,      // SVIN_STEP_HOOK_IN_EVAL: the inspection hook svin_ba_debug_trust_region_step (form 3) takes its step through
                            // k_post_solve without the tail + k_eval_build where solve() would (tests: the pair against the tail, on one handle)
+  kOptImuRound64,          // SVIN_IMU_ROUND64: the IMU integration runs its per-step phases in rounds of 64 steps, two per covariance block,
+                           // not one round of up to 128 (read at every launch of a kernel that integrates; same bits either way)
   kOptCount
 };
 

@@ -68,7 +68,7 @@ struct OptionTable {
         {kOptSlabChunks, "SVIN_SLAB_CHUNKS"}, {kOptNoSbEarly, "SVIN_NO_SB_EARLY"},
         {kOptNoRowSplit, "SVIN_NO_ROW_SPLIT"}, {kOptNoEvalBuild, "SVIN_NO_EVAL_BUILD"},
         {kOptLinearizeEvalBuild, "SVIN_LINEARIZE_EVAL_BUILD"}, {kOptNoStepInEval, "SVIN_NO_STEP_IN_EVAL"},
-        {kOptStepHookInEval, "SVIN_STEP_HOOK_IN_EVAL"}};
+        {kOptStepHookInEval, "SVIN_STEP_HOOK_IN_EVAL"}, {kOptImuRound64, "SVIN_IMU_ROUND64"}};
     static_assert(sizeof(kNames) / sizeof(kNames[0]) == kOptCount, "every option has its environment variable");
     for (const auto& n : kNames) {
       name[n.which] = n.env;
