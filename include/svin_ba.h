@@ -563,6 +563,26 @@ int svin_ba_debug_solve_dense(int d, int dC, int sb_chain, int s_padded, int ld_
                               uint64_t s_offset, const double* g, const double* h_c, const double* scale_c, double mu, int fuse_finalize,
                               int init_scale, int scratch_fill, double* y, double* htil, int32_t* chol_fail, int32_t* info10,
                               double* s_buffer_after, double* scratch, uint64_t cap_scratch);
+/* The marginalisation algebra M2 / M3 on a caller-supplied system, on the current HIP device: the launches a job of these
+ * dimensions runs after M1 (the function Window::launchMarginalization itself calls, walking the plan planMargJob gives for
+ * (m, Lm, nk, nm) and the option SVIN_MARG_EIG), on buffers of the call's own.  Test hook.
+ * Inputs, in the layout of svin_ba_get_marg_pre: U (m x m), ba (m), W (m x 3 Lm), V (Lm x 9), bb (3 Lm), marg_rows[m] (1: the row
+ * is marginalised by the dense part; the kept and the marginalised rows keep their ascending order).  stages: 1 landmark part
+ * (U -= W V^+ W^T, ba -= W V^+ bb) | 2 dense part (Hk | bk = the Schur complement of the marginalised rows, or the copy of U | ba
+ * when there are none) | 4 M3 (needs 2).  m, Lm, nk and nm may each be 0.
+ * Outputs (those of a stage that does not run are left alone): U_out, ba_out as the landmark part leaves them; Hk (nk x nk), bk;
+ * J (nk x nk), e0, Ht = J^T J, bp = J^T e0; scal3 = c0 = e0.e0, and the two scalars the M3 route reports (the smallest and largest
+ * eigenvalue of the Jacobi-scaled Hk, or the certificate's lower bound and nk); flags8 = the job's flag words ([1] Jacobi sweeps,
+ * [2] dropped eigen-directions, [3] M3 route: -8 certified Cholesky, -7 direct eigen-solve, -4 / -6 Cholesky-preconditioned Jacobi
+ * in LDS / in global memory, 0 the Jacobi fall-back, [4] 1 when k_marg_final_chol / _dc produced the prior, [5] 1 when the dense
+ * part took its certified Cholesky route); info16 = nk, nm, the grids of k_marg_lm_prepare / _apply / _update and k_marg_dense,
+ * denseUseLds, denseProdLds, denseTileChol, copyPair, the grids of k_marg_final_chol / _dc / k_marg_final, finalMode,
+ * finalFallbackLds, finalSkipIfDone -- the plan as it was walked.
+ * Returns 1; SVIN_ERR_INVALID_ARG for negative or oversized dimensions (m > 4096), a missing array, an entry of marg_rows other
+ * than 0 / 1, or a stage mask outside 1 .. 7 or with M3 but without the dense part. */
+int svin_ba_debug_marginalize(int m, int Lm, const int32_t* marg_rows, int stages, const double* U, const double* ba, const double* W,
+                              const double* V, const double* bb, double* U_out, double* ba_out, double* Hk, double* bk, double* J,
+                              double* e0, double* Ht, double* bp, double* scal3, int32_t* flags8, int32_t* info16);
 /* Debug / A-B options of the library (svin_amd/csrc/options.hpp; INTEGRATION.md §5 lists them).  Each option is named after the
  * environment variable that initialises it -- the library looks at the environment ONCE, when the first of them is asked for
  * (svin_ba_create at the latest) -- and only changes through svin_ba_debug_set_option afterwards; a later setenv() of the host

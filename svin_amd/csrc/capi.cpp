@@ -628,6 +628,15 @@ int svin_ba_debug_solve_dense(int d, int dC, int sb_chain, int s_padded, int ld_
   return svin::debugSolveDense(in, out);
   GUARD_END(SVIN_ERR_DEVICE)
 }
+int svin_ba_debug_marginalize(int m, int Lm, const int32_t* marg_rows, int stages, const double* U, const double* ba, const double* W,
+                              const double* V, const double* bb, double* U_out, double* ba_out, double* Hk, double* bk, double* J,
+                              double* e0, double* Ht, double* bp, double* scal3, int32_t* flags8, int32_t* info16) {
+  GUARD_BEGIN
+  const svin::DebugMargIn in{m, Lm, marg_rows, stages, U, ba, W, V, bb};
+  const svin::DebugMargOut out{U_out, ba_out, Hk, bk, J, e0, Ht, bp, scal3, flags8, info16};
+  return svin::debugMarginalize(in, out);
+  GUARD_END(SVIN_ERR_DEVICE)
+}
 int svin_ba_debug_set_option(const char* name, int value) { return svin::setDebugOption(name, value); }
 int svin_ba_debug_get_option(const char* name, int* value) { return svin::debugOptionByName(name, value); }
 int svin_ba_debug_set_switch(const char* name, int value) { return svin::setDebugOption(name, value ? 1 : 0); }

@@ -791,6 +791,25 @@ __device__ bool margFinalCholesky(const FinalArgs& a, P lds, int ld) {
     lds[i * ld + j] = v;
   }
   __syncthreads();
+  // One step of refinement of e0 against J^T e0 = -b0 (on the kept directions): the rows the Jacobi leaves are orthogonal to
+  // kJacobiOrthTol = 2e-14 only, and e0 above takes them for orthogonal -- J^T e0 + b0 came out at 125 eps of a scaled unit at
+  // n = 17.  rho = -b0 - J^T e0, e0_i += (J_i / p) . (rho / p) / lambda_i.
+  {
+    double* rho = rsig;   // (1 / sigma is not read again)
+    for (int j = t; j < n; j += nt) {
+      double s = 0;
+      for (int k = 0; k < n; ++k) s += lds[k * ld + j] * a.e0[k];
+      rho[j] = (-a.b0[j] - s) / (p[j] * p[j]);
+    }
+    __syncthreads();
+    for (int i = grp; i < n; i += nGroups) {
+      double e = 0;
+      for (int j = gl; j < n; j += 16) e += lds[i * ld + j] * rho[j];
+      e = rowSum16(e);
+      if (gl == 0 && ev[i] > tol) a.e0[i] += e / ev[i];
+    }
+    __syncthreads();
+  }
   for (int idx = t; idx < n * n; idx += nt) {
     const int i = idx / n, j = idx - i * n;
     double s = 0;
@@ -857,7 +876,7 @@ __global__ __launch_bounds__(1024) void k_marg_final_chol(FinalArgs a) {
     A[idx] = (r < n && cc < n) ? 0.5 * (a.H[(size_t)r * n + cc] + a.H[(size_t)cc * n + r]) / (p[r] * p[cc]) : ((r == cc) ? 1.0 : 0.0);
   }
   __syncthreads();
-  tileCholFactor<16>(A, ld, nT, DgGen, dinvGen, &sFail);
+  tileCholFactor<16, true>(A, ld, nT, DgGen, dinvGen, &sFail);   // (refined panels: L leaves the library as J)
   if (sFail) return;   // (uniform) a pivot was not positive: the eigen-solve behind this launch decides
   const long long tChol = wall_clock64();
   {
@@ -878,6 +897,34 @@ __global__ __launch_bounds__(1024) void k_marg_final_chol(FinalArgs a) {
     }
     e = symeig::sum8(e);
     if (i < n && sub == 0) a.e0[i] = -e;
+  }
+  // One step of refinement against L e0 = -b0 / p: the product with the explicit inverse leaves J^T e0 + b0 at kappa(L) eps
+  // (4 700 eps of a scaled unit on a prior of condition 7e8 that passes the certificate), the step brings it to a few n eps.
+  {
+    double* rho = a.tmp + 2 * n;   // n: b0 / p + L e0
+    __syncthreads();
+    const int i = t >> 3, sub = t & 7;
+    double r = 0.0;
+    if (i < n) {
+      const int bi = i >> 4;
+      for (int j = sub; j <= i; j += 8) {
+        const double lv = ((j >> 4) < bi) ? (double)A[i * ld + j] : (double)Dg[bi * 16 * kPanelLd + (i & 15) * kPanelLd + (j & 15)];
+        r = __builtin_fma(lv, a.e0[j], r);
+      }
+    }
+    r = symeig::sum8(r);
+    if (i < n && sub == 0) rho[i] = bt[i] + r;
+    __syncthreads();
+    double e = 0.0;
+    if (i < n) {
+      const int bi = i >> 4;
+      for (int j = sub; j <= i; j += 8) {
+        const double yv = ((j >> 4) < bi) ? (double)A[j * ld + i] : tileLinvAt(Dg, dinv, bi, i & 15, j & 15);
+        e = __builtin_fma(yv, rho[j], e);
+      }
+    }
+    e = symeig::sum8(e);
+    if (i < n && sub == 0) a.e0[i] -= e;
   }
   if (t == 0) {
     double f2 = 0;
@@ -1626,6 +1673,48 @@ void Window::margReserveAndStage(MargJob& job) {
   if (job.dims.nk > 0) priorHostValid_ = false;  // results stay on the device (solver reads Ht / bp / c0 in place); getPrior() fetches
 }
 
+// ---- the algebra of the job, M2 and M3, on the system M1 has left in the job buffers: U | ba | W | V | bb in bU / bVec / bW2 / bV,
+// the keep | marg lists in bIdxList.  Walks the plan like the rest of step 5.  Its own function because the inspection hook below
+// (debugMarginalize) runs it on a system of the caller's: what a test sees there are the job's launches, not a restatement.
+static void launchMargAlgebra(const MargBuffers& mb, const MargPlan& pl, const MargDims& d, hipStream_t s) {
+  MargDev md;
+  md.m = d.m; md.Lm = d.Lm; md.N = d.N; md.F = d.F;
+  md.U = mb.bU.p; md.ba = mb.bVec.p + pl.ba.off; md.W = mb.bW2.p; md.V = mb.bV.p; md.bb = mb.bVec.p + pl.bb.off;
+  double* vb = mb.bVec.p + pl.vb.off;
+  // M2 landmark part
+  if (pl.lmPrepare.grid) {
+    launch(k_marg_lm_prepare, dim3(pl.lmPrepare.grid), dim3(128), pl.lmPrepare.ldsBytes, s, md, vb);
+    launch(k_marg_lm_apply, dim3(pl.lmApply.grid), dim3(256), pl.lmApply.ldsBytes, s, md, (const double*)vb);
+    launch(k_marg_lm_update, dim3(pl.lmUpdate.grid), dim3(64), pl.lmUpdate.ldsBytes, s, md);
+  }
+  // M2 dense part
+  if (pl.dense.grid) {
+    DenseArgs da;
+    da.m = d.m; da.nk = d.nk; da.nm = d.nm;
+    da.keep = mb.bIdxList.p; da.marg = mb.bIdxList.p + d.nk;
+    da.U = mb.bU.p; da.ba = mb.bVec.p + pl.ba.off;
+    da.Hk = mb.bHk.p + pl.Hk.off; da.bk = mb.bHk.p + pl.bk.off;
+    da.Vm = mb.bScratch.p + pl.Vm.off; da.Qm = mb.bScratch.p + pl.Qm.off; da.tmp = mb.bScratch.p + pl.denseTmp.off;
+    da.flag = mb.bFlag.p;
+    launch(k_marg_dense, dim3(pl.dense.grid), dim3(1024), pl.dense.ldsBytes, s, da, pl.denseUseLds, pl.denseProdLds, pl.denseTileChol);
+  } else if (pl.copyPair) {
+    HIP_OK(hipMemcpyAsync(mb.bHk.p + pl.Hk.off, mb.bU.p, sizeof(double) * pl.Hk.len, hipMemcpyDeviceToDevice, s));
+    HIP_OK(hipMemcpyAsync(mb.bHk.p + pl.bk.off, mb.bVec.p + pl.ba.off, sizeof(double) * pl.bk.len, hipMemcpyDeviceToDevice, s));
+  }
+  // M3 (which eigen-solvers run, and k_marg_final's mode: planMargJob)
+  if (pl.final.grid) {
+    FinalArgs fa;
+    fa.n = d.nk; fa.H = mb.bHk.p + pl.Hk.off; fa.b0 = mb.bHk.p + pl.bk.off;
+    fa.G = mb.bOut.p + pl.G.off; fa.Q = mb.bOut.p + pl.Q.off; fa.J = mb.bOut.p + pl.J.off; fa.Ht = mb.bOut.p + pl.Ht.off;
+    fa.e0 = mb.bOut.p + pl.e0.off; fa.bp = mb.bOut.p + pl.bp.off; fa.scal = mb.bOut.p + pl.scal.off;
+    fa.tmp = mb.bOut.p + pl.finalTmp.off;
+    fa.flag = mb.bFlag.p;
+    if (pl.finalChol.grid) launch(k_marg_final_chol, dim3(pl.finalChol.grid), dim3(1024), pl.finalChol.ldsBytes, s, fa);
+    if (pl.finalDc.grid) launch(k_marg_final_dc, dim3(pl.finalDc.grid), dim3(1024), pl.finalDc.ldsBytes, s, fa, pl.finalDcAfterChol);
+    launch(k_marg_final, dim3(pl.final.grid), dim3(1024), pl.final.ldsBytes, s, fa, pl.finalMode, pl.finalFallbackLds, pl.finalSkipIfDone);
+  }
+}
+
 // ---- step 5: M1-M3, next to their kernels.  Everything the launches need was fixed by steps 3 and 4: no allocation and no host
 // table is touched here, so the launches themselves (a DMA, the scatter and 6-13 kernels: 25-50 us of API calls) can be issued by
 // the handle's enqueue thread while the call goes on with the graph update and returns (Window::quiesce joins it before the stream,
@@ -1719,38 +1808,7 @@ void Window::launchMarginalization(const MargJob& job) {
       for (int k = 0; k < pb.mdim; ++k) margPre_.margRows.push_back(mg ? 1 : 0);
     }
   }
-  // M2 landmark part
-  if (pl.lmPrepare.grid) {
-    launch(k_marg_lm_prepare, dim3(pl.lmPrepare.grid), dim3(128), pl.lmPrepare.ldsBytes, s, md, vb);
-    launch(k_marg_lm_apply, dim3(pl.lmApply.grid), dim3(256), pl.lmApply.ldsBytes, s, md, (const double*)vb);
-    launch(k_marg_lm_update, dim3(pl.lmUpdate.grid), dim3(64), pl.lmUpdate.ldsBytes, s, md);
-  }
-  // M2 dense part
-  if (pl.dense.grid) {
-    DenseArgs da;
-    da.m = d.m; da.nk = d.nk; da.nm = d.nm;
-    da.keep = mb.bIdxList.p; da.marg = mb.bIdxList.p + d.nk;
-    da.U = mb.bU.p; da.ba = mb.bVec.p + pl.ba.off;
-    da.Hk = mb.bHk.p + pl.Hk.off; da.bk = mb.bHk.p + pl.bk.off;
-    da.Vm = mb.bScratch.p + pl.Vm.off; da.Qm = mb.bScratch.p + pl.Qm.off; da.tmp = mb.bScratch.p + pl.denseTmp.off;
-    da.flag = mb.bFlag.p;
-    launch(k_marg_dense, dim3(pl.dense.grid), dim3(1024), pl.dense.ldsBytes, s, da, pl.denseUseLds, pl.denseProdLds, pl.denseTileChol);
-  } else if (pl.copyPair) {
-    HIP_OK(hipMemcpyAsync(mb.bHk.p + pl.Hk.off, mb.bU.p, sizeof(double) * pl.Hk.len, hipMemcpyDeviceToDevice, s));
-    HIP_OK(hipMemcpyAsync(mb.bHk.p + pl.bk.off, mb.bVec.p + pl.ba.off, sizeof(double) * pl.bk.len, hipMemcpyDeviceToDevice, s));
-  }
-  // M3 (which eigen-solvers run, and k_marg_final's mode: planMargJob)
-  if (pl.final.grid) {
-    FinalArgs fa;
-    fa.n = d.nk; fa.H = mb.bHk.p + pl.Hk.off; fa.b0 = mb.bHk.p + pl.bk.off;
-    fa.G = mb.bOut.p + pl.G.off; fa.Q = mb.bOut.p + pl.Q.off; fa.J = mb.bOut.p + pl.J.off; fa.Ht = mb.bOut.p + pl.Ht.off;
-    fa.e0 = mb.bOut.p + pl.e0.off; fa.bp = mb.bOut.p + pl.bp.off; fa.scal = mb.bOut.p + pl.scal.off;
-    fa.tmp = mb.bOut.p + pl.finalTmp.off;
-    fa.flag = mb.bFlag.p;
-    if (pl.finalChol.grid) launch(k_marg_final_chol, dim3(pl.finalChol.grid), dim3(1024), pl.finalChol.ldsBytes, s, fa);
-    if (pl.finalDc.grid) launch(k_marg_final_dc, dim3(pl.finalDc.grid), dim3(1024), pl.finalDc.ldsBytes, s, fa, pl.finalDcAfterChol);
-    launch(k_marg_final, dim3(pl.final.grid), dim3(1024), pl.final.ldsBytes, s, fa, pl.finalMode, pl.finalFallbackLds, pl.finalSkipIfDone);
-  }
+  launchMargAlgebra(mb, pl, d, s);
 }
 
 // SVIN_MARG_TIMING: what the device reports of the job it has just run (the launches were issued inline)
@@ -1837,6 +1895,80 @@ int Window::applyMarginalizationStrategy(size_t numKeyframes, size_t numImuFrame
   if (timing)
     std::printf("[marg] policy %.0f us, job assembly %.0f us, upload+enqueue %.0f us, device wait %.0f us, graph update %.0f us\n",
                 1e6 * (tm1 - tm0), 1e6 * (tm2 - tm1), 1e6 * (tm3 - tm2), 1e6 * (tm4 - tm3), 1e6 * (nowSec() - tm4));
+  return 1;
+}
+
+// inspection hook (svin_ba_debug_marginalize): launchMargAlgebra on a caller-supplied system after M1.  No window: the current
+// device, the default stream, buffers of its own reserved by the plan's sizes like Window::margReserveAndStage does.  The plan is
+// the one a job of these dimensions walks (planMargJob, the same SVIN_MARG_EIG option, sizeof(JacobiShared)); a stage the mask
+// leaves out is taken out of the plan (its grid set to 0), nothing else is changed.  What the launches do not write is NaN
+// beforehand (Hk | bk, the scratch of the dense part, G | Q | J | Ht | e0 | bp | scal | tmp): a window's job buffers are not
+// cleared either, so nothing may depend on what they held.  The flag words start from 0, as in a handle's first job.
+int debugMarginalize(const DebugMargIn& in, const DebugMargOut& out) {
+  const int m = in.m, Lm = in.Lm;
+  if (m < 0 || m > 4096 || Lm < 0 || Lm > (1 << 20) || !out.info || !out.flags) return -1 /* SVIN_ERR_INVALID_ARG */;
+  if (in.stages < 1 || in.stages > 7 || ((in.stages & 4) && !(in.stages & 2))) return -1 /* SVIN_ERR_INVALID_ARG */;   // (M3 reads what the dense part leaves)
+  if (m > 0 && (!in.margRows || !in.U || !in.ba || !out.U || !out.ba)) return -1 /* SVIN_ERR_INVALID_ARG */;
+  if (Lm > 0 && (!in.V || !in.bb || (m > 0 && !in.W))) return -1 /* SVIN_ERR_INVALID_ARG */;
+  std::vector<int> idxLists, margIdx;   // keep | marg, both ascending (margBuildTables' idxLists)
+  for (int i = 0; i < m; ++i) {
+    if (in.margRows[i] != 0 && in.margRows[i] != 1) return -1 /* SVIN_ERR_INVALID_ARG */;
+    (in.margRows[i] ? margIdx : idxLists).push_back(i);
+  }
+  const int nk = (int)idxLists.size(), nm = (int)margIdx.size();
+  idxLists.insert(idxLists.end(), margIdx.begin(), margIdx.end());
+  if (nk > 0 && (in.stages & 2) && (!out.Hk || !out.bk)) return -1 /* SVIN_ERR_INVALID_ARG */;
+  if (nk > 0 && (in.stages & 4) && (!out.J || !out.e0 || !out.Ht || !out.bp || !out.scal)) return -1 /* SVIN_ERR_INVALID_ARG */;
+  const MargDims d{m, Lm, 0, 0, nk, nm, 0, 0, 0, 0, 0};
+  MargPlan pl = planMargJob(d, MargSwitches{debugOption(kOptMargEig)}, MargKernelSizes{sizeof(JacobiShared)});
+  if (!(in.stages & 1)) pl.lmPrepare.grid = pl.lmApply.grid = pl.lmUpdate.grid = 0;
+  if (!(in.stages & 2)) { pl.dense.grid = 0; pl.copyPair = false; }
+  if (!(in.stages & 4)) pl.finalChol.grid = pl.finalDc.grid = pl.final.grid = 0;
+  int32_t* info = out.info;
+  info[0] = nk; info[1] = nm; info[2] = pl.lmPrepare.grid; info[3] = pl.lmApply.grid; info[4] = pl.lmUpdate.grid;
+  info[5] = pl.dense.grid; info[6] = pl.denseUseLds; info[7] = pl.denseProdLds; info[8] = pl.denseTileChol; info[9] = pl.copyPair ? 1 : 0;
+  info[10] = pl.finalChol.grid; info[11] = pl.finalDc.grid; info[12] = pl.final.grid;
+  info[13] = pl.finalMode; info[14] = pl.finalFallbackLds; info[15] = pl.finalSkipIfDone;
+  MargBuffers mb;
+  mb.bU.reserve(pl.bU); mb.bW2.reserve(pl.bW2); mb.bV.reserve(pl.bV); mb.bVec.reserve(pl.bVec);
+  mb.bIdxList.reserve(std::max<size_t>(idxLists.size(), 1));
+  mb.bFlag.reserve(pl.bFlag); mb.bHk.reserve(pl.bHk); mb.bScratch.reserve(pl.bScratch); mb.bOut.reserve(pl.bOut);
+  HIP_OK(hipMemset(mb.bU.p, 0, sizeof(double) * pl.bU)); HIP_OK(hipMemset(mb.bW2.p, 0, sizeof(double) * pl.bW2));
+  HIP_OK(hipMemset(mb.bV.p, 0, sizeof(double) * pl.bV)); HIP_OK(hipMemset(mb.bVec.p, 0, sizeof(double) * pl.bVec));
+  HIP_OK(hipMemset(mb.bFlag.p, 0, sizeof(int) * pl.bFlag));
+  HIP_OK(hipMemset(mb.bHk.p, 0xff, sizeof(double) * pl.bHk));
+  if (pl.bScratch) HIP_OK(hipMemset(mb.bScratch.p, 0xff, sizeof(double) * pl.bScratch));
+  if (pl.bOut) HIP_OK(hipMemset(mb.bOut.p, 0xff, sizeof(double) * pl.bOut));
+  const size_t L3 = (size_t)3 * Lm;
+  if (m > 0) {
+    HIP_OK(hipMemcpy(mb.bU.p, in.U, sizeof(double) * m * m, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(mb.bVec.p + pl.ba.off, in.ba, sizeof(double) * m, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(mb.bIdxList.p, idxLists.data(), sizeof(int) * m, hipMemcpyHostToDevice));
+  }
+  if (Lm > 0) {
+    if (m > 0) HIP_OK(hipMemcpy(mb.bW2.p, in.W, sizeof(double) * m * L3, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(mb.bV.p, in.V, sizeof(double) * 9 * Lm, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(mb.bVec.p + pl.bb.off, in.bb, sizeof(double) * L3, hipMemcpyHostToDevice));
+  }
+  launchMargAlgebra(mb, pl, d, 0);
+  HIP_OK(hipStreamSynchronize(0));
+  HIP_OK(hipMemcpy(out.flags, mb.bFlag.p, sizeof(int) * 8, hipMemcpyDeviceToHost));
+  if (m > 0) {
+    HIP_OK(hipMemcpy(out.U, mb.bU.p, sizeof(double) * m * m, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(out.ba, mb.bVec.p + pl.ba.off, sizeof(double) * m, hipMemcpyDeviceToHost));
+  }
+  if (nk > 0 && (in.stages & 2)) {
+    HIP_OK(hipMemcpy(out.Hk, mb.bHk.p + pl.Hk.off, sizeof(double) * nk * nk, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(out.bk, mb.bHk.p + pl.bk.off, sizeof(double) * nk, hipMemcpyDeviceToHost));
+  }
+  if (nk > 0 && (in.stages & 4)) {
+    const size_t n2 = (size_t)nk * nk;
+    HIP_OK(hipMemcpy(out.J, mb.bOut.p + pl.J.off, sizeof(double) * n2, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(out.Ht, mb.bOut.p + pl.Ht.off, sizeof(double) * n2, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(out.e0, mb.bOut.p + pl.e0.off, sizeof(double) * nk, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(out.bp, mb.bOut.p + pl.bp.off, sizeof(double) * nk, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(out.scal, mb.bOut.p + pl.scal.off, sizeof(double) * 3, hipMemcpyDeviceToHost));
+  }
   return 1;
 }
 

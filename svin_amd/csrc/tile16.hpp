@@ -153,7 +153,11 @@ __device__ __forceinline__ double tileLinvAt(const lds_f64* Dg, const lds_f64* d
   const double off = Dg[K * 16 * kPanelLd + col * kPanelLd + row], dg = dinv[16 * K + row];
   return (col < row) ? off : ((col == row) ? dg : 0.0);
 }
-template <int NW>
+// kRefine: every panel tile takes one step of refinement against its own equation, X += (A_IK - X L_KK^T) L_KK^-T.  The product with
+// the explicit inverse alone leaves |A_IK - X L_KK^T| at kappa(L_KK) eps |X| |L_KK|; with the step it is a few eps, as from a
+// substitution (k_marg_final_chol, whose factor leaves the library as J).  The tile (I, K) is its wave's own: the accumulator
+// layout is turned into the operand layout through the tile itself, behind a wait for the wave's LDS traffic.
+template <int NW, bool kRefine = false>
 __device__ __forceinline__ void tileCholFactor(lds_f64* A, int ld, int nT, double* DgGen, double* dinvGen, int* sFail) {
   const int t = threadIdx.x, wave = t >> 6, lane = t & 63, g = lane >> 4, c = lane & 15;
   const lds_f64* Dg = tileToLds(DgGen);
@@ -182,6 +186,27 @@ __device__ __forceinline__ void tileCholFactor(lds_f64* A, int ld, int nT, doubl
         }
 #pragma unroll
         for (int q = 0; q < 4; ++q) x = __builtin_amdgcn_mfma_f64_16x16x4f64(av[q], bv[q], x, 0, 0, 0);
+        if (kRefine) {
+          d4_t res = loadAcc(I, K);   // A_IK in the accumulator layout
+          storeAcc(I, K, x);
+          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+          double lv[4];
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            av[q] = -A[(16 * I + c) * ld + 16 * K + 4 * q + g];                                       // -X[i = c][k]
+            lv[q] = (4 * q + g <= c) ? (double)Dg[K * 16 * kPanelLd + c * kPanelLd + 4 * q + g] : 0.0;   // L_KK^T[k][j = c] = L_KK[c][k]
+          }
+#pragma unroll
+          for (int q = 0; q < 4; ++q) res = __builtin_amdgcn_mfma_f64_16x16x4f64(av[q], lv[q], res, 0, 0, 0);
+          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+          storeAcc(I, K, res);
+          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+          for (int q = 0; q < 4; ++q) av[q] = A[(16 * I + c) * ld + 16 * K + 4 * q + g];             // the residual, [i = c][k]
+#pragma unroll
+          for (int q = 0; q < 4; ++q) x = __builtin_amdgcn_mfma_f64_16x16x4f64(av[q], bv[q], x, 0, 0, 0);
+          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        }
         storeAcc(I, K, x);
       }
     }

@@ -700,4 +700,15 @@ struct DebugDenseOut {
   double* sBufAfter; double* scratch; size_t capScratch;
 };
 int debugSolveDense(const DebugDenseIn& in, const DebugDenseOut& out);
+// inspection hook of the marginalisation algebra (svin_ba_debug_marginalize, marg.hip): the job's M2 / M3 launches on a
+// caller-supplied system after M1
+struct DebugMargIn {
+  int m, Lm; const int32_t* margRows; int stages;   // stages: 1 landmark part | 2 dense part | 4 M3
+  const double *U, *ba, *W, *V, *bb;
+};
+struct DebugMargOut {
+  double *U, *ba, *Hk, *bk, *J, *e0, *Ht, *bp, *scal;   // scal: 3 doubles
+  int32_t *flags, *info;                                // 8 and 16 ints, svin_ba.h
+};
+int debugMarginalize(const DebugMargIn& in, const DebugMargOut& out);
 }  // namespace svin

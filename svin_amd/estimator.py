@@ -56,7 +56,7 @@ EXPORTS = [
     "svin_ba_set_camera_sensor_states", "svin_ba_set_landmark", "svin_ba_num_frames", "svin_ba_num_landmarks",
     "svin_ba_current_keyframe_id", "svin_ba_current_frame_id", "svin_ba_frame_id_by_age", "svin_ba_is_keyframe",
     "svin_ba_is_in_imu_window", "svin_ba_frame_ids", "svin_ba_landmark_ids", "svin_ba_imu_propagation",
-    "svin_ba_eval_reprojection", "svin_ba_observation_ids", "svin_ba_eval_factors", "svin_ba_linearize", "svin_ba_debug_reduced_solve", "svin_ba_debug_reduced_solve_ex", "svin_ba_debug_build_arrays", "svin_ba_debug_trust_region_step", "svin_ba_debug_set_switch", "svin_ba_debug_set_option", "svin_ba_debug_get_option", "svin_ba_debug_sym_eig", "svin_ba_get_path_counters", "svin_ba_debug_landmark_handles", "svin_ba_wait_idle", "svin_ba_debug_peek_solver_scratch", "svin_ba_debug_solve_dense", "svin_ba_debug_last_system",
+    "svin_ba_eval_reprojection", "svin_ba_observation_ids", "svin_ba_eval_factors", "svin_ba_linearize", "svin_ba_debug_reduced_solve", "svin_ba_debug_reduced_solve_ex", "svin_ba_debug_build_arrays", "svin_ba_debug_trust_region_step", "svin_ba_debug_set_switch", "svin_ba_debug_set_option", "svin_ba_debug_get_option", "svin_ba_debug_sym_eig", "svin_ba_get_path_counters", "svin_ba_debug_landmark_handles", "svin_ba_wait_idle", "svin_ba_debug_peek_solver_scratch", "svin_ba_debug_solve_dense", "svin_ba_debug_last_system", "svin_ba_debug_marginalize",
     "svin_ba_get_prior", "svin_ba_get_prior_lin", "svin_ba_describe_block", "svin_ba_bench_jacobian_eval", "svin_ba_bench_jacobian_eval_b2b", "svin_ba_set_pack_mode", "svin_ba_debug_csr", "svin_ba_residual_info",
     "svin_ba_map_add_parameter_block", "svin_ba_set_parameter_block", "svin_ba_map_remove_parameter_block", "svin_ba_map_add_pose_error",
     "svin_ba_map_add_speed_and_bias_error", "svin_ba_map_add_relative_pose_error", "svin_ba_map_add_reprojection_error",
@@ -184,6 +184,7 @@ def load_library():
     sig("svin_ba_debug_peek_solver_scratch", i32, vp, u64, u64, pd)
     sig("svin_ba_debug_last_system", i32, vp, pd, pd, i32)
     sig("svin_ba_debug_solve_dense", i32, i32, i32, i32, i32, i32, pd, u64, u64, pd, pd, pd, f64, i32, i32, i32, pd, pd, pi32, pi32, pd, pd, u64)
+    sig("svin_ba_debug_marginalize", i32, i32, i32, pi32, i32, pd, pd, pd, pd, pd, pd, pd, pd, pd, pd, pd, pd, pd, pd, pi32, pi32)
     sig("svin_ba_get_prior", i32, vp, pd, pd, pd, pd, pu64, pi32, pi32, pi32, i32)
     sig("svin_ba_get_prior_lin", i32, vp, pd, i32)
     sig("svin_ba_describe_block", i32, vp, u64, pu64, pi32, pi32)
@@ -918,6 +919,44 @@ class Estimator:
         names = ("chainMode", "route", "dSolve", "border", "bigChainGrid", "helperTasks", "nBackPanels", "chainOverflow")
         out = dict(zip(names, (int(v) for v in info[:8])))
         out.update(y=y, htil=htil, cholFail=int(fail[0]), S_after=after, scratch=scratch, end=int(info[8]) + (int(info[9]) << 31))
+        return out
+
+    MARG_LANDMARKS, MARG_DENSE, MARG_FINAL = 1, 2, 4   # the stage mask of debug_marginalize
+
+    @staticmethod
+    def debug_marginalize(U, ba, W, V, bb, marg_rows, stages=7):
+        """the marginalisation algebra M2 / M3 on a caller-supplied system after M1 (include/svin_ba.h: svin_ba_debug_marginalize),
+        in the layout marg_pre() returns: U (m x m), ba (m), W (m x 3 Lm), V (Lm x 9), bb (3 Lm), marg_rows (m, 0 / 1).
+        -> dict(U, ba after the landmark part; Hk, bk; J, e0, Ht, bp, c0, scal (the three scalars) -- None for a stage that did not
+        run or has nothing to write; flags (8 ints); nk, nm and the plan as it was walked: lmPrepare_grid, lmApply_grid,
+        lmUpdate_grid, dense_grid, denseUseLds, denseProdLds, denseTileChol, copyPair, finalChol_grid, finalDc_grid, final_grid,
+        finalMode, finalFallbackLds, finalSkipIfDone)"""
+        marg_rows = np.ascontiguousarray(marg_rows, dtype=np.int32).ravel()
+        m, Lm = marg_rows.size, int(np.asarray(V).size // 9)
+        U = np.ascontiguousarray(U, dtype=np.float64).reshape(m, m)
+        ba = np.ascontiguousarray(ba, dtype=np.float64).reshape(m)
+        W = np.ascontiguousarray(W, dtype=np.float64).reshape(m, 3 * Lm)
+        V = np.ascontiguousarray(V, dtype=np.float64).reshape(Lm, 9)
+        bb = np.ascontiguousarray(bb, dtype=np.float64).reshape(3 * Lm)
+        nk = int((marg_rows == 0).sum())
+        Uo, bao = np.zeros((m, m)), np.zeros(m)
+        Hk, bk = np.full((nk, nk), np.nan), np.full(nk, np.nan)
+        J, Ht, e0, bp = np.full((nk, nk), np.nan), np.full((nk, nk), np.nan), np.full(nk, np.nan), np.full(nk, np.nan)
+        scal, flags, info = np.full(3, np.nan), np.zeros(8, np.int32), np.zeros(16, np.int32)
+        L = load_library()
+        rc = L.svin_ba_debug_marginalize(m, Lm, marg_rows.ctypes.data_as(pi32), int(stages), _d(U), _d(ba), _d(W), _d(V), _d(bb), _d(Uo), _d(bao),
+                                         _d(Hk), _d(bk), _d(J), _d(e0), _d(Ht), _d(bp), _d(scal), flags.ctypes.data_as(pi32),
+                                         info.ctypes.data_as(pi32))
+        if rc != 1:
+            raise RuntimeError("svin_ba_debug_marginalize: %d (%s)" % (rc, L.svin_ba_last_error().decode()))
+        names = ("nk", "nm", "lmPrepare_grid", "lmApply_grid", "lmUpdate_grid", "dense_grid", "denseUseLds", "denseProdLds", "denseTileChol",
+                 "copyPair", "finalChol_grid", "finalDc_grid", "final_grid", "finalMode", "finalFallbackLds", "finalSkipIfDone")
+        out = dict(zip(names, (int(v) for v in info)))
+        dense = nk > 0 and (out["dense_grid"] or out["copyPair"])
+        final = nk > 0 and out["final_grid"]
+        out.update(U=Uo, ba=bao, Hk=Hk if dense else None, bk=bk if dense else None, J=J if final else None, e0=e0 if final else None,
+                   Ht=Ht if final else None, bp=bp if final else None, c0=float(scal[0]) if final else None, scal=scal if final else None,
+                   flags=[int(v) for v in flags])
         return out
 
     _MARG_EIG = {"": 0, None: 0, "direct": 1, "cholesky": 2, "jacobi": 3}

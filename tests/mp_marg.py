@@ -43,7 +43,7 @@ def _pinv_sym(V):
                     out[i, j] += Q[i, k] * Q[j, k] / E[k]
         else:
             dropped += 1
-    return out, dropped, [E[k] / lmax for k in range(n)]
+    return out, dropped, [E[k] / lmax if lmax != 0 else mp.mpf(0) for k in range(n)]   # (V = 0: a constant landmark)
 
 
 def _stage(H, b, ranges, per_block):
@@ -79,8 +79,9 @@ def _stage(H, b, ranges, per_block):
     return Hn, bn, keep, info
 
 
-def marginalize_mp(H, b0, lm_ranges, dense_ranges, dps=40):
-    """returns dict(H, b0 after M2; JtJ, Jte0, rank after M3; diagnostics) as float arrays"""
+def marginalize_mp(H, b0, lm_ranges, dense_ranges, dps=40, raw=False):
+    """returns dict(H, b0 after M2; JtJ, Jte0, rank after M3; diagnostics) as float arrays; raw: the four as mpmath matrices and
+    their dimension n (for a comparison finer than double)"""
     mp.mp.dps = dps
     Hm = mp.matrix(H.tolist())
     bm = mp.matrix(b0.tolist())
@@ -112,6 +113,9 @@ def marginalize_mp(H, b0, lm_ranges, dense_ranges, dps=40):
     Jte0 = mp.matrix(n, 1)
     for i in range(n):
         Jte0[i] = -p[i] * sum(Pm[i, j] * bs[j] for j in range(n))
+
+    if raw:
+        return dict(H=Hm, b0=bm, JtJ=JtJ, Jte0=Jte0, n=n, **diag)
 
     def arr(M, r, c):
         return np.array([[float(M[i, j]) for j in range(c)] for i in range(r)])
