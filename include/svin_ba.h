@@ -563,6 +563,20 @@ int svin_ba_debug_solve_dense(int d, int dC, int sb_chain, int s_padded, int ld_
                               uint64_t s_offset, const double* g, const double* h_c, const double* scale_c, double mu, int fuse_finalize,
                               int init_scale, int scratch_fill, double* y, double* htil, int32_t* chol_fail, int32_t* info10,
                               double* s_buffer_after, double* scratch, uint64_t cap_scratch);
+/* svin_ba_debug_solve_dense with a tile skyline for the LDS-resident solver (d <= 176): tile_cut holds four bits per tile column k of
+ * the padded system, nT - 1 - hi[k], hi[k] the last tile row of the column that can hold a non-zero (0: the dense profile, which is
+ * svin_ba_debug_solve_dense itself).  The caller vouches that S is zero below the profile it gives and that the profile is closed
+ * under the fill of the factorisation (pack_plan.hpp planTileSkyline); the other routes do not read it.  With
+ * SVIN_CHECK_TILE_SKYLINE on, S is held against tile_cut itself -- the profile AFTER the fill, a weaker check than a window's,
+ * whose pack() carries the profile before the fill.  Test hook. */
+int svin_ba_debug_solve_dense_profiled(int d, int dC, int sb_chain, int s_padded, int ld_s, const double* s_buffer, uint64_t s_buffer_doubles,
+                                       uint64_t s_offset, const double* g, const double* h_c, const double* scale_c, double mu, int fuse_finalize,
+                                       int init_scale, int scratch_fill, double* y, double* htil, int32_t* chol_fail, int32_t* info10,
+                                       double* s_buffer_after, double* scratch, uint64_t cap_scratch, uint64_t tile_cut);
+/* read-only: the tile skyline the handle's last pack() planned for its reduced system, as DeviceProblem carries it -- cut2[0] after
+ * the fill of the factorisation (what the solver, alone or as a slot of a batch, factors inside), cut2[1] before it; four bits per
+ * tile column, nT - 1 - hi[k]; 0 = dense.  Launches nothing.  Returns 1.  Test hook. */
+int svin_ba_debug_tile_skyline(svin_ba* h, uint64_t* cut2);
 /* The marginalisation algebra M2 / M3 on a caller-supplied system, on the current HIP device: the launches a job of these
  * dimensions runs after M1 (the function Window::launchMarginalization itself calls, walking the plan planMargJob gives for
  * (m, Lm, nk, nm) and the option SVIN_MARG_EIG), on buffers of the call's own.  Test hook.

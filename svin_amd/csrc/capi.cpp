@@ -628,6 +628,27 @@ int svin_ba_debug_solve_dense(int d, int dC, int sb_chain, int s_padded, int ld_
   return svin::debugSolveDense(in, out);
   GUARD_END(SVIN_ERR_DEVICE)
 }
+int svin_ba_debug_tile_skyline(svin_ba* h, uint64_t* cut2) {
+  if (!h || !cut2) return SVIN_ERR_INVALID_ARG;
+  GUARD_BEGIN
+  unsigned long long w[2];
+  win(h).debugTileSkyline(w);
+  cut2[0] = w[0]; cut2[1] = w[1];
+  return 1;
+  GUARD_END(SVIN_ERR_DEVICE)
+}
+int svin_ba_debug_solve_dense_profiled(int d, int dC, int sb_chain, int s_padded, int ld_s, const double* s_buffer, uint64_t s_buffer_doubles,
+                                       uint64_t s_offset, const double* g, const double* h_c, const double* scale_c, double mu, int fuse_finalize,
+                                       int init_scale, int scratch_fill, double* y, double* htil, int32_t* chol_fail, int32_t* info10,
+                                       double* s_buffer_after, double* scratch, uint64_t cap_scratch, uint64_t tile_cut) {
+  GUARD_BEGIN
+  svin::DebugDenseIn in{d, dC, sb_chain, s_padded, ld_s, s_buffer, (size_t)s_buffer_doubles, (size_t)s_offset, g, h_c, scale_c,
+                        mu, fuse_finalize, init_scale, scratch_fill};
+  in.tileCut = tile_cut & ((1ull << 44) - 1);
+  const svin::DebugDenseOut out{y, htil, chol_fail, info10, s_buffer_after, scratch, (size_t)cap_scratch};
+  return svin::debugSolveDense(in, out);
+  GUARD_END(SVIN_ERR_DEVICE)
+}
 int svin_ba_debug_marginalize(int m, int Lm, const int32_t* marg_rows, int stages, const double* U, const double* ba, const double* W,
                               const double* V, const double* bb, double* U_out, double* ba_out, double* Hk, double* bk, double* J,
                               double* e0, double* Ht, double* bp, double* scal3, int32_t* flags8, int32_t* info16) {

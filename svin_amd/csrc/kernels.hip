@@ -4511,6 +4511,13 @@ __device__ __forceinline__ void k_chol_solve_lds_body(const DeviceProblem& p, in
   int* fl = reinterpret_cast<int*>(htil + dpad);   // kCholFlagInts
   int* bail = fl + 26;
   const int g = lane >> 4, c = lane & 15;
+  // the tile skyline (DeviceProblem::tileCut, pack_plan.hpp planTileSkyline) in two SGPRs: tileHi(k) = the last tile row of column k
+  // that can hold a non-zero.  The border variants take the dense profile.
+  unsigned long long tileCut = 0;
+  if constexpr (kBorder == 0)
+    tileCut = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(p.tileCut >> 32)) << 32) |
+              (unsigned)__builtin_amdgcn_readfirstlane((int)(p.tileCut & 0xffffffffu));
+  auto tileHi = [&](int k) { return nT - 1 - (int)((tileCut >> (4 * k)) & 15); };
 #ifdef SVIN_CHOL_TIMING
   const long long ql0 = __builtin_readcyclecounter();
   long long qWait = 0, qBusy = 0;
@@ -5125,14 +5132,21 @@ __device__ __forceinline__ void k_chol_solve_lds_body(const DeviceProblem& p, in
       // -- it needs wave 0's panel tile only -- and, if pivot kb+1 is out already (rows far from the diagonal run behind wave 0),
       // the panel tile X(I, kb+1) right away: the other rows wait for panel tiles, not for finished rows, and an owner that
       // first completes its whole row (up to nine products) holds all of them up;  then the rest of the row.
+      // Tile skyline: a row I > tileHi(kb) has NO arithmetic in column kb -- tile (I, kb) is zero since the load, no earlier column
+      // reached it (the fill of the skyline: a column that eliminates into row I lengthens every column between them to I), so
+      // X(I, kb) = 0 is there already and the row's other tiles keep their values.  The wave stores the same flags in the same
+      // order, without waiting for a pivot it does not read.  Rows inside the skyline run on their whole segment kb+1 .. I: every
+      // panel tile it multiplies with lies inside the skyline too.
       unsigned early = 0;   // bit I: X(I, kb+1) was solved ahead of column kb+1
       for (int kb = 0; kb < kbEnd; ++kb) {
         const int k0 = 16 * kb;
         const double* D = tileAt(tiles, kb, kb);
+        const int hi0 = tileHi(kb), hi1 = tileHi(kb + 1);
         bool waited = false;
         const unsigned done = early;
         early = 0;
         if (((done >> (kb + 2)) & 1) && owns(kb + 2)) {   // look-ahead row whose panel tile is there already
+          // (inside this column's skyline: a panel tile is solved early only for I <= tileHi of the column it belongs to)
           CHOL_SPINS(cholFlagWait(fl + 1 + kb + 1, kb + 1, bail));
           updateRow(kb + 2, kb, 0);
           cholFlagSet(fl + 13 + kb + 2, kb + 1, lane);
@@ -5140,27 +5154,36 @@ __device__ __forceinline__ void k_chol_solve_lds_body(const DeviceProblem& p, in
         }
         for (int I = kb + 2; I < nT; ++I) {
           if (!owns(I) || ((done >> I) & 1)) continue;
-          if (!waited) CHOL_SPINS(cholFlagWait(fl + 0, kb + 1, bail)); waited = true;
-          panelSolve(tileAt(tiles, I, kb), D, k0);
+          const bool in0 = I <= hi0;
+          if (in0) {
+            if (!waited) CHOL_SPINS(cholFlagWait(fl + 0, kb + 1, bail)); waited = true;
+            panelSolve(tileAt(tiles, I, kb), D, k0);
+          }
           cholFlagSet(fl + 1 + I, kb + 1, lane);
           if (I == kb + 2) {   // the look-ahead row: wave 0 waits for its two tiles next
-            CHOL_SPINS(cholFlagWait(fl + 1 + kb + 1, kb + 1, bail));
-            updateRow(I, kb, 0);
+            if (in0) {
+              CHOL_SPINS(cholFlagWait(fl + 1 + kb + 1, kb + 1, bail));
+              updateRow(I, kb, 0);
+            }
             cholFlagSet(fl + 13 + I, kb + 1, lane);
             CHOL_STAMP_FINE(7, kb);
           }
         }
         for (int I = kb + 3; I < nT; ++I) {
           if (!owns(I)) continue;
-          CHOL_SPINS(cholFlagWait(fl + 1 + kb + 1, kb + 1, bail));
-          updateOne(I, kb);
-          if (__hip_atomic_load(fl + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >= kb + 2) {
+          const bool in0 = I <= hi0;
+          if (in0) {
+            CHOL_SPINS(cholFlagWait(fl + 1 + kb + 1, kb + 1, bail));
+            updateOne(I, kb);
+          }
+          // (a row outside this column's skyline and inside the next one's: tile (I, kb+1) is final as it stands)
+          if (I <= hi1 && __hip_atomic_load(fl + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >= kb + 2) {
             asm volatile("" ::: "memory");
             panelSolve(tileAt(tiles, I, kb + 1), tileAt(tiles, kb + 1, kb + 1), k0 + 16);
             cholFlagSet(fl + 1 + I, kb + 2, lane);
             early |= 1u << I;
           }
-          {
+          if (in0) {
             // the rest needs the panel tiles of rows kb+2 .. I-1 (row I is mine)
             CHOL_SPINS(cholFlagWaitAll(fl + 1 + kb + 2, I - kb - 2, kb + 1, lane, bail));
             updateRow(I, kb, 1);
@@ -7106,6 +7129,21 @@ __global__ __launch_bounds__(kBorderPrepThreads) void k_chol_border_prepare(Devi
 static ReducedSolvePlan solvePlanOf(const DeviceProblem& p) {
   return planReducedSolve(SolveDims{p.d, p.dC, p.sbChain, p.sPadded}, SolveSwitches{optOn(kOptNoLL), optOn(kOptNoSbElim), optOn(kOptNoLdsBorder)});
 }
+static std::atomic<unsigned long long> gLastTileCut{0};
+unsigned long long lastTileCut() { return gLastTileCut.load(std::memory_order_relaxed); }
+// SVIN_CHECK_TILE_SKYLINE (tests): S as the LDS-resident solver is about to load it holds nothing but zeros below the skyline the
+// window was packed with -- the profile BEFORE the fill, which is what the build may write.  Synchronises; never on a timed path.
+static void checkTileSkyline(const DeviceProblem& p, const ReducedSolvePlan& q, hipStream_t s) {
+  HIP_OK(hipStreamSynchronize(s));
+  const int d = p.d, ld = p.ldS ? p.ldS : d, nT = q.dpad / 16;
+  std::vector<double> h((size_t)d * ld);
+  HIP_OK(hipMemcpy(h.data(), p.S, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+  for (int i = 0; i < d; ++i)
+    for (int j = 0; j <= i; ++j)
+      if (i / 16 > tileHiOf(p.tileCutPre, nT, j / 16) && h[(size_t)i * ld + j] != 0.0)
+        throw std::runtime_error("svin_ba: S(" + std::to_string(i) + ", " + std::to_string(j) + ") = " + std::to_string(h[(size_t)i * ld + j]) +
+                                 " lies outside the tile skyline of the reduced system");
+}
 // the dense solve of plan q: of p's own system, of the compact kept system (p is then the view of it), or, with `sb`, of the kept
 // rows the chain elimination leaves in the blocked solver's matrix
 static void launchSolveDense(const DeviceProblem& p, const ReducedSolvePlan& q, hipStream_t s, double mu, bool initScale, bool fuseFinalize,
@@ -7126,6 +7164,8 @@ static void launchSolveDense(const DeviceProblem& p, const ReducedSolvePlan& q, 
              (const double*)nullptr);
       break;
     case kRouteLdsWhole:
+      if (p.tileCutPre & kTileCheckBit) checkTileSkyline(p, q, s);
+      gLastTileCut.store(p.tileCut, std::memory_order_relaxed);
       launch(k_chol_solve_lds<0>, dim3(q.cholLds.grid), dim3(kCholLdsThreads), q.cholLds.ldsBytes, s, p, q.dpad, mu, init, fuse, 0,
              (const double*)nullptr);
       break;
@@ -7197,6 +7237,7 @@ void launchSolveReduced(const DeviceProblem& p, hipStream_t s, double mu, bool i
     launch(k_sb_load, dim3(q.sbLoad.grid), dim3(256), q.sbLoad.ldsBytes, s, p, sb, mu, initScale ? 1 : 0, fuseFinalize ? 1 : 0, (int*)nullptr, 0);
     DeviceProblem v = p;   // the kept system as a problem of its own: rows 0 .. dK of every vector are the kept rows
     v.d = sb.dK; v.S = sb.Sout; v.ldS = sb.ldOut; v.sPadded = 1; v.gRed = sb.gOut; v.sbChain = 0;
+    v.tileCut = v.tileCutPre = 0;   // (the kept system is dense)
     launchSolveDense(v, q, s, 0.0, false, false, nullptr);   // (metric and damping are in S' already)
   }
   launch(k_sb_back, dim3(q.sbBack.grid), dim3(256), q.sbBack.ldsBytes, s, p, sb);
@@ -7847,6 +7888,7 @@ void launchBatchRound(const BatchSlot* dSlots, const DeviceProblem& geom, const 
     launch(k_reduce_slabs_batch, dim3(plan.reduceSlabs.grid, n), dim3(256), 0, s, dSlots);   // (every window sums its own nSlabs)
     const ReducedSolvePlan q = solvePlanOf(p);
     if (!batchedSolverTakes(q)) throw std::logic_error("launchBatchRound: a window batchSupported refuses");
+    gLastTileCut.store(p.tileCut, std::memory_order_relaxed);   // (every window factors inside the skyline of its own slot; this is geom's)
     launch(k_chol_solve_lds_batch<0>, dim3(q.cholLds.grid, n), dim3(kCholLdsThreads), q.cholLds.ldsBytes, s, dSlots, q.dpad, 1, 0, (const double*)nullptr);
     if (p.anyExtVariable) launch(k_post_solve_batch<true>, dim3(grid.post, n), dim3(256), 0, s, dSlots);
     else launch(k_post_solve_batch<false>, dim3(grid.post, n), dim3(256), 0, s, dSlots);

@@ -225,7 +225,14 @@ struct DeviceProblem {
   // isotropic: the evaluation reads obsW alone and takes the scalar arithmetic.  When set, |obsW| = s00 and only its sign
   // (constant landmark) is read.  Host-packed windows only (the device-resident window's records carry one weight).
   const double* obsS;
+  // Tile skyline of S for the LDS-resident solver (pack_plan.hpp planTileSkyline): four bits per tile column k, nT - 1 - hi[k], hi[k]
+  // the last tile row of the column that can hold a non-zero -- after the fill of the factorisation (tileCut: k_chol_solve_lds<0>
+  // leaves the tiles below it alone) and before it (tileCutPre: what SVIN_CHECK_TILE_SKYLINE holds S against).  0 -- a cleared
+  // problem, every caller but Window::pack() -- is the dense profile.  kTileCheckBit of tileCutPre: SVIN_CHECK_TILE_SKYLINE was on at pack().
+  unsigned long long tileCut, tileCutPre;
 };
+constexpr unsigned long long kTileCheckBit = 1ull << 63;
+unsigned long long lastTileCut();   // tileCut of the last launch of k_chol_solve_lds<0> / _batch<0> (options.hpp SVIN_LAST_TILE_SKYLINE_LO / _HI)
 
 // ---- batched solve (svin_ba_solve_prepared_batch: B independent windows through ONE launch sequence per trust-region round, the
 // window as blockIdx.y).  The windows of a batch agree in what the launcher computes once per launch (batch_plan.hpp

@@ -47,6 +47,10 @@ enum DebugOption : int {
                            // k_post_solve without the tail + k_eval_build where solve() would (tests: the pair against the tail, on one handle)
   kOptImuRound64,          // SVIN_IMU_ROUND64: the IMU integration runs its per-step phases in rounds of 64 steps, two per covariance block,
                            // not one round of up to 128 (read at every launch of a kernel that integrates; same bits either way)
+  kOptNoTileSkyline,       // SVIN_NO_TILE_SKYLINE: the LDS-resident reduced solve factors every tile, as if the window's tile skyline
+                           // (pack_plan.hpp planTileSkyline) were dense (read by pack(); same bits either way)
+  kOptCheckTileSkyline,    // SVIN_CHECK_TILE_SKYLINE: launchSolveReduced first synchronises, copies S to the host and throws if a tile
+                           // outside the skyline holds anything but zeros (read by pack(); tests only)
   kOptCount
 };
 
@@ -60,6 +64,8 @@ int lastBatchIdlePpm();
 // read-only inspection field "SVIN_EVAL_BUILD_LAUNCHES": how many times this process has launched k_eval_build (kernels.hpp)
 // read-only inspection field "SVIN_STEP_IN_EVAL_LAUNCHES": how many post-solve passes this process has launched without their tail,
 // the step left to the blocks of the k_eval_build launch behind them (kernels.hpp)
+// read-only inspection fields "SVIN_LAST_TILE_SKYLINE_LO" / "SVIN_LAST_TILE_SKYLINE_HI": the tile skyline the LDS-resident reduced
+// solve was launched with last, as nT - 1 - hi[k] in four bits per tile column -- columns 0 .. 6 / 7 .. 10 (kernels.hpp)
 inline bool optOn(DebugOption which) { return debugOption(which) != 0; }
 
 }  // namespace svin

@@ -151,6 +151,64 @@ inline int speedBiasChainLength(const std::vector<int>& sbOff, int dC, int d, co
   return (ok && d == dC + 9 * n) ? n : 0;
 }
 
+// ---- The tile skyline of the reduced system for the LDS-resident solver (kernels.hip k_chol_solve_lds_body<0>): hi[k] = the last
+// tile row of tile column k (16-row tiling of the padded system) that can hold a non-zero, so that the factorisation leaves the
+// tiles below it alone.  Structure: the camera part (rows < dC: landmarks couple any two poses / extrinsics) is one dense clique;
+// every factor couples all of its variable blocks pairwise, and so does the prior -- each is a CLIQUE, a list of row ranges
+// (cliquePtr: CSR over blkOff / blkLen; fixed blocks are left out by the caller).  Locked rows only lose entries.
+// `pre` is the profile of S as the build leaves it, `hi` the one the factorisation keeps: for k ascending column k eliminates into
+// rows k+1 .. hi[k] only, so each of those columns reaches at least as far down (skyline fill).  hi[k] >= k always.
+// recognised = false (a factor of unknown kind, a host-evaluated factor, any caller that has no block lists) or a system of more
+// than kTileSkylineMaxTiles tile rows: the dense profile.  `cut` / `cutPre` carry the profiles in DeviceProblem: nibble k =
+// nT - 1 - hi[k], so that 0 -- a cleared problem -- is the dense profile.
+constexpr int kTileSkylineMaxTiles = 11;   // (= kCholLdsMaxTiles, solve_plan.hpp: the largest system the LDS-resident solver holds)
+struct TileSkyline {
+  int nT;
+  int hi[kTileSkylineMaxTiles], pre[kTileSkylineMaxTiles];
+  uint64_t cut, cutPre;
+};
+inline uint64_t packTileCut(const int* hi, int nT) {
+  uint64_t w = 0;
+  for (int k = 0; k < nT && k < kTileSkylineMaxTiles; ++k) w |= (uint64_t)(nT - 1 - hi[k]) << (4 * k);
+  return w;
+}
+inline int tileHiOf(uint64_t cut, int nT, int k) { return nT - 1 - (int)((cut >> (4 * k)) & 15); }
+inline TileSkyline planTileSkyline(int d, int dC, const std::vector<int>& cliquePtr, const std::vector<int>& blkOff,
+                                   const std::vector<int>& blkLen, bool recognised) {
+  TileSkyline t{};
+  const int nT = (std::max(d, 0) + 15) / 16;
+  t.nT = nT;
+  if (nT > kTileSkylineMaxTiles) return t;   // (not a system of the LDS-resident solver: nothing reads the profile)
+  for (int k = 0; k < nT; ++k) t.pre[k] = k;
+  bool ok = recognised && dC >= 0 && dC <= d;
+  auto addClique = [&](uint32_t tiles) {   // bit I: the clique has a row in tile row I
+    if (!tiles) return;
+    int top = 0;
+    for (int I = 0; I < nT; ++I) if ((tiles >> I) & 1) top = I;
+    for (int J = 0; J < nT; ++J) if ((tiles >> J) & 1) t.pre[J] = std::max(t.pre[J], top);
+  };
+  auto tilesOf = [&](int off, int len) {
+    uint32_t m = 0;
+    if (off < 0 || len <= 0 || off + len > d) { ok = ok && len <= 0; return m; }
+    for (int I = off / 16; I <= (off + len - 1) / 16; ++I) m |= 1u << I;
+    return m;
+  };
+  if (ok && dC > 0) addClique(tilesOf(0, dC));
+  for (size_t c = 0; ok && c + 1 < cliquePtr.size(); ++c) {
+    uint32_t m = 0;
+    if (cliquePtr[c] < 0 || cliquePtr[c + 1] < cliquePtr[c] || (size_t)cliquePtr[c + 1] > blkOff.size() || blkLen.size() != blkOff.size()) { ok = false; break; }
+    for (int k = cliquePtr[c]; k < cliquePtr[c + 1]; ++k) m |= tilesOf(blkOff[k], blkLen[k]);
+    addClique(m);
+  }
+  if (!ok) for (int k = 0; k < nT; ++k) t.pre[k] = nT - 1;
+  for (int k = 0; k < nT; ++k) t.hi[k] = t.pre[k];
+  for (int k = 0; k < nT; ++k)
+    for (int r = k + 1; r <= t.hi[k]; ++r) t.hi[r] = std::max(t.hi[r], t.hi[k]);
+  t.cut = packTileCut(t.hi, nT);
+  t.cutPre = packTileCut(t.pre, nT);
+  return t;
+}
+
 // ---- the SLOTS of the block-pair form -- one per (landmark, distinct variable pose), ascending with the pose inside a landmark,
 // each with the list of its observations (two for a stereo pair) -- are structure, built once per pack(); k_blocks_slots writes a
 // 24-double record per slot and build.

@@ -68,7 +68,8 @@ struct OptionTable {
         {kOptSlabChunks, "SVIN_SLAB_CHUNKS"}, {kOptNoSbEarly, "SVIN_NO_SB_EARLY"},
         {kOptNoRowSplit, "SVIN_NO_ROW_SPLIT"}, {kOptNoEvalBuild, "SVIN_NO_EVAL_BUILD"},
         {kOptLinearizeEvalBuild, "SVIN_LINEARIZE_EVAL_BUILD"}, {kOptNoStepInEval, "SVIN_NO_STEP_IN_EVAL"},
-        {kOptStepHookInEval, "SVIN_STEP_HOOK_IN_EVAL"}, {kOptImuRound64, "SVIN_IMU_ROUND64"}};
+        {kOptStepHookInEval, "SVIN_STEP_HOOK_IN_EVAL"}, {kOptImuRound64, "SVIN_IMU_ROUND64"},
+        {kOptNoTileSkyline, "SVIN_NO_TILE_SKYLINE"}, {kOptCheckTileSkyline, "SVIN_CHECK_TILE_SKYLINE"}};
     static_assert(sizeof(kNames) / sizeof(kNames[0]) == kOptCount, "every option has its environment variable");
     for (const auto& n : kNames) {
       name[n.which] = n.env;
@@ -94,6 +95,8 @@ int debugOptionByName(const char* name, int* value) {
   if (std::strcmp(name, "SVIN_LAST_SCHUR_FORM") == 0) { if (value) *value = lastSchurForm(); return 1; }   // read-only: not in the table
   if (std::strcmp(name, "SVIN_EVAL_BUILD_LAUNCHES") == 0) { if (value) *value = evalBuildLaunches(); return 1; }   // read-only (kernels.hpp)
   if (std::strcmp(name, "SVIN_STEP_IN_EVAL_LAUNCHES") == 0) { if (value) *value = stepInEvalLaunches(); return 1; }   // read-only (kernels.hpp)
+  if (std::strcmp(name, "SVIN_LAST_TILE_SKYLINE_LO") == 0) { if (value) *value = (int)(lastTileCut() & 0xfffffffull); return 1; }   // read-only (kernels.hpp)
+  if (std::strcmp(name, "SVIN_LAST_TILE_SKYLINE_HI") == 0) { if (value) *value = (int)(lastTileCut() >> 28 & 0xffffull); return 1; }
   if (std::strcmp(name, "SVIN_LAST_BATCH_IDLE_PPM") == 0) { if (value) *value = lastBatchIdlePpm(); return 1; }   // read-only (options.hpp)
   OptionTable& t = optionTable();
   for (int k = 0; k < kOptCount; ++k)
@@ -1689,6 +1692,7 @@ struct PackHost {
   int F = 0;
   std::vector<PriorBlock> hPb;
   int priorM = 0, sbChain = 0;
+  unsigned long long tileCut = 0, tileCutPre = 0;   // the tile skyline of S (pack_plan.hpp planTileSkyline), as DeviceProblem carries it
   // the plan (pack_plan.hpp)
   SchurForm form{};
   std::vector<int> hObsOrder;
@@ -2005,6 +2009,11 @@ void Window::packFactors(PackHost& a) {
     }
   }
   a.sbChain = packSpeedBiasChain(a);
+  if (!optOn(kOptNoTileSkyline)) {
+    const TileSkyline sky = packTileSkyline(a);
+    a.tileCut = sky.cut; a.tileCutPre = sky.cutPre;
+  }
+  if (optOn(kOptCheckTileSkyline)) a.tileCutPre |= kTileCheckBit;
 }
 
 // the chain test of the variable speed / bias blocks (pack_plan.hpp speedBiasChainLength) over the factors of ANY rank and the prior
@@ -2021,6 +2030,33 @@ int Window::packSpeedBiasChain(const PackHost& a) const {
     for (const PriorBlockHost& pb : priorBlocks_)
       if (pb.kind != B_POSE && pb.kind != B_EXT && a.hSbOff[sbSlot_.at(pb.id)] >= 0) priorSlots.push_back(sbSlot_.at(pb.id));
   return speedBiasChainLength(a.hSbOff, a.dC, a.d, facPtr, facSlots, priorSlots);
+}
+
+// the tile skyline of the reduced system (pack_plan.hpp planTileSkyline) from the same block lists: every factor of ANY rank and
+// the prior as cliques of their variable blocks' rows
+TileSkyline Window::packTileSkyline(const PackHost& a) const {
+  std::vector<int> ptr(1, 0), off, len;
+  bool recognised = true;
+  auto add = [&](const Block& blk) {
+    int o = -1;
+    if (blk.kind == B_POSE) o = a.hPoseOff[poseSlot_.at(blk.id)];
+    else if (blk.kind == B_EXT) o = a.hExtOff[extSlot_.at(blk.id)];
+    else if (blk.kind == B_SB) o = a.hSbOff[sbSlot_.at(blk.id)];
+    else recognised = false;
+    if (o >= 0) { off.push_back(o); len.push_back(blk.kind == B_SB ? 9 : 6); }
+  };
+  for (const auto& kv : factors_) {
+    const Factor& f = kv.second;
+    if (f.kind < F_IMU || f.kind > F_DEPTH) recognised = false;   // host-evaluated, or a kind this list does not know
+    for (int b = 0; b < f.nblk && recognised; ++b) add(blocks_.at(f.blocks[b]));
+    ptr.push_back((int)off.size());
+  }
+  if (hasPrior_) {
+    for (const PriorBlockHost& pb : priorBlocks_)
+      if (recognised) add(blocks_.at(pb.id));
+    ptr.push_back((int)off.size());
+  }
+  return planTileSkyline(a.d, a.dC, ptr, off, len, recognised);
 }
 
 // Device buffers grow to what the window needs; every host array is queued in `pending` (sources stay in `a`).  The order of the
@@ -2163,6 +2199,7 @@ void Window::packFillProblem(const PackHost& a) {
   p.yL = dLmVec_.p + 15 * LL; p.deltaL = dLmVec_.p + 18 * LL; p.vL = dLmVec_.p + 21 * LL;
   p.lmFactor = dLmVec_.p + 27 * LL;
   p.sbChain = a.sbChain;
+  p.tileCut = a.tileCut; p.tileCutPre = a.tileCutPre;
   p.slabs = dSlabs_.p; p.nSlabs = a.form.nSlabs;
   p.cholL = dChol_.p;
   p.scal = dScal_.p;
@@ -3719,6 +3756,8 @@ int debugSolveDense(const DebugDenseIn& in, const DebugDenseOut& out) {
   dp.d = d; dp.dC = in.dC; dp.sbChain = in.sbChain; dp.sPadded = in.sPadded ? 1 : 0; dp.ldS = in.ldS;
   dp.S = dS.p + in.sOff; dp.gRed = dG; dp.gFull = dGFull; dp.hC = dHc; dp.htilC = dHtil; dp.scaleC = dScale; dp.yC = dY; dp.vC = dVc;
   dp.cholL = dChol.p; dp.scal = dScal.p;
+  dp.tileCut = dp.tileCutPre = in.tileCut;
+  if (optOn(kOptCheckTileSkyline)) dp.tileCutPre |= kTileCheckBit;
   launchSolveReduced(dp, 0, in.mu, in.initScale != 0, in.fuseFinalize != 0);
   HIP_OK(hipStreamSynchronize(0));
   SolverScalars sc;

@@ -385,6 +385,8 @@ class Window {
   int debugPeekSolverScratch(uint64_t off, uint64_t count, double* out);
   // read-only inspection (svin_ba_debug_last_system): S and g as the last build / reduced solve left them on the device
   int debugLastSystem(double* S, double* g, int capD);
+  // the tile skyline the last pack() gave this window (DeviceProblem::tileCut, tileCutPre without the check bit); launches nothing
+  void debugTileSkyline(unsigned long long* cut2) const { cut2[0] = prob_.tileCut; cut2[1] = prob_.tileCutPre & ~kTileCheckBit; }
   // one trust-region iteration with everything the step is made of read back (window.cpp); the arrays may be null
   struct DebugStepOut {
     double* scalars;                               // 38: SolverScalars after the candidate evaluation, cholFail last
@@ -491,6 +493,7 @@ class Window {
   void packLandmarks(PackHost& a);         // landmarks + observations on the host path
   void packFactors(PackHost& a);           // factors, prior blocks, the speed / bias chain test
   int packSpeedBiasChain(const PackHost& a) const;
+  TileSkyline packTileSkyline(const PackHost& a) const;
   void packReserveAndStage(PackHost& a, std::vector<StagedCopy>& pending);   // device buffers; every upload queued in `pending`
   void packFillProblem(const PackHost& a);   // prob_
   void packEarlyImu(const PackHost& a);      // optimize() on the resident path: the pre-integration on the side stream
@@ -694,6 +697,7 @@ struct DebugDenseIn {
   const double* sBuf; size_t sBufDoubles, sOff;   // the buffer S lies in, and where S starts in it
   const double *g, *hC, *scaleC;
   double mu; int fuseFinalize, initScale, scratchFill;
+  unsigned long long tileCut = 0;   // DeviceProblem::tileCut (svin_ba_debug_solve_dense_profiled; 0: the dense profile)
 };
 struct DebugDenseOut {
   double *y, *htil; int* cholFail; int32_t* info;   // info: 10 ints, svin_ba.h

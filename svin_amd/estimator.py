@@ -56,7 +56,7 @@ EXPORTS = [
     "svin_ba_set_camera_sensor_states", "svin_ba_set_landmark", "svin_ba_num_frames", "svin_ba_num_landmarks",
     "svin_ba_current_keyframe_id", "svin_ba_current_frame_id", "svin_ba_frame_id_by_age", "svin_ba_is_keyframe",
     "svin_ba_is_in_imu_window", "svin_ba_frame_ids", "svin_ba_landmark_ids", "svin_ba_imu_propagation",
-    "svin_ba_eval_reprojection", "svin_ba_observation_ids", "svin_ba_eval_factors", "svin_ba_linearize", "svin_ba_debug_reduced_solve", "svin_ba_debug_reduced_solve_ex", "svin_ba_debug_build_arrays", "svin_ba_debug_trust_region_step", "svin_ba_debug_set_switch", "svin_ba_debug_set_option", "svin_ba_debug_get_option", "svin_ba_debug_sym_eig", "svin_ba_get_path_counters", "svin_ba_debug_landmark_handles", "svin_ba_wait_idle", "svin_ba_debug_peek_solver_scratch", "svin_ba_debug_solve_dense", "svin_ba_debug_last_system", "svin_ba_debug_marginalize",
+    "svin_ba_eval_reprojection", "svin_ba_observation_ids", "svin_ba_eval_factors", "svin_ba_linearize", "svin_ba_debug_reduced_solve", "svin_ba_debug_reduced_solve_ex", "svin_ba_debug_build_arrays", "svin_ba_debug_trust_region_step", "svin_ba_debug_set_switch", "svin_ba_debug_set_option", "svin_ba_debug_get_option", "svin_ba_debug_sym_eig", "svin_ba_get_path_counters", "svin_ba_debug_landmark_handles", "svin_ba_wait_idle", "svin_ba_debug_peek_solver_scratch", "svin_ba_debug_solve_dense", "svin_ba_debug_solve_dense_profiled", "svin_ba_debug_tile_skyline","svin_ba_debug_last_system", "svin_ba_debug_marginalize",
     "svin_ba_get_prior", "svin_ba_get_prior_lin", "svin_ba_describe_block", "svin_ba_bench_jacobian_eval", "svin_ba_bench_jacobian_eval_b2b", "svin_ba_set_pack_mode", "svin_ba_debug_csr", "svin_ba_residual_info",
     "svin_ba_map_add_parameter_block", "svin_ba_set_parameter_block", "svin_ba_map_remove_parameter_block", "svin_ba_map_add_pose_error",
     "svin_ba_map_add_speed_and_bias_error", "svin_ba_map_add_relative_pose_error", "svin_ba_map_add_reprojection_error",
@@ -816,6 +816,15 @@ class Estimator:
         self._check(self.L.svin_ba_debug_last_system(self.h, _d(S), _d(g), d), "debug_last_system")
         return S, g
 
+    def debug_tile_skyline(self):
+        """(tileCut, tileCutPre) of the handle's last pack(): the tile skyline of its reduced system after / before the fill, four
+        bits per tile column (svin_ba_debug_tile_skyline; 0 = dense)"""
+        out = np.zeros(2, np.uint64)
+        fn = self.L.svin_ba_debug_tile_skyline   # (typed here: a library of the ABI before it still loads)
+        fn.restype, fn.argtypes = i32, [C.c_void_p, pu64]
+        self._check(fn(self.h, out.ctypes.data_as(pu64)), "debug_tile_skyline")
+        return int(out[0]), int(out[1])
+
     def debug_build_arrays(self):
         """svin_ba_debug_build_arrays: g_full, h_c, Vinv, b_l, h_l, scale_l of the last build and the IMU factors' redo counters"""
         sizes = np.zeros(3, np.int32)
@@ -884,11 +893,12 @@ class Estimator:
 
     @staticmethod
     def debug_solve_dense(S_buffer, g, d, dC=0, sb_chain=0, padded=True, ldS=0, offset=0, mu=0.0, fused=False, init_scale=True, hC=None,
-                          scaleC=None, want_scratch=False, scratch_fill=0):
+                          scaleC=None, want_scratch=False, scratch_fill=0, tile_cut=None):
         """the reduced solve on a caller-supplied system (include/svin_ba.h: svin_ba_debug_solve_dense).  S_buffer: the flat buffer
         S lies in, from `offset` with leading dimension ldS.  -> dict(y, htil, cholFail, S_after (the buffer read back), scratch
         (the first plan.end doubles of the solver's scratch, or None), and the plan as the library took it: chainMode, route,
-        dSolve, border, bigChainGrid, helperTasks, nBackPanels, chainOverflow, end)"""
+        dSolve, border, bigChainGrid, helperTasks, nBackPanels, chainOverflow, end).
+        tile_cut: the tile skyline of S as DeviceProblem carries it (svin_ba_debug_solve_dense_profiled); None: the dense profile"""
         buf = np.ascontiguousarray(S_buffer, dtype=np.float64).ravel()
         g = np.ascontiguousarray(g, dtype=np.float64)
         hC = None if hC is None else np.ascontiguousarray(hC, dtype=np.float64)
@@ -901,10 +911,15 @@ class Estimator:
         fail, info = np.zeros(1, np.int32), np.zeros(10, np.int32)
 
         def call(scratch, cap):
-            return L.svin_ba_debug_solve_dense(int(d), int(dC), int(sb_chain), 1 if padded else 0, int(ldS), _d(buf), buf.size, int(offset), _d(g),
-                                               None if hC is None else _d(hC), None if scaleC is None else _d(scaleC), float(mu),
-                                               1 if fused else 0, 1 if init_scale else 0, int(scratch_fill), _d(y), _d(htil),
-                                               fail.ctypes.data_as(pi32), info.ctypes.data_as(pi32), _d(after), scratch, cap)
+            args = (int(d), int(dC), int(sb_chain), 1 if padded else 0, int(ldS), _d(buf), buf.size, int(offset), _d(g),
+                    None if hC is None else _d(hC), None if scaleC is None else _d(scaleC), float(mu),
+                    1 if fused else 0, 1 if init_scale else 0, int(scratch_fill), _d(y), _d(htil),
+                    fail.ctypes.data_as(pi32), info.ctypes.data_as(pi32), _d(after), scratch, cap)
+            if tile_cut is None:
+                return L.svin_ba_debug_solve_dense(*args)
+            fn = L.svin_ba_debug_solve_dense_profiled   # (typed here: a library of the ABI before it still loads)
+            fn.restype, fn.argtypes = i32, list(L.svin_ba_debug_solve_dense.argtypes) + [u64]
+            return fn(*args, int(tile_cut))
         scratch = None
         if want_scratch:
             rc = call(_d(np.zeros(1)), 0)   # sizes only
