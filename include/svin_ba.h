@@ -577,6 +577,13 @@ int svin_ba_debug_solve_dense_profiled(int d, int dC, int sb_chain, int s_padded
  * the fill of the factorisation (what the solver, alone or as a slot of a batch, factors inside), cut2[1] before it; four bits per
  * tile column, nT - 1 - hi[k]; 0 = dense.  Launches nothing.  Returns 1.  Test hook. */
 int svin_ba_debug_tile_skyline(svin_ba* h, uint64_t* cut2);
+/* read-only: the deal of the reduced system's tile rows to the waves of the LDS-resident solver that the handle's last pack() planned
+ * from that skyline (pack_plan.hpp planTileDeal), as DeviceProblem carries it: four bits per tile row I >= 2, the wave (1-3, 5-7) a row
+ * moved to from the wave that shares a SIMD with the pivot wave; 0 = the row keeps the solver's closed-form deal.  The whole word is 0
+ * for a dense profile, for a system of at most seven tile rows and with SVIN_NO_TILE_DEAL on at pack().  The deal changes which wave
+ * computes a tile row, never a value.  svin_ba_debug_solve_dense_profiled plans the same deal from the profile it is given (and
+ * reads SVIN_NO_TILE_DEAL itself).  Launches nothing.  Returns 1.  Test hook. */
+int svin_ba_debug_tile_deal(svin_ba* h, uint64_t* deal);
 /* The marginalisation algebra M2 / M3 on a caller-supplied system, on the current HIP device: the launches a job of these
  * dimensions runs after M1 (the function Window::launchMarginalization itself calls, walking the plan planMargJob gives for
  * (m, Lm, nk, nm) and the option SVIN_MARG_EIG), on buffers of the call's own.  Test hook.

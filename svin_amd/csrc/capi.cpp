@@ -637,6 +637,13 @@ int svin_ba_debug_tile_skyline(svin_ba* h, uint64_t* cut2) {
   return 1;
   GUARD_END(SVIN_ERR_DEVICE)
 }
+int svin_ba_debug_tile_deal(svin_ba* h, uint64_t* deal) {
+  if (!h || !deal) return SVIN_ERR_INVALID_ARG;
+  GUARD_BEGIN
+  *deal = win(h).debugTileDeal();
+  return 1;
+  GUARD_END(SVIN_ERR_DEVICE)
+}
 int svin_ba_debug_solve_dense_profiled(int d, int dC, int sb_chain, int s_padded, int ld_s, const double* s_buffer, uint64_t s_buffer_doubles,
                                        uint64_t s_offset, const double* g, const double* h_c, const double* scale_c, double mu, int fuse_finalize,
                                        int init_scale, int scratch_fill, double* y, double* htil, int32_t* chol_fail, int32_t* info10,

@@ -4881,6 +4881,24 @@ __device__ __forceinline__ void k_chol_solve_lds_body(const DeviceProblem& p, in
     // arithmetic of a loader there took twice as long as anywhere else (it reached the load barrier 1.4-2.5 k cycles after the
     // other six) and slowed that first pivot tile down as well.
     const int ldr = wave < nW / 2 ? wave - 1 : wave - 2;   // loader index 0 .. 5 (waves 1-3, 5-7)
+    // the tile rows I >= 2 this wave owns during the factorisation, bit I, in one SGPR: the deal of the window (DeviceProblem::tileDeal,
+    // pack_plan.hpp planTileDeal): the closed form, then the rows the word names -- each one leaves the quiet wave for the wave in its
+    // nibble.  A dozen scalar instructions per moved row (two on the bench window, none for the zero word and the border variants);
+    // a loader walks the word while its loads are in flight -- behind them it reached the load barrier 350 cycles later.
+    unsigned myRows = tileDealBaseRows(nT, wave);
+    auto dealRows = [&]() {
+      if constexpr (kBorder == 0) {
+        unsigned long long deal = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(p.tileDeal >> 32)) << 32) |
+                                  (unsigned)__builtin_amdgcn_readfirstlane((int)(p.tileDeal & 0xffffffffu));
+        while (deal) {
+          const int I = __builtin_ctzll(deal) >> 2;
+          const unsigned bit = 1u << I;
+          myRows = (int)((deal >> (4 * I)) & 15) == wave ? (myRows | bit) : (myRows & ~bit);
+          deal &= ~(15ull << (4 * I));
+        }
+      }
+    };
+    if (wave == nW / 2) dealRows();
     if (wave != nW / 2) {
       // Diagonal tiles 1 .. nT-1: tiles 1 + ldr and 7 + ldr (nT <= 11); off-diagonal tiles dealt round robin, at most
       // ten per loader (55 at nT = 11).  Tile indices are scalar and computed first, so that what follows is ONE batch of
@@ -4970,6 +4988,7 @@ __device__ __forceinline__ void k_chol_solve_lds_body(const DeviceProblem& p, in
         for (int it = 0; it < kMaxOff; ++it) tileRequest(oI[it], oJ[it], vo[it]);
       }
       if (wave == 1) CHOL_STAMP_FINE(8, 0);   // requests issued
+      dealRows();
       __builtin_amdgcn_sched_barrier(0);   // nothing that consumes a loaded value moves above this line: one batch of ~44 loads
 #pragma unroll
       for (int sl = 0; sl < 2; ++sl) tileSelect(dI[sl], dI[sl], vd[sl]);
@@ -5116,18 +5135,19 @@ __device__ __forceinline__ void k_chol_solve_lds_body(const DeviceProblem& p, in
     const int quiet = nW / 2;  // shares SIMD 0 with wave 0
     {
       // ------------------------------------------------------------------ tile-row owners (and the forward substitution)
-      // Rows nT-1 .. nT-6: ONE row per owner wave (1-3, 5-7).  The rows above those (2 .. nT-7: rows 2 and 3 at nT = 10) go to the
-      // wave that shares SIMD 0 with wave 0, ahead of its forward substitution: they are the look-ahead rows of the first
-      // columns, and on an owner wave they queued behind that wave's other row -- wave 0 polled 36 + 15 times (~9 k cycles)
-      // for rows 3 and 4 while their owner finished four more tiles of the column before.  SIMD 0's matrix pipe carries wave
-      // 0's sixteen products per column; ten more chains in the first two columns cost it less than those waits.
+      // The closed form (pack_plan.hpp tileDealBaseRows) -- rows nT-1 .. nT-6: ONE row per owner wave (1-3, 5-7).  The rows above
+      // those (2 .. nT-7: rows 2 and 3 at nT = 10) go to the wave that shares SIMD 0 with wave 0, ahead of its forward substitution:
+      // they are the look-ahead rows of the first columns, and on an owner wave they queued behind that wave's other row -- wave 0
+      // polled 36 + 15 times (~9 k cycles) for rows 3 and 4 while their owner finished four more tiles of the column before.
+      // SIMD 0's matrix pipe carries wave 0's sixteen products per column; ten more chains in the first two columns cost it less
+      // than those waits.
+      // Waves w and w + 4 share a SIMD: the longest row goes with the shortest (9 | 4, 8 | 5, 7 | 6 at nT = 10) -- two long rows on
+      // one matrix pipe starve each other (their look-ahead turns came 5 k cycles late), two short ones leave it idle.
+      // Inside a skyline the long rows have no work in the first columns, so a planned deal (planTileDeal) hands the quiet wave's
+      // rows to owners that are idle there: nothing queues behind anything, and the products leave wave 0's matrix pipe.
       const bool isQuiet = wave == quiet;
-      // waves w and w + 4 share a SIMD: the longest row goes with the shortest (9 | 4, 8 | 5, 7 | 6 at nT = 10) -- two long rows on
-      // one matrix pipe starve each other (their look-ahead turns came 5 k cycles late), two short ones leave it idle
-      const int nWork = nW - 2, widx = wave < quiet ? wave - 1 : nWork + quiet - wave;
-      const int rowMaxQ = nT - 1 - nWork;   // last row of the quiet wave (none if < 2)
-      auto owns = [&](int I) { return isQuiet ? (I >= 2 && I <= rowMaxQ) : (I > rowMaxQ && nT - 1 - I == widx); };
-      const int kbEnd = isQuiet ? rowMaxQ - 1 : nT - 2;   // columns kb < kbEnd have work for this wave
+      auto owns = [&](int I) { return ((myRows >> I) & 1u) != 0; };
+      const int kbEnd = myRows ? 30 - __builtin_clz(myRows) : 0;   // columns kb < kbEnd have work for this wave: its last row's column I - 2 is the last
       // Per column kb and own row I (ascending, the look-ahead row kb+2 first):  panel tile X(I, kb);  then tile (I, kb+1) ALONE
       // -- it needs wave 0's panel tile only -- and, if pivot kb+1 is out already (rows far from the diagonal run behind wave 0),
       // the panel tile X(I, kb+1) right away: the other rows wait for panel tiles, not for finished rows, and an owner that
@@ -7237,7 +7257,7 @@ void launchSolveReduced(const DeviceProblem& p, hipStream_t s, double mu, bool i
     launch(k_sb_load, dim3(q.sbLoad.grid), dim3(256), q.sbLoad.ldsBytes, s, p, sb, mu, initScale ? 1 : 0, fuseFinalize ? 1 : 0, (int*)nullptr, 0);
     DeviceProblem v = p;   // the kept system as a problem of its own: rows 0 .. dK of every vector are the kept rows
     v.d = sb.dK; v.S = sb.Sout; v.ldS = sb.ldOut; v.sPadded = 1; v.gRed = sb.gOut; v.sbChain = 0;
-    v.tileCut = v.tileCutPre = 0;   // (the kept system is dense)
+    v.tileCut = v.tileCutPre = v.tileDeal = 0;   // (the kept system is dense)
     launchSolveDense(v, q, s, 0.0, false, false, nullptr);   // (metric and damping are in S' already)
   }
   launch(k_sb_back, dim3(q.sbBack.grid), dim3(256), q.sbBack.ldsBytes, s, p, sb);

@@ -230,6 +230,9 @@ struct DeviceProblem {
   // leaves the tiles below it alone) and before it (tileCutPre: what SVIN_CHECK_TILE_SKYLINE holds S against).  0 -- a cleared
   // problem, every caller but Window::pack() -- is the dense profile.  kTileCheckBit of tileCutPre: SVIN_CHECK_TILE_SKYLINE was on at pack().
   unsigned long long tileCut, tileCutPre;
+  // The deal of the tile rows to the waves of that solver (pack_plan.hpp planTileDeal): four bits per tile row I >= 2, the wave that
+  // owns the row; 0 -- a cleared problem, every caller but Window::pack() -- is the closed form for that row (tileDealBaseOwner).
+  unsigned long long tileDeal;
 };
 constexpr unsigned long long kTileCheckBit = 1ull << 63;
 unsigned long long lastTileCut();   // tileCut of the last launch of k_chol_solve_lds<0> / _batch<0> (options.hpp SVIN_LAST_TILE_SKYLINE_LO / _HI)

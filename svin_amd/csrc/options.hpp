@@ -51,6 +51,9 @@ enum DebugOption : int {
                            // (pack_plan.hpp planTileSkyline) were dense (read by pack(); same bits either way)
   kOptCheckTileSkyline,    // SVIN_CHECK_TILE_SKYLINE: launchSolveReduced first synchronises, copies S to the host and throws if a tile
                            // outside the skyline holds anything but zeros (read by pack(); tests only)
+  kOptNoTileDeal,          // SVIN_NO_TILE_DEAL: the LDS-resident reduced solve keeps the closed-form deal of its tile rows to its waves
+                           // instead of the one planned from the window's tile skyline (pack_plan.hpp planTileDeal; read by pack() and by
+                           // svin_ba_debug_solve_dense_profiled; same bits either way)
   kOptCount
 };
 

@@ -209,6 +209,70 @@ inline TileSkyline planTileSkyline(int d, int dC, const std::vector<int>& clique
   return t;
 }
 
+// ---- The deal of the tile rows I >= 2 to the waves of the LDS-resident solver (kernels.hip k_chol_solve_lds_body<0>: wave 0 is the
+// serial chain and owns rows 0 and 1; waves 1-3 and 5-7 are the owners; wave 4, the quiet wave, shares SIMD 0 with wave 0).
+// The closed form (tileDealBaseOwner) gives rows nT-1 .. nT-6 one per owner -- waves 1, 2, 3, 7, 6, 5, so that the waves w and w + 4
+// of one SIMD hold the longest row with the shortest -- and rows 2 .. nT-7 to the quiet wave, where their products come out of wave
+// 0's matrix pipe.  Inside a skyline, row I has work in the columns first[I] .. I-2 only, first[I] = min{k : hi[k] >= I}: a long row
+// starts late, a quiet-wave row ends early, and an owner whose own rows are idle in a row's columns takes it at no cost to itself.
+// planTileDeal moves each row of the quiet wave, longest first, to the owner whose rows start latest among those whose work
+// intervals are all disjoint from the row's (ties: the owner of the longer row); a row no owner is free for stays where it is.  No
+// owner ever has two rows with work in one column, and a row keeps its owner for the whole factorisation (one writer per flag).
+// `word` carries the deal in DeviceProblem::tileDeal: nibble I = the wave of a row that MOVED, 0 = the closed form for this row, so
+// that a cleared problem, the dense profile and every nT <= 7 (no row on the quiet wave) keep the closed form unchanged.
+constexpr int kTileDealQuietWave = 4;
+constexpr int tileDealBaseOwner(int nT, int I) {   // I >= 2
+  return nT - 1 - I >= 6 ? kTileDealQuietWave : (nT - 1 - I < 3 ? nT - I : 11 - nT + I);   // r = nT - 1 - I: r + 1 | 10 - r
+}
+// the rows of wave w in the closed form, bit I (the kernel starts from this mask and walks the non-zero nibbles of the word alone:
+// decoding row by row cost every wave ~250 scalar instructions ahead of the load barrier, 1.8 k cycles of the solve)
+constexpr unsigned tileDealBaseRows(int nT, int w) {
+  return w == kTileDealQuietWave ? (nT >= 9 ? ((1u << (nT - 6)) - 1u) & ~3u : 0u)
+                                 : (w < 1 || w > 7 || nT - (w < 4 ? w : 11 - w) < 2 ? 0u : 1u << (nT - (w < 4 ? w : 11 - w)));
+}
+inline int tileDealOwnerOf(uint64_t word, int nT, int I) {
+  const int nib = (int)((word >> (4 * I)) & 15);
+  return nib ? nib : tileDealBaseOwner(nT, I);
+}
+struct TileDeal {
+  int owner[kTileSkylineMaxTiles];   // wave of tile row I (0 for rows 0, 1 and beyond nT: wave 0's, or none)
+  uint64_t word;
+};
+inline TileDeal planTileDeal(int nT, const int* hi) {
+  TileDeal t{};
+  if (nT < 2 || nT > kTileSkylineMaxTiles) return t;
+  int first[kTileSkylineMaxTiles];
+  for (int I = 0; I < nT; ++I) {
+    first[I] = I;
+    for (int k = I; k >= 0; --k) if (hi[k] >= I) first[I] = k;
+  }
+  for (int I = 2; I < nT; ++I) t.owner[I] = tileDealBaseOwner(nT, I);
+  // [first[a], a - 2] and [first[b], b - 2] share a column (an empty interval shares none)
+  auto meet = [&](int a, int b) { return std::max(first[a], first[b]) <= std::min(a, b) - 2; };
+  for (int I = nT - 7; I >= 2; --I) {
+    int best = 0, bestStart = -1, bestRow = -1;
+    for (int w = 1; w < 8; ++w) {
+      if (w == kTileDealQuietWave) continue;
+      bool free = true;
+      int baseRow = -1;
+      for (int J = 2; J < nT; ++J) {
+        if (t.owner[J] != w) continue;
+        free = free && !meet(I, J);
+        baseRow = std::max(baseRow, J);
+      }
+      if (!free || baseRow < 0) continue;
+      if (first[baseRow] > bestStart || (first[baseRow] == bestStart && baseRow > bestRow)) { best = w; bestStart = first[baseRow]; bestRow = baseRow; }
+    }
+    if (best) { t.owner[I] = best; t.word |= (uint64_t)best << (4 * I); }
+  }
+  return t;
+}
+inline TileDeal planTileDeal(int nT, uint64_t cut) {   // from the profile as DeviceProblem::tileCut carries it
+  int hi[kTileSkylineMaxTiles] = {};
+  for (int k = 0; k < nT && k < kTileSkylineMaxTiles; ++k) hi[k] = tileHiOf(cut, nT, k);
+  return planTileDeal(nT, hi);
+}
+
 // ---- the SLOTS of the block-pair form -- one per (landmark, distinct variable pose), ascending with the pose inside a landmark,
 // each with the list of its observations (two for a stereo pair) -- are structure, built once per pack(); k_blocks_slots writes a
 // 24-double record per slot and build.

@@ -69,7 +69,8 @@ struct OptionTable {
         {kOptNoRowSplit, "SVIN_NO_ROW_SPLIT"}, {kOptNoEvalBuild, "SVIN_NO_EVAL_BUILD"},
         {kOptLinearizeEvalBuild, "SVIN_LINEARIZE_EVAL_BUILD"}, {kOptNoStepInEval, "SVIN_NO_STEP_IN_EVAL"},
         {kOptStepHookInEval, "SVIN_STEP_HOOK_IN_EVAL"}, {kOptImuRound64, "SVIN_IMU_ROUND64"},
-        {kOptNoTileSkyline, "SVIN_NO_TILE_SKYLINE"}, {kOptCheckTileSkyline, "SVIN_CHECK_TILE_SKYLINE"}};
+        {kOptNoTileSkyline, "SVIN_NO_TILE_SKYLINE"}, {kOptCheckTileSkyline, "SVIN_CHECK_TILE_SKYLINE"},
+        {kOptNoTileDeal, "SVIN_NO_TILE_DEAL"}};
     static_assert(sizeof(kNames) / sizeof(kNames[0]) == kOptCount, "every option has its environment variable");
     for (const auto& n : kNames) {
       name[n.which] = n.env;
@@ -1693,6 +1694,7 @@ struct PackHost {
   std::vector<PriorBlock> hPb;
   int priorM = 0, sbChain = 0;
   unsigned long long tileCut = 0, tileCutPre = 0;   // the tile skyline of S (pack_plan.hpp planTileSkyline), as DeviceProblem carries it
+  unsigned long long tileDeal = 0;                  // the deal of its tile rows to the solver's waves (planTileDeal), likewise
   // the plan (pack_plan.hpp)
   SchurForm form{};
   std::vector<int> hObsOrder;
@@ -2012,6 +2014,7 @@ void Window::packFactors(PackHost& a) {
   if (!optOn(kOptNoTileSkyline)) {
     const TileSkyline sky = packTileSkyline(a);
     a.tileCut = sky.cut; a.tileCutPre = sky.cutPre;
+    if (!optOn(kOptNoTileDeal)) a.tileDeal = planTileDeal(sky.nT, sky.hi).word;   // (a dense profile keeps the closed form: 0)
   }
   if (optOn(kOptCheckTileSkyline)) a.tileCutPre |= kTileCheckBit;
 }
@@ -2199,7 +2202,7 @@ void Window::packFillProblem(const PackHost& a) {
   p.yL = dLmVec_.p + 15 * LL; p.deltaL = dLmVec_.p + 18 * LL; p.vL = dLmVec_.p + 21 * LL;
   p.lmFactor = dLmVec_.p + 27 * LL;
   p.sbChain = a.sbChain;
-  p.tileCut = a.tileCut; p.tileCutPre = a.tileCutPre;
+  p.tileCut = a.tileCut; p.tileCutPre = a.tileCutPre; p.tileDeal = a.tileDeal;
   p.slabs = dSlabs_.p; p.nSlabs = a.form.nSlabs;
   p.cholL = dChol_.p;
   p.scal = dScal_.p;
@@ -3757,6 +3760,7 @@ int debugSolveDense(const DebugDenseIn& in, const DebugDenseOut& out) {
   dp.S = dS.p + in.sOff; dp.gRed = dG; dp.gFull = dGFull; dp.hC = dHc; dp.htilC = dHtil; dp.scaleC = dScale; dp.yC = dY; dp.vC = dVc;
   dp.cholL = dChol.p; dp.scal = dScal.p;
   dp.tileCut = dp.tileCutPre = in.tileCut;
+  if (in.tileCut && !optOn(kOptNoTileDeal)) dp.tileDeal = planTileDeal(dpad / 16, in.tileCut).word;   // (the deal pack() would give this profile)
   if (optOn(kOptCheckTileSkyline)) dp.tileCutPre |= kTileCheckBit;
   launchSolveReduced(dp, 0, in.mu, in.initScale != 0, in.fuseFinalize != 0);
   HIP_OK(hipStreamSynchronize(0));

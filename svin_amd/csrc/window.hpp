@@ -387,6 +387,8 @@ class Window {
   int debugLastSystem(double* S, double* g, int capD);
   // the tile skyline the last pack() gave this window (DeviceProblem::tileCut, tileCutPre without the check bit); launches nothing
   void debugTileSkyline(unsigned long long* cut2) const { cut2[0] = prob_.tileCut; cut2[1] = prob_.tileCutPre & ~kTileCheckBit; }
+  // the deal of the tile rows to the solver's waves the last pack() gave this window (DeviceProblem::tileDeal); launches nothing
+  unsigned long long debugTileDeal() const { return prob_.tileDeal; }
   // one trust-region iteration with everything the step is made of read back (window.cpp); the arrays may be null
   struct DebugStepOut {
     double* scalars;                               // 38: SolverScalars after the candidate evaluation, cholFail last

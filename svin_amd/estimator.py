@@ -56,7 +56,7 @@ EXPORTS = [
     "svin_ba_set_camera_sensor_states", "svin_ba_set_landmark", "svin_ba_num_frames", "svin_ba_num_landmarks",
     "svin_ba_current_keyframe_id", "svin_ba_current_frame_id", "svin_ba_frame_id_by_age", "svin_ba_is_keyframe",
     "svin_ba_is_in_imu_window", "svin_ba_frame_ids", "svin_ba_landmark_ids", "svin_ba_imu_propagation",
-    "svin_ba_eval_reprojection", "svin_ba_observation_ids", "svin_ba_eval_factors", "svin_ba_linearize", "svin_ba_debug_reduced_solve", "svin_ba_debug_reduced_solve_ex", "svin_ba_debug_build_arrays", "svin_ba_debug_trust_region_step", "svin_ba_debug_set_switch", "svin_ba_debug_set_option", "svin_ba_debug_get_option", "svin_ba_debug_sym_eig", "svin_ba_get_path_counters", "svin_ba_debug_landmark_handles", "svin_ba_wait_idle", "svin_ba_debug_peek_solver_scratch", "svin_ba_debug_solve_dense", "svin_ba_debug_solve_dense_profiled", "svin_ba_debug_tile_skyline","svin_ba_debug_last_system", "svin_ba_debug_marginalize",
+    "svin_ba_eval_reprojection", "svin_ba_observation_ids", "svin_ba_eval_factors", "svin_ba_linearize", "svin_ba_debug_reduced_solve", "svin_ba_debug_reduced_solve_ex", "svin_ba_debug_build_arrays", "svin_ba_debug_trust_region_step", "svin_ba_debug_set_switch", "svin_ba_debug_set_option", "svin_ba_debug_get_option", "svin_ba_debug_sym_eig", "svin_ba_get_path_counters", "svin_ba_debug_landmark_handles", "svin_ba_wait_idle", "svin_ba_debug_peek_solver_scratch", "svin_ba_debug_solve_dense", "svin_ba_debug_solve_dense_profiled", "svin_ba_debug_tile_skyline","svin_ba_debug_tile_deal","svin_ba_debug_last_system", "svin_ba_debug_marginalize",
     "svin_ba_get_prior", "svin_ba_get_prior_lin", "svin_ba_describe_block", "svin_ba_bench_jacobian_eval", "svin_ba_bench_jacobian_eval_b2b", "svin_ba_set_pack_mode", "svin_ba_debug_csr", "svin_ba_residual_info",
     "svin_ba_map_add_parameter_block", "svin_ba_set_parameter_block", "svin_ba_map_remove_parameter_block", "svin_ba_map_add_pose_error",
     "svin_ba_map_add_speed_and_bias_error", "svin_ba_map_add_relative_pose_error", "svin_ba_map_add_reprojection_error",
@@ -824,6 +824,15 @@ class Estimator:
         fn.restype, fn.argtypes = i32, [C.c_void_p, pu64]
         self._check(fn(self.h, out.ctypes.data_as(pu64)), "debug_tile_skyline")
         return int(out[0]), int(out[1])
+
+    def debug_tile_deal(self):
+        """tileDeal of the handle's last pack(): the wave each tile row of its reduced system moved to, four bits per tile row
+        (svin_ba_debug_tile_deal; 0 = the solver's closed-form deal)"""
+        out = np.zeros(1, np.uint64)
+        fn = self.L.svin_ba_debug_tile_deal   # (typed here: a library of the ABI before it still loads)
+        fn.restype, fn.argtypes = i32, [C.c_void_p, pu64]
+        self._check(fn(self.h, out.ctypes.data_as(pu64)), "debug_tile_deal")
+        return int(out[0])
 
     def debug_build_arrays(self):
         """svin_ba_debug_build_arrays: g_full, h_c, Vinv, b_l, h_l, scale_l of the last build and the IMU factors' redo counters"""
