@@ -193,6 +193,27 @@ int svin_ba_rccl_unique_id(unsigned char id_out[128]);
 int svin_ba_set_distributed_rccl(svin_ba* h, int rank, int world, const unsigned char id[128]);
 /* solver tolerances (::ceres::Solver::Options defaults: 1e-6, 1e-10, 1e-8) */
 int svin_ba_set_solver_tolerances(svin_ba* h, double function_tol, double gradient_tol, double parameter_tol);
+/* Trust-region strategy and radii of the solves to come (::ceres::Solver::Options trust_region_strategy_type,
+ * initial_trust_region_radius, max_trust_region_radius).  A new handle has SVIN_STRATEGY_DOGLEG, 1e4, 1e16 -- what the reference's
+ * Estimator::optimize sets or leaves at Ceres' default.  SVIN_STRATEGY_LEVENBERG_MARQUARDT follows Ceres 2.2's
+ * LevenbergMarquardtStrategy: damping diag(J'J) / radius (the diagonal clamped to [1e-6, 1e32] in the Jacobi-scaled system), the step
+ * of that damped system taken whole, radius / max(1/3, 1 - (2 rho - 1)^3) after an accepted step, radius divided by 2, 4, 8, ... after
+ * consecutive rejected or invalid steps, a failed factorisation an invalid step.  Both radii apply to both strategies.
+ * Returns 1; SVIN_ERR_INVALID_ARG for an unknown strategy, a radius that is not finite and positive, or max_radius < initial_radius
+ * (nothing is changed); SVIN_ERR_UNSUPPORTED for Levenberg-Marquardt in landmark-sharded mode (svin_ba_set_distributed with
+ * world > 1, svin_ba_set_distributed_rccl), and those two return it for a handle that has Levenberg-Marquardt set.
+ * Neither call changes a value of the window: what svin_ba_map_get_lhs and the covariance queries keep stays kept. */
+#define SVIN_STRATEGY_DOGLEG 0
+#define SVIN_STRATEGY_LEVENBERG_MARQUARDT 1
+int svin_ba_set_trust_region(svin_ba* h, int strategy, double initial_radius, double max_radius);
+int svin_ba_get_trust_region(svin_ba* h, int* strategy, double* initial_radius, double* max_radius);
+/* The iterations of the last solve (svin_ba_optimize, svin_ba_solve_prepared, a window of svin_ba_solve_prepared_batch), what
+ * `verbose` prints: one row of 6 doubles per iteration that ended in a decision -- cost held after the iteration, relative decrease
+ * (cost change / model cost change; 0 for an invalid step), radius after the iteration, step norm (0 for an invalid step), the
+ * damping mu the iteration's system was built with, outcome (0 accepted, 1 rejected, 2 invalid).  An iteration on which the solve
+ * terminates (a tolerance met, failure) has no row.  *n_rows receives the number of rows of the solve; min(cap_rows, *n_rows) rows
+ * are written to `out` (may be NULL with cap_rows 0).  Host memory only: launches nothing.  Returns 1. */
+int svin_ba_get_iteration_log(svin_ba* h, int cap_rows, double* out, int* n_rows);
 
 /* ---- getters / setters (Estimator.cpp:955-1316) -------------------------------------------- */
 int svin_ba_get_T_WS(svin_ba* h, uint64_t pose_id, double T[7]);

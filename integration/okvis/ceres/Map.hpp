@@ -50,11 +50,16 @@ namespace ceres {
 class Map {
  public:
   /// The fields of ::ceres::Solver::Options the reference sets (Estimator.cpp:878-890) or tests touch.  The device
-  /// solver IS Ceres 2.2's trust-region minimiser with DOGLEG + Schur elimination restated, so
-  /// linear_solver_type / trust_region_strategy_type are accepted and recorded, not dispatched on.
+  /// solver IS Ceres 2.2's trust-region minimiser with Schur elimination restated, so linear_solver_type is accepted
+  /// and recorded, not dispatched on.  trust_region_strategy_type and the two radii ARE dispatched on (solve() hands them to
+  /// svin_ba_set_trust_region): DOGLEG is TRADITIONAL_DOGLEG, LEVENBERG_MARQUARDT is Ceres 2.2's LevenbergMarquardtStrategy.
+  /// The default here stays DOGLEG -- what the reference's Estimator sets -- although ::ceres::Solver::Options' own default is
+  /// LEVENBERG_MARQUARDT: a caller who constructs a Map and never touches the field keeps the solve it had before the field was
+  /// honoured.  Set LEVENBERG_MARQUARDT to get what the same code gets from Ceres.
   struct Options {
     ::ceres::LinearSolverType linear_solver_type = ::ceres::SPARSE_SCHUR;
     ::ceres::TrustRegionStrategyType trust_region_strategy_type = ::ceres::DOGLEG;
+    double initial_trust_region_radius = 1e4, max_trust_region_radius = 1e16;   ///< Ceres' defaults; both strategies
     int num_threads = 1;               ///< accepted and ignored: the solve runs on the GPU
     int max_num_iterations = 50;
     bool minimizer_progress_to_stdout = false;
@@ -330,6 +335,10 @@ class Map {
     // current parameters go to the device, the result comes back into the same objects
     for (const auto& kv : blocks_) svin_ba_set_parameter_block(h_, kv.first, kv.second->parameters());
     svin_ba_set_solver_tolerances(h_, options.function_tolerance, options.gradient_tolerance, options.parameter_tolerance);
+    if (svin_ba_set_trust_region(h_, options.trust_region_strategy_type == ::ceres::LEVENBERG_MARQUARDT ? SVIN_STRATEGY_LEVENBERG_MARQUARDT
+                                                                                                       : SVIN_STRATEGY_DOGLEG,
+                                 options.initial_trust_region_radius, options.max_trust_region_radius) < 0)
+      throw std::runtime_error(std::string("svin_ba_set_trust_region: ") + svin_ba_last_error());
     if (svin_ba_optimize(h_, (uint64_t)options.max_num_iterations, (uint64_t)options.num_threads,
                          options.minimizer_progress_to_stdout ? 1 : 0) < 0)
       throw std::runtime_error(std::string("svin_ba_optimize: ") + svin_ba_last_error());

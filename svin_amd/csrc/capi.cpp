@@ -252,6 +252,10 @@ int svin_ba_set_distributed(svin_ba* h, int rank, int world, svin_allreduce_fn f
     svin::lastError() = "set_distributed: the window has residuals with a non-default loss function (not available in sharded mode)";
     return SVIN_ERR_UNSUPPORTED;
   }
+  if (world > 1 && ro(h).levenbergMarquardt()) {   // (svin_ba_set_trust_region refuses it in sharded mode, too)
+    svin::lastError() = "set_distributed: the handle has the Levenberg-Marquardt strategy set (not available in sharded mode)";
+    return SVIN_ERR_UNSUPPORTED;
+  }
   win(h).setDistributed(rank, world, fn, user);
   return 1;
 } CATCH_ALL(SVIN_ERR_DEVICE)
@@ -271,12 +275,33 @@ int svin_ba_set_distributed_rccl(svin_ba* h, int rank, int world, const unsigned
     svin::lastError() = "set_distributed_rccl: the window has residuals with a non-default loss function (not available in sharded mode)";
     return SVIN_ERR_UNSUPPORTED;
   }
+  if (ro(h).levenbergMarquardt()) {
+    svin::lastError() = "set_distributed_rccl: the handle has the Levenberg-Marquardt strategy set (not available in sharded mode)";
+    return SVIN_ERR_UNSUPPORTED;
+  }
   return win(h).setDistributedRccl(rank, world, id);
   GUARD_END(SVIN_ERR_DEVICE)
 }
 int svin_ba_set_solver_tolerances(svin_ba* h, double f, double g, double p) try {
   if (!h) return SVIN_ERR_INVALID_ARG;
   win(h).setTolerances(f, g, p);
+  return 1;
+} CATCH_ALL(SVIN_ERR_DEVICE)
+// (neither goes through win(): no value of the window changes, the kept getLhs / covariance passes stay)
+int svin_ba_set_trust_region(svin_ba* h, int strategy, double initial_radius, double max_radius) try {
+  return h ? h->w.setTrustRegion(strategy, initial_radius, max_radius) : SVIN_ERR_INVALID_ARG;
+} CATCH_ALL(SVIN_ERR_DEVICE)
+int svin_ba_get_trust_region(svin_ba* h, int* strategy, double* initial_radius, double* max_radius) try {
+  if (!h) return SVIN_ERR_INVALID_ARG;
+  ro(h).getTrustRegion(strategy, initial_radius, max_radius);
+  return 1;
+} CATCH_ALL(SVIN_ERR_DEVICE)
+int svin_ba_get_iteration_log(svin_ba* h, int cap_rows, double* out, int* n_rows) try {
+  if (!h || cap_rows < 0 || (cap_rows > 0 && !out)) return SVIN_ERR_INVALID_ARG;
+  const std::vector<double>& log = ro(h).iterationLog();
+  const int n = (int)(log.size() / 6);
+  if (n_rows) *n_rows = n;
+  std::copy(log.begin(), log.begin() + 6 * (size_t)std::min(n, cap_rows), out);
   return 1;
 } CATCH_ALL(SVIN_ERR_DEVICE)
 int svin_ba_get_T_WS(svin_ba* h, uint64_t id, double T[7]) try { return h ? ro(h).get_T_WS(id, T) : SVIN_ERR_INVALID_ARG; } CATCH_ALL(SVIN_ERR_DEVICE)

@@ -64,6 +64,11 @@ int debugOptionByName(const char* name, int* value);       // 1 and *value, or 0
 // whose grid differs from window to window, the share (parts per million) that left at once -- beyond their window's own extent, or
 // of a window sitting out the stage (window.cpp, batch_plan.hpp)
 int lastBatchIdlePpm();
+// read-only inspection fields "SVIN_SPEC_BUILD_HITS" / "SVIN_SPEC_BUILD_MISSES": speculative builds of Window::solve this process has
+// kept (the step was accepted and left the damping the build assumed) and discarded (window.cpp), either strategy
+void countSpecBuild(bool kept);
+long long specBuildHits();
+long long specBuildMisses();
 // read-only inspection field "SVIN_EVAL_BUILD_LAUNCHES": how many times this process has launched k_eval_build (kernels.hpp)
 // read-only inspection field "SVIN_STEP_IN_EVAL_LAUNCHES": how many post-solve passes this process has launched without their tail,
 // the step left to the blocks of the k_eval_build launch behind them (kernels.hpp)

@@ -6,7 +6,12 @@
 // decisions read come from ONE record per evaluation (SolverScalars); in the landmark-sharded mode every field read here is
 // either all-reduced or computed redundantly from all-reduced data, so the ranks take identical decisions
 // (tests/test_trust_region_host.py feeds two instances the same reduced fields and different rank-local ones).
-// Included by window.cpp (the driver: launches + read-back) and by tests/csrc/trust_region_shim.cpp (g++, no GPU).
+// A second strategy, Ceres 2.2's LevenbergMarquardtStrategy, is a choice of the same state machine (configure()): the damping is
+// 1 / radius, the step is the Gauss-Newton step of the damped system (the driver hands the device an infinite step radius, so
+// doglegCoefficients takes its first branch: delta = -y, jdSq = jySq, jdDotR = -jyDotR), a rejected or invalid step divides the
+// radius by a factor that doubles, and every such step is followed by a new build at the same point under the new damping.
+// Included by window.cpp (the driver: launches + read-back) and by tests/csrc/trust_region_shim.cpp and
+// tests/csrc/trust_region_lm_shim.cpp (g++, no GPU).
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -63,14 +68,29 @@ struct TrustRegionHost {
   // options
   double fTol = 1e-6, gTol = 1e-10, pTol = 1e-8;
   int maxIterations = 10;
+  enum Strategy { kDogleg = 0, kLevenbergMarquardt = 1 };
+  int strategy = kDogleg;
+  double initialRadius = 1e4, maxRadius = 1e16;   // (ceres: initial_trust_region_radius, max_trust_region_radius; both strategies)
   // state
   double radius = 1e4, mu = 1e-8, x_cost = 0;
+  double decreaseFactor = 2.0;   // Levenberg-Marquardt: what the next rejected or invalid step divides the radius by
   bool reuse = false, initScale = true;
   int invalid = 0, iteration = 0, successful = 0;
   int termination = 1;   // 0 convergence, 1 max iterations, 2 time limit (callback), 3 failure
   bool stepOk = true;
   static constexpr double kMinMu = 1e-8, kMaxMu = 1.0, kMuIncrease = 10.0;
 
+  // strategy and radii, before start(); an object that is never configured is the dogleg solve with ceres' default radii
+  void configure(int strategy_, double initialRadius_, double maxRadius_) {
+    strategy = strategy_; initialRadius = initialRadius_; maxRadius = maxRadius_;
+    radius = initialRadius;
+    if (lm()) mu = 1.0 / radius;
+  }
+  bool lm() const { return strategy == kLevenbergMarquardt; }
+  // the radius the device takes its step in: Levenberg-Marquardt's step is the whole Gauss-Newton step of the damped system
+  double stepRadius() const { return lm() ? HUGE_VAL : radius; }
+  // LevenbergMarquardtStrategy::StepAccepted: radius / max(1/3, 1 - (2 rho - 1)^3), at most maxRadius
+  double lmAcceptedRadius(double shrink) const { return std::min(maxRadius, radius / std::max(1.0 / 3.0, shrink)); }
   void start(double initialCost) { x_cost = initialCost; }
   // top of an iteration: false = the loop ends here with `termination` set (stopRequested: the time-limit callback)
   bool beginIteration(bool stopRequested) {
@@ -82,11 +102,18 @@ struct TrustRegionHost {
     return true;
   }
   // damping an accepted step would leave behind (what the speculative build of the next iteration assumes)
-  double muAfterAccept() const { return std::max(kMinMu, 2.0 * mu / kMuIncrease); }
+  // (Levenberg-Marquardt: of a step accepted with the 1/3 clamp active -- rho above 0.937, what a converging solve mostly sees;
+  // the expression is endIteration()'s own, so the driver's test `specMu == mu` holds exactly when the clamp was active)
+  double muAfterAccept() const {
+    if (lm()) return 1.0 / lmAcceptedRadius(0.0);
+    return std::max(kMinMu, 2.0 * mu / kMuIncrease);
+  }
   // after the candidate evaluation of a FRESH linearisation: true = the factorisation failed and the same iteration is
   // retried with a larger mu (DoglegStrategy::ComputeStep's retry ladder); false = go on to endIteration()
+  // Levenberg-Marquardt has no ladder: a failed factorisation is an invalid step (the radius shrinks, endIteration())
   bool retryFactorisation(const TrScalars& sc) {
     if (reuse || sc.failMax == 0.0) return false;
+    if (lm()) { stepOk = false; return false; }
     mu *= kMuIncrease;
     if (mu < kMaxMu) return true;
     stepOk = false;
@@ -100,6 +127,7 @@ struct TrustRegionHost {
     const double model_cost_change = -(sc.jdDotR + 0.5 * sc.jdSq);
     if (!stepOk || !(model_cost_change > 0.0)) {
       if (++invalid >= 5) { termination = 3; return kTerminated; }
+      if (lm()) { lmShrink(); return kInvalid; }
       mu *= kMuIncrease;
       reuse = false;
       return kInvalid;
@@ -115,18 +143,41 @@ struct TrustRegionHost {
     if (relative_decrease > 1e-3) {
       x_cost = candidate_cost;
       ++successful;
+      if (lm()) {
+        radius = lmAcceptedRadius(1.0 - std::pow(2.0 * relative_decrease - 1.0, 3));
+        decreaseFactor = 2.0;
+        mu = 1.0 / radius;
+        reuse = false;
+        return kAccepted;
+      }
       if (relative_decrease < 0.25) radius *= 0.5;
       if (relative_decrease > 0.75) radius = std::max(radius, 3.0 * sc.doglegStepNorm);
-      radius = std::min(radius, 1e16);
+      radius = std::min(radius, maxRadius);
       mu = muAfterAccept();
       reuse = false;
       return kAccepted;
     }
+    if (lm()) { lmShrink(); return kRejected; }
     radius *= 0.5;
     reuse = true;
     return kRejected;
   }
   double relative_decrease = 0, last_step_norm = 0;   // of the last accepted / rejected step (progress output)
+  // one row of the iteration log (svin_ba_get_iteration_log) for the iteration endIteration() has just decided with outcome o
+  // (not kTerminated), muUsed = mu as it stood before that call: cost held, relative decrease, radius after, step norm, mu, outcome
+  void logRow(double muUsed, Outcome o, double row[6]) const {
+    row[0] = x_cost; row[1] = o == kInvalid ? 0.0 : relative_decrease; row[2] = radius; row[3] = o == kInvalid ? 0.0 : last_step_norm;
+    row[4] = muUsed; row[5] = (double)(int)o;
+  }
+
+ private:
+  // LevenbergMarquardtStrategy::StepRejected / StepIsInvalid; the same linearisation is solved again under the new damping
+  void lmShrink() {
+    radius /= decreaseFactor;
+    decreaseFactor *= 2.0;
+    mu = 1.0 / radius;
+    reuse = false;
+  }
 };
 
 }  // namespace svin

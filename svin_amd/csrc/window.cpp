@@ -95,6 +95,8 @@ int debugOptionByName(const char* name, int* value) {
   if (!name) return 0;
   if (std::strcmp(name, "SVIN_LAST_SCHUR_FORM") == 0) { if (value) *value = lastSchurForm(); return 1; }   // read-only: not in the table
   if (std::strcmp(name, "SVIN_EVAL_BUILD_LAUNCHES") == 0) { if (value) *value = evalBuildLaunches(); return 1; }   // read-only (kernels.hpp)
+  if (std::strcmp(name, "SVIN_SPEC_BUILD_HITS") == 0) { if (value) *value = (int)specBuildHits(); return 1; }       // read-only (options.hpp)
+  if (std::strcmp(name, "SVIN_SPEC_BUILD_MISSES") == 0) { if (value) *value = (int)specBuildMisses(); return 1; }
   if (std::strcmp(name, "SVIN_STEP_IN_EVAL_LAUNCHES") == 0) { if (value) *value = stepInEvalLaunches(); return 1; }   // read-only (kernels.hpp)
   if (std::strcmp(name, "SVIN_LAST_TILE_SKYLINE_LO") == 0) { if (value) *value = (int)(lastTileCut() & 0xfffffffull); return 1; }   // read-only (kernels.hpp)
   if (std::strcmp(name, "SVIN_LAST_TILE_SKYLINE_HI") == 0) { if (value) *value = (int)(lastTileCut() >> 28 & 0xffffull); return 1; }
@@ -180,6 +182,19 @@ int Window::setDistributedRccl(int rank, int world, const unsigned char* id128) 
 }
 void Window::dropRcclComm() {
   if (rcclComm_) { (void)rccl().commDestroy(static_cast<ncclComm_t>(rcclComm_)); rcclComm_ = nullptr; }
+}
+int Window::setTrustRegion(int strategy, double initialRadius, double maxRadius) {
+  if (strategy != TrustRegionHost::kDogleg && strategy != TrustRegionHost::kLevenbergMarquardt) return -1 /* SVIN_ERR_INVALID_ARG */;
+  if (!std::isfinite(initialRadius) || !std::isfinite(maxRadius) || !(initialRadius > 0.0) || !(maxRadius >= initialRadius)) {
+    lastError() = "set_trust_region: the radii are finite, positive and initial_radius <= max_radius";
+    return -1;
+  }
+  if (strategy == TrustRegionHost::kLevenbergMarquardt && sharded()) {
+    lastError() = "set_trust_region: Levenberg-Marquardt is not available in landmark-sharded mode";
+    return -4 /* SVIN_ERR_UNSUPPORTED */;
+  }
+  trStrategy_ = strategy; trInitialRadius_ = initialRadius; trMaxRadius_ = maxRadius;
+  return 1;
 }
 void Window::setDistributed(int rank, int world, AllReduceFn fn, void* user) {
   quiesce();
@@ -2398,6 +2413,7 @@ void Window::solve(size_t numIter, bool verbose) {
   DeviceProblem& p = prob_;
   hipStream_t s = stream_;
   summary_.iterations = 0; summary_.num_successful_steps = 0; summary_.termination = 1;
+  iterationLog_.clear();
   if (p.d + 3 * p.L == 0) { summary_.termination = 0; summary_.initial_cost = summary_.final_cost = 0; return; }
   // landmark-sharded mode: partial sums are all-reduced at three points per iteration
   const bool forceDist = optOn(kOptForceDistributed);   // single-rank RCCL: exercises the sharded code path on one GPU
@@ -2435,6 +2451,9 @@ void Window::solve(size_t numIter, bool verbose) {
   struct SbEarlyGuard { DeviceProblem& q; ~SbEarlyGuard() { q.sideLane = 0; } } sbEarlyGuard{p};
   p.sideLane = (!dist && !optOn(kOptNoSbEarly)) ? 1 : 0;
   TrustRegionHost tr;   // every decision of the loop (trust_region.hpp: HIP-free, replayed on the CPU by the tests)
+  if (trStrategy_ != TrustRegionHost::kDogleg || trInitialRadius_ != tr.initialRadius || trMaxRadius_ != tr.maxRadius)
+    tr.configure(trStrategy_, trInitialRadius_, trMaxRadius_);
+  if (tr.lm() && dist) throw std::logic_error("solve: Levenberg-Marquardt in landmark-sharded mode");
   // The first build depends on no decision (initial damping, metric fixed here): it is enqueued right behind the initial
   // evaluation instead of after the host has seen that evaluation's cost (one mailbox round trip of an idle device per solve).
   // A build enqueued behind an evaluation rides in the evaluation's launch where k_eval_build takes the window (one GPU,
@@ -2477,6 +2496,9 @@ void Window::solve(size_t numIter, bool verbose) {
   bool accumulatorsClean = true;   // S / gRed / hC zero (pack() or k_post_solve), nothing speculative in them
   bool specValid = false;          // the accumulators hold the build of the candidate with damping specMu
   double specMu = 0;
+  // a speculative build is enqueued and not yet kept or discarded (SVIN_SPEC_BUILD_HITS / _MISSES); whatever is pending when the
+  // loop ends -- a termination, a rejected step on the last iteration -- was built for nothing
+  struct SpecPending { bool on = false; ~SpecPending() { if (on) countSpecBuild(false); } } specPending;
   while (true) {
     // the time-limit callback (CeresIterationCallback.hpp:80-94).  One GPU: this rank's clock.  Sharded: a rank that left
     // the loop on its own clock would leave the others blocked in the next all-reduce, so the ranks vote (below, with the
@@ -2491,7 +2513,9 @@ void Window::solve(size_t numIter, bool verbose) {
         const bool haveFirst = firstBuilt && tr.initScale && tr.mu == firstMu;   // the build enqueued ahead of the loop
         if (firstBuilt && !haveFirst) accumulatorsClean = false;                 // (a retry with more damping: it has to go)
         firstBuilt = false;
-        if (!haveFirst && !(specValid && specMu == tr.mu && !tr.initScale))
+        const bool specKept = !haveFirst && specValid && specMu == tr.mu && !tr.initScale;
+        if (specPending.on) { countSpecBuild(specKept); specPending.on = false; }
+        if (!haveFirst && !specKept)
           launchAccumulateNormalEquations(p, tr.mu, tr.initScale, s, /*zeroFirst=*/!accumulatorsClean);  // pack() / k_post_solve cleared them
         specValid = false;
         if (dist && p.d > 0) {   // one message: lower triangle of S + gRed + gFull + hC (half of what the full matrix would be)
@@ -2506,24 +2530,26 @@ void Window::solve(size_t numIter, bool verbose) {
         stepInEval = fuseStep && deferLm && evalBuild &&
                      stepInEvalTaken(p, dist, specBuildWanted(speculate, /*accumulatorsClean=*/true, tr.iteration, (int)numIter), tr.reuse,
                                      !hostFactors_.empty(), deviceComputeUnits());
-        launchDoglegPrepare(p, s, fuseStep ? tr.radius : -1.0, stepInEval);
+        launchDoglegPrepare(p, s, fuseStep ? tr.stepRadius() : -1.0, stepInEval);
         accumulatorsClean = true;
         AR(scalD + kScalGroupB, 8 + kScalGatherSlots, 0);   // group B and every rank's (gradMax, failMax) pair: one message
       }
-      if (tr.reuse || !fuseStep) launchDoglegStep(p, tr.radius, s);
+      if (tr.reuse || !fuseStep) launchDoglegStep(p, tr.stepRadius(), s);
       p.lmDeferred = (deferLm && !tr.reuse) ? 1 : 0;
       const bool specWanted = specBuildWanted(speculate, accumulatorsClean, tr.iteration, (int)numIter);
       if (specWanted) specMu = tr.muAfterAccept();
       if (stepInEval && !(specWanted && evalBuild)) throw std::logic_error("solve: the step was left to a build that is not enqueued");
-      const bool specFused = evaluateAll(true, s, (specWanted && evalBuild) ? &specMu : nullptr, false, stepInEval ? tr.radius : -1.0);
+      const bool specFused = evaluateAll(true, s, (specWanted && evalBuild) ? &specMu : nullptr, false, stepInEval ? tr.stepRadius() : -1.0);
       p.lmDeferred = 0;
       if (specWanted && specFused) {   // (k_eval_build built on the candidate's sets itself: no swapped view)
         accumulatorsClean = false;
         specValid = true;
+        specPending.on = true;
       } else if (specWanted) {
         launchAccumulateNormalEquations(withSetsSwapped(p), specMu, false, s, /*zeroFirst=*/false);   // the problem as it looks after an accepted step
         accumulatorsClean = false;
         specValid = true;
+        specPending.on = true;
       }
       if (dist) {  // this iteration will be complete when the vote is read: `iteration` already counts it, and its own duration
                    // so far stands in for the callback's iteration_time_in_seconds (CeresIterationCallback.hpp:86-89)
@@ -2544,8 +2570,10 @@ void Window::solve(size_t numIter, bool verbose) {
       if (tr.retryFactorisation(toTr(sc))) { specValid = false; continue; }   // (the speculative damping assumed an accepted step)
       break;
     }
+    const double muUsed = tr.mu;
     const TrustRegionHost::Outcome o = tr.endIteration(toTr(sc));
     if (o == TrustRegionHost::kTerminated) break;
+    { double row[6]; tr.logRow(muUsed, o, row); iterationLog_.insert(iterationLog_.end(), row, row + 6); }
     if (o == TrustRegionHost::kInvalid) { specValid = false; lastIterTime = nowSec() - tIter; continue; }
     if (o == TrustRegionHost::kAccepted) swapSets();
     else specValid = false;   // rejected: the speculative build is discarded (accumulators are re-zeroed before the next one)
@@ -2589,7 +2617,11 @@ BatchGroupKey batchKeyOf(const DeviceProblem& p) {
 // blocks of the extent-carrying launches of the last svin_ba_solve_prepared_batch: all of them, and those that left at once
 // (beyond their window's extent, or of a window sitting out the stage)
 std::atomic<long long> gBatchBlocksLaunched{0}, gBatchBlocksIdle{0};
+std::atomic<long long> gSpecBuildHits{0}, gSpecBuildMisses{0};
 }  // namespace
+void countSpecBuild(bool kept) { (kept ? gSpecBuildHits : gSpecBuildMisses).fetch_add(1, std::memory_order_relaxed); }
+long long specBuildHits() { return gSpecBuildHits.load(std::memory_order_relaxed); }
+long long specBuildMisses() { return gSpecBuildMisses.load(std::memory_order_relaxed); }
 int lastBatchIdlePpm() {
   const long long n = gBatchBlocksLaunched.load(std::memory_order_relaxed), idle = gBatchBlocksIdle.load(std::memory_order_relaxed);
   return n > 0 ? (int)(1000000.0 * (double)idle / (double)n + 0.5) : 0;
@@ -2608,7 +2640,9 @@ int Window::solvePreparedBatch(Window* const* ws, int n, size_t numIter, bool ve
       if (ws[j] == w) throw std::invalid_argument("svin_ba_solve_prepared_batch: a handle appears twice");
     w->maxIterationsOption_ = numIter;
     const DeviceProblem& p = w->prob_;
-    const bool ok = w->world_ <= 1 && !w->rcclComm_ && w->device_ == ws[0]->device_ && w->mailbox_ && p.d + 3 * p.L > 0 && batchSupported(p);
+    // (a Levenberg-Marquardt window takes the ordinary path inside the call: its rejected steps rebuild, which kBatchReuse is not)
+    const bool ok = w->world_ <= 1 && !w->rcclComm_ && w->device_ == ws[0]->device_ && w->mailbox_ && p.d + 3 * p.L > 0 && batchSupported(p) &&
+                    !w->levenbergMarquardt();
     if (ok) groups[batchKeyOf(p)].push_back(w);
     else alone.push_back(w);
   }
@@ -2681,6 +2715,9 @@ void Window::solveBatchGroup(const std::vector<Window*>& group, size_t numIter, 
     st[i].deferLm = p.L > 0 && p.N > 0;   // (batchSupported: fused step, fused evaluation)
     st[i].tr.fTol = w->fTol_; st[i].tr.gTol = w->gTol_; st[i].tr.pTol = w->pTol_;
     st[i].tr.maxIterations = (int)numIter;
+    if (w->trInitialRadius_ != st[i].tr.initialRadius || w->trMaxRadius_ != st[i].tr.maxRadius)   // (dogleg: the radius is the slot's own)
+      st[i].tr.configure(TrustRegionHost::kDogleg, w->trInitialRadius_, w->trMaxRadius_);
+    w->iterationLog_.clear();
   }
   // one round of a lane: the slots of its windows that take part -> device, the launches; false if no window takes part
   long long blocksLaunched = 0, blocksIdle = 0;
@@ -2758,8 +2795,10 @@ void Window::solveBatchGroup(const std::vector<Window*>& group, size_t numIter, 
         throw std::runtime_error("svin_ba: a device-side wait in the reduced-system solver timed out (cholFail " + std::to_string((int)t.failMax) +
                                  "): synchronisation fault, not a numerical failure");
       if (tr.retryFactorisation(t)) continue;   // the same iteration again, with more damping (next round: a fresh build)
+      const double muUsed = tr.mu;
       const TrustRegionHost::Outcome o = tr.endIteration(t);
       if (o == TrustRegionHost::kTerminated) { finishWindow(i); continue; }
+      { double row[6]; tr.logRow(muUsed, o, row); g[i]->iterationLog_.insert(g[i]->iterationLog_.end(), row, row + 6); }
       if (o == TrustRegionHost::kAccepted) g[i]->swapStateSets();
       if (verbose && o != TrustRegionHost::kInvalid)
         std::printf("[svin_ba batch %d] it %d cost %.9e rel_dec %.3e radius %.3e step %.3e\n", i, tr.iteration, tr.x_cost, tr.relative_decrease,

@@ -355,6 +355,19 @@ class Window {
   bool isInImuWindow(uint64_t id) const;
   const Summary& summary() const { return summary_; }
   void setTolerances(double f, double g, double p) { fTol_ = f; gTol_ = g; pTol_ = p; }
+  // trust-region strategy (0 dogleg, 1 Levenberg-Marquardt: trust_region.hpp) and radii of the solves to come.  Changes no value of
+  // the window, so the C ABI does not drop the kept getLhs / covariance passes for it (capi.cpp).
+  // 1, SVIN_ERR_INVALID_ARG (nothing changed), SVIN_ERR_UNSUPPORTED (Levenberg-Marquardt in landmark-sharded mode)
+  int setTrustRegion(int strategy, double initialRadius, double maxRadius);
+  void getTrustRegion(int* strategy, double* initialRadius, double* maxRadius) const {
+    if (strategy) *strategy = trStrategy_;
+    if (initialRadius) *initialRadius = trInitialRadius_;
+    if (maxRadius) *maxRadius = trMaxRadius_;
+  }
+  bool sharded() const { return world_ > 1 || rcclComm_ != nullptr; }
+  bool levenbergMarquardt() const { return trStrategy_ != 0; }
+  // the last solve's iterations, one row of 6 doubles each (svin_ba.h svin_ba_get_iteration_log); host memory, launches nothing
+  const std::vector<double>& iterationLog() const { return iterationLog_; }
   // landmark-sharded multi-GPU mode: every rank holds all states and the factors between them, plus its own
   // range of landmarks; `fn` all-reduces `count` doubles at device address `ptr` in place (op 0 = sum, 1 = max).
   typedef int (*AllReduceFn)(void* ptr, uint64_t count, int op, void* user);
@@ -611,6 +624,9 @@ class Window {
 
   // solver options
   double fTol_ = 1e-6, gTol_ = 1e-10, pTol_ = 1e-8;
+  int trStrategy_ = 0;                             // TrustRegionHost::Strategy
+  double trInitialRadius_ = 1e4, trMaxRadius_ = 1e16;
+  std::vector<double> iterationLog_;               // 6 doubles per decided iteration of the last solve (TrustRegionHost::logRow)
   double timeLimit_ = -1.0;
   int minIterations_ = 0;
   bool hasCallback_ = false;

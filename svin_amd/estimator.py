@@ -51,7 +51,7 @@ EXPORTS = [
     "svin_ba_remove_observation", "svin_ba_remove_observation_by_id", "svin_ba_optimize", "svin_ba_prepare",
     "svin_ba_solve_prepared", "svin_ba_finish", "svin_ba_invalidate_preintegration",
     "svin_ba_set_optimization_time_limit", "svin_ba_apply_marginalization_strategy", "svin_ba_get_summary",
-    "svin_ba_set_solver_tolerances", "svin_ba_set_distributed", "svin_ba_get_T_WS", "svin_ba_get_speed_and_bias", "svin_ba_get_camera_sensor_states",
+    "svin_ba_set_solver_tolerances", "svin_ba_set_trust_region", "svin_ba_get_trust_region", "svin_ba_get_iteration_log", "svin_ba_set_distributed", "svin_ba_get_T_WS", "svin_ba_get_speed_and_bias", "svin_ba_get_camera_sensor_states",
     "svin_ba_get_landmark", "svin_ba_is_landmark_added", "svin_ba_set_T_WS", "svin_ba_set_speed_and_bias",
     "svin_ba_set_camera_sensor_states", "svin_ba_set_landmark", "svin_ba_num_frames", "svin_ba_num_landmarks",
     "svin_ba_current_keyframe_id", "svin_ba_current_frame_id", "svin_ba_frame_id_by_age", "svin_ba_is_keyframe",
@@ -146,6 +146,9 @@ def load_library():
     sig("svin_ba_apply_marginalization_strategy", i32, vp, u64, u64, pu64, i32, C.POINTER(C.c_int))
     sig("svin_ba_get_summary", i32, vp, C.POINTER(SummaryStruct))
     sig("svin_ba_set_solver_tolerances", i32, vp, f64, f64, f64)
+    sig("svin_ba_set_trust_region", i32, vp, i32, f64, f64)
+    sig("svin_ba_get_trust_region", i32, vp, pi32, pd, pd)
+    sig("svin_ba_get_iteration_log", i32, vp, i32, pd, pi32)
     sig("svin_ba_set_distributed", i32, vp, i32, i32, C.c_void_p, C.c_void_p)
     sig("svin_ba_get_T_WS", i32, vp, u64, pd)
     sig("svin_ba_get_speed_and_bias", i32, vp, u64, u64, pd)
@@ -567,6 +570,32 @@ class Estimator:
     def set_solver_options(self, function_tol=1e-6, gradient_tol=1e-10, parameter_tol=1e-8, jacobi_scaling=True):
         assert jacobi_scaling, "the device solver always applies Ceres' default Jacobi scaling"
         self.L.svin_ba_set_solver_tolerances(self.h, function_tol, gradient_tol, parameter_tol)
+
+    STRATEGIES = {"dogleg": 0, "lm": 1}
+
+    def set_trust_region(self, strategy="dogleg", initial_radius=1e4, max_radius=1e16):
+        """trust-region strategy ("dogleg" or "lm", Ceres 2.2's LevenbergMarquardtStrategy) and radii of the solves to come
+        (include/svin_ba.h: svin_ba_set_trust_region); both radii apply to both strategies"""
+        if strategy not in self.STRATEGIES:
+            raise ValueError("strategy is 'dogleg' or 'lm', not %r" % (strategy,))
+        self._check(self.L.svin_ba_set_trust_region(self.h, self.STRATEGIES[strategy], float(initial_radius), float(max_radius)), "set_trust_region")
+
+    def get_trust_region(self):
+        """-> dict(strategy="dogleg" | "lm", initial_radius, max_radius)"""
+        k, r = np.zeros(1, dtype=np.int32), np.zeros(2)
+        self._check(self.L.svin_ba_get_trust_region(self.h, k.ctypes.data_as(C.POINTER(C.c_int32)), _d(r[0:1]), _d(r[1:2])), "get_trust_region")
+        return dict(strategy={v: n for n, v in self.STRATEGIES.items()}[int(k[0])], initial_radius=float(r[0]), max_radius=float(r[1]))
+
+    def iteration_log(self):
+        """the last solve's iterations as an (n, 6) array: cost held after the iteration, relative decrease, radius after, step norm,
+        mu used, outcome (0 accepted, 1 rejected, 2 invalid) -- what verbose prints (svin_ba_get_iteration_log; launches nothing)"""
+        n = np.zeros(1, dtype=np.int32)
+        pn = n.ctypes.data_as(C.POINTER(C.c_int32))
+        self._check(self.L.svin_ba_get_iteration_log(self.h, 0, None, pn), "iteration_log")
+        out = np.zeros((int(n[0]), 6))
+        if n[0] > 0:
+            self._check(self.L.svin_ba_get_iteration_log(self.h, int(n[0]), _d(out), pn), "iteration_log")
+        return out
 
     # -- getters / setters --------------------------------------------------------------------------
     def get_T_WS(self, fid):
