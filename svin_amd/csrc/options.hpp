@@ -66,7 +66,7 @@ int debugOptionByName(const char* name, int* value);       // 1 and *value, or 0
 int lastBatchIdlePpm();
 // read-only inspection fields "SVIN_SPEC_BUILD_HITS" / "SVIN_SPEC_BUILD_MISSES": speculative builds of Window::solve this process has
 // kept (the step was accepted and left the damping the build assumed) and discarded (window.cpp), either strategy
-void countSpecBuild(bool kept);
+void countSpecBuild(bool kept, int n = 1);
 long long specBuildHits();
 long long specBuildMisses();
 // read-only inspection field "SVIN_EVAL_BUILD_LAUNCHES": how many times this process has launched k_eval_build (kernels.hpp)

@@ -2403,6 +2403,19 @@ SolverScalars Window::readScalars() {
   return sc;
 }
 
+// the fields the trust region reads; gatherRanks (sharded): every rank's (gradMax, failMax) pair was gathered by the sum
+// all-reduce of [group B | gather]
+static TrScalars toTrScalars(const SolverScalars& r, bool gatherRanks) {
+  TrScalars t;
+  t.cost = r.cost; t.stepNormSq = r.stepNormSq; t.xNormSq = r.xNormSq; t.gradMax = r.gradMax; t.failMax = r.failMax;
+  t.jdSq = r.jdSq; t.jdDotR = r.jdDotR; t.doglegStepNorm = r.doglegStepNorm;
+  if (gatherRanks) {
+    t.gradMax = 0.0; t.failMax = 0.0;
+    for (int k = 0; k < kScalGatherSlots / 2; ++k) { t.gradMax = std::max(t.gradMax, r.gather[2 * k]); t.failMax = std::max(t.failMax, r.gather[2 * k + 1]); }
+  }
+  return t;
+}
+
 // ------------------------------------------------------------------------------------------ trust-region loop
 // Ceres 2.2 TrustRegionMinimizer + DoglegStrategy(TRADITIONAL_DOGLEG) semantics with the options
 // Estimator::optimize sets (:878-890): Jacobi scaling, monotonic steps, min_relative_decrease 1e-3,
@@ -2448,7 +2461,7 @@ void Window::solve(size_t numIter, bool verbose) {
   // one GPU: the builds of this solve also run the speed / bias chain's factorisation, beside the landmark elimination (kernels.hpp
   // DeviceProblem::sideLane; every build below is followed by a solve with the same mu / initScale, or not used at all).  Sharded: the
   // chain's blocks are complete only after the all-reduce.
-  struct SbEarlyGuard { DeviceProblem& q; ~SbEarlyGuard() { q.sideLane = 0; } } sbEarlyGuard{p};
+  struct SbEarlyGuard { DeviceProblem& q; ~SbEarlyGuard() { q.sideLane = 0; q.lmDeferred = 0; } } sbEarlyGuard{p};
   p.sideLane = (!dist && !optOn(kOptNoSbEarly)) ? 1 : 0;
   TrustRegionHost tr;   // every decision of the loop (trust_region.hpp: HIP-free, replayed on the CPU by the tests)
   if (trStrategy_ != TrustRegionHost::kDogleg || trInitialRadius_ != tr.initialRadius || trMaxRadius_ != tr.maxRadius)
@@ -2460,13 +2473,19 @@ void Window::solve(size_t numIter, bool verbose) {
   // speculation on: evalBuild; otherwise, and wherever launchEvalBuild declines, the two launches).
   const bool noSpeculation = optOn(kOptNoSpeculation);
   const bool evalBuild = !dist && !noSpeculation;
-  bool firstBuilt = false;
+  // What the accumulators S / gRed / hC hold (iteration_plan.hpp).  Its counts of speculative builds kept and discarded reach
+  // SVIN_SPEC_BUILD_HITS / _MISSES however the solve ends; what is pending then was built for nothing.
+  struct LedgerGuard {
+    AccumulatorLedger l;
+    ~LedgerGuard() { l.close(); countSpecBuild(true, l.hits); countSpecBuild(false, l.misses); }
+  } ledgerGuard;
+  AccumulatorLedger& ledger = ledgerGuard.l;
   const double firstMu = tr.mu;
   const bool firstWanted = !dist && numIter > 0;
   const bool firstFused = evaluateAll(false, s, (firstWanted && evalBuild) ? &firstMu : nullptr, true);
   if (firstWanted) {
     if (!firstFused) launchAccumulateNormalEquations(p, firstMu, true, s, /*zeroFirst=*/false);   // pack() cleared the accumulators
-    firstBuilt = true;
+    ledger.firstEnqueued(firstMu);
   }
   AR(scalD, 4, 0);
   publish();
@@ -2477,117 +2496,97 @@ void Window::solve(size_t numIter, bool verbose) {
   summary_.initial_cost = sc.cost;
   double lastIterTime = 0;
   double stopVotes = 0.0;   // sharded mode: number of ranks whose clock asked to stop (identical on every rank)
-  auto swapSets = [&]() { swapStateSets(); };
-  auto toTr = [&](const SolverScalars& r) {
-    TrScalars t;
-    t.cost = r.cost; t.stepNormSq = r.stepNormSq; t.xNormSq = r.xNormSq; t.gradMax = r.gradMax; t.failMax = r.failMax;
-    t.jdSq = r.jdSq; t.jdDotR = r.jdDotR; t.doglegStepNorm = r.doglegStepNorm;
-    if (dist) {   // every rank's (gradMax, failMax) pair was gathered by the sum all-reduce of [group B | gather]
-      t.gradMax = 0.0; t.failMax = 0.0;
-      for (int k = 0; k < kScalGatherSlots / 2; ++k) { t.gradMax = std::max(t.gradMax, r.gather[2 * k]); t.failMax = std::max(t.failMax, r.gather[2 * k + 1]); }
-    }
-    return t;
-  };
   // Speculative build (single GPU): most steps are accepted, and the host needs ~7 us from the mailbox to the first
   // launch of the next iteration.  Right behind the candidate evaluation the normal equations of the NEXT iteration
   // are enqueued on the candidate's linearisation (the sets an accepted step swaps in) with the damping an accepted
   // step gets; on acceptance they are simply kept, otherwise the accumulators are re-zeroed before the next build.
   const bool speculate = !noSpeculation && (!dist || distNative_);
-  bool accumulatorsClean = true;   // S / gRed / hC zero (pack() or k_post_solve), nothing speculative in them
-  bool specValid = false;          // the accumulators hold the build of the candidate with damping specMu
-  double specMu = 0;
-  // a speculative build is enqueued and not yet kept or discarded (SVIN_SPEC_BUILD_HITS / _MISSES); whatever is pending when the
-  // loop ends -- a termination, a rejected step on the last iteration -- was built for nothing
-  struct SpecPending { bool on = false; ~SpecPending() { if (on) countSpecBuild(false); } } specPending;
   while (true) {
-    // the time-limit callback (CeresIterationCallback.hpp:80-94).  One GPU: this rank's clock.  Sharded: a rank that left
-    // the loop on its own clock would leave the others blocked in the next all-reduce, so the ranks vote (below, with the
-    // evaluation's all-reduce) and stop on the common result
-    const bool stop = dist ? stopVotes > 0.0
-                           : (timeLimit_ >= 0.0 && tr.iteration >= minIterations_ && (nowSec() - tStart) + lastIterTime > timeLimit_);
+    // the time-limit callback.  One GPU: this rank's clock.  Sharded: a rank that left the loop on its own clock would leave
+    // the others blocked in the next all-reduce, so the ranks vote (below, with the evaluation's all-reduce) and stop on the
+    // common result
+    const bool stop = dist ? stopVotes > 0.0 : timeLimitReached(tr.iteration, nowSec() - tStart, lastIterTime);
     if (!tr.beginIteration(stop)) break;
     const double tIter = nowSec();
-    while (true) {
-      bool stepInEval = false;   // this pass of the loop: k_post_solve ends at its partials, k_eval_build takes the step
-      if (!tr.reuse) {
-        const bool haveFirst = firstBuilt && tr.initScale && tr.mu == firstMu;   // the build enqueued ahead of the loop
-        if (firstBuilt && !haveFirst) accumulatorsClean = false;                 // (a retry with more damping: it has to go)
-        firstBuilt = false;
-        const bool specKept = !haveFirst && specValid && specMu == tr.mu && !tr.initScale;
-        if (specPending.on) { countSpecBuild(specKept); specPending.on = false; }
-        if (!haveFirst && !specKept)
-          launchAccumulateNormalEquations(p, tr.mu, tr.initScale, s, /*zeroFirst=*/!accumulatorsClean);  // pack() / k_post_solve cleared them
-        specValid = false;
-        if (dist && p.d > 0) {   // one message: lower triangle of S + gRed + gFull + hC (half of what the full matrix would be)
+    PassEnd end;
+    do {
+      // plan the pass.  The step at the head of the candidate evaluation's blocks (build_plan.hpp stepInEvalTaken): where
+      // k_eval_build follows -- a speculative build is wanted behind this iteration's evaluation (the accumulators are clean
+      // behind the post-solve pass), so never on the last iteration, which k_eval_all ends
+      const bool stepInEval = !tr.reuse && fuseStep && deferLm && evalBuild &&
+                              stepInEvalTaken(p, dist, specBuildWanted(speculate, /*accumulatorsClean=*/true, tr.iteration, (int)numIter), tr.reuse,
+                                              !hostFactors_.empty(), deviceComputeUnits());
+      const IterationPass pass = planPass(stepMode, dist, evalBuild, speculate, tr, (int)numIter, stepInEval, ledger);
+      if (pass.stepInEval && !pass.specInEval) throw std::logic_error("solve: the step was left to a build that is not enqueued");
+      // enqueue the pass
+      if (pass.solve) {
+        if (pass.build.launch) launchAccumulateNormalEquations(p, tr.mu, tr.initScale, s, pass.build.zeroFirst);
+        if (pass.allReduceSystem && p.d > 0) {   // one message: lower triangle of S + gRed + gFull + hC (half of what the full matrix would be)
           launchPackSystem(p, /*unpack=*/false, s);
           AR(p.cholL, packedSystemDoubles(p), 0);
           launchPackSystem(p, /*unpack=*/true, s);
         }
         launchSolveReduced(p, s, tr.mu, tr.initScale, /*fuseFinalize=*/true);
-        p.lmDeferred = deferLm ? 1 : 0;
-        // the step at the head of the candidate evaluation's blocks (build_plan.hpp stepInEvalTaken): where k_eval_build follows --
-        // a speculative build is wanted behind this iteration's evaluation, so never on the last iteration, which k_eval_all ends
-        stepInEval = fuseStep && deferLm && evalBuild &&
-                     stepInEvalTaken(p, dist, specBuildWanted(speculate, /*accumulatorsClean=*/true, tr.iteration, (int)numIter), tr.reuse,
-                                     !hostFactors_.empty(), deviceComputeUnits());
-        launchDoglegPrepare(p, s, fuseStep ? tr.stepRadius() : -1.0, stepInEval);
-        accumulatorsClean = true;
+        p.lmDeferred = pass.lmDeferredPost;
+        launchDoglegPrepare(p, s, pass.prepareRadius, pass.stepInEval);
         AR(scalD + kScalGroupB, 8 + kScalGatherSlots, 0);   // group B and every rank's (gradMax, failMax) pair: one message
       }
-      if (tr.reuse || !fuseStep) launchDoglegStep(p, tr.stepRadius(), s);
-      p.lmDeferred = (deferLm && !tr.reuse) ? 1 : 0;
-      const bool specWanted = specBuildWanted(speculate, accumulatorsClean, tr.iteration, (int)numIter);
-      if (specWanted) specMu = tr.muAfterAccept();
-      if (stepInEval && !(specWanted && evalBuild)) throw std::logic_error("solve: the step was left to a build that is not enqueued");
-      const bool specFused = evaluateAll(true, s, (specWanted && evalBuild) ? &specMu : nullptr, false, stepInEval ? tr.stepRadius() : -1.0);
+      if (pass.doglegStep) launchDoglegStep(p, tr.stepRadius(), s);
+      p.lmDeferred = pass.lmDeferredEval;
+      const bool specFused = evaluateAll(true, s, pass.specInEval ? &pass.specMu : nullptr, false, pass.stepInEval ? tr.stepRadius() : -1.0);
       p.lmDeferred = 0;
-      if (specWanted && specFused) {   // (k_eval_build built on the candidate's sets itself: no swapped view)
-        accumulatorsClean = false;
-        specValid = true;
-        specPending.on = true;
-      } else if (specWanted) {
-        launchAccumulateNormalEquations(withSetsSwapped(p), specMu, false, s, /*zeroFirst=*/false);   // the problem as it looks after an accepted step
-        accumulatorsClean = false;
-        specValid = true;
-        specPending.on = true;
+      if (pass.specWanted) {
+        // the problem as it looks after an accepted step (k_eval_build built on the candidate's sets itself: no swapped view)
+        if (!specFused) launchAccumulateNormalEquations(withSetsSwapped(p), pass.specMu, false, s, /*zeroFirst=*/false);
+        ledger.specEnqueued(pass.specMu);
       }
       if (dist) {  // this iteration will be complete when the vote is read: `iteration` already counts it, and its own duration
                    // so far stands in for the callback's iteration_time_in_seconds (CeresIterationCallback.hpp:86-89)
         const double tNow = nowSec();
-        launchSetStopVote(p.scal, (timeLimit_ >= 0.0 && tr.iteration >= minIterations_ && (tNow - tStart) + (tNow - tIter) > timeLimit_) ? 1.0 : 0.0, s);
+        launchSetStopVote(p.scal, timeLimitReached(tr.iteration, tNow - tStart, tNow - tIter) ? 1.0 : 0.0, s);
       }
       AR(scalD, 8, 0);
       publish();
+      // read the scalars, decide
       sc = readScalars();
       if (dist) stopVotes = sc.spareA0;
-      // failMax carries the cholFail bits (max over the ranks): 4 | 8 = a bounded wait inside a solver kernel timed out.  That is
-      // a synchronisation fault, not a numerical event -- it must not disappear into the mu ladder as "not positive definite"
-      if (toTr(sc).failMax >= 4.0) {
-        distNative_ = false;
-        throw std::runtime_error("svin_ba: a device-side wait in the reduced-system solver timed out (cholFail " +
-                                 std::to_string((int)toTr(sc).failMax) + "): synchronisation fault, not a numerical failure");
-      }
-      if (tr.retryFactorisation(toTr(sc))) { specValid = false; continue; }   // (the speculative damping assumed an accepted step)
-      break;
-    }
-    const double muUsed = tr.mu;
-    const TrustRegionHost::Outcome o = tr.endIteration(toTr(sc));
-    if (o == TrustRegionHost::kTerminated) break;
-    { double row[6]; tr.logRow(muUsed, o, row); iterationLog_.insert(iterationLog_.end(), row, row + 6); }
-    if (o == TrustRegionHost::kInvalid) { specValid = false; lastIterTime = nowSec() - tIter; continue; }
-    if (o == TrustRegionHost::kAccepted) swapSets();
-    else specValid = false;   // rejected: the speculative build is discarded (accumulators are re-zeroed before the next one)
-    if (verbose)
-      std::printf("[svin_ba] it %d cost %.9e rel_dec %.3e radius %.3e step %.3e\n", tr.iteration, tr.x_cost, tr.relative_decrease,
-                  tr.radius, tr.last_step_norm);
-    lastIterTime = nowSec() - tIter;
+      end = finishPass(tr, toTrScalars(sc, dist), tIter, lastIterTime, verbose, -1);
+      ledger.end(end);
+    } while (end == kPassRetry);
+    if (end == kPassTerminated) break;
   }
+  writeSummary(tr, tStart);
+  distNative_ = false;
+}
+
+// failMax carries the cholFail bits (max over the ranks): 4 | 8 = a bounded wait inside a solver kernel timed out.  That is
+// a synchronisation fault, not a numerical event -- it must not disappear into the mu ladder as "not positive definite"
+PassEnd Window::finishPass(TrustRegionHost& tr, const TrScalars& t, double tIter, double& lastIterTime, bool verbose, int batchIndex) {
+  if (t.failMax >= 4.0) {
+    distNative_ = false;
+    throw std::runtime_error("svin_ba: a device-side wait in the reduced-system solver timed out (cholFail " + std::to_string((int)t.failMax) +
+                             "): synchronisation fault, not a numerical failure");
+  }
+  if (tr.retryFactorisation(t)) return kPassRetry;   // the same iteration again, with more damping and a fresh build
+  const double muUsed = tr.mu;
+  const TrustRegionHost::Outcome o = tr.endIteration(t);
+  if (o == TrustRegionHost::kTerminated) return kPassTerminated;
+  { double row[6]; tr.logRow(muUsed, o, row); iterationLog_.insert(iterationLog_.end(), row, row + 6); }
+  if (o == TrustRegionHost::kAccepted) swapStateSets();
+  if (verbose && o != TrustRegionHost::kInvalid) {
+    if (batchIndex < 0) std::printf("[svin_ba] it");
+    else std::printf("[svin_ba batch %d] it", batchIndex);
+    std::printf(" %d cost %.9e rel_dec %.3e radius %.3e step %.3e\n", tr.iteration, tr.x_cost, tr.relative_decrease, tr.radius, tr.last_step_norm);
+  }
+  lastIterTime = nowSec() - tIter;
+  return o == TrustRegionHost::kAccepted ? kPassAccepted : o == TrustRegionHost::kRejected ? kPassRejected : kPassInvalid;
+}
+void Window::writeSummary(const TrustRegionHost& tr, double tStart) {
   summary_.termination = tr.termination;
   summary_.final_cost = tr.x_cost;
   summary_.iterations = tr.iteration;
   summary_.num_successful_steps = tr.successful;
   summary_.total_time = nowSec() - tStart;
-  distNative_ = false;
 }
 
 void Window::swapStateSets() { prob_ = withSetsSwapped(prob_); }
@@ -2619,7 +2618,7 @@ BatchGroupKey batchKeyOf(const DeviceProblem& p) {
 std::atomic<long long> gBatchBlocksLaunched{0}, gBatchBlocksIdle{0};
 std::atomic<long long> gSpecBuildHits{0}, gSpecBuildMisses{0};
 }  // namespace
-void countSpecBuild(bool kept) { (kept ? gSpecBuildHits : gSpecBuildMisses).fetch_add(1, std::memory_order_relaxed); }
+void countSpecBuild(bool kept, int n) { (kept ? gSpecBuildHits : gSpecBuildMisses).fetch_add(n, std::memory_order_relaxed); }
 long long specBuildHits() { return gSpecBuildHits.load(std::memory_order_relaxed); }
 long long specBuildMisses() { return gSpecBuildMisses.load(std::memory_order_relaxed); }
 int lastBatchIdlePpm() {
@@ -2756,25 +2755,15 @@ void Window::solveBatchGroup(const std::vector<Window*>& group, size_t numIter, 
     blocksIdle += grid.blocks(uni) * ln.count - busy;
     return true;
   };
-  auto toTr = [](const SolverScalars& r) {
-    TrScalars t;
-    t.cost = r.cost; t.stepNormSq = r.stepNormSq; t.xNormSq = r.xNormSq; t.gradMax = r.gradMax; t.failMax = r.failMax;
-    t.jdSq = r.jdSq; t.jdDotR = r.jdDotR; t.doglegStepNorm = r.doglegStepNorm;
-    return t;
-  };
   auto finishWindow = [&](int i) {
-    Window* w = g[i];
-    const TrustRegionHost& tr = st[i].tr;
     st[i].active = false;
-    w->summary_.termination = tr.termination; w->summary_.final_cost = tr.x_cost; w->summary_.iterations = tr.iteration;
-    w->summary_.num_successful_steps = tr.successful; w->summary_.total_time = nowSec() - tStart;
+    g[i]->writeSummary(st[i].tr, tStart);
   };
   // top of an iteration for window i (solve(): the time-limit callback, then TrustRegionHost::beginIteration)
   auto begin = [&](int i) {
     Window* w = g[i];
     TrustRegionHost& tr = st[i].tr;
-    const bool stop = w->timeLimit_ >= 0.0 && tr.iteration >= w->minIterations_ && (nowSec() - tStart) + st[i].lastIterTime > w->timeLimit_;
-    if (!tr.beginIteration(stop)) { finishWindow(i); return; }
+    if (!tr.beginIteration(w->timeLimitReached(tr.iteration, nowSec() - tStart, st[i].lastIterTime))) { finishWindow(i); return; }
     st[i].tIter = nowSec();
   };
   // the records of the lane's round in flight, and what each of its windows does with them
@@ -2790,21 +2779,10 @@ void Window::solveBatchGroup(const std::vector<Window*>& group, size_t numIter, 
         begin(i);
         continue;
       }
-      const TrScalars t = toTr(sc);
-      if (t.failMax >= 4.0)
-        throw std::runtime_error("svin_ba: a device-side wait in the reduced-system solver timed out (cholFail " + std::to_string((int)t.failMax) +
-                                 "): synchronisation fault, not a numerical failure");
-      if (tr.retryFactorisation(t)) continue;   // the same iteration again, with more damping (next round: a fresh build)
-      const double muUsed = tr.mu;
-      const TrustRegionHost::Outcome o = tr.endIteration(t);
-      if (o == TrustRegionHost::kTerminated) { finishWindow(i); continue; }
-      { double row[6]; tr.logRow(muUsed, o, row); g[i]->iterationLog_.insert(g[i]->iterationLog_.end(), row, row + 6); }
-      if (o == TrustRegionHost::kAccepted) g[i]->swapStateSets();
-      if (verbose && o != TrustRegionHost::kInvalid)
-        std::printf("[svin_ba batch %d] it %d cost %.9e rel_dec %.3e radius %.3e step %.3e\n", i, tr.iteration, tr.x_cost, tr.relative_decrease,
-                    tr.radius, tr.last_step_norm);
-      st[i].lastIterTime = nowSec() - st[i].tIter;
-      begin(i);
+      const PassEnd end = g[i]->finishPass(tr, toTrScalars(sc, /*gatherRanks=*/false), st[i].tIter, st[i].lastIterTime, verbose, i);
+      if (end == kPassRetry) continue;   // the same iteration again, with more damping (next round: a fresh build)
+      if (end == kPassTerminated) finishWindow(i);
+      else begin(i);
     }
   };
   const bool timing = optOn(kOptBatchTiming);

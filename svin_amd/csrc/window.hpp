@@ -25,6 +25,7 @@
 #include <unordered_map>
 #include <vector>
 #include "flat_map.hpp"
+#include "iteration_plan.hpp"
 #include "kernels.hpp"
 #include "resident.hpp"
 
@@ -472,6 +473,13 @@ class Window {
   void evaluateHostFactors(bool cand, hipStream_t s);   // F_HOST factors: callbacks at the current / candidate blocks, r and J into their FactorLin records
   void solve(size_t numIter, bool verbose);
   static void solveBatchGroup(const std::vector<Window*>& g, size_t numIter, bool verbose);
+  // the end of a pass of either loop, from the scalars of its candidate evaluation onward: the decision, the log row, the swap
+  // of an accepted step, the progress line (batchIndex < 0: solve()'s), lastIterTime
+  PassEnd finishPass(TrustRegionHost& tr, const TrScalars& t, double tIter, double& lastIterTime, bool verbose, int batchIndex);
+  bool timeLimitReached(int iteration, double elapsed, double lastIterTime) const {   // the time-limit callback (CeresIterationCallback.hpp:80-94)
+    return timeLimit_ >= 0.0 && iteration >= minIterations_ && elapsed + lastIterTime > timeLimit_;
+  }
+  void writeSummary(const TrustRegionHost& tr, double tStart);
   void swapStateSets();   // an accepted step: the candidate sets become the current ones
   SolverScalars readScalars();
   // the record of the last evaluation has reached the mailbox (no mailbox: true -- readScalars() synchronises)
