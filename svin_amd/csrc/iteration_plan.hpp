@@ -8,6 +8,8 @@
 // accumulators that knows nothing of the ledger).  Inline, on the stack, no allocation: the host has some 7 us between the
 // mailbox record and the first launch of the next iteration.
 #pragma once
+#include <stdexcept>
+#include "batch_plan.hpp"     // kBatchFull / kBatchReuse / kBatchEval
 #include "build_plan.hpp"     // StepMode, specBuildWanted
 #include "trust_region.hpp"   // TrustRegionHost
 
@@ -65,9 +67,9 @@ struct IterationPass {
   bool allReduceSystem;    // ... sharded: the system travels between the build and the solve
   double prepareRadius;    // ... launchDoglegPrepare's radius: the pass takes the step itself (fused), or -1
   bool stepInEval;         // ... the pass ends at its partials, k_eval_build takes the step at the head of its blocks
-  int lmDeferredPost;      // DeviceProblem::lmDeferred for the post-solve pass
+  int lmDeferredPost;      // PassArgs::lmDeferred (kernels.hpp) for the post-solve pass
   bool doglegStep;         // launchDoglegStep: a re-used linearisation, or a step that is not fused
-  int lmDeferredEval;      // DeviceProblem::lmDeferred for the candidate evaluation
+  int lmDeferredEval;      // PassArgs::lmDeferred for the candidate evaluation
   bool specWanted;         // a speculative build behind the candidate evaluation, with damping specMu,
   double specMu;
   bool specInEval;         // asked of evaluateAll (k_eval_build) -- otherwise, and where evaluateAll declines, a launch of its own
@@ -94,6 +96,18 @@ inline IterationPass planPass(const StepMode& sm, bool dist, bool evalBuild, boo
   if (q.specWanted) q.specMu = tr.muAfterAccept();
   q.specInEval = q.specWanted && evalBuild;
   return q;
+}
+
+// A window of a batched solve (Window::solveBatchGroup) plans its pass like any other -- one GPU, no speculation, no k_eval_build, a
+// ledger of its own -- and the round's stages (batch_plan.hpp, BatchSlot::stages) are that pass: the initial evaluation (!cand, no
+// pass) is kBatchEval alone.  A round has no launch for a zeroing build, a kept build, a system all-reduce, a speculative build or a
+// step that is not the fused one.
+inline int batchStagesOf(const IterationPass& q, bool cand) {
+  if (!cand) return kBatchEval;
+  const bool full = q.solve && q.build.launch && !q.build.zeroFirst && !q.allReduceSystem && !q.stepInEval && q.prepareRadius > 0.0 && !q.doglegStep;
+  const bool reuse = !q.solve && q.doglegStep;
+  if (!(full || reuse) || q.specWanted) throw std::logic_error("batchStagesOf: a pass a batched round has no launches for");
+  return (full ? kBatchFull : kBatchReuse) | kBatchEval;
 }
 
 }  // namespace svin

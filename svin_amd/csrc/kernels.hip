@@ -1950,8 +1950,8 @@ void launchImuPropagation(const DevImu* im, const uint32_t* T, const double* M, 
   launch(k_imu_propagation, dim3(1), dim3(256), 0, s, im, T, M, io, jac, cov, used, imuRound64Arg());
 }
 
-void launchEvalFactors(const DeviceProblem& p, bool cand, hipStream_t s, bool sumCost) {
-  launch(k_eval_factors, dim3(p.F), dim3(256), 0, s, p, cand ? 1 : 0, sumCost ? (p.N > 0 ? evalGrid(p.N) : 0) : -1, imuRound64Arg());
+void launchEvalFactors(const DeviceProblem& p, const PassArgs& a, bool cand, hipStream_t s, bool sumCost) {
+  launch(k_eval_factors, dim3(p.F), dim3(256), 0, s, withPassArgs(p, a), cand ? 1 : 0, sumCost ? (p.N > 0 ? evalGrid(p.N) : 0) : -1, imuRound64Arg());
 }
 // which kernel of evaluateAll sums the cost: 2 = prior evaluation, 1 = factor evaluation, 0 = separate launch
 int costSummedBy(const DeviceProblem& p) {
@@ -2021,10 +2021,10 @@ __global__ __launch_bounds__(256) void k_prior_eval(DeviceProblem p, int cand, i
 }
 
 // reprojBlocks: number of reprojection cost partials to sum (-1: the stand-alone evaluation's grid)
-void launchEvalPrior(const DeviceProblem& p, bool cand, hipStream_t s, bool sumCost, int reprojBlocks) {
+void launchEvalPrior(const DeviceProblem& p, const PassArgs& a, bool cand, hipStream_t s, bool sumCost, int reprojBlocks) {
   if (p.priorM == 0 || !p.ownsCamera) return;
   const int nA = reprojBlocks >= 0 ? reprojBlocks : (p.N > 0 ? evalGrid(p.N) : 0);
-  launch(k_prior_eval, dim3(1), dim3(256), 0, s, p, cand ? 1 : 0, sumCost ? nA : -1);
+  launch(k_prior_eval, dim3(1), dim3(256), 0, s, withPassArgs(p, a), cand ? 1 : 0, sumCost ? nA : -1);
 }
 
 // partial slots of the post-solve pass
@@ -2323,7 +2323,8 @@ StepMode stepModeOf(const DeviceProblem& p, bool sharded) {
                     StepSwitches{optOn(kOptSplitEval), optOn(kOptNoFuseStep), optOn(kOptNoDeferLm)}, sharded);
 }
 bool canFuseEvaluation(const DeviceProblem& p) { return evalPlanOf(p).fusable; }
-void launchEvalAll(const DeviceProblem& p, bool cand, bool sumCost, hipStream_t s) {
+void launchEvalAll(const DeviceProblem& window, const PassArgs& a, bool cand, bool sumCost, hipStream_t s) {
+  const DeviceProblem p = withPassArgs(window, a);
   const EvalPlan e = evalPlanOf(p);
   const int nR = e.nR, pri = e.pri;
   if (sumCost && e.split) {
@@ -4227,7 +4228,7 @@ int schurDenseABlocks(const DeviceProblem& p) {
   return (q.form == kBuildDense && q.aBlocks) ? 1 : 0;
 }
 static ReducedSolvePlan solvePlanOf(const DeviceProblem& p);                                // (behind the solver kernels, below)
-static bool sbEarlyActive(const DeviceProblem& p, const ReducedSolvePlan& q);
+static bool sbEarlyActive(const DeviceProblem& p, const ReducedSolvePlan& q, bool sideLane);
 static void launchSbEarly(const DeviceProblem& p, const ReducedSolvePlan& q, hipStream_t side, double mu, bool initScale);
 static std::atomic<int> gLastSchurForm{0};
 int lastSchurForm() { return gLastSchurForm.load(std::memory_order_relaxed); }
@@ -4241,7 +4242,7 @@ static auto denseKernelOf(DenseVariant v) -> decltype(&k_schur_dense<9, false, 4
   }
   return k_schur_dense<9, false, 4>;
 }
-void launchAccumulateNormalEquations(const DeviceProblem& p, double mu, bool initScale, hipStream_t s, bool zeroFirst) {
+void launchAccumulateNormalEquations(const DeviceProblem& p, double mu, bool initScale, hipStream_t s, bool zeroFirst, bool sideLane) {
   if (zeroFirst) launchZeroBuild(p, s);
   const BuildPlan q = buildPlanOf(p);
   const int nFac = q.nFac;   // this rank's factors; the prior rides along as extra blocks of the same launch
@@ -4263,14 +4264,14 @@ void launchAccumulateNormalEquations(const DeviceProblem& p, double mu, bool ini
     // Round 6: the block-pair form (k_blocks_slots + k_schur_rows) is the default; pack() decides (DeviceProblem::schurBlocks,
     // its slot tables) -- SVIN_PANELS_OLD=1 at pack() time keeps the round-4 / 5 tile form, whose work list holds fewer chunks per
     // workgroup.
-    // p.sideLane (one GPU, wide window; DeviceProblem): the small factors -- and behind them the factorisation and the forward
+    // sideLane (one GPU, wide window; kernels.hpp): the small factors -- and behind them the factorisation and the forward
     // substitution of the speed / bias chain, which read nothing the landmarks contribute to (S_ss, S_sk and g_s come from the IMU
     // factors and the prior alone) -- run on a side stream beside the landmark elimination: 22 + 35 + 29 us off the iteration's
     // critical path.  The pose blocks of S receive the factors' atomic adds AND the plain read-modify-writes of
     // k_blocks_pose_reduce: the latter waits for the former (event `mid`).
     SideLane* lane = nullptr;
     const ReducedSolvePlan solvePlan = solvePlanOf(p);   // (the plan the solve of this iteration computes as well)
-    const bool early = sbEarlyActive(p, solvePlan);
+    const bool early = sbEarlyActive(p, solvePlan, sideLane);
     if (early) {
       lane = &sideLaneOf(s);
       HIP_OK(hipEventRecord(lane->fork, s));
@@ -4389,15 +4390,15 @@ bool stepInEvalTaken(const DeviceProblem& p, bool sharded, bool buildWanted, boo
   in.chunkLdsBytes = q.schurDense.ldsBytes; in.stageBytes = e.stageBytes; in.factorSharedBytes = sizeof(FactorShared);
   return stepInEvalTaken(in);
 }
-bool launchEvalBuild(const DeviceProblem& p, bool cand, double mu, bool initScale, bool factorsCommute, int computeUnits, hipStream_t s,
-                     double stepRadius) {
+bool launchEvalBuild(const DeviceProblem& p, const PassArgs& a, bool cand, double mu, bool initScale, bool factorsCommute, int computeUnits,
+                     hipStream_t s, double stepRadius) {
   const BuildPlan q = buildPlanOf(p);
   const EvalPlan e = evalPlanOf(p);
   const bool head = stepRadius > 0.0;
-  if (head && !(cand && p.lmDeferred)) throw std::logic_error("launchEvalBuild: the step rides in the candidate evaluation with deferred landmarks only");
+  if (head && !(cand && a.lmDeferred)) throw std::logic_error("launchEvalBuild: the step rides in the candidate evaluation with deferred landmarks only");
   if (!evalBuildTaken(buildDimsOf(p), q, e, p.world > 1, computeUnits, sizeof(FactorShared))) return false;
   const int nR = e.nR, pri = e.pri, nEval = e.evalAll.grid;
-  DeviceProblem pb = p;
+  DeviceProblem pb = withPassArgs(p, a);
   pb.aBlocks = 0;   // (the form taken is k_schur_dense<9, false, 4>'s: q.variant == kDense9Copies4, q.formCode 1090)
   gLastSchurForm.store(q.formCode, std::memory_order_relaxed);
   gEvalBuildLaunches.fetch_add(1, std::memory_order_relaxed);
@@ -7235,20 +7236,20 @@ static void launchSbChainFactor(const DeviceProblem& p, const ReducedSolvePlan& 
   launch(k_sb_forward, dim3(q.sbForward.grid), dim3(256), q.sbForward.ldsBytes, s, p, sb);
 }
 // ONE predicate for the build (which then launches the chain's kernels on the side stream) and the solve (which then skips them)
-static bool sbEarlyActive(const DeviceProblem& p, const ReducedSolvePlan& q) {
-  return q.chainMode != 0 && p.sideLane != 0 && p.L > 0 && p.N > 0 && p.dC > 0 && !p.schurDense && p.schurPanels && p.schurBlocks && p.nLocked == 0 &&
+static bool sbEarlyActive(const DeviceProblem& p, const ReducedSolvePlan& q, bool sideLane) {
+  return q.chainMode != 0 && sideLane && p.L > 0 && p.N > 0 && p.dC > 0 && !p.schurDense && p.schurPanels && p.schurBlocks && p.nLocked == 0 &&
          p.F + priorAccBlocks(p) > 0;
 }
 static void launchSbEarly(const DeviceProblem& p, const ReducedSolvePlan& q, hipStream_t side, double mu, bool initScale) {
   launchSbChainFactor(p, q, sbElimArgs(q, p.cholL), side, mu, initScale, /*fuseFinalize=*/true);
 }
-void launchSolveReduced(const DeviceProblem& p, hipStream_t s, double mu, bool initScale, bool fuseFinalize) {
+void launchSolveReduced(const DeviceProblem& p, hipStream_t s, double mu, bool initScale, bool fuseFinalize, bool sideLane) {
   launch(k_lock_rows, dim3(p.nLocked), dim3(256), 0, s, p);
   const ReducedSolvePlan q = solvePlanOf(p);
   if (!q.chainMode) { launchSolveDense(p, q, s, mu, initScale, fuseFinalize, nullptr); return; }
   const SbElimArgs sb = sbElimArgs(q, p.cholL);
   // (early: the build of this iteration has run them already, with this mu and initScale -- launchAccumulateNormalEquations)
-  const bool early = sbEarlyActive(p, q);
+  const bool early = sbEarlyActive(p, q, sideLane);
   if (early && !fuseFinalize) throw std::logic_error("sbEarly without the fused finalisation");
   if (!early) launchSbChainFactor(p, q, sb, s, mu, initScale, fuseFinalize);
   if (q.chainMode == 1) {
@@ -7843,7 +7844,8 @@ __global__ __launch_bounds__(256, SVIN_BATCH_OCC_POST) void k_post_solve_batch(c
 
 static std::atomic<int> gStepInEvalLaunches{0};
 int stepInEvalLaunches() { return gStepInEvalLaunches.load(std::memory_order_relaxed); }
-void launchDoglegPrepare(const DeviceProblem& p, hipStream_t s, double fuseRadius, bool noTail) {
+void launchDoglegPrepare(const DeviceProblem& window, const PassArgs& a, hipStream_t s, double fuseRadius, bool noTail) {
+  const DeviceProblem p = withPassArgs(window, a);
   const EvalPlan e = evalPlanOf(p);
   const int nLm = e.postLm, nFac = e.postFac;
   if (noTail && (e.postSplit || !(fuseRadius > 0.0))) throw std::logic_error("launchDoglegPrepare: the pass without a tail is the narrow window's fused step");
@@ -7864,8 +7866,8 @@ __global__ __launch_bounds__(256) void k_reduce_cost(DeviceProblem p, int nA, in
   reduceCost(p, nA, nB, red);
 }
 
-void launchCost(const DeviceProblem& p, hipStream_t s) {
-  launch(k_reduce_cost, dim3(1), dim3(256), 0, s, p, p.N > 0 ? evalGrid(p.N) : 0, p.F);
+void launchCost(const DeviceProblem& p, const PassArgs& a, hipStream_t s) {
+  launch(k_reduce_cost, dim3(1), dim3(256), 0, s, withPassArgs(p, a), p.N > 0 ? evalGrid(p.N) : 0, p.F);
 }
 
 void launchDoglegStep(const DeviceProblem& p, double radius, hipStream_t s) {

@@ -163,7 +163,8 @@ struct DeviceProblem {
   double* blkPartial;                        // per workgroup of k_blocks_slots: (dC / 6) x 28 sums of Jp^T Jp (21) and Jp^T r (6)
   double *obsUv, *obsW;
   uint32_t* obsIdx;
-  int dCPose, aBlocks;   // rows of the variable poses in the reduced camera system; dense Schur: A accumulated block-wise in LDS
+  int dCPose, aBlocks;   // rows of the variable poses in the reduced camera system; dense Schur: A accumulated block-wise in LDS (aBlocks:
+                         // zero in a window's own problem at all times -- the build launchers set it in their copy, the batched loop in the slot's)
   const int* obsOrder;   // dense Schur with the A part on MFMA: the observations of every 16-landmark chunk sorted by pose (or null)
   int* obsLm;
   // linearisation buffers (cur = accepted point, cand = candidate)
@@ -197,6 +198,8 @@ struct DeviceProblem {
   SolverScalars* scal;
   double* partial;                           // reduction scratch
   unsigned int* tickets;                     // last-block-done counters of the fused reductions
+  // What ONE launch is told besides the window (PassArgs, below): null / zero in a window's own problem at all times, set by the
+  // launcher in the copy it launches with (withPassArgs), by the batched loop in the slot's copy
   ScalarMailbox* mailbox;                    // host-visible copy of the scalars (nullptr: disabled)
   unsigned long long mailboxSeq;             // sequence number to publish with this evaluation
   int lmDeferred;                            // fused step: the landmark part of the retraction is taken by the candidate evaluation
@@ -213,12 +216,7 @@ struct DeviceProblem {
   const int* lockedRows;
   int nLocked;
   int nHostFactors;   // factors of kind F_HOST in `factors` (such a window is not batched: the host evaluates between the launches)
-  // Set by Window::solve for the duration of a one-GPU solve: launches may fork onto the side stream of the solver's stream
-  // (kernels.hip sideLaneOf).  Wide windows: the build also launches the small factors and the speed / bias chain's factorisation
-  // and forward substitution (k_factors_only, k_sb_factor, k_sb_forward) there, beside the landmark elimination, whose results
-  // they do not read, and launchSolveReduced skips them -- build and solve of an iteration must then see the same mu / initScale,
-  // which is what the trust-region loop does anyway.
-  int sideLane;
+  int reservedZero;   // always zero, never read (a host flag once travelled here): the slot stays so that the device code compares equal
   const double* lossTab;   // reprojection loss table: (kind, a) per selector of the packed index; nullptr = every selector 0 (CauchyLoss(1))
   // General 2x2 information on reprojection residuals: the upper-triangular square-root information S = (s00, s01, s11) of every
   // observation, component-major with stride N like the Jacobian arrays (obsS[c * N + o]).  nullptr = every observation is
@@ -235,6 +233,18 @@ struct DeviceProblem {
   unsigned long long tileDeal;
 };
 constexpr unsigned long long kTileCheckBit = 1ull << 63;
+// What a single launch is told besides the window.  A window's problem is constant from one pack() to the next, apart from the set
+// swap of an accepted step; the launchers that can publish the scalars or read lmDeferred take this record and launch with a copy.
+struct PassArgs {
+  ScalarMailbox* mailbox = nullptr;      // where the launch's cost sum publishes the scalars (nullptr: it does not)
+  unsigned long long mailboxSeq = 0;     // ... with this sequence number
+  int lmDeferred = 0;                    // DeviceProblem::lmDeferred
+};
+inline DeviceProblem withPassArgs(const DeviceProblem& p, const PassArgs& a) {
+  DeviceProblem q = p;
+  q.mailbox = a.mailbox; q.mailboxSeq = a.mailboxSeq; q.lmDeferred = a.lmDeferred;
+  return q;
+}
 unsigned long long lastTileCut();   // tileCut of the last launch of k_chol_solve_lds<0> / _batch<0> (options.hpp SVIN_LAST_TILE_SKYLINE_LO / _HI)
 
 // ---- batched solve (svin_ba_solve_prepared_batch: B independent windows through ONE launch sequence per trust-region round, the
@@ -287,7 +297,7 @@ int schurDenseABlocks(const DeviceProblem& p);   // DeviceProblem::aBlocks as la
 // 4000 / 4001 pairwise k_schur with LDS slabs / global atomics; 5000 small factors only.
 int lastSchurForm();
 // Evaluation and the build of the normal equations AT THE EVALUATED POINT in one launch (k_eval_build) + k_reduce_slabs: what
-// launchEvalAll(p, cand, true, s) followed by launchAccumulateNormalEquations(view, mu, initScale, s, false) computes, `view` being
+// launchEvalAll(p, a, cand, true, s) followed by launchAccumulateNormalEquations(view, mu, initScale, s, false) computes, `view` being
 // `p` itself for cand = false and `p` with its current / candidate sets swapped for cand = true.  The accumulators are clean.
 // Returns false, having launched nothing, for a window the launch does not take (build_plan.hpp evalBuildTaken: any form but the
 // narrow dense one with fixed extrinsics, a sharded window, more workgroups than compute units): the caller issues the two launches.
@@ -298,24 +308,30 @@ int lastSchurForm();
 // stepRadius > 0 (cand only, behind launchDoglegPrepare(..., noTail = true)): every evaluation and chunk block first takes the dogleg
 // step of that radius itself, from the partials of the post-solve pass (stepHead, kernels.hip), and evaluates at the candidate it
 // holds in its own LDS; the first reprojection block stores the candidate blocks and the step's record.
-bool launchEvalBuild(const DeviceProblem& p, bool cand, double mu, bool initScale, bool factorsCommute, int computeUnits, hipStream_t s,
-                     double stepRadius = -1.0);
+bool launchEvalBuild(const DeviceProblem& p, const PassArgs& a, bool cand, double mu, bool initScale, bool factorsCommute, int computeUnits,
+                     hipStream_t s, double stepRadius = -1.0);
 int evalBuildLaunches();   // launches of k_eval_build in this process so far (svin_ba_debug_get_option("SVIN_EVAL_BUILD_LAUNCHES"))
 int stepInEvalLaunches();  // post-solve passes launched without their tail so far (svin_ba_debug_get_option("SVIN_STEP_IN_EVAL_LAUNCHES"))
 // Whether the step of this window moves from k_post_solve's tail to the head of k_eval_build's blocks (build_plan.hpp stepInEvalTaken)
 bool stepInEvalTaken(const DeviceProblem& p, bool sharded, bool buildWanted, bool reuse, bool hostFactors, int computeUnits);
 
-// ---- launch wrappers (kernels.hip).  `cand` selects candidate tables/buffers.
+// ---- launch wrappers (kernels.hip).  `cand` selects candidate tables/buffers; `a`: what this launch publishes and defers (a launch
+// that sums no cost publishes nothing: PassArgs{}).  launchEvalReproj hands its kernel single fields, none of them the record's.
 void launchEvalReproj(const DeviceProblem& p, bool cand, bool robust, hipStream_t s);
-void launchEvalFactors(const DeviceProblem& p, bool cand, hipStream_t s, bool sumCost = false);
-void launchEvalPrior(const DeviceProblem& p, bool cand, hipStream_t s, bool sumCost = false, int reprojBlocks = -1);
+void launchEvalFactors(const DeviceProblem& p, const PassArgs& a, bool cand, hipStream_t s, bool sumCost = false);
+void launchEvalPrior(const DeviceProblem& p, const PassArgs& a, bool cand, hipStream_t s, bool sumCost = false, int reprojBlocks = -1);
 // fused evaluation (small factors + reprojection residuals in one launch, 256 observations per block)
 bool canFuseEvaluation(const DeviceProblem& p);   // EvalPlan::fusable
-void launchEvalAll(const DeviceProblem& p, bool cand, bool sumCost, hipStream_t s);
+void launchEvalAll(const DeviceProblem& p, const PassArgs& a, bool cand, bool sumCost, hipStream_t s);
 int costSummedBy(const DeviceProblem& p);  // 2 = prior evaluation, 1 = factor evaluation, 0 = separate launchCost
 void launchBuildNormalEquations(const DeviceProblem& p, double mu, bool initScale, hipStream_t s);
 // the same in two halves, so that a landmark-sharded solve can all-reduce [S | gRed | gFull | hC] in between
-void launchAccumulateNormalEquations(const DeviceProblem& p, double mu, bool initScale, hipStream_t s, bool zeroFirst = true);
+// sideLane (a one-GPU solve: Window::solve hands one value to every build and to the reduced solve behind it): launches may fork onto
+// the side stream of the solver's stream (kernels.hip sideLaneOf).  Wide windows: the build also launches the small factors and the
+// speed / bias chain's factorisation and forward substitution (k_factors_only, k_sb_factor, k_sb_forward) there, beside the landmark
+// elimination, whose results they do not read, and launchSolveReduced skips them -- build and solve of an iteration must then see the
+// same mu / initScale, which is what the trust-region loop does anyway.
+void launchAccumulateNormalEquations(const DeviceProblem& p, double mu, bool initScale, hipStream_t s, bool zeroFirst = true, bool sideLane = false);
 void launchZeroBuild(const DeviceProblem& p, hipStream_t s);
 // Staged upload: the host arrays of a window arrive as ONE block (one DMA from pinned memory); the segment table at
 // the head of the block tells this kernel where each array belongs.  Offsets and sizes are multiples of 16 bytes.
@@ -328,7 +344,8 @@ struct GatherArgs { const void* src[8]; unsigned long long off[8], bytes[8]; int
 void launchGatherStaged(void* block, const GatherArgs& a, hipStream_t s);
 void launchFinalizeNormalEquations(const DeviceProblem& p, double mu, bool initScale, hipStream_t s);
 // Cholesky + GN step of the reduced system; fuseFinalize applies k_finalize_diag (metric + damping) while loading S
-void launchSolveReduced(const DeviceProblem& p, hipStream_t s, double mu = 0.0, bool initScale = false, bool fuseFinalize = false);
+// sideLane: as the build in front was told (launchAccumulateNormalEquations)
+void launchSolveReduced(const DeviceProblem& p, hipStream_t s, double mu = 0.0, bool initScale = false, bool fuseFinalize = false, bool sideLane = false);
 // the blocked route's factorisation alone, at any size; the factor stays in p.cholL at the returned plan's bigM / dinvG / diagF
 ReducedSolvePlan launchFactorBlocked(const DeviceProblem& p, hipStream_t s);
 // grants a kernel `bytes` of dynamic LDS (hipFuncSetAttribute) once per (device, kernel) and only ever upwards: the attribute
@@ -363,7 +380,7 @@ void launch(void (*kernel)(P...), dim3 grid, dim3 block, size_t ldsBytes, hipStr
 // step with that radius and retracts (single GPU, narrow windows) -- launchDoglegStep is then not needed
 // noTail: the blocks store their partials, y_l and v_l and return -- no ticket, no reduction, no step; the launch behind it is
 // launchEvalBuild with the same radius as stepRadius
-void launchDoglegPrepare(const DeviceProblem& p, hipStream_t s, double fuseRadius = -1.0, bool noTail = false);
+void launchDoglegPrepare(const DeviceProblem& p, const PassArgs& a, hipStream_t s, double fuseRadius = -1.0, bool noTail = false);
 void launchDoglegStep(const DeviceProblem& p, double radius, hipStream_t s);  // delta, J*delta pass, candidate, norms
 // sharded mode: the (all-reduced) scalars + sequence number into the pinned-host mailbox, as one wave-wide store
 void launchPublishScalars(const SolverScalars* scal, ScalarMailbox* mailbox, unsigned long long seq, hipStream_t s);
@@ -371,7 +388,7 @@ void launchSetStopVote(SolverScalars* scal, double vote, hipStream_t s);
 // sharded mode: [lower triangle of S | gRed | gFull | hC] <-> one contiguous message in p.cholL (packedSystemDoubles long)
 size_t packedSystemDoubles(const DeviceProblem& p);
 void launchPackSystem(const DeviceProblem& p, bool unpack, hipStream_t s);
-void launchCost(const DeviceProblem& p, hipStream_t s);                  // sums partial costs into scal->cost
+void launchCost(const DeviceProblem& p, const PassArgs& a, hipStream_t s);   // sums partial costs into scal->cost
 void launchImuPropagation(const DevImu* im /*device*/, const uint32_t* T, const double* M, double* io, double* jac, double* cov,
                           int* used, hipStream_t s);
 void launchLandmarkQuality(const DeviceProblem& p, double* quality, hipStream_t s);

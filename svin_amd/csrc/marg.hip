@@ -1781,7 +1781,7 @@ void Window::launchMarginalization(const MargJob& job) {
     }
   }
   if (pl.factors) {
-    launchEvalFactors(q, false, s);
+    launchEvalFactors(q, PassArgs{}, false, s);
     launch(k_marg_accum_factors, dim3(pl.accumFactors.grid), dim3(256), pl.accumFactors.ldsBytes, s, q, md);
   }
   if (job.keepPre) {   // inspection: the system after M1 (svin_ba_get_marg_pre), before anything is eliminated

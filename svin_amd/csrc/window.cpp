@@ -2237,7 +2237,7 @@ void Window::packEarlyImu(const PackHost& a) {
   for (const DevImu& im : a.hImu) anyRedo |= im.redo != 0;
   if (!anyRedo) return;
   HIP_OK(hipStreamWaitEvent(stream2_, evUploaded_, 0));
-  launchEvalFactors(prob_, false, stream2_, false);
+  launchEvalFactors(prob_, PassArgs{}, false, stream2_, false);
   HIP_OK(hipEventRecord(evImuReady_, stream2_));
   HIP_OK(hipStreamWaitEvent(stream_, evImuReady_, 0));
 }
@@ -2356,34 +2356,34 @@ void Window::downloadStates() {
 
 // buildMu: the caller enqueues the build of the normal equations at the evaluated point (damping *buildMu, clean accumulators)
 // right behind this evaluation -- true is returned when the evaluation's launch has taken that build along (k_eval_build)
-bool Window::evaluateAll(bool cand, hipStream_t s, const double* buildMu, bool buildInitScale, double stepRadius) {
+bool Window::evaluateAll(bool cand, hipStream_t s, ScalarMailbox* publishTo, int lmDeferred, const double* buildMu, bool buildInitScale,
+                         double stepRadius) {
   const bool stepInEval = stepRadius > 0.0;   // (stepInEvalTaken said so in front of the post-solve pass: the same predicate governs both)
   if (stepInEval && !hostFactors_.empty()) throw std::logic_error("evaluateAll: the step at the head of the evaluation with host-evaluated factors");
   evaluateHostFactors(cand, s);
-  prob_.mailbox = distNative_ ? nullptr : mailboxDev_;   // sharded: published after the all-reduce (launchPublishScalars)
-  prob_.mailboxSeq = ++mailboxSeq_;
+  const PassArgs a{publishTo, ++mailboxSeq_, lmDeferred};
   const int who = costSummedBy(prob_);
   if (canFuseEvaluation(prob_) && !optOn(kOptSplitEval)) {
     if (buildMu && !optOn(kOptNoEvalBuild) &&
-        launchEvalBuild(prob_, cand, *buildMu, buildInitScale, maxTermsPerBlock_ <= 2, deviceComputeUnits(), s, stepInEval ? stepRadius : -1.0))
+        launchEvalBuild(prob_, a, cand, *buildMu, buildInitScale, maxTermsPerBlock_ <= 2, deviceComputeUnits(), s, stepInEval ? stepRadius : -1.0))
       return true;
     // the post-solve pass without its tail is enqueued already: nothing else takes the step
     if (stepInEval) throw std::logic_error("evaluateAll: k_eval_build declined a window whose step it was to take");
     // one launch: the reprojection blocks and the prior run next to the (much longer) IMU factor blocks
-    launchEvalAll(prob_, cand, true, s);  // factor, reprojection and prior blocks; the last one sums the cost
+    launchEvalAll(prob_, a, cand, true, s);  // factor, reprojection and prior blocks; the last one sums the cost
     return false;
   }
   if (stepInEval) throw std::logic_error("evaluateAll: the split evaluation cannot take the step");
   launchEvalReproj(prob_, cand, true, s);
-  launchEvalFactors(prob_, cand, s, who == 1);
-  launchEvalPrior(prob_, cand, s, who == 2);
-  if (who == 0) launchCost(prob_, s);
+  launchEvalFactors(prob_, a, cand, s, who == 1);
+  launchEvalPrior(prob_, a, cand, s, who == 2);
+  if (who == 0) launchCost(prob_, a, s);
   return false;
 }
 
-SolverScalars Window::readScalars() {
+SolverScalars Window::readScalars(bool fromMailbox) {
   SolverScalars sc;
-  if (mailbox_ && (world_ <= 1 || distNative_)) {
+  if (mailbox_ && fromMailbox) {
     // wait for the sequence number of the last evaluateAll(); bounded spin, then fall back to a real synchronise
     volatile unsigned long long* seq = &mailbox_->seq;
     const double tSpin = nowSec();
@@ -2423,7 +2423,7 @@ static TrScalars toTrScalars(const SolverScalars& r, bool gatherRanks) {
 // takes the accept/reject decision from one SolverScalars read-back per iteration.
 void Window::solve(size_t numIter, bool verbose) {
   const double tStart = nowSec();
-  DeviceProblem& p = prob_;
+  const DeviceProblem& p = prob_;
   hipStream_t s = stream_;
   summary_.iterations = 0; summary_.num_successful_steps = 0; summary_.termination = 1;
   iterationLog_.clear();
@@ -2442,9 +2442,11 @@ void Window::solve(size_t numIter, bool verbose) {
   };
   // the scalars reach the host through the mailbox once they are complete: on one GPU the evaluation kernel publishes
   // them itself; in sharded mode they are complete only after the all-reduce, so a one-wave kernel publishes them then
-  distNative_ = dist && rcclComm_ != nullptr;
+  const bool distNative = dist && rcclComm_ != nullptr;
+  ScalarMailbox* const publishTo = distNative ? nullptr : mailboxDev_;
+  const bool fromMailbox = world_ <= 1 || distNative;
   auto publish = [&]() {
-    if (distNative_ && mailbox_) launchPublishScalars(p.scal, mailboxDev_, mailboxSeq_, s);
+    if (distNative && mailbox_) launchPublishScalars(p.scal, mailboxDev_, mailboxSeq_, s);
   };
   double* scalD = reinterpret_cast<double*>(p.scal);  // [0..7] group A, [8..15] group B, [16..31] the ranks' (gradMax, failMax) pairs
   // the post-solve pass can take the dogleg step itself when no all-reduce sits between them and one workgroup
@@ -2459,10 +2461,9 @@ void Window::solve(size_t numIter, bool verbose) {
   // landmark step: the two never meet because a sharded solve takes neither the fused nor the deferred step
   if (dist && (fuseStep || deferLm)) throw std::logic_error("sharded solve with a fused step");
   // one GPU: the builds of this solve also run the speed / bias chain's factorisation, beside the landmark elimination (kernels.hpp
-  // DeviceProblem::sideLane; every build below is followed by a solve with the same mu / initScale, or not used at all).  Sharded: the
-  // chain's blocks are complete only after the all-reduce.
-  struct SbEarlyGuard { DeviceProblem& q; ~SbEarlyGuard() { q.sideLane = 0; q.lmDeferred = 0; } } sbEarlyGuard{p};
-  p.sideLane = (!dist && !optOn(kOptNoSbEarly)) ? 1 : 0;
+  // launchAccumulateNormalEquations; every build below is followed by a solve with the same mu / initScale, or not used at all).
+  // Sharded: the chain's blocks are complete only after the all-reduce.  Every build and the reduced solve get this one value.
+  const bool sideLane = !dist && !optOn(kOptNoSbEarly);
   TrustRegionHost tr;   // every decision of the loop (trust_region.hpp: HIP-free, replayed on the CPU by the tests)
   if (trStrategy_ != TrustRegionHost::kDogleg || trInitialRadius_ != tr.initialRadius || trMaxRadius_ != tr.maxRadius)
     tr.configure(trStrategy_, trInitialRadius_, trMaxRadius_);
@@ -2482,14 +2483,14 @@ void Window::solve(size_t numIter, bool verbose) {
   AccumulatorLedger& ledger = ledgerGuard.l;
   const double firstMu = tr.mu;
   const bool firstWanted = !dist && numIter > 0;
-  const bool firstFused = evaluateAll(false, s, (firstWanted && evalBuild) ? &firstMu : nullptr, true);
+  const bool firstFused = evaluateAll(false, s, publishTo, 0, (firstWanted && evalBuild) ? &firstMu : nullptr, true);
   if (firstWanted) {
-    if (!firstFused) launchAccumulateNormalEquations(p, firstMu, true, s, /*zeroFirst=*/false);   // pack() cleared the accumulators
+    if (!firstFused) launchAccumulateNormalEquations(p, firstMu, true, s, /*zeroFirst=*/false, sideLane);   // pack() cleared the accumulators
     ledger.firstEnqueued(firstMu);
   }
   AR(scalD, 4, 0);
   publish();
-  SolverScalars sc = readScalars();
+  SolverScalars sc = readScalars(fromMailbox);
   tr.fTol = fTol_; tr.gTol = gTol_; tr.pTol = pTol_;
   tr.maxIterations = (int)numIter;
   tr.start(sc.cost);
@@ -2500,7 +2501,7 @@ void Window::solve(size_t numIter, bool verbose) {
   // launch of the next iteration.  Right behind the candidate evaluation the normal equations of the NEXT iteration
   // are enqueued on the candidate's linearisation (the sets an accepted step swaps in) with the damping an accepted
   // step gets; on acceptance they are simply kept, otherwise the accumulators are re-zeroed before the next build.
-  const bool speculate = !noSpeculation && (!dist || distNative_);
+  const bool speculate = !noSpeculation && (!dist || distNative);
   while (true) {
     // the time-limit callback.  One GPU: this rank's clock.  Sharded: a rank that left the loop on its own clock would leave
     // the others blocked in the next all-reduce, so the ranks vote (below, with the evaluation's all-reduce) and stop on the
@@ -2520,24 +2521,22 @@ void Window::solve(size_t numIter, bool verbose) {
       if (pass.stepInEval && !pass.specInEval) throw std::logic_error("solve: the step was left to a build that is not enqueued");
       // enqueue the pass
       if (pass.solve) {
-        if (pass.build.launch) launchAccumulateNormalEquations(p, tr.mu, tr.initScale, s, pass.build.zeroFirst);
+        if (pass.build.launch) launchAccumulateNormalEquations(p, tr.mu, tr.initScale, s, pass.build.zeroFirst, sideLane);
         if (pass.allReduceSystem && p.d > 0) {   // one message: lower triangle of S + gRed + gFull + hC (half of what the full matrix would be)
           launchPackSystem(p, /*unpack=*/false, s);
           AR(p.cholL, packedSystemDoubles(p), 0);
           launchPackSystem(p, /*unpack=*/true, s);
         }
-        launchSolveReduced(p, s, tr.mu, tr.initScale, /*fuseFinalize=*/true);
-        p.lmDeferred = pass.lmDeferredPost;
-        launchDoglegPrepare(p, s, pass.prepareRadius, pass.stepInEval);
+        launchSolveReduced(p, s, tr.mu, tr.initScale, /*fuseFinalize=*/true, sideLane);
+        launchDoglegPrepare(p, PassArgs{nullptr, 0, pass.lmDeferredPost}, s, pass.prepareRadius, pass.stepInEval);
         AR(scalD + kScalGroupB, 8 + kScalGatherSlots, 0);   // group B and every rank's (gradMax, failMax) pair: one message
       }
       if (pass.doglegStep) launchDoglegStep(p, tr.stepRadius(), s);
-      p.lmDeferred = pass.lmDeferredEval;
-      const bool specFused = evaluateAll(true, s, pass.specInEval ? &pass.specMu : nullptr, false, pass.stepInEval ? tr.stepRadius() : -1.0);
-      p.lmDeferred = 0;
+      const bool specFused = evaluateAll(true, s, publishTo, pass.lmDeferredEval, pass.specInEval ? &pass.specMu : nullptr, false,
+                                         pass.stepInEval ? tr.stepRadius() : -1.0);
       if (pass.specWanted) {
         // the problem as it looks after an accepted step (k_eval_build built on the candidate's sets itself: no swapped view)
-        if (!specFused) launchAccumulateNormalEquations(withSetsSwapped(p), pass.specMu, false, s, /*zeroFirst=*/false);
+        if (!specFused) launchAccumulateNormalEquations(withSetsSwapped(p), pass.specMu, false, s, /*zeroFirst=*/false, sideLane);
         ledger.specEnqueued(pass.specMu);
       }
       if (dist) {  // this iteration will be complete when the vote is read: `iteration` already counts it, and its own duration
@@ -2548,7 +2547,7 @@ void Window::solve(size_t numIter, bool verbose) {
       AR(scalD, 8, 0);
       publish();
       // read the scalars, decide
-      sc = readScalars();
+      sc = readScalars(fromMailbox);
       if (dist) stopVotes = sc.spareA0;
       end = finishPass(tr, toTrScalars(sc, dist), tIter, lastIterTime, verbose, -1);
       ledger.end(end);
@@ -2556,17 +2555,14 @@ void Window::solve(size_t numIter, bool verbose) {
     if (end == kPassTerminated) break;
   }
   writeSummary(tr, tStart);
-  distNative_ = false;
 }
 
 // failMax carries the cholFail bits (max over the ranks): 4 | 8 = a bounded wait inside a solver kernel timed out.  That is
 // a synchronisation fault, not a numerical event -- it must not disappear into the mu ladder as "not positive definite"
 PassEnd Window::finishPass(TrustRegionHost& tr, const TrScalars& t, double tIter, double& lastIterTime, bool verbose, int batchIndex) {
-  if (t.failMax >= 4.0) {
-    distNative_ = false;
+  if (t.failMax >= 4.0)
     throw std::runtime_error("svin_ba: a device-side wait in the reduced-system solver timed out (cholFail " + std::to_string((int)t.failMax) +
                              "): synchronisation fault, not a numerical failure");
-  }
   if (tr.retryFactorisation(t)) return kPassRetry;   // the same iteration again, with more damping and a fresh build
   const double muUsed = tr.mu;
   const TrustRegionHost::Outcome o = tr.endIteration(t);
@@ -2704,14 +2700,14 @@ void Window::solveBatchGroup(const std::vector<Window*>& group, size_t numIter, 
     }
     ln.hs = ln.lead->batchSlotsHost_;
   }
-  struct State { TrustRegionHost tr; bool active = true; bool deferLm = false; double lastIterTime = 0, tIter = 0; };
+  // a window's passes are planned as solve() plans them (iteration_plan.hpp), with a ledger of its own: one GPU, no speculation,
+  // no k_eval_build, and the step mode batchSupported asked for -- fused, the landmarks moved by the evaluation
+  struct State { TrustRegionHost tr; AccumulatorLedger ledger; StepMode stepMode; bool active = true; double lastIterTime = 0, tIter = 0; };
   std::vector<State> st((size_t)B);
   for (int i = 0; i < B; ++i) {
     Window* w = g[i];
-    const DeviceProblem& p = w->prob_;
     w->summary_.iterations = 0; w->summary_.num_successful_steps = 0; w->summary_.termination = 1;
-    w->distNative_ = false;
-    st[i].deferLm = p.L > 0 && p.N > 0;   // (batchSupported: fused step, fused evaluation)
+    st[i].stepMode = stepModeOf(w->prob_, /*sharded=*/false);
     st[i].tr.fTol = w->fTol_; st[i].tr.gTol = w->gTol_; st[i].tr.pTol = w->pTol_;
     st[i].tr.maxIterations = (int)numIter;
     if (w->trInitialRadius_ != st[i].tr.initialRadius || w->trMaxRadius_ != st[i].tr.maxRadius)   // (dogleg: the radius is the slot's own)
@@ -2732,16 +2728,16 @@ void Window::solveBatchGroup(const std::vector<Window*>& group, size_t numIter, 
       sl.stages = 0;
       if (!st[i].active) continue;
       const TrustRegionHost& tr = st[i].tr;
-      DeviceProblem& p = w->prob_;
-      p.mailbox = w->mailboxDev_;
-      p.mailboxSeq = ++w->mailboxSeq_;
-      p.lmDeferred = (cand && st[i].deferLm && !tr.reuse) ? 1 : 0;
-      p.aBlocks = schurDenseABlocks(p);
-      sl.p = p;
+      const DeviceProblem& p = w->prob_;
+      IterationPass pass{};   // (the initial evaluation has none)
+      if (cand) pass = planPass(st[i].stepMode, /*dist=*/false, /*evalBuild=*/false, /*speculate=*/false, tr, (int)numIter, false, st[i].ledger);
+      // the slot's copy carries what every launch of the round is told: the evaluation's mailbox record, and the landmarks deferred
+      // to it (a fresh linearisation's post-solve pass of the same round reads the same flag)
+      sl.p = withPassArgs(p, PassArgs{w->mailboxDev_, ++w->mailboxSeq_, pass.lmDeferredEval});
+      sl.p.aBlocks = schurDenseABlocks(p);
       anyObsS = anyObsS || p.obsS != nullptr;
-      p.lmDeferred = 0;
       sl.mu = tr.mu; sl.radius = tr.radius; sl.initScale = tr.initScale ? 1 : 0;
-      sl.stages = !cand ? kBatchEval : (tr.reuse ? (kBatchReuse | kBatchEval) : (kBatchFull | kBatchEval));
+      sl.stages = batchStagesOf(pass, cand);
       sl.ext = batchExtentsOf(batchDimsOf(sl.p));
       grid.include(sl.ext, sl.stages);
       busy += batchBusyBlocks(sl.ext, sl.stages);
@@ -2771,7 +2767,7 @@ void Window::solveBatchGroup(const std::vector<Window*>& group, size_t numIter, 
     for (int k = 0; k < ln.count; ++k) {
       const int i = ln.first + k;
       if (!ln.hs[k].stages) continue;
-      const SolverScalars sc = g[i]->readScalars();
+      const SolverScalars sc = g[i]->readScalars(/*fromMailbox=*/true);
       TrustRegionHost& tr = st[i].tr;
       if (!ln.cand) {   // the initial evaluation
         tr.start(sc.cost);
@@ -2780,6 +2776,7 @@ void Window::solveBatchGroup(const std::vector<Window*>& group, size_t numIter, 
         continue;
       }
       const PassEnd end = g[i]->finishPass(tr, toTrScalars(sc, /*gatherRanks=*/false), st[i].tIter, st[i].lastIterTime, verbose, i);
+      st[i].ledger.end(end);
       if (end == kPassRetry) continue;   // the same iteration again, with more damping (next round: a fresh build)
       if (end == kPassTerminated) finishWindow(i);
       else begin(i);
@@ -2970,7 +2967,7 @@ int Window::evalFactors(int32_t* kind, int32_t* m, int32_t* ncols, double* r, do
   const DeviceProblem& p = prob_;
   if (p.F == 0) return 0;
   evaluateHostFactors(false, stream_);
-  launchEvalFactors(p, false, stream_);
+  launchEvalFactors(p, PassArgs{}, false, stream_);
   std::vector<FactorLin> h(p.F);
   std::vector<DevImu> hImu(p.nImu);
   HIP_OK(hipMemcpyAsync(h.data(), p.linCur, sizeof(FactorLin) * p.F, hipMemcpyDeviceToHost, stream_));
@@ -2999,15 +2996,14 @@ int Window::evalFactors(int32_t* kind, int32_t* m, int32_t* ncols, double* r, do
 }
 int Window::linearize(double mu, double* S, double* g, uint64_t* blockIds, int32_t* blockOff, int32_t* nBlocks,
                       int capD, double* cost) {
-  distNative_ = false;
   pack();
-  DeviceProblem& p = prob_;
+  const DeviceProblem& p = prob_;
   if (p.d > capD) return -p.d;
   const bool viaEvalBuild = optOn(kOptLinearizeEvalBuild);
   if (viaEvalBuild) launchZeroBuild(p, stream_);   // (k_eval_build takes clean accumulators)
-  if (evaluateAll(false, stream_, viaEvalBuild ? &mu : nullptr, true)) launchFinalizeNormalEquations(p, mu, true, stream_);
+  if (evaluateAll(false, stream_, mailboxDev_, 0, viaEvalBuild ? &mu : nullptr, true)) launchFinalizeNormalEquations(p, mu, true, stream_);
   else launchBuildNormalEquations(p, mu, true, stream_);
-  SolverScalars sc = readScalars();
+  SolverScalars sc = readScalars(world_ <= 1);
   if (cost) *cost = sc.cost;
   if (S) HIP_OK(hipMemcpy2D(S, sizeof(double) * p.d, p.S, sizeof(double) * p.ldS, sizeof(double) * p.d, p.d, hipMemcpyDeviceToHost));
   if (g) HIP_OK(hipMemcpy(g, p.gRed, sizeof(double) * p.d, hipMemcpyDeviceToHost));
@@ -3031,13 +3027,12 @@ int Window::linearize(double mu, double* S, double* g, uint64_t* blockIds, int32
 // inspection hook: the Gauss-Newton step of the reduced system as the solver kernels compute it (whichever of the four paths the
 // size selects), for the tests to hold against a host solve of linearize()'s system
 int Window::debugReducedSolve(double mu, double* y, int capD, bool fuseFinalize) {
-  distNative_ = false;
   pack();
-  DeviceProblem& p = prob_;
+  const DeviceProblem& p = prob_;
   if (p.d > capD) return -p.d;
   const bool viaEvalBuild = fuseFinalize && optOn(kOptLinearizeEvalBuild);
   if (viaEvalBuild) launchZeroBuild(p, stream_);
-  const bool built = evaluateAll(false, stream_, viaEvalBuild ? &mu : nullptr, true);
+  const bool built = evaluateAll(false, stream_, mailboxDev_, 0, viaEvalBuild ? &mu : nullptr, true);
   if (fuseFinalize) {   // what solve() enqueues: metric and damping applied inside the solver's load phase
     if (!built) launchAccumulateNormalEquations(p, mu, true, stream_, /*zeroFirst=*/!viaEvalBuild);
     launchSolveReduced(p, stream_, mu, true, /*fuseFinalize=*/true);
@@ -3072,11 +3067,10 @@ int Window::debugBuildArrays(double* gFull, double* hC, int capD, double* Vinv, 
 // window, 1 the fused step with the landmarks moved by k_post_solve's tail, 2 k_post_solve without a radius + k_step_retract,
 // 3 the fused step with the landmarks moved by the candidate evaluation.  A form the window cannot take is an error, never another form.
 int Window::debugTrustRegionStep(double mu, double radius, int form, int commit, const DebugStepOut& o) {
-  distNative_ = false;
   if (form < 0 || form > 3 || !(radius > 0.0) || !o.info) return -1 /* SVIN_ERR_INVALID_ARG */;
   if (world_ > 1 || rcclComm_) return -4 /* SVIN_ERR_UNSUPPORTED */;   // (the sharded step has all-reduces between these launches: solve() only)
   pack();
-  DeviceProblem& p = prob_;
+  const DeviceProblem& p = prob_;
   hipStream_t s = stream_;
   const int nBlk = (int)(poseIds_.size() + extIds_.size() + sbIds_.size());
   // the choice of solve()
@@ -3092,22 +3086,20 @@ int Window::debugTrustRegionStep(double mu, double radius, int form, int commit,
   if (run == 1 && !small) return -4 /* SVIN_ERR_UNSUPPORTED */;   // (one workgroup moves every landmark: solve() never asks that of more)
   if (p.d > o.capD || p.L > o.capL || nBlk > o.capBlocks) return 0;   // sizes only
   {
-    struct SbEarlyGuard { DeviceProblem& q; ~SbEarlyGuard() { q.sideLane = 0; q.lmDeferred = 0; } } guard{p};
-    p.sideLane = optOn(kOptNoSbEarly) ? 0 : 1;
-    evaluateAll(false, s);
-    launchAccumulateNormalEquations(p, mu, true, s, /*zeroFirst=*/true);
-    launchSolveReduced(p, s, mu, true, /*fuseFinalize=*/true);
-    p.lmDeferred = run == 3 ? 1 : 0;
+    const bool sideLane = !optOn(kOptNoSbEarly);   // (as solve() on one GPU: one value for the build and the reduced solve)
+    const int lmDeferred = run == 3 ? 1 : 0;
+    evaluateAll(false, s, mailboxDev_);
+    launchAccumulateNormalEquations(p, mu, true, s, /*zeroFirst=*/true, sideLane);
+    launchSolveReduced(p, s, mu, true, /*fuseFinalize=*/true, sideLane);
     // SVIN_STEP_HOOK_IN_EVAL: form 3 through the pair solve() takes -- the pass without its tail, the step at the head of k_eval_build's
     // blocks, whose build (damping mu, on the candidate's sets) lands in the accumulators the pass has just cleared
     const bool viaHead = run == 3 && optOn(kOptStepHookInEval) && stepInEvalTaken(p, false, true, false, !hostFactors_.empty(), deviceComputeUnits());
-    launchDoglegPrepare(p, s, run == 2 ? -1.0 : radius, viaHead);
+    launchDoglegPrepare(p, PassArgs{nullptr, 0, lmDeferred}, s, run == 2 ? -1.0 : radius, viaHead);
     if (run == 2) launchDoglegStep(p, radius, s);
-    if (viaHead) evaluateAll(true, s, &mu, false, radius);
-    else evaluateAll(true, s);
-    p.lmDeferred = 0;
+    if (viaHead) evaluateAll(true, s, mailboxDev_, lmDeferred, &mu, false, radius);
+    else evaluateAll(true, s, mailboxDev_, lmDeferred);
   }
-  const SolverScalars sc = readScalars();
+  const SolverScalars sc = readScalars(/*fromMailbox=*/true);
   HIP_OK(hipStreamSynchronize(s));
   if (o.scalars) {
     static_assert(sizeof(SolverScalars) == 38 * sizeof(double), "svin_ba_debug_trust_region_step lays the record out as 38 doubles");
@@ -3285,7 +3277,7 @@ void Window::computeLhs() {
   if (!facs.empty()) HIP_OK(hipMemcpyAsync(dLhsFacs_.p, facs.data(), sizeof(int2) * facs.size(), hipMemcpyHostToDevice, s));
   if (p.F > 0) {
     evaluateHostFactors(false, s);
-    launchEvalFactors(p, false, s);
+    launchEvalFactors(p, PassArgs{}, false, s);
   }
   launchLhsAll(p, dLhsItems_.p, (int)items.size(), dLhsBlocks_.p, (int)blk.size(), dLhsFacs_.p, dLhsPartial_.p, dLhs_.p, offLm, s);
   lhsHost_.assign(total, 0.0);
@@ -3625,7 +3617,7 @@ int Window::benchKernelTimes(int iters, double* evalMs, double* buildMs, double*
     for (int i = 0; i < reps; ++i) {
       invalidatePreintegration();
       pack();
-      launchEvalFactors(prob_, false, stream_);
+      launchEvalFactors(prob_, PassArgs{}, false, stream_);
       HIP_OK(hipStreamSynchronize(stream_));
     }
     double dbg[16];
@@ -3633,7 +3625,7 @@ int Window::benchKernelTimes(int iters, double* evalMs, double* buildMs, double*
     const double n = 9.0 * reps;
     {  // the evaluation without re-integration (most iterations)
       debugImuTiming(nullptr, true);
-      for (int i = 0; i < reps; ++i) { launchEvalFactors(prob_, false, stream_); HIP_OK(hipStreamSynchronize(stream_)); }
+      for (int i = 0; i < reps; ++i) { launchEvalFactors(prob_, PassArgs{}, false, stream_); HIP_OK(hipStreamSynchronize(stream_)); }
       double d2[16];
       debugImuTiming(d2, false);
       std::printf("[imu eval cycles, no redo] factors counted %.0f: staging %.0f, serial F/e block %.0f (shared quantities %.0f, position/velocity blocks %.0f; part 1 %.0f, part 3 %.0f), whole block %.0f\n", d2[11],
@@ -3644,9 +3636,9 @@ int Window::benchKernelTimes(int iters, double* evalMs, double* buildMs, double*
         float tot = 0;
         for (int i = 0; i < 20; ++i) {
           HIP_OK(hipEventRecord(a, stream_));
-          if (variant == 0) evaluateAll(false, stream_);
-          else if (variant == 1) launchEvalFactors(prob_, false, stream_);
-          else launchEvalAll(prob_, false, false, stream_);
+          if (variant == 0) evaluateAll(false, stream_, mailboxDev_);
+          else if (variant == 1) launchEvalFactors(prob_, PassArgs{}, false, stream_);   // (no cost sum: nothing is published)
+          else launchEvalAll(prob_, PassArgs{}, false, false, stream_);
           HIP_OK(hipEventRecord(b, stream_));
           HIP_OK(hipEventSynchronize(b));
           float ms = 0;
@@ -3660,9 +3652,9 @@ int Window::benchKernelTimes(int iters, double* evalMs, double* buildMs, double*
                 dbg[1] / n, dbg[6] / n, dbg[7] / n, dbg[5] / n, dbg[2] / n, dbg[14] / n, dbg[3] / n, dbg[4] / n);
   }
 #endif
-  DeviceProblem& p = prob_;
+  const DeviceProblem& p = prob_;
   hipStream_t s = stream_;
-  evaluateAll(false, s);
+  evaluateAll(false, s, mailboxDev_);
   launchBuildNormalEquations(p, 1e-8, true, s);
   launchSolveReduced(p, s);
   HIP_OK(hipStreamSynchronize(s));

@@ -467,8 +467,11 @@ class Window {
   // device side
   void pack(bool solveFollows = false);   // host graph -> device arrays (sets prob_); solveFollows: called by optimize()
   void downloadStates();       // device tables -> host blocks / landmarks / imu states
+  // publishTo: where the launch that sums the cost publishes the scalars (mailboxDev_; nullptr: the caller publishes them itself,
+  // behind its all-reduce); lmDeferred: PassArgs::lmDeferred of the evaluation's launches
   // stepRadius > 0: the post-solve pass in front ended at its partials (launchDoglegPrepare noTail) -- k_eval_build takes the step
-  bool evaluateAll(bool cand, hipStream_t s, const double* buildMu = nullptr, bool buildInitScale = false, double stepRadius = -1.0);
+  bool evaluateAll(bool cand, hipStream_t s, ScalarMailbox* publishTo, int lmDeferred = 0, const double* buildMu = nullptr, bool buildInitScale = false,
+                   double stepRadius = -1.0);
   int maxTermsPerBlock_ = 0;   // packFactors: small factors + prior that add to one parameter block's diagonal block, at most
   void evaluateHostFactors(bool cand, hipStream_t s);   // F_HOST factors: callbacks at the current / candidate blocks, r and J into their FactorLin records
   void solve(size_t numIter, bool verbose);
@@ -481,7 +484,9 @@ class Window {
   }
   void writeSummary(const TrustRegionHost& tr, double tStart);
   void swapStateSets();   // an accepted step: the candidate sets become the current ones
-  SolverScalars readScalars();
+  // fromMailbox: the record of the last evaluateAll() is published there (one GPU: by the evaluation; a solve that all-reduces
+  // through rcclComm_: by launchPublishScalars behind the reduction) -- otherwise, and without a mailbox, a synchronising copy
+  SolverScalars readScalars(bool fromMailbox);
   // the record of the last evaluation has reached the mailbox (no mailbox: true -- readScalars() synchronises)
   bool scalarsReady() const { return !mailbox_ || *reinterpret_cast<const volatile unsigned long long*>(&mailbox_->seq) == mailboxSeq_; }
 
@@ -503,7 +508,6 @@ class Window {
   int rank_ = 0, world_ = 1;
   AllReduceFn allreduce_ = nullptr;
   void* allreduceUser_ = nullptr;
-  bool distNative_ = false;    // the current solve all-reduces through rcclComm_ (scalars published after the reduction)
   void* rcclComm_ = nullptr;   // ncclComm_t of the native path (RCCL resolved at run time, see window.cpp)
   hipStream_t stream_ = nullptr;
   hipStream_t stream2_ = nullptr;                       // side stream: the early IMU pre-integration of optimize() (pack())
@@ -646,6 +650,8 @@ class Window {
   std::unordered_map<uint64_t, int> poseSlot_, extSlot_, sbSlot_;
   std::vector<uint64_t> redBlockIds_;
   std::vector<int32_t> redBlockOff_;
+  // constant from one pack() to the next, apart from the set swap of an accepted step (swapStateSets): written by the constructor,
+  // pack() and swapStateSets() alone.  What a single launch is told besides it is an argument of that launch (kernels.hpp PassArgs).
   DeviceProblem prob_;
 
   // device buffers

@@ -3,6 +3,8 @@
 // -fsanitize=address,undefined -fno-sanitize-recover=all, hands it cases of that test as a text file and holds what it prints
 // against the shim's answers.
 // One case per line:  cfg[0..5] nPass event[0] .. event[nPass-1]   ->   the passes run, then their rows (iteration_plan_shim.cpp)
+// A second file, if given, holds passes put together by hand, one per line:  f[0..6] prepareRadius cand   ->   ip_batch_stages' answer
+// (the branches of batchStagesOf that throw are reached this way only)
 #include <cstdio>
 #include <vector>
 #include "iteration_plan_shim.cpp"
@@ -27,5 +29,15 @@ int main(int argc, char** argv) {
     ++cases;
   }
   std::fclose(f);
+  if (argc > 2) {
+    std::FILE* h = std::fopen(argv[2], "r");
+    if (!h) return 2;
+    int32_t p[7];
+    double radius;
+    int cand;
+    while (std::fscanf(h, "%d %d %d %d %d %d %d %lf %d", &p[0], &p[1], &p[2], &p[3], &p[4], &p[5], &p[6], &radius, &cand) == 9)
+      std::printf("stages %d\n", ip_batch_stages(p, radius, cand));
+    std::fclose(h);
+  }
   return cases > 0 ? 0 : 1;
 }

@@ -4,7 +4,9 @@
 // every sequence of a given length.  The test interprets those rows; nothing here judges them.
 //
 // cfg: strategy (0 dogleg, 1 Levenberg-Marquardt), SVIN_NO_SPECULATION, SVIN_NO_EVAL_BUILD, mode (0 one GPU, 1 sharded with the
-//      native all-reduce, 2 sharded with the callback), numIter, what stepInEvalTaken answers for the window's sizes
+//      native all-reduce, 2 sharded with the callback, 3 a window of a batched solve: Window::solveBatchGroup's loop, which plans
+//      without speculation and k_eval_build whatever the switches say and enqueues no build behind the initial evaluation),
+//      numIter, what stepInEvalTaken answers for the window's sizes
 // events, one per pass: 0 the factorisation fails, 1 a step accepted at the 1/3 clamp (it leaves the damping a speculative build
 //      assumes), 2 a step accepted with rho = 0.5 (Levenberg-Marquardt: another damping), 3 rejected, 4 invalid, 5 gradient below tolerance
 // a row, kIpFields doubles: see the enum
@@ -14,7 +16,8 @@
 namespace {
 using namespace svin;
 enum { kAlive, kReuse, kMu, kInitScale, kIteration, kSolve, kLaunch, kZeroFirst, kAllReduceSystem, kPrepareRadius, kStepInEval, kLmDeferredPost,
-       kDoglegStep, kLmDeferredEval, kSpecWanted, kSpecMu, kSpecInEval, kSpecFused, kEnd, kHitsIfClosed, kMissesIfClosed, kStepRadius, kIpFields };
+       kDoglegStep, kLmDeferredEval, kSpecWanted, kSpecMu, kSpecInEval, kSpecFused, kEnd, kHitsIfClosed, kMissesIfClosed, kStepRadius,
+       kBatchStages /* mode 3: batchStagesOf(pass, cand = true), -1 where it throws */, kIpFields };
 constexpr int kIpEvents = 6;
 
 TrScalars scalarsOf(int event, const TrustRegionHost& tr) {
@@ -37,9 +40,14 @@ PassEnd finishPass(TrustRegionHost& tr, const TrScalars& t) {
   return o == TrustRegionHost::kAccepted ? kPassAccepted : o == TrustRegionHost::kRejected ? kPassRejected : kPassInvalid;
 }
 
+int batchStagesOrMinusOne(const IterationPass& pass, bool cand) {
+  try { return batchStagesOf(pass, cand); } catch (const std::logic_error&) { return -1; }
+}
+
 // Window::solve; rows: nPass x kIpFields, zeroed by the caller.  Returns the passes run.
 int run(const int32_t* cfg, const int32_t* events, int nPass, double* rows) {
-  const bool lm = cfg[0] != 0, noSpeculation = cfg[1] != 0, noEvalBuild = cfg[2] != 0, dist = cfg[3] != 0, distNative = cfg[3] == 1;
+  const bool batched = cfg[3] == 3;
+  const bool lm = cfg[0] != 0, noSpeculation = cfg[1] != 0 || batched, noEvalBuild = cfg[2] != 0, dist = cfg[3] == 1 || cfg[3] == 2, distNative = cfg[3] == 1;
   const int numIter = cfg[4];
   const bool headFits = cfg[5] != 0;
   const StepMode stepMode = stepModeOf(StepDims{10, 2, 10, 100, 1000, true}, StepSwitches{false, false, false}, dist);
@@ -47,7 +55,7 @@ int run(const int32_t* cfg, const int32_t* events, int nPass, double* rows) {
   if (lm) tr.configure(TrustRegionHost::kLevenbergMarquardt, 1e4, 1e16);
   const bool evalBuild = !dist && !noSpeculation;
   AccumulatorLedger ledger;
-  if (!dist && numIter > 0) ledger.firstEnqueued(tr.mu);
+  if (!dist && !batched && numIter > 0) ledger.firstEnqueued(tr.mu);
   tr.maxIterations = numIter;
   tr.start(100.0);
   const bool speculate = !noSpeculation && (!dist || distNative);
@@ -67,6 +75,7 @@ int run(const int32_t* cfg, const int32_t* events, int nPass, double* rows) {
       r[kDoglegStep] = pass.doglegStep; r[kLmDeferredEval] = pass.lmDeferredEval; r[kSpecWanted] = pass.specWanted; r[kSpecMu] = pass.specMu;
       r[kSpecInEval] = pass.specInEval;
       r[kSpecFused] = pass.specInEval && !noEvalBuild;   // evaluateAll's answer
+      if (batched) r[kBatchStages] = batchStagesOrMinusOne(pass, true);
       if (pass.specWanted) ledger.specEnqueued(pass.specMu);
       end = finishPass(tr, scalarsOf(events[k], tr));
       ledger.end(end);
@@ -96,6 +105,14 @@ void ip_run_all(const int32_t* cfg, int nPass, double* rows) {
     for (int k = nPass - 1; k >= 0; --k) { events[k] = (int32_t)(v % kIpEvents); v /= kIpEvents; }
     run(cfg, events, nPass, rows + (size_t)q * (size_t)nPass * kIpFields);
   }
+}
+// batchStagesOf on a pass put together by hand.  f: solve, build.launch, build.zeroFirst, allReduceSystem, stepInEval, doglegStep,
+// specWanted; -1 where it throws
+int ip_batch_stages(const int32_t* f, double prepareRadius, int cand) {
+  IterationPass q{};
+  q.solve = f[0] != 0; q.build = BuildNeed{f[1] != 0, f[2] != 0}; q.allReduceSystem = f[3] != 0; q.stepInEval = f[4] != 0; q.doglegStep = f[5] != 0;
+  q.specWanted = f[6] != 0; q.prepareRadius = prepareRadius;
+  return batchStagesOrMinusOne(q, cand != 0);
 }
 // The speculative builds a solve on one GPU kept and discarded, from its iteration log (n rows of 6: TrustRegionHost::logRow) -- for
 // tests/test_gpu_solve_loop.py, which holds SVIN_SPEC_BUILD_HITS / _MISSES against it.  The trust region's state in front of every

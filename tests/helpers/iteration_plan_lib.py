@@ -9,10 +9,11 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 FIELDS = ("alive", "reuse", "mu", "initScale", "iteration", "solve", "launch", "zeroFirst", "allReduceSystem", "prepareRadius", "stepInEval",
           "lmDeferredPost", "doglegStep", "lmDeferredEval", "specWanted", "specMu", "specInEval", "specFused", "end", "hitsIfClosed",
-          "missesIfClosed", "stepRadius")
+          "missesIfClosed", "stepRadius", "batchStages")
 RETRY, TERMINATED, ACCEPTED, REJECTED, INVALID = range(5)   # PassEnd
 ZERO, BUILD, STALE = range(3)                               # AccumulatorLedger::Contents
-ONE_GPU, NATIVE, CALLBACK = range(3)
+ONE_GPU, NATIVE, CALLBACK, BATCHED = range(4)               # mode; BATCHED: a window of a batched solve
+BATCH_FULL, BATCH_REUSE, BATCH_EVAL = 1, 2, 4               # batch_plan.hpp: stages of a round
 
 
 def build_shim(directory):
@@ -27,6 +28,7 @@ def build_shim(directory):
     lib.ip_need.restype = None
     lib.ip_replay.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
     lib.ip_replay.restype = None
+    lib.ip_batch_stages.argtypes = [C.c_void_p, C.c_double, C.c_int]
     assert lib.ip_fields() == len(FIELDS)
     return lib
 

@@ -1,5 +1,5 @@
 """The round-6 forms of the wide-window iteration against each other: the side lane (small factors and the speed / bias chain's
-factorisation beside the landmark elimination, DeviceProblem::sideLane), the split block rows of k_schur_rows' work list and the
+factorisation beside the landmark elimination, launchAccumulateNormalEquations' sideLane), the split block rows of k_schur_rows' work list and the
 split evaluation / fused step are ORDERINGS of the same sums -- a wide window solved with each of them switched off must end
 where the default path ends, to rounding.  (Parity of the default path with the oracle: test_wide_window_* / test_config4_* in
 tests/test_gpu_parity.py.)"""

@@ -9,7 +9,10 @@ assumes, accepted and leaves another, rejected, invalid, the solve terminates) -
    Four planted defects, applied to the launch list, must each fail that.
 2. Equivalence.  The six locals Window::solve kept before the ledger, transcribed once, give the same launches, zeroFirst flags
    and hit / miss counts.
-3. The same cases through a stand-alone program under AddressSanitizer and UndefinedBehaviorSanitizer
+3. The batched round.  A window of a batched solve plans its passes with the same planPass (one GPU, no speculation, no
+   k_eval_build, a ledger of its own, no build behind the initial evaluation); the stages of its round (batchStagesOf) and the
+   slot's lmDeferred must be the expressions Window::solveBatchGroup wrote out by hand before, its build {launch, no zeroing}.
+4. The same cases through a stand-alone program under AddressSanitizer and UndefinedBehaviorSanitizer
    (tests/csrc/iteration_plan_sanitize.cpp), whose answers must be the shim's.
 
 Everything is evaluated for all 6^6 sequences of a configuration at once: arrays of shape (sequences, passes)."""
@@ -22,8 +25,8 @@ import numpy as np
 import pytest
 
 from helpers import iteration_plan_lib as ip
-from helpers.iteration_plan_lib import (ACCEPTED, BUILD, CALLBACK, FIELDS, INVALID, NATIVE, ONE_GPU, REJECTED, RETRY,   # noqa: F401
-                                        STALE, ZERO)
+from helpers.iteration_plan_lib import (ACCEPTED, BATCH_EVAL, BATCH_FULL, BATCH_REUSE, BATCHED, BUILD, CALLBACK, FIELDS,   # noqa: F401
+                                        INVALID, NATIVE, ONE_GPU, REJECTED, RETRY, STALE, ZERO)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N_PASS, N_EVENTS = 6, 6
@@ -39,6 +42,12 @@ def configurations():
         for head in ((0, 1) if mode == ONE_GPU and not no_spec and num_iter > 1 else (0,)):
             out.append((lm, no_spec, no_eval_build, mode, num_iter, head))
     return out
+
+
+def batched_configurations():
+    """a window of a batched solve: dogleg, one GPU, SVIN_NO_SPECULATION set, no k_eval_build; the step mode of the shim's window
+    is the fused step with the landmarks deferred, which batchSupported requires"""
+    return [(0, 1, 1, BATCHED, num_iter, 0) for num_iter in (0, 1, 2, 6)]
 
 
 @pytest.fixture(scope="module")
@@ -262,24 +271,82 @@ def test_replay_of_an_iteration_log_counts_as_the_loop_does(lib):
     assert ip.replay(lib, log, "lm", 0, 9) == (1, 3, 4)
 
 
-# ------------------------------------------------------------------------------------------------ 3. under a sanitizer
+# ------------------------------------------------------------------------------------------------ 3. the batched round
+def hand_made_passes():
+    """(solve, build.launch, build.zeroFirst, allReduceSystem, stepInEval, doglegStep, specWanted), prepareRadius, cand -> stages, -1
+    where batchStagesOf throws; every pass also as the initial evaluation (cand = 0), which reads none of it"""
+    fused = 1e4
+    cases = {(1, 1, 0, 0, 0, 0, 0): BATCH_FULL | BATCH_EVAL, (0, 0, 0, 0, 0, 1, 0): BATCH_REUSE | BATCH_EVAL,
+             (1, 1, 1, 0, 0, 0, 0): -1,    # a zeroing build
+             (1, 0, 0, 0, 0, 0, 0): -1,    # a build kept from an earlier round
+             (1, 1, 0, 1, 0, 0, 0): -1,    # a system all-reduce
+             (1, 1, 0, 0, 0, 0, 1): -1, (0, 0, 0, 0, 0, 1, 1): -1,   # a speculative build
+             (1, 1, 0, 0, 1, 0, 0): -1,    # the step left to k_eval_build
+             (1, 1, 0, 0, 0, 1, 0): -1,    # a step that is not fused
+             (0, 0, 0, 0, 0, 0, 0): -1}    # neither a solve nor a step
+    out = []
+    for fields, want in cases.items():
+        out += [(fields, fused, 1, want), (fields, fused, 0, BATCH_EVAL)]
+    return out + [((1, 1, 0, 0, 0, 0, 0), -1.0, 1, -1)]   # the post-solve pass without a radius
+
+
+HAND_MADE_PASSES = hand_made_passes()
+
+
+def test_batched_round_is_the_pass_solve_batch_group_wrote_out_by_hand(lib):
+    """Every event sequence of a batched window.  Before, Window::solveBatchGroup kept `deferLm = p.L > 0 && p.N > 0` per window and
+    issued  stages = !cand ? kBatchEval : (tr.reuse ? kBatchReuse | kBatchEval : kBatchFull | kBatchEval)  and
+    lmDeferred = cand && deferLm && !tr.reuse;  the rows are passes, cand = true (the initial evaluation, cand = false, has no pass)."""
+    passes = 0
+    for cfg in batched_configurations():
+        r = run_all(lib, cfg)
+        alive, reuse = r["alive"] > 0, r["reuse"] > 0
+        defer_lm = True   # the shim's window: L = 100, N = 1000
+        stages_before = np.where(reuse, BATCH_REUSE | BATCH_EVAL, BATCH_FULL | BATCH_EVAL)
+        assert np.array_equal(r["batchStages"][alive], stages_before[alive]), cfg
+        assert np.array_equal(r["lmDeferredEval"][alive] > 0, (defer_lm & ~reuse)[alive]), cfg
+        # the build of every pass that has one -- a fresh linearisation, the retry ladder included -- is launched into clean accumulators
+        fresh = alive & ~reuse
+        assert np.array_equal(r["solve"] > 0, fresh) and (r["launch"][fresh] > 0).all() and not (r["zeroFirst"][alive] > 0).any(), cfg
+        assert (r["end"][fresh] == RETRY).any() or cfg[4] == 0
+        assert not (r["specWanted"][alive] > 0).any() and not (r["allReduceSystem"][alive] > 0).any() and not (r["stepInEval"][alive] > 0).any()
+        assert np.array_equal(r["doglegStep"] > 0, alive & reuse)   # kBatchReuse: k_step_retract alone
+        assert np.array_equal(r["prepareRadius"][fresh], r["stepRadius"][fresh])   # (dogleg: the slot's radius, tr.radius)
+        ok, kept = model(cfg, r)   # and the accumulators hold exactly that build in front of every reduced solve
+        assert ok.all() and not kept.any(), cfg
+        passes += int(alive.sum())
+    assert passes > 10 ** 5
+    # the initial evaluation, and what a round has no launches for
+    for fields, radius, cand, want in HAND_MADE_PASSES:
+        f = np.array(fields, np.int32)
+        assert lib.ip_batch_stages(f.ctypes.data_as(C.c_void_p), radius, cand) == want, (fields, radius, cand)
+
+
+# ------------------------------------------------------------------------------------------------ 4. under a sanitizer
 def test_ledger_and_pass_under_address_and_undefined_behaviour_sanitizers(lib, tmp_path):
-    exe, cases = str(tmp_path / "iteration_plan_sanitize"), str(tmp_path / "cases.txt")
+    exe, cases, passes = str(tmp_path / "iteration_plan_sanitize"), str(tmp_path / "cases.txt"), str(tmp_path / "passes.txt")
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
                            os.path.join(ROOT, "tests", "csrc", "iteration_plan_sanitize.cpp"), "-o", exe])
     rng = np.random.default_rng(5)
     scripts = []
-    for cfg in configurations():
+    for cfg in configurations() + batched_configurations():
         for n in (0, 1, 3, 6, 12):
             scripts.append((cfg, [int(v) for v in rng.integers(0, N_EVENTS, n)]))
         scripts.append((cfg, [0] * 9))   # the mu ladder to its end
     with open(cases, "w") as f:
         for cfg, ev in scripts:
             f.write(" ".join(str(v) for v in list(cfg) + [len(ev)] + ev) + "\n")
-    out = subprocess.run([exe, cases], stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True)
+    with open(passes, "w") as f:   # the hand-made passes of the batched round, the throwing branches of batchStagesOf among them
+        for fields, radius, cand, _ in HAND_MADE_PASSES:
+            f.write(" ".join(str(v) for v in fields) + " %r %d\n" % (radius, cand))
+    out = subprocess.run([exe, cases, passes], stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True)
     assert out.returncode == 0, out.stderr
     lines = out.stdout.strip().split("\n")
-    assert len(lines) == len(scripts)
+    assert len(lines) == len(scripts) + len(HAND_MADE_PASSES)
+    stages, lines = lines[len(scripts):], lines[:len(scripts)]
+    for (fields, radius, cand, want), line in zip(HAND_MADE_PASSES, stages):
+        f = np.array(fields, np.int32)
+        assert line == "stages %d" % lib.ip_batch_stages(f.ctypes.data_as(C.c_void_p), radius, cand) == "stages %d" % want, (fields, radius, cand)
     for (cfg, ev), line in zip(scripts, lines):
         c, e, rows = np.array(cfg, np.int32), np.array(ev + [0], np.int32), np.zeros(len(ev) * len(FIELDS))
         ran = lib.ip_run(c.ctypes.data_as(C.c_void_p), e.ctypes.data_as(C.c_void_p), len(ev), rows.ctypes.data_as(C.c_void_p))
